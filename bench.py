@@ -14,9 +14,14 @@ clean configuration): no dedup, no pruning.  The two legal work-pruning options 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-The default single-GPU run prints ONE JSON line: the headline plus `secondary` — the other BASELINE configurations and
+A plain run sets up, warms up, times the K steps and prints ONE JSON line with the headline.  Every step starts from the
+same trainer state and dropout seed (`Uncached.step`), so `--dump-outputs DIR`, which writes what the last timed step
+computed (loss, updated trainables, their gradients) as DIR/<name>.npy, gives the same arrays in every run.  `--full` adds
+everything else to the same line: the kernel-family check before the timed steps, a second instrumented pass of the K
+steps (`roofline.dominant_kernel`, multi-rank all-reduce times), `secondary` — the other BASELINE configurations and
 ablations timed in the same process (each a few seconds): the CLS-only last block (`--cls-prune`, work pruning), bf16
-encoder operands, Code_Cached at bs=1024 (config 3), IISAN-Versa shapes (config 5) and the eval path (users/s).
+encoder operands, Code_Cached at bs=1024 (config 3), IISAN-Versa shapes (config 5) and the eval path (users/s) — and the
+CPU baseline.
 """
 import argparse
 import ctypes as C
@@ -47,6 +52,11 @@ def parse(argv=None):
     ap.add_argument("--bs", type=int, default=None, help="sequences per GPU (default 128; 1024 with --cached, 128 with --versa)")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"], help="MFMA operand type of the frozen encoders")
     ap.add_argument("--chunk", type=int, default=0, help="items per encoder chunk (0 = whole batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the kernel-family check, the instrumented second pass, `secondary` and the CPU "
+                         "baseline (the three --no-* options below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (headline path only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="headline only (no `secondary` list)")
     ap.add_argument("--no-check", action="store_true",
@@ -80,6 +90,8 @@ def parse(argv=None):
                     help="secondary workload (SURVEY 8f-2, never the headline): the eval path at Scientific size — users/s of "
                          "evaluate_ranks end to end, of iisan_score_rank alone, and items/s of item_table from cached taps")
     a = ap.parse_args(argv)
+    if a.dump_outputs and (a.cached or a.eval):
+        ap.error("--dump-outputs writes the outputs of the headline path: not with --cached or --eval")
     if a.bs is None:
         a.bs = 128 if (a.versa or not a.cached) else 1024
     a.full_blocks = not a.cls_prune
@@ -387,6 +399,8 @@ class Uncached:
         self.model.train()
         self.tr = trainer.FlatTrainer(self.model, self.args, world)
         self.tr.broadcast_params()
+        self.flat0 = self.tr.flat.clone()      # the state every step starts from (see step)
+        self.rng0 = torch.get_rng_state()       # ... and the generator its SASRec dropout seed is drawn from
         self.ids = self.batch.ids.view(-1)
 
     def set_full_blocks(self, on):
@@ -404,8 +418,17 @@ class Uncached:
                 m._packed = None                       # repack the frozen weights in the new operand type
 
     def step(self):
-        b = self.batch
-        return self.tr.step(self.ids, b.images, b.text, b.log_mask)
+        """One fwd+bwd+Adam step from the trainer's initial state (the seeded parameters, zero Adam moments, step 1, the same
+        dropout seed): the backward pass reduces with float atomics, so updates carried from step to step would compound their
+        last-bit order and the last step would compute from different inputs in every run; with the reset every step is the
+        same computation, whatever --steps and --warmup are.  It costs one 16.5 MB copy and two fills."""
+        tr, b = self.tr, self.batch
+        torch.set_rng_state(self.rng0)
+        tr.flat.copy_(self.flat0)
+        tr.m.zero_()
+        tr.v.zero_()
+        tr.step_no = 0
+        return tr.step(self.ids, b.images, b.text, b.log_mask)
 
     def kernel_family_check(self):
         """The bench batch through the product's GEMM dispatch (the persistent 256x256 kernels at this size) vs every encoder
@@ -447,27 +470,46 @@ class Uncached:
         return {"loss_auto_dispatch": loss["auto"], "loss_v1_kernels": loss["v1"], "loss_rel": rel, "worst_tap_layer_rel": tap_rel,
                 "worst_tap_layer_rel_layernorm_images": tap_img}
 
-    def dist_info(self, steps):
-        """What a multi-rank line actually ran on: backend, world size, every rank's device, and the
-        device time of the one data-path collective per step.  Two ranks on one device under backend nccl (RCCL) would be a
-        mis-launch: refuse to print a line for it."""
+    def dist_info(self, steps, timed=True):
+        """What a multi-rank line actually ran on: backend, world size, every rank's device, and (`timed`:
+        after the instrumented pass) the device time of the one data-path collective per step.  Two ranks on one device under
+        backend nccl (RCCL) would be a mis-launch: refuse to print a line for it."""
         p = torch.cuda.get_device_properties(self.dev)
         mine = {"rank": self.rank, "host": socket.gethostname(), "device": self.dev.index, "name": p.name,
                 "uuid": str(getattr(p, "uuid", "")), "pci_bus_id": getattr(p, "pci_bus_id", None)}
-        n_ar, ar_ms = self.tr.allreduce_ms()
-        mine["allreduce_ms_per_step"] = ar_ms / max(n_ar, 1)
+        if timed:
+            n_ar, ar_ms = self.tr.allreduce_ms()
+            mine["allreduce_ms_per_step"] = ar_ms / max(n_ar, 1)
         every = [None] * self.world
         dist.all_gather_object(every, mine)
         backend = dist.get_backend()
         check_one_device_per_rank(backend, every)
-        return {"backend": backend, "world": dist.get_world_size(), "devices": [d["device"] for d in every],
-                "device_uuids": [d["uuid"] for d in every], "hosts": sorted(set(d["host"] for d in every)),
-                "collective": f"one SUM all-reduce of the flat gradient buffer per step ({self.tr.grad.numel() * 4 / 1e6:.2f} MB fp32)",
-                "allreduces_timed": n_ar, "steps_timed": steps,
-                "allreduce_ms_per_step": [round(d["allreduce_ms_per_step"], 4) for d in every],
-                "allreduce_ms_per_step_max": max(d["allreduce_ms_per_step"] for d in every)}
+        out = {"backend": backend, "world": dist.get_world_size(), "devices": [d["device"] for d in every],
+               "device_uuids": [d["uuid"] for d in every], "hosts": sorted(set(d["host"] for d in every)),
+               "collective": f"one SUM all-reduce of the flat gradient buffer per step ({self.tr.grad.numel() * 4 / 1e6:.2f} MB fp32)"}
+        if timed:
+            out.update({"allreduces_timed": n_ar, "steps_timed": steps,
+                        "allreduce_ms_per_step": [round(d["allreduce_ms_per_step"], 4) for d in every],
+                        "allreduce_ms_per_step_max": max(d["allreduce_ms_per_step"] for d in every)})
+        return out
 
-    def line(self, steps, warmup, dtype="fp16", full_blocks=True, headline=True, overlap=None):
+    def dump_outputs(self, path, loss):
+        """What the timed step hands its caller, taken right after the last timed step: the loss, every trainable tensor after
+        the Adam update and the gradient that update used, flattened in `model.parameters()` order (4.1 M fp32 trainables:
+        33 MB in all)."""
+        import numpy as np
+        ps = [p for p in self.model.parameters() if p.requires_grad]
+        arrays = {"loss": loss.detach().reshape(1), "params": torch.cat([p.detach().reshape(-1) for p in ps]),
+                  "grads": torch.cat([p.grad.reshape(-1) for p in ps])}
+        if sum(t.numel() * 4 for t in arrays.values()) > 64 << 20:
+            raise SystemExit("bench.py: --dump-outputs would write more than 64 MB")
+        os.makedirs(path, exist_ok=True)
+        for name, t in arrays.items():
+            np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+    def line(self, steps, warmup, dtype="fp16", full_blocks=True, headline=True, overlap=None, instrumented=True, dump=None):
+        """`instrumented`: time the dominant kernel (and a multi-rank run's all-reduces) in a second pass of the same steps.
+        `dump`: a directory for `dump_outputs` after the timed pass."""
         a, lib, world = self.a, self.lib, self.world
         self.set_dtype(dtype)
         self.set_full_blocks(full_blocks)
@@ -477,34 +519,34 @@ class Uncached:
             enc.overlap_towers = overlap
         clock = Clock(self.dev, world)
         try:
-            # Two passes of the same K steps (round 5; the Cached line has always done this): `value` / `ms_per_step` come from a pass
+            # `instrumented`: two passes of the same K steps (round 5; the Cached line has always done this): `value` / `ms_per_step` come from a pass
             # with NO instrumentation inside the timed region, scheduled as the product schedules it (round 6: the two towers on two
             # HIP streams).  The per-launch HIP events of `roofline.dominant_kernel` (194 event records per step on the launching
             # stream) and the all-reduce events of a multi-rank run ride on a second pass with the towers BACK TO BACK on one stream:
             # kernels of two overlapped towers share the CUs and their durations are not kernel measures
             # (profiles/r4_overlap_by_stream.md); the events themselves cost +0.34 ms per step (profiles/r5_overlap.md).
             elapsed, loss = clock.run(self.step, warmup, steps)
+            if dump and self.rank == 0:
+                self.dump_outputs(dump, loss)
             overlapped = enc.overlap_towers
-            enc.overlap_towers = False
-            if world > 1:
-                self.tr.time_allreduce = True
-                self.tr.allreduce_ms()
-            elapsed_ev, _ = clock.run(self.step, 0, steps, lib, timed=self.rank == 0)
-            self.tr.time_allreduce = False
+            if instrumented:
+                enc.overlap_towers = False
+                if world > 1:
+                    self.tr.time_allreduce = True
+                    self.tr.allreduce_ms()
+                elapsed_ev, _ = clock.run(self.step, 0, steps, lib, timed=self.rank == 0)
+                self.tr.time_allreduce = False
         finally:
             self.set_full_blocks(False)
             enc.overlap_towers = prev_overlap
             self.tr.time_allreduce = False
-        dinfo = self.dist_info(steps) if world > 1 else None
+        dinfo = self.dist_info(steps, instrumented) if world > 1 else None
         if not torch.isfinite(loss).item():
             raise SystemExit("bench.py: loss is not finite")
-        ms, fl = C.c_double(0), C.c_double(0)
-        n_launch = lib.iisan_timing_collect(C.byref(ms), C.byref(fl)) if self.rank == 0 else 0
         slots = a.bs * 11
         value = slots * world * steps / elapsed
-        gemm_tflops = fl.value / (ms.value * 1e-3) / 1e12 if ms.value > 0 else 0.0
         traffic = pmc_traffic(a) if (headline and dtype == a.dtype and full_blocks == a.full_blocks) else None
-        return {
+        out = {
             "metric": "items/s (fwd+bwd) ViT-B+BERT-B IISAN uncached, Scientific, bs=128",
             "value": value, "unit": "items/s", "n_gpus": world, "steps": steps, "warmup": warmup,
             "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -514,7 +556,8 @@ class Uncached:
                        "global_batch": a.bs * world, "parallelism": f"dp{world}", "loss": float(loss.item()),
                        **({"distributed": dinfo} if dinfo else {}),
                        "towers": ("image tower on a high-priority HIP stream, text tower on a normal-priority one beside it (the product default: same kernels, "
-                                  "bit-identical results); `roofline.dominant_kernel` is timed in a second pass with the towers back to back on one stream") if overlapped
+                                  "bit-identical results)" + ("; `roofline.dominant_kernel` is timed in a second pass with the towers back to back on one stream"
+                                                              if instrumented else "")) if overlapped
                                  else "both towers back to back on one stream (--no-overlap-towers: the profiling form)",
                        "encoder_blocks": "all tokens in every block" if full_blocks else
                                          "WORK PRUNING: last block computes K/V for all tokens, attention/O/MLP for the CLS rows only (only hidden_states[i][:,0] is consumed; taps identical)"},
@@ -525,23 +568,28 @@ class Uncached:
             "roofline": {"bound": "mfma", "achieved": value / world * FLOP_PER_SLOT / 1e12, "peak": MFMA_PEAK / 1e12, "unit": "TFLOP/s",
                          "frac": value / world * FLOP_PER_SLOT / MFMA_PEAK,
                          "definition": "whole step (SURVEY 8d): items/s per GPU x 40.28e9 FLOP per item slot / 2.5e15",
-                         "executed_gemm_flops_frac": fl.value / elapsed_ev / MFMA_PEAK,
                          # bytes per launch of the dominant kernel at the L2's memory side: NOT measured by this run (PMC counters
                          # cannot be read from inside it) but read from the committed summary of two rocprofv3 --pmc passes of this
                          # command with this configuration; null for any other configuration
-                         "traffic": traffic, "traffic_source": "profiles/pmc_traffic.json (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, corrected per MI355X_MICROARCH.md; per gemm16 launch)" if traffic is not None else None,
-                         # the dominant kernel class, measured live with HIP events on the launching stream around every launch
-                         "dominant_kernel": {
-                             "kernel": "gemm16 (gemm16_h256_kernel: QKV/O/FC1/FC2 GEMMs of the frozen encoders"
-                                       "; flops = executed, by launch)",
-                             "bound": "mfma", "achieved": gemm_tflops, "peak": MFMA_PEAK / 1e12, "unit": "TFLOP/s",
-                             "frac": gemm_tflops / (MFMA_PEAK / 1e12),
-                             "launches": int(n_launch), "avg_launch_ms": ms.value / max(n_launch, 1),
-                             "flop_per_launch": fl.value / max(n_launch, 1),
-                             "ms_per_step": ms.value / max(steps, 1),
-                             "measured_in": f"a second pass of the same {steps} steps, towers back to back on one stream, HIP events around every launch ({elapsed_ev / steps * 1e3:.3f} ms per step that way)",
-                             "traffic": traffic, "traffic_algorithmic": lib.iisan_timing_last_bytes() / max(n_launch, 1)}},
+                         "traffic": traffic, "traffic_source": "profiles/pmc_traffic.json (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, corrected per MI355X_MICROARCH.md; per gemm16 launch)" if traffic is not None else None},
         }
+        if instrumented:
+            ms, fl = C.c_double(0), C.c_double(0)
+            n_launch = lib.iisan_timing_collect(C.byref(ms), C.byref(fl)) if self.rank == 0 else 0
+            gemm_tflops = fl.value / (ms.value * 1e-3) / 1e12 if ms.value > 0 else 0.0
+            out["roofline"]["executed_gemm_flops_frac"] = fl.value / elapsed_ev / MFMA_PEAK
+            # the dominant kernel class, measured live with HIP events on the launching stream around every launch
+            out["roofline"]["dominant_kernel"] = {
+                "kernel": "gemm16 (gemm16_h256_kernel: QKV/O/FC1/FC2 GEMMs of the frozen encoders"
+                          "; flops = executed, by launch)",
+                "bound": "mfma", "achieved": gemm_tflops, "peak": MFMA_PEAK / 1e12, "unit": "TFLOP/s",
+                "frac": gemm_tflops / (MFMA_PEAK / 1e12),
+                "launches": int(n_launch), "avg_launch_ms": ms.value / max(n_launch, 1),
+                "flop_per_launch": fl.value / max(n_launch, 1),
+                "ms_per_step": ms.value / max(steps, 1),
+                "measured_in": f"a second pass of the same {steps} steps, towers back to back on one stream, HIP events around every launch ({elapsed_ev / steps * 1e3:.3f} ms per step that way)",
+                "traffic": traffic, "traffic_algorithmic": lib.iisan_timing_last_bytes() / max(n_launch, 1)}
+        return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -700,15 +748,15 @@ def main():
         out = cached_line(a, lib, dev, rank, world, a.steps, a.warmup)
     else:
         unc = Uncached(a, lib, dev, rank, world)
-        check = unc.kernel_family_check() if (world == 1 and a.bs >= 64 and not a.dedup and not a.no_check) else None
-        out = unc.line(a.steps, a.warmup, a.dtype, a.full_blocks)
+        check = unc.kernel_family_check() if (a.full and world == 1 and a.bs >= 64 and not a.dedup and not a.no_check) else None
+        out = unc.line(a.steps, a.warmup, a.dtype, a.full_blocks, instrumented=a.full, dump=a.dump_outputs)
         if check:
             out["config"]["kernel_family_check"] = check
         default = (world == 1 and a.bs == 128 and a.dtype == "fp16" and a.full_blocks and not a.dedup
                    and a.overlap_towers and a.chunk == 0)
-        if default and not a.no_secondary:
+        if a.full and default and not a.no_secondary:
             out["secondary"] = secondary_lines(a, unc, lib, dev, rank, world)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
     if _lib.dev_knobs():                 # a run with re-routed kernels must say so in its own line
         out.setdefault("config", {})["dev_knobs"] = _lib.dev_knobs()

@@ -8,6 +8,7 @@ Reference behaviour being matched: DDP (`Code_Uncached/run.py:287`) = parameters
 averaged over ranks, every rank applies the same Adam step (`run.py:413`); `DistributedSampler` shards (`run.py:146,395`)
 stay rank-local as negatives (`model.py:86`)."""
 import os
+import shutil
 import socket
 import subprocess
 import sys
@@ -127,7 +128,7 @@ def test_two_ranks_two_gpus_rccl():
 
 
 def test_bench_launches_its_own_ranks():
-    """`python bench.py --gpus 2` outside a rank environment (it used to exit non-zero): the script starts two
+    """`python bench.py --gpus 2 --full` outside a rank environment (it used to exit non-zero): the script starts two
     fresh ranks through torch.distributed.run before touching the GPU, runs warm-up + timed steps of the product DP step
     (barrier + sync on both sides, MAX over ranks, one gradient all-reduce per step) and rank 0 prints one JSON line.  On
     this single-GPU box both ranks share cuda:0 and the collectives go through gloo (env test hook of bench.py)."""
@@ -136,8 +137,9 @@ def test_bench_launches_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     root = os.path.dirname(HERE)
+    dump = tempfile.mkdtemp(prefix="iisan_bench_dump_")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--bs", "16",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--dump-outputs", dump], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -152,3 +154,10 @@ def test_bench_launches_its_own_ranks():
     assert len(di["allreduce_ms_per_step"]) == 2 and all(t > 0 for t in di["allreduce_ms_per_step"])
     assert "16." in di["collective"] and "all-reduce" in di["collective"]
     assert d["value"] > 0 and d["ms_per_step"] > 0 and "cpu_baseline" not in d and "secondary" not in d
+    # --dump-outputs: rank 0 writes the last timed step's loss, updated trainables and their gradients (fp32)
+    import numpy as np
+    out = {n: np.load(os.path.join(dump, n + ".npy")) for n in ("loss", "params", "grads")}
+    assert all(v.dtype == np.float32 for v in out.values())
+    assert out["loss"].shape == (1,) and out["loss"][0] == np.float32(d["config"]["loss"])
+    assert out["params"].shape == out["grads"].shape and np.isfinite(out["params"]).all() and np.isfinite(out["grads"]).all()
+    shutil.rmtree(dump)

@@ -242,6 +242,7 @@ def test_bench_starts_its_own_ranks_and_describes_the_host():
     exit non-zero), with the rendezvous on 127.0.0.1 and its own arguments passed through."""
     import importlib.util
     import sys
+    import pytest
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(gio.GOLDEN.rstrip("/")), "..", "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
@@ -253,6 +254,10 @@ def test_bench_starts_its_own_ranks_and_describes_the_host():
     i = cmd.index(os.path.abspath(bench.__file__))
     assert cmd[i + 1:] == ["--gpus", "8", "--steps", "4", "--warmup", "1"]
     assert bench.parse([]).bs == 128 and bench.parse(["--cached", "fp32"]).bs == 1024 and bench.parse(["--cached", "fp16", "--versa"]).bs == 128
+    assert not bench.parse([]).full and bench.parse(["--full"]).full and bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    for other in (["--eval"], ["--cached", "fp32"]):          # --dump-outputs writes the headline path's outputs only
+        with pytest.raises(SystemExit):
+            bench.parse(["--dump-outputs", "d"] + other)
     cores, model = bench.host_cpu()
     assert 1 <= cores <= (os.cpu_count() or 1) and isinstance(model, str) and model
 

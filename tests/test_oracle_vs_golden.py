@@ -19,6 +19,21 @@ def _close(a, b, rtol, atol, what):
     assert err <= atol + rtol * ref, f"{what}: max|err| {err:.3e} vs scale {ref:.3e}"
 
 
+def _grads_by_tower(names):
+    """Parameter names grouped for a gradient comparison: ([name], name) for a tensor, ([gate names], tower) for the one-scalar
+    gate gradients of a tower, joined into the one vector they form.  A gate gradient is a sum of cancelling
+    <dF, tap_cv - tap_text> products: its fp32 value moves with the CPU's summation order by more than a per-scalar tolerance
+    (the reference's own fp32 value of `side_gate_params_mm.1` [gelu] is off a float64 evaluation of the same formula by 1.3x
+    that tolerance), so it is held to the tolerance of its tower's gate vector, as in tests/test_gpu_trainable.py."""
+    out, gates = [], {}
+    for n in names:
+        if "side_gate" in n:
+            gates.setdefault(n.rsplit(".", 1)[0], []).append(n)
+        else:
+            out.append(([n], n))
+    return out + [(ns, tower) for tower, ns in gates.items()]
+
+
 def test_encoders_full_taps_match_reference():
     z, vw, bw, b = gio.encoders_full_inputs()
     torch.set_num_threads(8)
@@ -45,24 +60,25 @@ def test_sidenet_sasrec_loss_and_grads_match_reference(variant):
         _close(aux[k].detach(), z[pre + k], 1e-5, 1e-5, f"{variant}:{k}")
     _close(loss.detach(), z[pre + "loss"], 1e-5, 0, f"{variant}:loss")
     loss.backward()
-    for n, p in P.items():
-        g = gio.sample_like_golden(p.grad)
-        _close(g, z[pre + "g/" + n], 2e-4, 1e-7, f"{variant}:grad {n}")
-        gn = z[pre + "gn/" + n]
-        assert abs(float(p.grad.double().norm()) - gn[0]) <= 2e-4 * gn[0] + 1e-7, n
+    for ns, what in _grads_by_tower(P):
+        g = np.concatenate([gio.sample_like_golden(P[n].grad) for n in ns])
+        _close(g, np.concatenate([z[pre + "g/" + n] for n in ns]), 2e-4, 1e-7, f"{variant}:grad {what}")
+        gn = float(np.sqrt(sum(z[pre + "gn/" + n][0] ** 2 for n in ns)))
+        norm = float(torch.cat([P[n].grad.double().reshape(-1) for n in ns]).norm())
+        assert abs(norm - gn) <= 2e-4 * gn + 1e-7, what
 
 
 def test_adam_step_matches_reference():
+    """The first Adam step of the five groups on the reference's own gradients (stored at the same elements as its step): a
+    first step is lr * g / (|g| + eps), which turns the last fp32 bits of a gradient near eps into 1e-3 of lr, so the oracle's
+    recomputed gradients (pinned by test_sidenet_sasrec_loss_and_grads_match_reference) would test the CPU's summation order."""
     z, b, taps_cv, taps_tx, P, kw = gio.sidenet_full_inputs("default")
-    P = {k: v.clone().requires_grad_(True) for k, v in P.items()}
-    layers = O.side_layer_list("1,3,5,7,9,11", False)
-    loss, _ = O.model_loss_from_taps(b.ids, taps_cv, taps_tx, b.log_mask, b.pop_prob, P, layers,
-                                     cv_head="mm_encoder.cv_pre_fc.", text_head="mm_encoder.bert_pre_fc.")
-    loss.backward()
     lrs = dict(recsys=2e-4, adapter_cv=1e-4, adapter_text=1e-4, image_net=1e-4, text_encoder=5e-5)
     for n, p in P.items():
-        new, _, _ = O.adam_step(p.detach(), p.grad, torch.zeros_like(p), torch.zeros_like(p), 1, lrs[O.adam_group_of(n)])
-        _close(gio.sample_like_golden(new - p.detach()), z["default/adam/" + n], 1e-3, 1e-9, f"adam delta {n}")
+        p = torch.from_numpy(gio.sample_like_golden(p))
+        g = torch.from_numpy(z["default/g/" + n])
+        new, _, _ = O.adam_step(p, g, torch.zeros_like(p), torch.zeros_like(p), 1, lrs[O.adam_group_of(n)])
+        _close(new - p, z["default/adam/" + n], 1e-3, 1e-9, f"adam delta {n}")
 
 
 def test_adam_groups_match_reference_rule():
@@ -113,11 +129,12 @@ def test_modality_inter_matches_reference():
     loss.backward()
     n_checked = 0
     for n, p in P.items():
-        if "g/" + n in z.files:
-            _close(gio.sample_like_golden(p.grad), z["g/" + n], 5e-4, 1e-7, f"grad {n}")
-            n_checked += 1
-        else:
+        if "g/" + n not in z.files:
             assert p.grad is None and ("classifier" in n or "title.fc" in n), n
+    for ns, what in _grads_by_tower(n for n in P if "g/" + n in z.files):
+        _close(np.concatenate([gio.sample_like_golden(P[n].grad) for n in ns]), np.concatenate([z["g/" + n] for n in ns]),
+               5e-4, 1e-7, f"grad {what}")
+        n_checked += len(ns)
     assert n_checked == len(P) - 4
     with pytest.raises(NotImplementedError):
         O.model_loss_from_taps(b.ids, taps_cv, taps_tx, b.log_mask, b.pop_prob, P, O.side_layer_list("0,1", False), modality="intra")

@@ -37,7 +37,7 @@ for cfg, (out, title) in titles.items():
         hdr += "\n" + note
     open(os.path.join(prof, f"{tag}_{out}_kernel_stats.md"), "w").write(hdr + "\n\n" + rd(f"{cfg}_kernel_stats.md"))
 
-cmd = f"rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-check --no-overlap-towers (two passes, round {R} code, tools/evidence_{tag}.sh {tag} pmc)"
+cmd = f"rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-secondary --no-check --no-overlap-towers (two passes, round {R} code, tools/evidence_{tag}.sh {tag} pmc)"
 parts = [f"# Round {R} — memory-side traffic (rocprofv3 PMC, 1 x MI355X)\n\nTwo passes per configuration (`FETCH_SIZE` and `WRITE_SIZE` do not fit the TCC counter slots of one pass on gfx950), counters only beside "
          f"`--kernel-trace` (`tools/evidence_{tag}.sh {tag} pmc`, summarised by `tools/pmc_traffic.py`; bytes = 2 x FETCH_SIZE + WRITE_SIZE, the gfx950 correction of MI355X_MICROARCH.md):\n\n    {cmd}\n"]
 for name, what in (("pmc_head_gemm16.md", "headline: the encoder GEMM launches (`roofline.traffic` of the bench line)"), ("pmc_head_attn.md", "headline: attention"),

@@ -6,8 +6,8 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 out=gpurun_out/ev_$tag
 mkdir -p $out
-HEAD="--steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-check"
-HEAD2="--steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-check"
+HEAD="--steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary --no-check"
+HEAD2="--steps 2 --warmup 1 --full --no-cpu-baseline --no-secondary --no-check"
 C3="--cached fp32 --bs 1024 --no-cpu-baseline"
 C5="--cached fp16 --versa --bs 128 --no-cpu-baseline"
 EV="--eval"

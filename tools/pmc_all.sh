@@ -11,7 +11,7 @@ pass() {   # name counter bench-args...
   rocprofv3 --pmc $ctr --kernel-trace -d $out/${name}_$ctr -o p -- python3 bench.py "$@" > $out/${name}_$ctr.log 2>&1
   find $out/${name}_$ctr -name "*.db" | head -1
 }
-HEAD="--steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-check"
+HEAD="--steps 2 --warmup 1 --full --no-cpu-baseline --no-secondary --no-check"
 f=$(pass head FETCH_SIZE $HEAD); w=$(pass head WRITE_SIZE $HEAD)
 python3 tools/pmc_traffic.py $f $w gemm16 > $out/head.md 2>&1
 python3 tools/pmc_traffic.py $f $w layernorm768 > $out/head_ln.md 2>&1

@@ -2,8 +2,8 @@
 """HBM-side traffic per launch from two rocprofv3 PMC passes of the same command (FETCH_SIZE and WRITE_SIZE do not fit
 one pass on gfx950: MI355X_MICROARCH.md, "rocprofv3 PMC slots"):
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace -d A -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace -d B -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace -d A -o p -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace -d B -o p -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline
     python tools/pmc_traffic.py A/p_results.db B/p_results.db [kernel-substring]
 
 The launch order is deterministic, so the i-th dispatch of a kernel in one pass is the i-th in the other.  Units: both
