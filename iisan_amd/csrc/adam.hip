@@ -38,9 +38,16 @@ extern "C" int iisan_adam_step(float* p, const float* g, float* m, float* v, int
                                const float* seg_lr, int32_t n_seg, int32_t step, float beta1, float beta2, float eps,
                                float grad_scale, void* stream) {
     IISAN_CHECK_SHAPE(n > 0 && n_seg >= 1 && n_seg <= 8 && step >= 1, "adam_step: bad arguments (n=%lld n_seg=%d step=%d)", (long long)n, n_seg, step);
+    // every element belongs to exactly one segment: ends non-decreasing (empty segments allowed), the last one at n.  An
+    // element past the last end would otherwise take the last rate, and one before a decreasing end its predecessor's.
+    IISAN_CHECK_SHAPE(seg_end != nullptr && seg_lr != nullptr, "adam_step: seg_end / seg_lr must not be NULL");
+    IISAN_CHECK_SHAPE(seg_end[n_seg - 1] == n, "adam_step: seg_end[n_seg-1]=%lld must equal n=%lld", (long long)seg_end[n_seg - 1],
+                      (long long)n);
     Segs s{};
     s.n = n_seg;
     for (int i = 0; i < n_seg; ++i) {
+        IISAN_CHECK_SHAPE(seg_end[i] >= (i ? seg_end[i - 1] : 0), "adam_step: seg_end must be non-decreasing from 0 (seg_end[%d]=%lld)", i,
+                          (long long)seg_end[i]);
         s.end[i] = seg_end[i];
         s.lr[i] = seg_lr[i];
     }

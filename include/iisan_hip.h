@@ -262,7 +262,9 @@ int iisan_score_topk(const float* prec, const float* item_emb, int64_t U, int64_
 
 /* ------------------------------------------------------------------------------------------------------------
  * Fused Adam over a flat fp32 parameter buffer with per-segment learning rates (torch.optim.Adam defaults, the
- * optimiser of Code_Uncached/run.py:323-336).  seg_end (host, int64[n_seg]) are exclusive end offsets.
+ * optimiser of Code_Uncached/run.py:323-336).  seg_end (host, int64[n_seg]) are exclusive end offsets: element i takes
+ * seg_lr[s] for the first s with i < seg_end[s].  IISAN_EBADSHAPE unless n > 0, 1 <= n_seg <= 8, step >= 1, seg_end is
+ * non-decreasing from 0 (empty segments allowed) and seg_end[n_seg-1] == n, so that every element has exactly one segment.
  * ---------------------------------------------------------------------------------------------------------- */
 int iisan_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end,
                     const float* seg_lr, int32_t n_seg, int32_t step, float beta1, float beta2, float eps,
