@@ -254,6 +254,22 @@ bool iisan_timing_on(hipStream_t s);   // class 1 (gemm16) enabled for launches 
 int iisan_timing_class();       // 0 = off, 1 = gemm16, 2 = the gemm32.hip family
 void iisan_timing_pre(hipStream_t s, double flops, double bytes);
 void iisan_timing_post(hipStream_t s);
+// The bracket of one timed launcher: opened here, closed on every exit of the scope.  Class 1 = launch_gemm16 (with the stream filter
+// of iisan_timing_on), class 2 = the gemm32.hip launchers; a class-2 launcher that re-enters another (split-K through the scratch
+// buffer) is timed once, as the caller sees it: product + reducer together.
+inline thread_local int iisan_timing_depth = 0;
+struct TimedLaunch {
+    hipStream_t s; int cls; bool on;
+    TimedLaunch(int cls_, hipStream_t s_, double flops, double bytes)
+        : s(s_), cls(cls_), on(cls_ == 1 ? iisan_timing_on(s_) : iisan_timing_class() == 2 && iisan_timing_depth == 0) {
+        if (cls == 2) ++iisan_timing_depth;
+        if (on) iisan_timing_pre(s, flops, bytes);
+    }
+    ~TimedLaunch() {
+        if (cls == 2) --iisan_timing_depth;
+        if (on) iisan_timing_post(s);
+    }
+};
 
 // internal launchers shared between translation units -----------------------------------------------------------
 struct Gemm16Args {
@@ -295,8 +311,16 @@ enum { EPI_OUT16 = 0, EPI_GELU16 = 1, EPI_RESID32 = 2, EPI_PATCH32 = 3, EPI_QKVH
 // EPI_QKVH16: 16-bit output scattered head-major, out[item][head][q|k|v][token][64] (item = m / S): every (item, head)
 // slice the attention kernel streams is then one contiguous block instead of 128-byte pieces at a 4.6 KB stride.
 int launch_gemm16(int dtype16, int mode, const Gemm16Args& a, hipStream_t s);
-bool gemm16_runs_h256(int dtype16, int mode, const Gemm16Args& a);       // gemm16.hip: would this product run on gemm16_h256 (EPI_STREAM16 exists only there)?
-bool gemm16_takes_rowstat(int dtype16, int mode, const Gemm16Args& a);   // gemm16.hip: would this product run on the kernel that applies LayerNorm in its epilogue?
+// gemm16.hip: the kernel family launch_gemm16 runs this product on under the current gemm16_variant — the whole decision, the shape checks
+// included; no device is touched.  G16_REJECTED: no kernel takes it (iisan_set_error has the reason; launch_gemm16: IISAN_EBADSHAPE).  The encoder
+// executors ask BEFORE they choose a LayerNorm strategy: LayerNorm in the epilogue (Gemm16Args::rowstat) and EPI_STREAM16 exist on G16_H256 only.
+enum { G16_REJECTED = -1, G16_V1 = 0, G16_S256 = 1, G16_H256 = 2 };
+int gemm16_route(int dtype16, int mode, const Gemm16Args& a);
+bool gemm16_s256_applicable(int mode, const Gemm16Args& a);      // gemm16_s256.hip
+int launch_gemm16_s256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s);
+bool gemm16_h256_applicable(int mode, const Gemm16Args& a);      // gemm16_h256.hip
+int launch_gemm16_h256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s);
+int launch_gemm16_f32(const Gemm16Args& a, int ksplit, hipStream_t s);      // gemm16.hip: fp32 output of the 128x128 kernel (split.hip)
 int launch_layernorm768(int dtype16, const float* x, const float* g, const float* b, float eps, void* out16,
                         float* out32, int64_t rows, hipStream_t s);
 // x (+ delta16) -> [sum32 = x + delta] -> LayerNorm -> out16 / out32 (any output may be null; g == null: no LayerNorm)
@@ -332,6 +356,14 @@ int launch_attention16(int dtype16, const void* qkv, const float* key_bias, void
 // CLS query only: ctx_cls [items, heads*64] (last executed encoder block)
 int launch_attention_cls16(int dtype16, const void* qkv, const float* key_bias, void* ctx_cls, int64_t items, int S,
                            int heads, hipStream_t s, const void* q_cls = nullptr);   // q_cls: [items, heads*64] 16-bit CLS queries
+// embedding and tap steps of the encoder executors (rowops.hip)
+int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64_t M, int C, int R, int p, hipStream_t s);
+int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M, int T, int D, hipStream_t s);
+int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, const float* pos, const float* type0,
+                         const float* g, const float* b, float eps, float* X, void* H, float* key_bias, int64_t M,
+                         int W, int vocab, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
+int launch_gather_cls(const float* X, float* taps, int64_t M, int T, int D, int n_taps, int k, hipStream_t s);
+int launch_gather_rows16(const void* H, void* out, int64_t M, int T, int D, hipStream_t s);   // out[m] = H[m*T] (16-bit rows)
 
 // split-operand fp32 GEMM on the 16-bit matrix cores (split.hip); same problem description and TA/TB/ACCUM flags as gemm32
 struct Gemm32Prob;
@@ -342,6 +374,8 @@ int launch_gemm_x3(const Gemm32Prob& p, int flags, void* ws, size_t ws_bytes, hi
 size_t gemm_x3_group_ws_bytes(const int64_t* M, const int64_t* N, const int64_t* K, int n);
 int launch_gemm_x3_group(const Gemm32Prob* probs, int n, int flags, void* ws, size_t ws_bytes, hipStream_t s);
 int gemm_x3_group_max();          // products per group (dev knob x3_group)
+double gemm_x3_get_min_flops();   // split.hip: products below this many FLOPs stay on the f32 matrix cores
+void gemm_x3_set_min_flops(double f);     // negative = the library default (split.hip: X3_DEFAULT_MIN_FLOPS, 4 GFLOP)
 
 // split-operand GEMM on shared planes (gemm16_x3.hip): images A2 [Mpad, 2 kp] = [hi | lo], B2 [Npad, 2 kp]; out fp32 = (Ah Bh^T + Ah Bl^T + Al Bh^T) * inv_a * inv_b
 // (+ bias) (+ resid), or raw split-K partials at out + y * split_stride; lo_a / lo_b: device flags "the lo plane has a non-zero element"
@@ -354,6 +388,7 @@ struct X3pArgs {
     int64_t split_stride;
 };
 int launch_gemm16_x3p(const X3pArgs& a, int ksplit, hipStream_t s);
+int x3p_tile_n(int64_t M, int64_t N);          // gemm16_x3.hip: 128 or 192 columns per tile
 
 // amax of up to 16 tensors in one launch (split.hip): x row-major [rows, cols] with leading dimension ld; out = the caller's zeroed amax slot
 struct AmaxBatch { const float* x[16]; int64_t rows[16], cols[16], ld[16]; uint32_t* out[16]; };
@@ -413,3 +448,31 @@ enum {
     G32_DROPOUT = 256, // scale by the dropout keep factor before the residual add  // also store the pre-activation into act_src (as float* out) -- fwd of GELU adapters
 };
 int launch_gemm32(const Gemm32Prob* probs, int nprob, int flags, hipStream_t s);
+// out[i][n] += sum_m X[i][m][n] for up to 4 problems in one launch (gemm32.hip): the bias gradients
+int launch_colsum(const float* const* X, float* const* out, const int64_t* M, const int32_t* N, const int32_t* ld,
+                  int nprob, hipStream_t s);
+
+// fused SANB step (sanb.hip): one tower of one launch, as plain pointers (the executor of sidenet.hip fills it)
+struct SanbTowerDesc {
+    const float* a; const float* b; const float* prev; int64_t lda, ldb, ldp; const float* gate; int32_t D, type;
+    const float* Wd; const float* bd; const float* Wu; const float* bu;
+    float* F; float* U; float* A; float* O;
+    const float* dO; const float* Upre; float* dU; float* dprev; float* da; float* db; float* dgate; float* dbu; float* dbd;
+};
+bool sanb_fused_ok(int D, int down);
+int launch_sanb_fwd(const SanbTowerDesc* towers, int n, int64_t M, int gelu, hipStream_t s);
+int launch_sanb_bwd(const SanbTowerDesc* towers, int n, int64_t M, int gelu, hipStream_t s);
+int launch_sanb_transpose(const float* const* in, float* const* out, const int32_t* rows, const int32_t* cols, int n, hipStream_t s);
+
+// one-launch SASRec forward / backward for the production shape (sasrec_fused.hip); works on the workspace slots sasrec.hip carves
+struct SasFusedPtrs {
+    float* Z0; float* X0;
+    float* Q[8]; float* K[8]; float* V[8]; float* P[8]; float* C[8]; float* Zattn[8]; float* X1[8]; float* Hf[8]; float* Zffn[8]; float* X2[8];
+};
+bool sasrec_fused_ok(const iisan_sasrec_cfg* cfg);
+bool sasrec_fused_shape_ok(const iisan_sasrec_cfg* cfg);
+int launch_sasrec_fused_fwd(const iisan_sasrec_cfg* cfg, const float* x, const float* log_mask, int64_t B, const void* const* params,
+                            float* y, const SasFusedPtrs& w, hipStream_t s);
+int64_t sasrec_fused_slab_floats(const iisan_sasrec_cfg* cfg, int64_t B);
+int launch_sasrec_fused_bwd(const iisan_sasrec_cfg* cfg, const float* log_mask, int64_t B, const void* const* params, const float* dy,
+                            float* dx, void* const* grads, const SasFusedPtrs& w, float* slab, hipStream_t s);

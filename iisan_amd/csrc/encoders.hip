@@ -5,14 +5,6 @@
 // Code_Cached/preprocess_vectors.py:68-112 precomputes.
 #include "common.h"
 
-int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64_t M, int C, int R, int p, hipStream_t s);
-int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M, int T, int D, hipStream_t s);
-int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, const float* pos, const float* type0,
-                         const float* g, const float* b, float eps, float* X, void* H, float* key_bias, int64_t M,
-                         int W, int vocab, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
-int launch_gather_cls(const float* X, float* taps, int64_t M, int T, int D, int n_taps, int k, hipStream_t s);
-int launch_gather_rows16(const void* H, void* out, int64_t M, int T, int D, hipStream_t s);   // out[m] = H[m*T] (16-bit rows)
-
 namespace {
 
 struct EncBufs {
@@ -186,22 +178,190 @@ extern "C" size_t iisan_vit_forward_taps_ws_bytes(const iisan_vit_weights* w, in
     return carve(c, b, Mc * (P + 1), Mc, w->hidden, w->mlp > pd ? w->mlp : pd, 0, vit_fold_layers(w), w->folded == nullptr);
 }
 
-static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images, int img_u8, int64_t M,
-                                 const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
-                                 void* ws, size_t ws_bytes, void* stream);
+namespace {
 
-extern "C" int iisan_vit_forward_taps(const iisan_vit_weights* w, const float* images, int64_t M,
-                                      const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
-                                      void* ws, size_t ws_bytes, void* stream) {
-    return vit_forward_taps_impl(w, images, 0, M, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream);
+// How one call carries the residual stream of the pre-LN tower; decided once per call (vit_strategy).  Each strategy is three steps of
+// VitChunk, every one a complete launch list: `open` (the stream becomes hidden state l; LN1), a full block, `close` (the last hidden
+// state, when it is tapped).
+enum VitStrategy {
+    VS_RESID32,     // dev knob resid32: the whole stream fp32 in X, LayerNorm images in H
+    VS_IMAGE,       // mixed stream (fp16 rows in X16, fp32 CLS rows in Xc), LayerNorm images in H: ln_fold = 0, bf16 operands, small batches
+    VS_FOLD,        // mixed stream, no image: the add kernels leave rstd per row, the QKV / FC1 products apply LayerNorm (ln_fold = 1)
+    VS_STREAM,      // ... and no add kernels: the O / FC2 products add into the stream in their epilogues (ln_fold = 2, the product route)
+};
+
+// LayerNorm in the epilogues of the QKV / FC1 products (g_ln_fold) only where those products run on the kernel that has it, and the
+// residual adds in the epilogues of the O / FC2 products likewise — for every chunk size of this call (the last chunk may be shorter)
+VitStrategy vit_strategy(const iisan_vit_weights* w, const EncBufs& b, int live, bool full_blocks, int64_t M, int64_t Mc, int T) {
+    if (g_resid32) return VS_RESID32;
+    if (!b.Wf || live == 0) return VS_IMAGE;
+    const int dt = w->dtype16, D = w->hidden, F = w->mlp;
+    bool fold = true, stream = g_ln_fold >= 2;
+    for (int64_t mc : {Mc, M % Mc == 0 ? Mc : M % Mc}) {
+        const int64_t tok = mc * T;
+        auto h256 = [&](int mode, const Gemm16Args& a) { return gemm16_route(dt, mode, a) == G16_H256; };
+        fold = fold && h256(EPI_QKVH16, gemm_args(EPI_QKVH16, nullptr, D, nullptr, nullptr, nullptr, 3 * D, tok, T, w->heads, 0, b.RS)) &&
+               h256(EPI_GELU16, gemm_args(EPI_GELU16, nullptr, D, nullptr, nullptr, nullptr, F, tok, 0, 0, 0, b.RS)) &&
+               (full_blocks || h256(EPI_QKVH16, gemm_args(EPI_QKVH16, nullptr, D, nullptr, nullptr, nullptr, 2 * D, tok, T, w->heads, 1, b.RS)));
+        Gemm16Args o = gemm_args(EPI_STREAM16, nullptr, D, nullptr, nullptr, nullptr, D, tok, T), f = gemm_args(EPI_STREAM16, nullptr, F, nullptr, nullptr, nullptr, D, tok, T);
+        o.rowpart = f.rowpart = b.RP;
+        stream = stream && h256(EPI_STREAM16, o) && h256(EPI_STREAM16, f);
+    }
+    return !fold ? VS_IMAGE : stream ? VS_STREAM : VS_FOLD;
 }
 
-extern "C" int iisan_vit_forward_taps_u8(const iisan_vit_weights* w, const uint8_t* images, int64_t M,
-                                         const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
-                                         void* ws, size_t ws_bytes, void* stream) {
-    IISAN_CHECK_SHAPE(w->image % 8 == 0, "vit u8: image side %d must be a multiple of 8", w->image);
-    return vit_forward_taps_impl(w, images, 1, M, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream);
-}
+constexpr int MX_ADD_STAT = MX_D1 | MX_RESV | MX_STAT;       // x += d (fp16 stream, fp32 CLS rows); row statistics
+
+// One chunk of a ViT forward: mc items, tok = mc * T token rows, tp = their rows of the tap tensor.
+// The O / FC2 products of resid32 / image / fold emit 16-bit DELTAS (dO in D16, dF in D16b); the residual add is fused into a later
+// LayerNorm kernel (HBM-bound) instead of a read-modify-write GEMM epilogue.  Pre-LN tower, resid32 / image: LN2 computes LN(x + dO)
+// WITHOUT writing x back; the next open step adds both deltas, (x + dO) + dF in fp32 — the same value — and writes x once per block
+// instead of twice.
+struct VitChunk {
+    const iisan_vit_weights* w; const EncBufs& b; VitStrategy st; hipStream_t s;
+    int dt, D, F, T, heads; float eps;
+    int64_t mc, tok; float* tp; int n_taps;
+
+    bool mixed() const { return st != VS_RESID32; }
+    const iisan_layer_weights& layer(int l) const { return w->layer[l]; }
+    // the folded set of layer l (vit_fold_all)
+    char* Wf_qkv(int l) const { return (char*)b.Wf + (size_t)l * (3 * D + F) * D * 2; }
+    char* Wf_fc1(int l) const { return Wf_qkv(l) + (size_t)3 * D * D * 2; }
+    float* bf_qkv(int l) const { return b.Bf + (size_t)l * (3 * D + F); }
+    float* bf_fc1(int l) const { return bf_qkv(l) + 3 * D; }
+
+    int embed(const void* img, int img_u8) const {
+        const int P = T - 1, pd = w->channels * w->patch * w->patch;
+        IISAN_TRY(launch_vit_im2col(dt, img, img_u8, b.F1, mc, w->channels, w->image, w->patch, s));
+        // patch embedding: resid32 = fp32 token rows with the position embedding added (128x128 kernel); mixed = 16-bit rows on the
+        // production GEMM (gemm16_h256, 0.40 against 0.59 ms at bs = 128), the position table is added by block 0's open step
+        if (mixed()) IISAN_TRY(gemm(dt, EPI_PATCH16, b.F1, pd, w->patch_w, w->patch_b, b.D16b, D, nullptr, mc * P, s, nullptr, P));
+        else IISAN_TRY(gemm(dt, EPI_PATCH32, b.F1, pd, w->patch_w, w->patch_b, b.X, D, nullptr, mc * P, s, w->pos_emb, P));
+        // CLS rows: cls + pos[0] — into the fp32 stream (token-major) or into the compact fp32 CLS stream
+        return launch_vit_cls_rows(mixed() ? b.Xc : b.X, w->cls_token, w->pos_emb, mc, mixed() ? 1 : T, D, s);
+    }
+    // the tapped rows of the current hidden state: CLS rows of X (stride T) or the compact CLS stream itself
+    int tap(int k) const { return mixed() ? launch_gather_cls(b.Xc, tp, mc, 1, D, n_taps, k, s) : launch_gather_cls(b.X, tp, mc, T, D, n_taps, k, s); }
+
+    // ---- VS_RESID32 ------------------------------------------------------------------------------------------------------------
+    int open_resid32(int l) const {     // x += dO + dF of block l - 1 ; h = LN1(x)
+        const iisan_layer_weights& L = layer(l);
+        if (l == 0) return launch_add2_layernorm768(dt, b.X, nullptr, nullptr, L.ln1_w, L.ln1_b, eps, nullptr, b.H, nullptr, tok, s);
+        return launch_add2_layernorm768(dt, b.X, b.D16, b.D16b, L.ln1_w, L.ln1_b, eps, b.X, b.H, nullptr, tok, s);
+    }
+    int full_resid32(int l) const {
+        const iisan_layer_weights& L = layer(l);
+        IISAN_TRY(gemm(dt, EPI_QKVH16, b.H, D, L.qkv_w, L.qkv_b, b.QKV, 3 * D, nullptr, tok, s, nullptr, 0, T, heads));
+        IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
+        IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
+        // h = LN2(x + dO)   (x itself is updated by the next open step)
+        IISAN_TRY(launch_add_layernorm768(dt, b.X, b.D16, L.ln2_w, L.ln2_b, eps, nullptr, b.H, nullptr, tok, s));
+        IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, tok, s));
+        return gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, nullptr, tok, s);
+    }
+    int close_resid32() const { return launch_add2_layernorm768(dt, b.X, b.D16, b.D16b, nullptr, nullptr, eps, b.X, nullptr, nullptr, tok, s); }
+
+    // ---- VS_IMAGE ----------------------------------------------------------------------------------------------------------------
+    int open_image(int l) const {
+        const iisan_layer_weights& L = layer(l);
+        if (l == 0)     // position table + 16-bit patch embedding -> fp16 stream of the patch rows (the CLS rows are in Xc already) + LN image
+            return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_LN, w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, L.ln1_w, L.ln1_b, eps, b.H, mc, T, s);
+        return launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_LN, nullptr, b.X16, b.Xc, b.D16, b.D16b, L.ln1_w, L.ln1_b, eps, b.H, mc, T, s);
+    }
+    int full_image(int l) const {
+        const iisan_layer_weights& L = layer(l);
+        IISAN_TRY(gemm(dt, EPI_QKVH16, b.H, D, L.qkv_w, L.qkv_b, b.QKV, 3 * D, nullptr, tok, s, nullptr, 0, T, heads));
+        IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
+        IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
+        // h = LN2(x + dO)   (x itself is updated by the next open step)
+        IISAN_TRY(launch_layernorm768_mixed(dt, MX_D1 | MX_LN, nullptr, b.X16, b.Xc, b.D16, nullptr, L.ln2_w, L.ln2_b, eps, b.H, mc, T, s));
+        IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, tok, s));
+        return gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, nullptr, tok, s);
+    }
+    // only the CLS rows of the last hidden state are consumed
+    int close_image() const { return launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, b.D16, b.D16b, nullptr, nullptr, eps, nullptr, mc, T, s); }
+
+    // ---- VS_FOLD: the stream + rstd per row; LN1 / LN2 are applied by the epilogues of the QKV / FC1 products -------------------------
+    int patches_to_stream() const {     // position table + 16-bit patch embedding -> fp16 stream of the patch rows (the CLS rows are in Xc already)
+        return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_ADD_STAT, w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s, b.RS);
+    }
+    int open_fold(int l) const {
+        if (l == 0) return patches_to_stream();
+        // x += dF of block l - 1 (x + dO is in the stream already: that block wrote it in its LN2 step)
+        return launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s, b.RS);
+    }
+    int full_fold(int l) const {
+        const iisan_layer_weights& L = layer(l);
+        IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l), bf_qkv(l), b.RS, b.QKV, 3 * D, tok, s, T, heads));
+        IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
+        IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
+        // x += dO (written: the FC1 product reads the stream); LN2 in the FC1 product's epilogue
+        IISAN_TRY(launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, b.D16, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s, b.RS));
+        IISAN_TRY(gemm_ln(dt, EPI_GELU16, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, s));
+        return gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, nullptr, tok, s);
+    }
+    // x + dO is in the stream: the CLS rows take dF
+    int close_fold() const { return launch_layernorm768_mixed(dt, MX_D1 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s); }
+
+    // ---- VS_STREAM: ... and the O / FC2 products add into the stream and leave its row statistics --------------------------------------
+    // x += A W^T + bias in the stream (fp16 rows in place, the CLS rows' fp32 stream through the finalize step); rstd of the new rows
+    int gemm_stream(const void* A, int K, const void* W, const float* bias) const {
+        Gemm16Args a = gemm_args(EPI_STREAM16, A, K, W, bias, b.X16, D, tok, T);
+        a.rowpart = b.RP;
+        IISAN_TRY(launch_gemm16(dt, EPI_STREAM16, a, s));
+        return launch_stream_stats_finalize(b.RP, D / 64, ceil_div(tok, 256) * 256, b.X16, b.Xc, b.RS, eps, mc, T, s);
+    }
+    int open_stream(int l) const {
+        if (l == 0) return patches_to_stream();
+        return IISAN_OK;        // the FC2 product of block l - 1 added into the stream and left its statistics
+    }
+    int full_stream(int l) const {
+        const iisan_layer_weights& L = layer(l);
+        IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l), bf_qkv(l), b.RS, b.QKV, 3 * D, tok, s, T, heads));
+        IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
+        IISAN_TRY(gemm_stream(b.H, D, L.o_w, L.o_b));
+        IISAN_TRY(gemm_ln(dt, EPI_GELU16, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, s));
+        return gemm_stream(b.F1, F, L.fc2_w, L.fc2_b);
+    }
+    int close_stream() const { return IISAN_OK; }       // the stream is the last hidden state already
+
+    // ---- the last LIVE block when later blocks are dead code: only the CLS token's output is consumed.  K/V are computed for every token,
+    // but attention, O, LN2, FC1, FC2 and the closing residual add run on one row per item; its output goes to tap k
+    int cls_block(int l, int k) const {
+        const iisan_layer_weights& L = layer(l);
+        // CLS rows only: compact [mc, D] 16-bit views in their own scratch
+        void* Hc = b.Cls;
+        void* Qc = (char*)b.Cls + (size_t)b.Mcp * D * 2;
+        if (st == VS_FOLD || st == VS_STREAM) {
+            // K / V of every token from the stream (LN1 in the epilogue); the CLS rows' LN1 image from their fp32 stream
+            IISAN_TRY(launch_layernorm768(dt, b.Xc, L.ln1_w, L.ln1_b, eps, Hc, nullptr, mc, s));
+            IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l) + (size_t)D * D * 2, bf_qkv(l) + D, b.RS, b.QKV, 2 * D, tok, s, T, heads, 1));
+            IISAN_TRY(gemm(dt, EPI_OUT16, Hc, D, L.qkv_w, L.qkv_b, Qc, D, nullptr, mc, s));
+        } else {
+            IISAN_TRY(launch_gather_rows16(b.H, Hc, mc, T, D, s));            // CLS rows of LN1(x)
+            IISAN_TRY(kv_all_q_cls(dt, L, b.H, b.QKV, Hc, Qc, tok, mc, T, heads, D, s));
+        }
+        IISAN_TRY(launch_attention_cls16(dt, b.QKV, nullptr, b.H, mc, T, heads, s, Qc));
+        float* Xc = (float*)b.QKV;      // free once the CLS attention has run (stream order)
+        IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, mc, s));
+        if (mixed()) IISAN_TRY(launch_gather_cls(b.Xc, Xc, mc, 1, D, 1, 0, s)); else IISAN_TRY(launch_gather_cls(b.X, Xc, mc, T, D, 1, 0, s));
+        IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, eps, Xc, b.H, nullptr, mc, s));
+        IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, mc, s));
+        IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, nullptr, mc, s));
+        IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, nullptr, nullptr, eps, Xc, nullptr, nullptr, mc, s));
+        return launch_gather_cls(Xc, tp, mc, 1, D, n_taps, k, s);     // hidden state `live` (before any final LayerNorm)
+    }
+};
+
+// the three steps of every strategy, indexed by VitStrategy
+const struct { int (VitChunk::*open)(int) const; int (VitChunk::*full)(int) const; int (VitChunk::*close)() const; } VIT_STEPS[] = {
+    {&VitChunk::open_resid32, &VitChunk::full_resid32, &VitChunk::close_resid32},
+    {&VitChunk::open_image, &VitChunk::full_image, &VitChunk::close_image},
+    {&VitChunk::open_fold, &VitChunk::full_fold, &VitChunk::close_fold},
+    {&VitChunk::open_stream, &VitChunk::full_stream, &VitChunk::close_stream},
+};
+
+}  // namespace
 
 static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images, int img_u8, int64_t M,
                                  const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
@@ -226,156 +386,46 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
         iisan_set_error("vit_forward_taps: workspace too small (%zu < %zu)", ws_bytes, c.off);
         return IISAN_EWORKSPACE;
     }
-    const int dt = w->dtype16;
     const bool full_blocks = g_full_blocks || w->full_blocks;
+    // Blocks after the deepest tapped hidden state are dead code (Versa configurations tap a prefix of the tower)
     const int live = full_blocks ? w->layers : max_tap(tap_layers, n_taps);
-    // LayerNorm in the epilogues of the QKV / FC1 products (g_ln_fold): only where those products run on the kernel that has it, for
-    // every chunk size of this call (the last chunk may be shorter)
-    bool lna = b.Wf != nullptr && live > 0;
-    for (int64_t mc : {Mc, M % Mc == 0 ? Mc : M % Mc}) {
-        const int64_t tok = mc * T;
-        lna = lna && gemm16_takes_rowstat(dt, EPI_QKVH16, gemm_args(EPI_QKVH16, nullptr, D, nullptr, nullptr, nullptr, 3 * D, tok, T, w->heads)) &&
-              gemm16_takes_rowstat(dt, EPI_GELU16, gemm_args(EPI_GELU16, nullptr, D, nullptr, nullptr, nullptr, F, tok)) &&
-              (full_blocks || gemm16_takes_rowstat(dt, EPI_QKVH16, gemm_args(EPI_QKVH16, nullptr, D, nullptr, nullptr, nullptr, 2 * D, tok, T, w->heads, 1)));
-    }
-    // ... and the residual adds in the epilogues of the O / FC2 products
-    bool lnb = lna && g_ln_fold >= 2;
-    for (int64_t mc : {Mc, M % Mc == 0 ? Mc : M % Mc}) {
-        const int64_t tok = mc * T;
-        Gemm16Args o = gemm_args(EPI_STREAM16, nullptr, D, nullptr, nullptr, nullptr, D, tok, T), f = gemm_args(EPI_STREAM16, nullptr, F, nullptr, nullptr, nullptr, D, tok, T);
-        o.rowpart = f.rowpart = b.RP;
-        lnb = lnb && gemm16_runs_h256(dt, EPI_STREAM16, o) && gemm16_runs_h256(dt, EPI_STREAM16, f);
-    }
-    // x += A W^T + bias in the stream (fp16 rows in place, the CLS rows' fp32 stream through the finalize step); rstd of the new rows
-    auto gemm_stream = [&](const void* A, int K, const void* W, const float* bias, int64_t mc) {
-        const int64_t tok = mc * T;
-        Gemm16Args a = gemm_args(EPI_STREAM16, A, K, W, bias, b.X16, D, tok, T);
-        a.rowpart = b.RP;
-        IISAN_TRY(launch_gemm16(dt, EPI_STREAM16, a, s));
-        return launch_stream_stats_finalize(b.RP, D / 64, ceil_div(tok, 256) * 256, b.X16, b.Xc, b.RS, w->eps, mc, T, s);
-    };
-    const size_t fold_w = (size_t)(3 * D + F) * D;          // elements of one layer's folded weights
-    auto Wf_qkv = [&](int l) { return (char*)b.Wf + (size_t)l * fold_w * 2; };
-    auto Wf_fc1 = [&](int l) { return Wf_qkv(l) + (size_t)3 * D * D * 2; };
-    auto bf_qkv = [&](int l) { return b.Bf + (size_t)l * (3 * D + F); };
-    auto bf_fc1 = [&](int l) { return bf_qkv(l) + 3 * D; };
-    if (lna && !w->folded) IISAN_TRY(vit_fold_all(w, live, full_blocks, (char*)b.Wf, b.Bf, s));
+    const VitStrategy st = vit_strategy(w, b, live, full_blocks, M, Mc, T);
+    const auto& step = VIT_STEPS[st];
+    if (st >= VS_FOLD && !w->folded) IISAN_TRY(vit_fold_all(w, live, full_blocks, (char*)b.Wf, b.Bf, s));
     const int64_t img_elems = (int64_t)w->channels * w->image * w->image;
     for (int64_t m0 = 0; m0 < M; m0 += Mc) {
         const int64_t mc = (M - m0 < Mc) ? M - m0 : Mc;
-        const int64_t tok = mc * T;
-        float* tp = taps + m0 * n_taps * D;
-        const void* img0 = img_u8 ? (const void*)((const uint8_t*)images + m0 * img_elems)
-                                  : (const void*)((const float*)images + m0 * img_elems);
-        IISAN_TRY(launch_vit_im2col(dt, img0, img_u8, b.F1, mc, w->channels, w->image, w->patch, s));
-        const bool mixed = !g_resid32;
-        // patch embedding: resid32 = fp32 token rows with the position embedding added (128x128 kernel); mixed = 16-bit rows on the
-        // production GEMM (gemm16_h256, 0.40 against 0.59 ms at bs = 128), the position table is added by block 0's LayerNorm
-        if (mixed) IISAN_TRY(gemm(dt, EPI_PATCH16, b.F1, pd, w->patch_w, w->patch_b, b.D16b, D, nullptr, mc * P, s, nullptr, P));
-        else IISAN_TRY(gemm(dt, EPI_PATCH32, b.F1, pd, w->patch_w, w->patch_b, b.X, D, nullptr, mc * P, s, w->pos_emb, P));
-        // CLS rows: cls + pos[0] — into the fp32 stream (token-major) or into the compact fp32 CLS stream
-        IISAN_TRY(launch_vit_cls_rows(mixed ? b.Xc : b.X, w->cls_token, w->pos_emb, mc, mixed ? 1 : T, D, s));
-        // the tapped rows of the current hidden state: CLS rows of X (stride T) or the compact CLS stream itself
-        auto tap = [&](int k) { return mixed ? launch_gather_cls(b.Xc, tp, mc, 1, D, n_taps, k, s) : launch_gather_cls(b.X, tp, mc, T, D, n_taps, k, s); };
+        const VitChunk ch{w, b, st, s, w->dtype16, D, F, T, w->heads, w->eps, mc, mc * T, taps + m0 * n_taps * D, n_taps};
+        IISAN_TRY(ch.embed(img_u8 ? (const void*)((const uint8_t*)images + m0 * img_elems) : (const void*)((const float*)images + m0 * img_elems), img_u8));
         int k = tap_index(tap_layers, n_taps, 0);
-        if (k >= 0) IISAN_TRY(tap(k));
-        // The O / FC2 GEMMs emit 16-bit deltas; the residual add is fused into the NEXT LayerNorm kernel (HBM-bound) instead
-        // of a read-modify-write GEMM epilogue.  `pending` = a delta not yet added to the stream.
-        // Residual bookkeeping (pre-LN tower): LN2 computes LN(x + dO) WITHOUT writing x back; the next LN1 adds both deltas,
-        // (x + dO) + dF in fp32 — the same value — and writes x once per block instead of twice.
-        const void* pend_o = nullptr;     // deltas not yet added to the stream
-        const void* pend_f = nullptr;
-        // Blocks after the deepest tapped hidden state are dead code (Versa configurations tap a prefix of the tower),
-        // and in the last LIVE block only the CLS token's output is consumed: K/V are computed for every token, but
-        // attention, O, LN2, FC1, FC2 and the closing residual add run on one row per item.
-        constexpr int MX_ADD_STAT = MX_D1 | MX_RESV | MX_STAT;       // x += d (fp16 stream, fp32 CLS rows); row statistics
+        if (k >= 0) IISAN_TRY(ch.tap(k));
         for (int l = 0; l < live; ++l) {
-            const iisan_layer_weights& L = w->layer[l];
-            // x += pending deltas of block l-1 ; h = LN1(x)            -> the stream is hidden state l
-            if (lna) {
-                // ... without the image h: the stream + (rstd, -mean rstd) per row; LN1 is applied by the QKV product's epilogue.
-                // (x + dO is in the stream already: this block's predecessor wrote it in its LN2 step)
-                if (l == 0)
-                    IISAN_TRY(launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_ADD_STAT, w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, w->eps, nullptr, mc, T, s, b.RS));
-                else if (!lnb)       // (lnb: the FC2 product of block l - 1 added into the stream and left its statistics)
-                    IISAN_TRY(launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, pend_f, nullptr, nullptr, nullptr, w->eps, nullptr, mc, T, s, b.RS));
-            } else if (!mixed)
-                IISAN_TRY(launch_add2_layernorm768(dt, b.X, pend_o, pend_f, L.ln1_w, L.ln1_b, w->eps, pend_o ? b.X : nullptr, b.H, nullptr, tok, s));
-            else if (l == 0)     // position table + 16-bit patch embedding -> fp16 stream of the patch rows (the CLS rows are in Xc already) + LN image
-                IISAN_TRY(launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_LN, w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, L.ln1_w, L.ln1_b, w->eps, b.H, mc, T, s));
-            else
-                IISAN_TRY(launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_LN, nullptr, b.X16, b.Xc, pend_o, pend_f, L.ln1_w, L.ln1_b, w->eps, b.H, mc, T, s));
-            pend_o = pend_f = nullptr;
+            IISAN_TRY((ch.*step.open)(l));       // -> the stream is hidden state l
             k = tap_index(tap_layers, n_taps, l);
-            if (k >= 0 && l > 0) IISAN_TRY(tap(k));
-            if (lnb && (l + 1 < live || full_blocks)) {
-                IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l), bf_qkv(l), b.RS, b.QKV, 3 * D, tok, s, T, w->heads));
-                IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, w->heads, s));
-                IISAN_TRY(gemm_stream(b.H, D, L.o_w, L.o_b, mc));
-                IISAN_TRY(gemm_ln(dt, EPI_GELU16, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, s));
-                IISAN_TRY(gemm_stream(b.F1, F, L.fc2_w, L.fc2_b, mc));
-            } else if (lna && (l + 1 < live || full_blocks)) {
-                IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l), bf_qkv(l), b.RS, b.QKV, 3 * D, tok, s, T, w->heads));
-                IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, w->heads, s));
-                IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
-                // x += dO (written: the FC1 product reads the stream); LN2 in the FC1 product's epilogue
-                IISAN_TRY(launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, b.D16, nullptr, nullptr, nullptr, w->eps, nullptr, mc, T, s, b.RS));
-                IISAN_TRY(gemm_ln(dt, EPI_GELU16, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, s));
-                IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, nullptr, tok, s));
-                pend_f = b.D16b;
-            } else if (l + 1 < live || full_blocks) {
-                IISAN_TRY(gemm(dt, EPI_QKVH16, b.H, D, L.qkv_w, L.qkv_b, b.QKV, 3 * D, nullptr, tok, s, nullptr, 0, T, w->heads));
-                IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, w->heads, s));
-                IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
-                // h = LN2(x + dO)   (x itself is updated by the next LN1)
-                if (!mixed)
-                    IISAN_TRY(launch_add_layernorm768(dt, b.X, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, b.H, nullptr, tok, s));
-                else
-                    IISAN_TRY(launch_layernorm768_mixed(dt, MX_D1 | MX_LN, nullptr, b.X16, b.Xc, b.D16, nullptr, L.ln2_w, L.ln2_b, w->eps, b.H, mc, T, s));
-                IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, tok, s));
-                IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, nullptr, tok, s));
-                pend_o = b.D16;
-                pend_f = b.D16b;
-            } else {
-                // CLS rows only: compact [mc, D] 16-bit views in their own scratch
-                void* Hc = b.Cls;
-                void* Qc = (char*)b.Cls + (size_t)b.Mcp * D * 2;
-                if (lna) {
-                    // K / V of every token from the stream (LN1 in the epilogue); the CLS rows' LN1 image from their fp32 stream
-                    IISAN_TRY(launch_layernorm768(dt, b.Xc, L.ln1_w, L.ln1_b, w->eps, Hc, nullptr, mc, s));
-                    IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l) + (size_t)D * D * 2, bf_qkv(l) + D, b.RS, b.QKV, 2 * D, tok, s, T, w->heads, 1));
-                    IISAN_TRY(gemm(dt, EPI_OUT16, Hc, D, L.qkv_w, L.qkv_b, Qc, D, nullptr, mc, s));
-                } else {
-                    IISAN_TRY(launch_gather_rows16(b.H, Hc, mc, T, D, s));            // CLS rows of LN1(x)
-                    IISAN_TRY(kv_all_q_cls(dt, L, b.H, b.QKV, Hc, Qc, tok, mc, T, w->heads, D, s));
-                }
-                IISAN_TRY(launch_attention_cls16(dt, b.QKV, nullptr, b.H, mc, T, w->heads, s, Qc));
-                float* Xc = (float*)b.QKV;      // free once the CLS attention has run (stream order)
-                IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, mc, s));
-                if (mixed) IISAN_TRY(launch_gather_cls(b.Xc, Xc, mc, 1, D, 1, 0, s)); else IISAN_TRY(launch_gather_cls(b.X, Xc, mc, T, D, 1, 0, s));
-                IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, Xc, b.H, nullptr, mc, s));
-                IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, mc, s));
-                IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, nullptr, mc, s));
-                IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, nullptr, nullptr, w->eps, Xc, nullptr, nullptr, mc, s));
-                k = tap_index(tap_layers, n_taps, live);     // hidden state `live` (before any final LayerNorm)
-                IISAN_TRY(launch_gather_cls(Xc, tp, mc, 1, D, n_taps, k, s));
-            }
+            if (k >= 0 && l > 0) IISAN_TRY(ch.tap(k));
+            if (l + 1 < live || full_blocks) IISAN_TRY((ch.*step.full)(l));
+            else IISAN_TRY(ch.cls_block(l, tap_index(tap_layers, n_taps, live)));
         }
-        if (full_blocks) {
-            k = tap_index(tap_layers, n_taps, w->layers);
-            if (k >= 0) {
-                if (lnb) {}     // the stream is hidden state `layers` already
-                else if (lna)   // x + dO is in the stream: the CLS rows take dF
-                    IISAN_TRY(launch_layernorm768_mixed(dt, MX_D1 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, pend_f, nullptr, nullptr, nullptr, w->eps, nullptr, mc, T, s));
-                else if (!mixed)
-                    IISAN_TRY(launch_add2_layernorm768(dt, b.X, pend_o, pend_f, nullptr, nullptr, w->eps, b.X, nullptr, nullptr, tok, s));
-                else            // only the CLS rows of the last hidden state are consumed
-                    IISAN_TRY(launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, pend_o, pend_f, nullptr, nullptr, w->eps, nullptr, mc, T, s));
-                IISAN_TRY(tap(k));
-            }
+        k = full_blocks ? tap_index(tap_layers, n_taps, w->layers) : -1;
+        if (k >= 0) {
+            IISAN_TRY((ch.*step.close)());
+            IISAN_TRY(ch.tap(k));
         }
     }
     return IISAN_OK;
+}
+
+extern "C" int iisan_vit_forward_taps(const iisan_vit_weights* w, const float* images, int64_t M,
+                                      const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
+                                      void* ws, size_t ws_bytes, void* stream) {
+    return vit_forward_taps_impl(w, images, 0, M, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream);
+}
+
+extern "C" int iisan_vit_forward_taps_u8(const iisan_vit_weights* w, const uint8_t* images, int64_t M,
+                                         const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
+                                         void* ws, size_t ws_bytes, void* stream) {
+    IISAN_CHECK_SHAPE(w->image % 8 == 0, "vit u8: image side %d must be a multiple of 8", w->image);
+    return vit_forward_taps_impl(w, images, 1, M, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream);
 }
 
 extern "C" size_t iisan_bert_forward_taps_ws_bytes(const iisan_bert_weights* w, int64_t M, int32_t words, int64_t chunk_items) {

@@ -244,20 +244,14 @@ extern "C" int iisan_gemm16_f32(const void* A, const void* W, float* out, int64_
     return launch_gemm16_f32(a, ksplit, (hipStream_t)stream);
 }
 
-bool gemm16_s256_applicable(int mode, const Gemm16Args& a);
-int launch_gemm16_s256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s);
-bool gemm16_h256_applicable(int mode, const Gemm16Args& a);
-int launch_gemm16_h256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s);
-
-// 0 = auto (persistent 256x256 kernels when the shape allows and there is at least half a tile per CU), 1 = force the
-// 128x128 v1 kernel, (2 = the lock-step 256x256 kernel of round 1, retired in round 4: treated as auto), 3 = force the staggered 256x256 kernel (gemm16_s256.hip), 4 = force
-// the staggered kernel with the half-slot tile boundary (gemm16_h256.hip).
+// 0 = auto (persistent 256x256 kernels when the shape allows and there is at least half a tile per CU), 1 and 2 = force the
+// 128x128 v1 kernel, 3 = force the staggered 256x256 kernel (gemm16_s256.hip), 4 = force the staggered kernel with the half-slot
+// tile boundary (gemm16_h256.hip).
 // Test/bench knob, not part of the product ABI.
 static int g_variant = 0;
-static int g_auto_staggered = 1;
-// auto policy: which staggered kernel takes the production shapes — 1 = gemm16_h256.hip (half-slot tile boundary: same-box
-// A/B of tools/gemm_var.py over three boxes: QKV +1..4 %, O +1 %, FC1 +-0, FC2 +3..4 %; bit-identical results), 0 = gemm16_s256.hip.
-// (round 5: the switch that sent the production shapes back to gemm16_s256.hip is retired; variant 3 still forces that kernel for the race screen)
+// auto policy: gemm16_h256.hip takes the production shapes (half-slot tile boundary: same-box A/B of tools/gemm_var.py over three
+// boxes against gemm16_s256.hip: QKV +1..4 %, O +1 %, FC1 +-0, FC2 +3..4 %; bit-identical results); variant 3 still forces
+// gemm16_s256.hip for the race screen
 IISAN_DEV_KNOB(gemm16_variant, g_variant);
 static int64_t g_cnt_h256 = 0, g_cnt_s256 = 0, g_cnt_v1 = 0;      // launches of launch_gemm16 by kernel family
 IISAN_DEV_COUNTER(gemm16_h256, g_cnt_h256);
@@ -269,77 +263,83 @@ static int g_walk_c = -1, g_walk_h = 0;
 IISAN_DEV_KNOB(gemm16_walk_c, g_walk_c);
 IISAN_DEV_KNOB(gemm16_walk_h, g_walk_h);
 
-int launch_gemm16(int dtype16, int mode, const Gemm16Args& a, hipStream_t s) {
-    IISAN_CHECK_SHAPE(a.M > 0 && a.N > 0 && a.K > 0, "gemm16: empty problem M=%lld N=%d K=%d", (long long)a.M, a.N, a.K);
-    IISAN_CHECK_SHAPE(a.N % BN == 0 && a.K % BK == 0, "gemm16: N (%d) must be a multiple of %d and K (%d) of %d", a.N, BN, a.K, BK);
-    IISAN_CHECK_SHAPE(ceil_div(a.M, BM) * (a.N / BN) < (1ll << 31), "gemm16: grid too large");
-    IISAN_CHECK_SHAPE(mode != EPI_PATCH32 || (a.patch_P > 0 && a.pos), "gemm16: patch mode needs P and pos");
-    IISAN_CHECK_SHAPE(mode != EPI_PATCH16 || a.patch_P > 0, "gemm16: patch mode needs P");
-    IISAN_CHECK_SHAPE(mode != EPI_RESID32 || a.resid, "gemm16: residual mode needs resid");
-    IISAN_CHECK_SHAPE(mode != EPI_STREAM16 || (a.rowpart && a.qkv_S > 0 && a.ldo == a.N), "gemm16: stream mode needs the row-sum buffer, S and ldo == N");
-    IISAN_CHECK_SHAPE(mode != EPI_QKVH16 || (a.qkv_S > 0 && a.qkv_heads > 0 && a.qkv_which0 >= 0 && a.qkv_which0 <= 2 && a.N == (3 - a.qkv_which0) * 64 * a.qkv_heads),
-                      "gemm16: head-major QKV mode needs S, heads and N == 3*64*heads");
-    const bool timed = iisan_timing_on(s);
-    if (timed) iisan_timing_pre(s, 2.0 * (double)a.M * a.N * a.K, 2.0 * ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N));
+static int reject(const char* what, int mode, const Gemm16Args& a) {
+    iisan_set_error("gemm16: %s (mode %d, M=%lld N=%d K=%d, variant %d)", what, mode, (long long)a.M, a.N, a.K, g_variant & 0xff);
+    return G16_REJECTED;
+}
+
+int gemm16_route(int dtype16, int mode, const Gemm16Args& a) {
+    if (mode < EPI_OUT16 || mode > EPI_STREAM16 || mode == EPI_F32) return reject("bad epilogue mode", mode, a);     // (EPI_F32: launch_gemm16_f32)
+    if (!(a.M > 0 && a.N > 0 && a.K > 0)) return reject("empty problem", mode, a);
+    if (!(a.N % BN == 0 && a.K % BK == 0)) return reject("N must be a multiple of 128 and K of 64", mode, a);
+    if (!(ceil_div(a.M, BM) * (a.N / BN) < (1ll << 31))) return reject("grid too large", mode, a);
+    if (mode == EPI_PATCH32 && !(a.patch_P > 0 && a.pos)) return reject("patch mode needs P and pos", mode, a);
+    if (mode == EPI_PATCH16 && !(a.patch_P > 0)) return reject("patch mode needs P", mode, a);
+    if (mode == EPI_RESID32 && !a.resid) return reject("residual mode needs resid", mode, a);
+    if (mode == EPI_STREAM16 && !(a.rowpart && a.qkv_S > 0 && a.ldo == a.N)) return reject("stream mode needs the row-sum buffer, S and ldo == N", mode, a);
+    if (mode == EPI_QKVH16 && !(a.qkv_S > 0 && a.qkv_heads > 0 && a.qkv_which0 >= 0 && a.qkv_which0 <= 2 && a.N == (3 - a.qkv_which0) * 64 * a.qkv_heads))
+        return reject("head-major QKV mode needs S, heads and N == (3 - which0)*64*heads", mode, a);
     const int var = g_variant & 0xff;
+    // the 256x256 kernels: forced (variants 3, 4), or where there is at least half a tile per CU (auto)
+    const bool big = var == 3 || var == 4 || (var == 0 && ceil_div(a.M, 256) * (a.N / 256) >= 128);
+    const bool h256 = big && var != 3 && gemm16_h256_applicable(mode, a);
+    // LayerNorm in the epilogue and the stream epilogue exist on gemm16_h256 alone, with fp16 operands
+    if (mode == EPI_STREAM16 || a.rowstat) {
+        if (!h256) return reject(a.rowstat ? "a product with LayerNorm row statistics runs on gemm16_h256 only" : "the stream epilogue runs on gemm16_h256 only", mode, a);
+        if (dtype16 != IISAN_F16) return reject("row statistics and the stream epilogue need fp16 operands", mode, a);
+    }
+    if (h256) return G16_H256;
+    // the staggered kernel without the half-slot boundary: variant 3 (the race-screen reference of gemm16_h256) and the shapes
+    // gemm16_h256_applicable() turns down
+    if (big && var != 4 && gemm16_s256_applicable(mode, a)) return G16_S256;
+    // everything else — small shapes, the fp32 / residual epilogues — on the 128x128 kernel
+    return G16_V1;
+}
+
+int launch_gemm16(int dtype16, int mode, const Gemm16Args& a, hipStream_t s) {
 #ifndef GEMM16_DEBUG_BITS
     // ablation / experiment bits (gemm16_variant = 4 | bits << 8) exist only in `make EXTRA=-DGEMM16_DEBUG_BITS` builds: a default
     // build would run the plain product kernel and the A/B tools (tools/gemm_walk.py, gemm_stream.py, gemm_slots_h.py) would read
     // numbers that mean nothing
     IISAN_CHECK_SHAPE((g_variant >> 8) == 0, "gemm16: debug bits 0x%x requested, but this library was built without -DGEMM16_DEBUG_BITS", (unsigned)(g_variant >> 8));
 #endif
-    const bool big = var == 3 || var == 4 || (var == 0 && ceil_div(a.M, 256) * (a.N / 256) >= 128);
-    int rc;
-    if (big && (var == 4 || (var == 0 && g_auto_staggered)) && gemm16_h256_applicable(mode, a)) {
-        Gemm16Args b = a;
-        b.debug = g_variant >> 8;
-        // auto policy (tools/gemm_walk.py, three boxes, interleaved rounds: QKV 1,010 -> 1,045, FC1 972 -> 990 TFLOP/s; the L2 read
-        // latency seen by the L1 falls from 396 to 239 cycles, profiles/r4_gemm_l2.md): panels of 3 column tiles walked down
-        // sub-slabs of 16 row tiles wherever a tile row is at least two panels wide and every XCD's slab holds a few sub-slabs
-        const bool auto_panel = a.N / 256 >= 6 && ceil_div(a.M, 256) >= 128;
-        b.walk_c = g_walk_c < 0 ? (auto_panel ? 3 : 0) : g_walk_c;
-        b.walk_h = g_walk_c < 0 ? 16 : g_walk_h;
-        ++g_cnt_h256;
-        rc = launch_gemm16_h256(dtype16, mode, b, s);
-        if (timed) iisan_timing_post(s);
-        return rc;
-    }
-    IISAN_CHECK_SHAPE(mode != EPI_STREAM16, "gemm16: the stream epilogue runs on gemm16_h256 only (M=%lld N=%d K=%d, variant %d)", (long long)a.M, a.N, a.K, var);
-    IISAN_CHECK_SHAPE(!a.rowstat, "gemm16: a product with LayerNorm row statistics runs on gemm16_h256 only (mode %d, M=%lld N=%d K=%d, variant %d)",
-                      mode, (long long)a.M, a.N, a.K, var);
-    // the staggered kernel without the half-slot boundary: variant 3 (the race-screen reference of gemm16_h256) and the shapes
-    // gemm16_h256_applicable() turns down
-    if (big && (var == 3 || (var == 0 && g_auto_staggered)) && gemm16_s256_applicable(mode, a)) {
-        Gemm16Args b = a;
-        b.debug = g_variant >> 8;
-        ++g_cnt_s256;
-        rc = launch_gemm16_s256(dtype16, mode, b, s);
-    }
-    // everything else — small shapes, the fp32 / residual epilogues (round 4 retired the lock-step 256x256 kernel gemm16_p256.hip: its
-    // last product, the patch embedding, runs on gemm16_h256 with a 16-bit output) — on the 128x128 kernel
-    else { ++g_cnt_v1; rc = dtype16 == IISAN_BF16 ? launch_t<BF16>(mode, a, s) : launch_t<F16>(mode, a, s); }
-    if (timed) iisan_timing_post(s);
-    return rc;
-}
-
-// would launch_gemm16 run this product on the kernel that applies LayerNorm in its epilogue (Gemm16Args::rowstat)?  The encoder
-// executors ask BEFORE they choose between the algebraic and the materialised LayerNorm; mirrors the routing above.
-bool gemm16_takes_rowstat(int dtype16, int mode, const Gemm16Args& a) {
-    const int var = g_variant & 0xff;
-    const bool big = var == 4 || (var == 0 && ceil_div(a.M, 256) * (a.N / 256) >= 128);
+    const int route = gemm16_route(dtype16, mode, a);
+    if (route == G16_REJECTED) return IISAN_EBADSHAPE;
+    TimedLaunch timed(1, s, 2.0 * (double)a.M * a.N * a.K, 2.0 * ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N));
     Gemm16Args b = a;
-    static const float dummy = 0.f;
-    if (!b.rowstat) b.rowstat = &dummy;
-    return dtype16 == IISAN_F16 && big && (var == 4 || g_auto_staggered) && a.N % BN == 0 && a.K % BK == 0 &&
-           gemm16_h256_applicable(mode, b);
+    switch (route) {
+        case G16_H256:
+            b.debug = g_variant >> 8;
+            {   // auto policy (tools/gemm_walk.py, three boxes, interleaved rounds: QKV 1,010 -> 1,045, FC1 972 -> 990 TFLOP/s; the L2 read
+                // latency seen by the L1 falls from 396 to 239 cycles, profiles/r4_gemm_l2.md): panels of 3 column tiles walked down
+                // sub-slabs of 16 row tiles wherever a tile row is at least two panels wide and every XCD's slab holds a few sub-slabs
+                const bool auto_panel = a.N / 256 >= 6 && ceil_div(a.M, 256) >= 128;
+                b.walk_c = g_walk_c < 0 ? (auto_panel ? 3 : 0) : g_walk_c;
+                b.walk_h = g_walk_c < 0 ? 16 : g_walk_h;
+            }
+            ++g_cnt_h256;
+            return launch_gemm16_h256(dtype16, mode, b, s);
+        case G16_S256:
+            b.debug = g_variant >> 8;
+            ++g_cnt_s256;
+            return launch_gemm16_s256(dtype16, mode, b, s);
+        default:
+            ++g_cnt_v1;
+            return dtype16 == IISAN_BF16 ? launch_t<BF16>(mode, a, s) : launch_t<F16>(mode, a, s);
+    }
 }
 
-// ... or on gemm16_h256 at all (EPI_STREAM16 exists only there)
-bool gemm16_runs_h256(int dtype16, int mode, const Gemm16Args& a) {
-    const int var = g_variant & 0xff;
-    const bool big = var == 4 || (var == 0 && ceil_div(a.M, 256) * (a.N / 256) >= 128);
-    return (mode != EPI_STREAM16 || dtype16 == IISAN_F16) && big && (var == 4 || g_auto_staggered) && a.N % BN == 0 &&
-           a.K % BK == 0 && gemm16_h256_applicable(mode, a);
+// the routing query for host-side tests (tests/test_host_logic.py): operands with natural leading dimensions, qkv_S doubles as the
+// patch count of EPI_PATCH16, non-null placeholders for the buffers the checks ask for; no device is touched
+extern "C" int32_t iisan_gemm16_route(int32_t dtype16, int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t qkv_heads,
+                                      int32_t qkv_which0, int32_t with_rowstat) {
+    static float dummy = 0.f;
+    Gemm16Args a{};
+    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N; a.qkv_S = qkv_S; a.qkv_heads = qkv_heads; a.qkv_which0 = qkv_which0;
+    a.patch_P = mode == EPI_PATCH16 || mode == EPI_PATCH32 ? qkv_S : 0;
+    a.rowstat = with_rowstat ? &dummy : nullptr;
+    a.rowpart = &dummy; a.resid = &dummy; a.pos = &dummy;
+    return gemm16_route(dtype16, mode, a);
 }
 
 // bench / test entry: x += A W^T + bias in the fp16 stream x [Mpad, N] (in place), per-slice row sums into rowpart [N / 64][Mpad][2]

@@ -860,7 +860,6 @@ __global__ __launch_bounds__(256) void gemm32_reduce_kernel(ReduceBatch rb, int 
 // each other's scratch
 thread_local float* g_scratch = nullptr;
 thread_local size_t g_scratch_floats = 0;
-constexpr int g_accum_via_scratch = 1;       // (weight-gradient split-K sums go through the executor's scratch; the atomics route's switch was retired in round 5)
 
 // launch-shape heuristics (constants since round 5; tools/step_ab.py measured them): workgroups wanted before the row tile shrinks /
 // before split-K stops adding slices
@@ -1033,8 +1032,6 @@ static int launch_gemm32_k64_gate_impl(const Gemm32Prob* probs, const K64Gate* g
     return IISAN_OK;
 }
 
-int launch_colsum(const float* const* X, float* const* out, const int64_t* M, const int32_t* N, const int32_t* ld,
-                  int nprob, hipStream_t s);
 static int launch_gemm32_impl(const Gemm32Prob* probs, int nprob, int flags, hipStream_t s) {
     IISAN_CHECK_SHAPE(nprob >= 1 && nprob <= G32_MAXP, "gemm32: 1..%d problems per launch (got %d)", G32_MAXP, nprob);
     Gemm32Batch b{};
@@ -1115,7 +1112,7 @@ static int launch_gemm32_impl(const Gemm32Prob* probs, int nprob, int flags, hip
     IISAN_CHECK_SHAPE(max_tiles < (1ll << 31), "gemm32: grid too large");
     // weight-gradient shape on whole 64-tiles: gemm32_dw_kernel (needs the scratch route for its raw split-K partials)
     bool dw_ok = g_use_dw && (flags & (G32_TA | G32_TB | G32_ACCUM)) == (G32_TA | G32_TB | G32_ACCUM) && (flags & ~(G32_TA | G32_TB | G32_ACCUM)) == 0 &&
-                 g_scratch && g_accum_via_scratch;
+                 g_scratch;
     for (int i = 0; i < nprob && dw_ok; ++i) {
         const Gemm32Prob& q = probs[i];
         dw_ok = (q.M & 63) == 0 && (q.N & 63) == 0 && (q.K & 63) == 0 && q.K >= 4 * TK && (q.lda & 3) == 0 && (q.ldb & 3) == 0 &&
@@ -1176,7 +1173,7 @@ static int launch_gemm32_impl(const Gemm32Prob* probs, int nprob, int flags, hip
     // (round 6: gemm32_dw_kernel also when ONE split is wanted — a group whose tiles already fill the chip, like Versa's fc weight
     //  gradients (400 tiles), fell back to the tiled kernel: 22 K-tiles in a row per workgroup, 77 us; the raw partial costs one more pass
     //  of the reducer over the output and is still the faster route)
-    if ((flags & G32_ACCUM) && g_scratch && g_accum_via_scratch && (splitk >= 2 || dw_ok)) {
+    if ((flags & G32_ACCUM) && g_scratch && (splitk >= 2 || dw_ok)) {
         {   // only NON-EMPTY K ranges: the kernel gives split y the K-tiles [y, y+1) * ceil(ktiles / splits) and a split whose
             // range is empty writes nothing — its partial would be read uninitialised by the reducer
             const int64_t ktiles = ceil_div(min_k, (int64_t)TK), per = ceil_div(ktiles, (int64_t)splitk);
@@ -1263,25 +1260,13 @@ static int launch_gemm32_impl(const Gemm32Prob* probs, int nprob, int flags, hip
 // ---- public launchers: the implementation above, bracketed by HIP events when bench.py times this kernel family (class 2).
 // A launcher that re-enters another (split-K through the scratch buffer) is timed once, as the caller sees it: product +
 // reducer together.
-namespace { thread_local int g_timing_depth = 0; }
-struct TimedG32 {
-    hipStream_t s; bool on;
-    TimedG32(hipStream_t s_, double flops, double bytes) : s(s_), on(iisan_timing_class() == 2 && g_timing_depth == 0) {
-        ++g_timing_depth;
-        if (on) iisan_timing_pre(s, flops, bytes);
-    }
-    ~TimedG32() {
-        --g_timing_depth;
-        if (on) iisan_timing_post(s);
-    }
-};
 int launch_gemm32(const Gemm32Prob* probs, int nprob, int flags, hipStream_t s) {
     double fl = 0, by = 0;
     for (int i = 0; i < nprob && i < G32_MAXP; ++i) {
         fl += 2.0 * (double)probs[i].M * probs[i].N * (double)probs[i].K;
         by += 4.0 * ((double)probs[i].M * probs[i].K + (double)probs[i].N * probs[i].K + (double)probs[i].M * probs[i].N);
     }
-    TimedG32 t(s, fl, by);
+    TimedLaunch t(2, s, fl, by);
     return launch_gemm32_impl(probs, nprob, flags, s);
 }
 int launch_gemm32_n64f(const N64FDesc* d, int n, int gelu, hipStream_t s) {
@@ -1290,7 +1275,7 @@ int launch_gemm32_n64f(const N64FDesc* d, int n, int gelu, hipStream_t s) {
         fl += 2.0 * (double)d[i].M * 64.0 * d[i].K;
         by += 4.0 * ((double)d[i].M * d[i].K * ((d[i].a ? 1 : 0) + (d[i].b ? 1 : 0) + (d[i].prev ? 1 : 0) + 1) + 64.0 * d[i].K + 2.0 * d[i].M * 64.0);
     }
-    TimedG32 t(s, fl, by);
+    TimedLaunch t(2, s, fl, by);
     return launch_gemm32_n64f_impl(d, n, gelu, s);
 }
 int launch_gemm32_k64_gate(const Gemm32Prob* probs, const K64Gate* gates, int nprob, hipStream_t s) {
@@ -1299,7 +1284,7 @@ int launch_gemm32_k64_gate(const Gemm32Prob* probs, const K64Gate* gates, int np
         fl += 2.0 * (double)probs[i].M * probs[i].N * 64.0;
         by += 4.0 * ((double)probs[i].M * 64.0 + (double)probs[i].N * 64.0 + 4.0 * (double)probs[i].M * probs[i].N);
     }
-    TimedG32 t(s, fl, by);
+    TimedLaunch t(2, s, fl, by);
     return launch_gemm32_k64_gate_impl(probs, gates, nprob, s);
 }
 

@@ -383,22 +383,11 @@ size_t lds_bytes(int D) { return (size_t)lds_floats(D) * sizeof(float); }
 // ---- host interface (sidenet.hip) -------------------------------------------------------------------------------
 bool sanb_fused_ok(int D, int down) { return down == RD && (D == 1024 || D == 768 || D == 512 || D == 256); }
 
-struct SanbTowerDesc {       // plain-pointer mirror of SanbTower for the executor
-    const float* a; const float* b; const float* prev; int64_t lda, ldb, ldp; const float* gate; int32_t D, type;
-    const float* Wd; const float* bd; const float* Wu; const float* bu;
-    float* F; float* U; float* A; float* O;
-    const float* dO; const float* Upre; float* dU; float* dprev; float* da; float* db; float* dgate; float* dbu; float* dbd;
-};
-
 static void fill(SanbTower& t, const SanbTowerDesc& d) {
     t.a = d.a; t.b = d.b; t.prev = d.prev; t.lda = d.lda; t.ldb = d.ldb; t.ldp = d.ldp; t.gate = d.gate; t.D = d.D; t.type = d.type;
     t.Wd = d.Wd; t.bd = d.bd; t.Wu = d.Wu; t.bu = d.bu; t.F = d.F; t.U = d.U; t.A = d.A; t.O = d.O;
     t.dO = d.dO; t.Upre = d.Upre; t.dU = d.dU; t.dprev = d.dprev; t.da = d.da; t.db = d.db; t.dgate = d.dgate; t.dbu = d.dbu; t.dbd = d.dbd;
 }
-
-// (round 5: the ablation bits, the start-stagger experiment and the non-persistent grid lost their switches: measured, documented in
-//  DESIGN 6c / 6d, never the product route)
-static constexpr int g_sanb_persist = 1;
 
 template <bool BWD>
 static int launch_sanb(const SanbTowerDesc* towers, int n, int64_t M, int gelu, hipStream_t s) {
@@ -413,7 +402,7 @@ static int launch_sanb(const SanbTowerDesc* towers, int n, int64_t M, int gelu, 
     const int cus = iisan_cu_count();
     const int64_t ntile = ceil_div(M, R);
     // persistent: one workgroup per CU and tower (three co-resident per CU), each walking tiles x, x + grid.x, ...
-    const unsigned gx = (unsigned)((g_sanb_persist && ntile > cus) ? cus : ntile);
+    const unsigned gx = (unsigned)(ntile > cus ? cus : ntile);
     const dim3 grid(gx, (unsigned)n), block(NT);
     const size_t lds = lds_bytes(D);
 #define SANB_LAUNCH(DD)                                                                                                \

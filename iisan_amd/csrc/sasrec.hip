@@ -15,22 +15,6 @@
 // attention / fc / FFN; cfg.dropout == 0 is the exact eval path.
 #include "common.h"
 
-int launch_colsum(const float* const* X, float* const* out, const int64_t* M, const int32_t* N, const int32_t* ld,
-                  int nprob, hipStream_t s);
-
-// one-launch forward / backward for the production shape (sasrec_fused.hip); works on the workspace slots carved here
-struct SasFusedPtrs {
-    float* Z0; float* X0;
-    float* Q[8]; float* K[8]; float* V[8]; float* P[8]; float* C[8]; float* Zattn[8]; float* X1[8]; float* Hf[8]; float* Zffn[8]; float* X2[8];
-};
-bool sasrec_fused_ok(const iisan_sasrec_cfg* cfg);
-bool sasrec_fused_shape_ok(const iisan_sasrec_cfg* cfg);
-int launch_sasrec_fused_fwd(const iisan_sasrec_cfg* cfg, const float* x, const float* log_mask, int64_t B, const void* const* params,
-                            float* y, const SasFusedPtrs& w, hipStream_t s);
-int64_t sasrec_fused_slab_floats(const iisan_sasrec_cfg* cfg, int64_t B);
-int launch_sasrec_fused_bwd(const iisan_sasrec_cfg* cfg, const float* log_mask, int64_t B, const void* const* params, const float* dy,
-                            float* dx, void* const* grads, const SasFusedPtrs& w, float* slab, hipStream_t s);
-
 namespace {
 
 constexpr int MAXE = 256;   // d_model up to 256 (multiple of 64)

@@ -627,11 +627,6 @@ int64_t sasrec_fused_slab_floats(const iisan_sasrec_cfg* cfg, int64_t B) {
     return ceil_div(B, FR / cfg->seq) * (int64_t)(SLAB_BLK0 + cfg->blocks * SLAB_BLK);
 }
 
-struct SasFusedPtrs {              // filled by sasrec.hip from its own carve
-    float* Z0; float* X0;
-    float* Q[8]; float* K[8]; float* V[8]; float* P[8]; float* C[8]; float* Zattn[8]; float* X1[8]; float* Hf[8]; float* Zffn[8]; float* X2[8];
-};
-
 static int64_t g_cnt_sasrec_fused = 0;       // one-launch SASRec forward passes (route counter, common.h)
 IISAN_DEV_COUNTER(sasrec_fused_fwd, g_cnt_sasrec_fused);
 

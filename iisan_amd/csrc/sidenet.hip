@@ -19,23 +19,6 @@
 // Saved for backward: F, pre-activation U, activation, state per step, the dim-aligned taps.
 #include "common.h"
 
-int launch_colsum(const float* const* X, float* const* out, const int64_t* M, const int32_t* N, const int32_t* ld,
-                  int nprob, hipStream_t s);
-
-// fused SANB step (sanb.hip)
-struct SanbTowerDesc {
-    const float* a; const float* b; const float* prev; int64_t lda, ldb, ldp; const float* gate; int32_t D, type;
-    const float* Wd; const float* bd; const float* Wu; const float* bu;
-    float* F; float* U; float* A; float* O;
-    const float* dO; const float* Upre; float* dU; float* dprev; float* da; float* db; float* dgate; float* dbu; float* dbd;
-};
-bool sanb_fused_ok(int D, int down);
-int launch_sanb_fwd(const SanbTowerDesc* towers, int n, int64_t M, int gelu, hipStream_t s);
-int launch_sanb_bwd(const SanbTowerDesc* towers, int n, int64_t M, int gelu, hipStream_t s);
-int launch_sanb_transpose(const float* const* in, float* const* out, const int32_t* rows, const int32_t* cols, int n, hipStream_t s);
-
-double gemm_x3_get_min_flops();     // split.hip
-
 namespace {
 
 // one tower of one fusion step.  type 0: F = g·a + (1-g)·prev ; type 1: F = prev + g·a + (1-g)·b  (not gated: plain sums)
@@ -472,7 +455,6 @@ int setup(Ctx& c, const iisan_side_cfg* cfg, const float* taps_cv, const float* 
 IISAN_DEV_KNOB(sanb_fused, g_use_sanb);
 IISAN_DEV_KNOB(sidenet_dw_merge, g_dw_merge);
 
-void gemm_x3_set_min_flops(double f);     // negative = the library default (split.hip: X3_DEFAULT_MIN_FLOPS, 4 GFLOP)
 // 0 = off, 1 = library default (the state of a process that never calls this knob), 2 = every product whose shape allows
 // it (tests: the small golden fixtures then run through the split-operand path too)
 static int g_x3_mode = 1;

@@ -304,15 +304,12 @@ int split_operand(const float* x, bool trans, int64_t op_rows, int64_t K, int64_
 
 }  // namespace
 
-int launch_gemm16_f32(const Gemm16Args& a, int ksplit, hipStream_t s);      // gemm16.hip
-
 // K-splits of a product.  Partial products go to the workspace and a small reducer adds them (fp32 atomics run at ~20 G/s chip-wide: a
 // split-K epilogue on them took 430 us for 8 M outputs, tools/g16f32_time.py).  Round 6: chosen by a cost estimate instead of "double until 384
 // workgroups" — the chip holds 2 x CUs workgroups of gemm16_x3p_kernel at a time, a split count that spills a few workgroups into another round
 // pays a whole round for them (Versa's dim-align product: 88 tiles x 8 splits = 704 workgroups on 512 slots, two rounds of 32 K-steps; five
 // splits = 440 workgroups, ONE round of 52), and every split costs a pass over its partial (written and read back: ~8 bytes per output).
 //   cost(ks) = ceil(tiles ks / slots) x (steps / ks + 4) K-step times (~1 us)  +  [ks > 1] ks x (8 M N bytes at ~5 TB/s)
-int x3p_tile_n(int64_t M, int64_t N);          // gemm16_x3.hip: 128 or 192 columns per tile
 static int g_x3_ks = 0;                  // > 0: this many K splits for every product (sweeps); 0 = by the cost estimate
 IISAN_DEV_KNOB(x3_force_ks, g_x3_ks);
 static int x3_ksplit(int64_t mp, int64_t np, int64_t kp) {

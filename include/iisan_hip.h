@@ -338,6 +338,11 @@ int iisan_stream_stats_finalize(const float* rowpart, int32_t nslots, int64_t Mp
 /* host-side predicate (no device touched): does the persistent 256x256 kernel take this product? */
 int32_t iisan_gemm16_h256_applicable(int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t qkv_heads,
                                      int32_t qkv_which0);
+/* host-side routing query (no device touched): the kernel family iisan_gemm16* runs this product on under the current
+ * gemm16_variant — 0 = 128x128, 1 = staggered 256x256 (gemm16_s256), 2 = gemm16_h256, negative = rejected (iisan_last_error).
+ * Operands with natural leading dimensions; qkv_S is the patch count of the patch modes; with_rowstat: LayerNorm in the epilogue. */
+int32_t iisan_gemm16_route(int32_t dtype16, int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t qkv_heads,
+                           int32_t qkv_which0, int32_t with_rowstat);
 
 /* ------------------------------------------------------------------------------------------------------------
  * DEV section — process-wide development switches and measurement hooks.  NOT part of the product contract: a

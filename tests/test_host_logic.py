@@ -310,6 +310,58 @@ def test_h256_head_major_addressing_bound_is_independent_of_which0():
     assert lib.iisan_gemm16_h256_applicable(0, 277376, 768, 64, 0, 0, 0) == 0                       # K / 64 < 2
 
 
+def test_gemm16_route_table_under_every_variant():
+    """The kernel family `launch_gemm16` gives a product (gemm16.hip: gemm16_route, the ONE place that decides), as a literal table:
+    2 = gemm16_h256, 1 = gemm16_s256, 0 = the 128x128 kernel, -1 = rejected, under gemm16_variant 0..4.  With T = ceil(M/256) * (N/256):
+    variant 0 takes h256, else s256, where T >= 128 and the kernel is applicable; 1 and 2 force 128x128; 3 forces s256 and 4 forces h256
+    where applicable; LayerNorm row statistics (+ln) and the stream epilogue exist on h256 with fp16 operands only.  A changed threshold
+    fails here, on a CPU, and not only in the GPU counter test of the bench shapes.  Pure host logic: no device is touched."""
+    from iisan_amd import _lib
+    lib = _lib.load()
+    F16, BF16 = 0, 1
+    OUT16, GELU16, RESID32, QKVH16, PATCH16, STREAM16 = 0, 1, 2, 4, 6, 7
+    M = 277_376                                   # bs = 128 headline batch: 1,408 images x 197 tokens
+    # (dtype, mode, M, N, K, S (P for PATCH16), heads, which0, +ln) -> route under variants 0..4
+    table = [
+        ((F16, QKVH16, M, 2304, 768, 197, 12, 0, 0), (2, 0, 0, 1, 2)),
+        ((F16, QKVH16, M, 2304, 768, 197, 12, 0, 1), (2, -1, -1, -1, 2)),
+        ((F16, QKVH16, M, 1536, 768, 197, 12, 1, 1), (2, -1, -1, -1, 2)),          # K / V only (CLS-pruned last block)
+        ((F16, GELU16, M, 3072, 768, 0, 0, 0, 0), (2, 0, 0, 1, 2)),
+        ((F16, GELU16, M, 3072, 768, 0, 0, 0, 1), (2, -1, -1, -1, 2)),
+        ((F16, STREAM16, M, 768, 768, 197, 0, 0, 0), (2, -1, -1, -1, 2)),
+        ((F16, STREAM16, M, 768, 3072, 197, 0, 0, 0), (2, -1, -1, -1, 2)),
+        ((F16, OUT16, M, 768, 768, 0, 0, 0, 0), (2, 0, 0, 1, 2)),
+        ((F16, OUT16, M, 768, 3072, 0, 0, 0, 0), (2, 0, 0, 1, 2)),
+        ((F16, PATCH16, 275_968, 768, 768, 196, 0, 0, 0), (2, 0, 0, 0, 2)),        # gemm16_s256 has no patch epilogue
+        ((F16, OUT16, 1_408, 768, 768, 0, 0, 0, 0), (0, 0, 0, 1, 2)),              # T = 18 < 128: auto stays on 128x128
+        ((F16, OUT16, M, 768, 64, 0, 0, 0, 0), (0, 0, 0, 0, 0)),                   # K / 64 < 2: no 256x256 kernel
+        ((F16, RESID32, M, 768, 768, 0, 0, 0, 0), (0, 0, 0, 0, 0)),                # fp32 epilogues: 128x128 only
+        ((F16, STREAM16, 1_408, 768, 768, 197, 0, 0, 0), (-1, -1, -1, -1, 2)),
+        ((BF16, STREAM16, M, 768, 768, 197, 0, 0, 0), (-1, -1, -1, -1, -1)),
+        ((BF16, QKVH16, M, 2304, 768, 197, 12, 0, 1), (-1, -1, -1, -1, -1)),
+        ((BF16, QKVH16, M, 2304, 768, 197, 12, 0, 0), (2, 0, 0, 1, 2)),
+        ((F16, OUT16, M, 768, 768, 0, 0, 0, 1), (-1, -1, -1, -1, -1)),             # +ln: QKV and FC1 products only
+        ((F16, GELU16, M, 8192, 768, 0, 0, 0, 1), (-1, -1, -1, -1, -1)),           # +ln: N <= 6144
+        ((F16, GELU16, M, 8192, 768, 0, 0, 0, 0), (2, 0, 0, 1, 2)),
+        ((F16, GELU16, M, 16384, 768, 0, 0, 0, 0), (0, 0, 0, 0, 0)),               # wider than the bias slot of either 256x256 kernel
+        # the size rule at its boundary (N / 256 = 4): 31 row tiles -> T = 124, one row more -> 32 row tiles, T = 128
+        ((F16, OUT16, 7_936, 1024, 768, 0, 0, 0, 0), (0, 0, 0, 1, 2)),
+        ((F16, OUT16, 7_937, 1024, 768, 0, 0, 0, 0), (2, 0, 0, 1, 2)),
+        # beyond the 32-bit addressing bound of gemm16_h256's head-major store (the test above): auto falls to s256, variant 4 never does
+        ((F16, QKVH16, 1_200_000, 2304, 768, 197, 12, 0, 0), (1, 0, 0, 1, 0)),
+        # the shape checks launch_gemm16 makes up front count as rejected
+        ((F16, OUT16, M, 832, 768, 0, 0, 0, 0), (-1, -1, -1, -1, -1)),             # N % 128
+        ((F16, OUT16, M, 768, 800, 0, 0, 0, 0), (-1, -1, -1, -1, -1)),             # K % 64
+        ((F16, QKVH16, M, 2304, 768, 197, 8, 0, 0), (-1, -1, -1, -1, -1)),         # N != 3 * 64 * heads
+        ((F16, PATCH16, 275_968, 768, 768, 0, 0, 0, 0), (-1, -1, -1, -1, -1)),     # patch mode needs P
+    ]
+    for variant in range(5):
+        with _lib.dev(gemm16_variant=variant):
+            for args, want in table:
+                got = lib.iisan_gemm16_route(*args)
+                assert (got if got >= 0 else -1) == want[variant], (variant, args, got, want[variant])
+
+
 def test_tools_compile_and_name_only_declared_entry_points():
     """a development tool that still iterated a table the ABI clean-up had removed died silently in every child process.  Every
     script under tools/ must byte-compile, and every `iisan_*` entry point it names must be one the loader binds (`_lib.SIGNATURES` =
