@@ -93,6 +93,8 @@ SIGNATURES = {
     "iisan_stream_stats_finalize": (i32, [vp, i32, i64, vp, vp, vp, f32, i64, i32, vp]),
     "iisan_gemm16_h256_applicable": (i32, [i32, i64, i32, i32, i32, i32, i32]),
     "iisan_gemm16_route": (i32, [i32, i32, i64, i32, i32, i32, i32, i32, i32]),
+    "iisan_gemm32_plan": (i32, [C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), i32, i32, i64, i32, C.POINTER(i32)]),
+    "iisan_inbatch_ce_route": (i32, [i64, i32]),
     # DEV section: the library's only process-global state (development switches + measurement hooks)
     "iisan_dev_set": (i32, [C.c_char_p, i64]),
     "iisan_dev_get": (i64, [C.c_char_p]),

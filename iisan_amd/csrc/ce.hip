@@ -12,6 +12,8 @@
 // matrix cores (v_mfma_f32_16x16x4_f32, K = E = 64) so a lane owns one X row and 4 Y columns per tile: the online
 // log-sum-exp is per-lane + two xor-shuffles, and the dZ registers are already the B operand of the second product
 // dX^T = Y^T·dZ^T.  The Y tile is staged once per wave in LDS (272-byte rows: conflict-free ds_read_b128).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -1306,18 +1308,33 @@ __global__ __launch_bounds__(256) void ce16_col_combine_kernel(CeBufs b, Ce16Buf
     }
 }
 
-// 1 (default): one fused FWD + DPREC row pass (online softmax) and the cooperative column pass — on the 16-bit matrix cores with split
-// operands (ce16_*) from C16_MIN_LOGITS logits on, on the f32 cores below; 2: separate FWD and DPREC row passes (round-2a form); 0: the
-// generic kernel everywhere; 3: ce16_* at every size; 4: the f32 fused passes at every size (test knobs)
+// The route of one loss call: which kernels run its row pass (forward) and its row and column passes (backward).  Chosen once, by the
+// forward call, from the dev switch ce_fast, the shape limits of the row-fixed kernels and C16_MIN_LOGITS; the backward call takes it
+// from the forward's token.  ce_fast:
+//   1 (default): one fused FWD + DPREC row pass (online softmax) and the cooperative column pass — on the 16-bit matrix cores with split
+//      operands (ce16_*) from C16_MIN_LOGITS logits on, on the f32 cores below; 2: separate FWD and DPREC row passes (round-2a form); 0: the
+//      generic kernel everywhere; 3: ce16_* at every size; 4: the f32 fused passes at every size (test knobs)
+enum { CE_ROUTE_GENERIC = 0,      // ce_pass_kernel for all three passes (any S <= 63)
+       CE_ROUTE_ROWPASS = 1,      // ce_rowpass_kernel<CE_FWD>, <CE_DPREC>, ce_colpass_kernel
+       CE_ROUTE_FUSED = 2,        // ce_rowpass_kernel<CE_FUSED> leaves d_prec for d_loss = 1 in the workspace; backward scales it + ce_colpass_kernel
+       CE_ROUTE_SPLIT16 = 3 };    // ce16_*: as FUSED, on split fp16 operand images kept in the workspace
 int g_ce_fast = 1;
-constexpr int g_ce_dbg = 0;      // (the ablation bits of the fused row pass: compile-time zero since round 5)
 // bs = 128 (1,280 x 1,408 logits): 29 us per f32 pass, launch-sized — the split route's four extra small launches would cost more than it gains
 constexpr int64_t C16_MIN_LOGITS = (int64_t)1 << 24;
-bool rowpass_ok(int64_t bs, int S) { return g_ce_fast && S >= 5 && S + 1 <= MAXS1 && bs * (int64_t)(S + 1) < (1ll << 31); }
-bool fused_ok(int64_t bs, int S) { return rowpass_ok(bs, S) && (g_ce_fast == 1 || g_ce_fast == 3 || g_ce_fast == 4); }
-bool ce16_ok(int64_t bs, int S) {
-    return rowpass_ok(bs, S) && (g_ce_fast == 3 || (g_ce_fast == 1 && bs * S * bs * (int64_t)(S + 1) >= C16_MIN_LOGITS));
+int ce_route(int64_t bs, int S) {
+    // the row-fixed kernels keep a sequence's ids in registers / LDS, span at most four sequences per 16-row tile and index with 32 bits
+    if (!g_ce_fast || S < 5 || S + 1 > MAXS1 || bs * (int64_t)(S + 1) >= (1ll << 31)) return CE_ROUTE_GENERIC;
+    if (g_ce_fast == 3 || (g_ce_fast == 1 && bs * S * bs * (int64_t)(S + 1) >= C16_MIN_LOGITS)) return CE_ROUTE_SPLIT16;
+    return (g_ce_fast == 1 || g_ce_fast == 4) ? CE_ROUTE_FUSED : CE_ROUTE_ROWPASS;
 }
+// The run-time S + 1 as the RS1 template argument (slots per sequence compared per logit): f(integral_constant<int, 11 or MAXS1>).  11 is the
+// reference's max_seq_len 10 + 1; every kernel's RS1 = 11 instantiation also handles shorter sequences, except the generic CE_DSCORE pass (below).
+template <class F>
+void with_rs1(int S, F&& f) {
+    if (S + 1 <= 11) f(std::integral_constant<int, 11>{});
+    else f(std::integral_constant<int, MAXS1>{});
+}
+#define CE_RS1 decltype(rs1)::value
 // ranges of Y per X block: about seven workgroups per CU (four are resident at a time) and >= 8 steps per range.  Same-box sweep at bs = 1024
 // (tools/ce_sweep.py, forward + backward of the loss, both passes with the same count): 4 ranges 402 - 407 us, 6 390, 8 365, 10 355 - 357,
 // 11 347 - 348, 12 357, 16 353; the f32 passes 852 - 891.
@@ -1330,31 +1347,26 @@ int ce16_ysplits(int64_t nx, int64_t ny, int nsub) {
     while (ys > 1 && steps / ys < 8) --ys;
     return ys < 1 ? 1 : (int)ys;
 }
-template <int NSUB>
-int launch_ce16_row(const float* log_mask, const CeBufs& b, const Ce16Bufs& c, int64_t bs, int S, hipStream_t s, int* ys_out) {
-    const int64_t T = bs * S, M = bs * (S + 1);
-    const int ys = ce16_ysplits(T, M, NSUB);
-    const int steps_per = (int)ceil_div(ceil_div(M, (int64_t)32), (int64_t)ys);
-    const dim3 grid((unsigned)ceil_div(T, (int64_t)64 * NSUB), (unsigned)ys);
-    if (S + 1 <= 11) hipLaunchKernelGGL((ce16_rowpass_kernel<11, NSUB>), grid, dim3(256), 0, s, log_mask, b, c, (int)bs, S, steps_per);
-    else hipLaunchKernelGGL((ce16_rowpass_kernel<MAXS1, NSUB>), grid, dim3(256), 0, s, log_mask, b, c, (int)bs, S, steps_per);
-    IISAN_LAUNCH_OK();
-    *ys_out = ys;
-    return IISAN_OK;
-}
-template <int NSUB>
-int launch_ce16_col(const float* log_mask, const CeBufs& b, const Ce16Bufs& c, int64_t bs, int S, hipStream_t s, int* ys_out) {
-    const int64_t T = bs * S, M = bs * (S + 1);
-    const int ys = ce16_ysplits(M, T, NSUB);
-    const int steps_per = (int)ceil_div(ceil_div(T, (int64_t)32), (int64_t)ys);
-    const dim3 grid((unsigned)ceil_div(M, (int64_t)64 * NSUB), (unsigned)ys);
-    if (S + 1 <= 11) hipLaunchKernelGGL((ce16_colpass_kernel<11, NSUB>), grid, dim3(256), 0, s, log_mask, b, c, (int)bs, S, steps_per);
-    else hipLaunchKernelGGL((ce16_colpass_kernel<MAXS1, NSUB>), grid, dim3(256), 0, s, log_mask, b, c, (int)bs, S, steps_per);
+// one pass of the split-operand route over nx rows of X against ny rows of Y (COL: X = score rows, the backward's column pass); returns its Y ranges
+template <bool COL, int NSUB>
+int launch_ce16_pass_n(const float* log_mask, const CeBufs& b, const Ce16Bufs& c, int64_t bs, int S, hipStream_t s, int* ys_out) {
+    const int64_t nx = COL ? bs * (S + 1) : bs * S, ny = COL ? bs * S : bs * (S + 1);
+    const int ys = ce16_ysplits(nx, ny, NSUB);
+    const int steps_per = (int)ceil_div(ceil_div(ny, (int64_t)32), (int64_t)ys);
+    const dim3 grid((unsigned)ceil_div(nx, (int64_t)64 * NSUB), (unsigned)ys);
+    with_rs1(S, [&](auto rs1) {
+        if constexpr (COL) hipLaunchKernelGGL((ce16_colpass_kernel<CE_RS1, NSUB>), grid, dim3(256), 0, s, log_mask, b, c, (int)bs, S, steps_per);
+        else hipLaunchKernelGGL((ce16_rowpass_kernel<CE_RS1, NSUB>), grid, dim3(256), 0, s, log_mask, b, c, (int)bs, S, steps_per);
+    });
     IISAN_LAUNCH_OK();
     *ys_out = ys;
     return IISAN_OK;
 }
 int g_ce16_nsub = 1;             // X blocks of 16 rows per wave (1 or 2)
+template <bool COL>
+int launch_ce16_pass(const float* log_mask, const CeBufs& b, const Ce16Bufs& c, int64_t bs, int S, hipStream_t s, int* ys_out) {
+    return g_ce16_nsub == 2 ? launch_ce16_pass_n<COL, 2>(log_mask, b, c, bs, S, s, ys_out) : launch_ce16_pass_n<COL, 1>(log_mask, b, c, bs, S, s, ys_out);
+}
 
 int check(int64_t bs, int S, int Ein) {
     IISAN_CHECK_SHAPE(bs > 0 && S >= 1 && S <= 63, "inbatch_ce: bs %lld / S %d unsupported", (long long)bs, S);
@@ -1373,7 +1385,8 @@ extern "C" size_t iisan_inbatch_ce_ws_bytes(int64_t bs, int32_t S) {
     return c.off;
 }
 
-// the forward call's token: a tag, the call shape and the route it took (1 = separate / generic passes, 2 = fused f32 row pass, 3 = split-operand passes)
+// the forward call's token: a tag, the call shape and the route it took (CE_ROUTE_*) — so that the backward call follows what THAT call
+// did, not the dev switch's later value, and the library keeps no per-call state
 static uint64_t ce_token(int64_t bs, int32_t S, int route) {
     return 0xCE00000000000000ull | ((uint64_t)(bs & 0xFFFFFFFFll) << 16) | ((uint64_t)(S & 0xFF) << 8) | (uint64_t)(route + 1);
 }
@@ -1382,6 +1395,8 @@ IISAN_DEV_KNOB(ce16_nsub, g_ce16_nsub);
 IISAN_DEV_KNOB(ce16_ys, g_ce16_ys);
 static int64_t g_cnt_ce16 = 0;            // forward calls on the split-operand route (route counter, common.h)
 IISAN_DEV_COUNTER(ce16, g_cnt_ce16);
+
+extern "C" int32_t iisan_inbatch_ce_route(int64_t bs, int32_t S) { return check(bs, S, E) == IISAN_OK ? ce_route(bs, S) : -1; }
 
 extern "C" int iisan_inbatch_ce_fwd(const int64_t* ids, const float* score, const float* prec, const float* log_mask,
                                     const float* pop_prob, int64_t n_pop, int64_t bs, int32_t S, int32_t Ein, float* loss,
@@ -1399,46 +1414,37 @@ extern "C" int iisan_inbatch_ce_fwd(const int64_t* ids, const float* score, cons
         return IISAN_EWORKSPACE;
     }
     const int64_t T = bs * S, M = bs * (S + 1);
+    const dim3 rows((unsigned)ceil_div(T, 16));
     hipLaunchKernelGGL(ce_prep_kernel, dim3((unsigned)ceil_div(M, 256)), dim3(256), 0, s, ids, log_mask, pop_prob, n_pop, b, bs, S);
     IISAN_LAUNCH_OK();
     hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(256), 0, s, log_mask, T, b.nvalid);
     IISAN_LAUNCH_OK();
-    if (ce16_ok(bs, S)) {
-        // split-operand route: amax -> images -> fused row pass per Y range -> combine (lse, row loss, d_prec for d_loss = 1 in the workspace)
-        IISAN_CHECK_SHAPE(fwd_token != nullptr, "inbatch_ce_fwd: fwd_token must not be null");
-        *fwd_token = ce_token(bs, S, 2);
-        ++g_cnt_ce16;
-        IISAN_HIP_OK(hipMemsetAsync(b16.amax, 0, 16, s));
-        hipLaunchKernelGGL(ce16_amax_kernel, dim3(64, 2), dim3(256), 0, s, prec, T * E, score, M * E, b16.amax);
-        IISAN_LAUNCH_OK();
-        hipLaunchKernelGGL(ce16_split_kernel, dim3((unsigned)ceil_div(M, 32), 2), dim3(256), 0, s, prec, T, score, M, b16);
-        IISAN_LAUNCH_OK();
-        int ys = 1;
-        if (g_ce16_nsub == 2) IISAN_TRY(launch_ce16_row<2>(log_mask, b, b16, bs, S, s, &ys));
-        else IISAN_TRY(launch_ce16_row<1>(log_mask, b, b16, bs, S, s, &ys));
-        hipLaunchKernelGGL(ce16_row_combine_kernel, dim3((unsigned)ceil_div(T * E, 256)), dim3(256), 0, s, score, log_mask, b, b16, (int)bs, S, ys);
-        IISAN_LAUNCH_OK();
-        hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, b.rowloss, T, b.nvalid, loss);
-        IISAN_LAUNCH_OK();
-        return IISAN_OK;
-    }
-    // fast path: the forward pass leaves d_prec (for d_loss = 1) in the workspace, the backward call only scales it — the
-    // route goes back to the caller as a token, so that the backward call follows what THIS call did, not the knob's later
-    // value, and the library keeps no per-call state
     IISAN_CHECK_SHAPE(fwd_token != nullptr, "inbatch_ce_fwd: fwd_token must not be null");
-    *fwd_token = ce_token(bs, S, fused_ok(bs, S) ? 1 : 0);
-    if (fused_ok(bs, S) && S + 1 <= 11)
-        hipLaunchKernelGGL((ce_rowpass_kernel<CE_FUSED, 11>), dim3((unsigned)ceil_div(T, 16)), dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, 0.f, (float*)nullptr, g_ce_dbg);
-    else if (fused_ok(bs, S))
-        hipLaunchKernelGGL((ce_rowpass_kernel<CE_FUSED, MAXS1>), dim3((unsigned)ceil_div(T, 16)), dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, 0.f, (float*)nullptr);
-    else if (rowpass_ok(bs, S) && S + 1 <= 11) hipLaunchKernelGGL((ce_rowpass_kernel<CE_FWD, 11>), dim3((unsigned)ceil_div(T, 16)), dim3(256), 0, s, prec, score,
-                       log_mask, b, (int)bs, S, 0.f, (float*)nullptr);
-    else if (rowpass_ok(bs, S)) hipLaunchKernelGGL((ce_rowpass_kernel<CE_FWD, MAXS1>), dim3((unsigned)ceil_div(T, 16)), dim3(256), 0, s, prec, score,
-                       log_mask, b, (int)bs, S, 0.f, (float*)nullptr);
-    else if (S + 1 <= 11) hipLaunchKernelGGL((ce_pass_kernel<CE_FWD, 11>), dim3((unsigned)ceil_div(T, 16)), dim3(256), 0, s, prec, score, log_mask, b, bs, S, 0.f,
-                       (float*)nullptr);
-    else hipLaunchKernelGGL((ce_pass_kernel<CE_FWD, MAXS1>), dim3((unsigned)ceil_div(T, 16)), dim3(256), 0, s, prec, score, log_mask, b, bs, S, 0.f,
-                       (float*)nullptr);
+    const int route = ce_route(bs, S);
+    *fwd_token = ce_token(bs, S, route);
+    float* const none = nullptr;
+    switch (route) {
+        case CE_ROUTE_SPLIT16: {     // amax -> images -> fused row pass per Y range -> combine (lse, row loss, d_prec for d_loss = 1 in the workspace)
+            ++g_cnt_ce16;
+            IISAN_HIP_OK(hipMemsetAsync(b16.amax, 0, 16, s));
+            hipLaunchKernelGGL(ce16_amax_kernel, dim3(64, 2), dim3(256), 0, s, prec, T * E, score, M * E, b16.amax);
+            IISAN_LAUNCH_OK();
+            hipLaunchKernelGGL(ce16_split_kernel, dim3((unsigned)ceil_div(M, 32), 2), dim3(256), 0, s, prec, T, score, M, b16);
+            IISAN_LAUNCH_OK();
+            int ys = 1;
+            IISAN_TRY(launch_ce16_pass<false>(log_mask, b, b16, bs, S, s, &ys));
+            hipLaunchKernelGGL(ce16_row_combine_kernel, dim3((unsigned)ceil_div(T * E, 256)), dim3(256), 0, s, score, log_mask, b, b16, (int)bs, S, ys);
+            break;
+        }
+        case CE_ROUTE_FUSED:         // the forward pass leaves d_prec (for d_loss = 1) in the workspace, the backward call only scales it
+            with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_FUSED, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, 0.f, none); });
+            break;
+        case CE_ROUTE_ROWPASS:
+            with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_FWD, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, 0.f, none); });
+            break;
+        default:
+            with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_pass_kernel<CE_FWD, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, bs, S, 0.f, none); });
+    }
     IISAN_LAUNCH_OK();
     hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, b.rowloss, T, b.nvalid, loss);
     IISAN_LAUNCH_OK();
@@ -1460,41 +1466,37 @@ extern "C" int iisan_inbatch_ce_bwd(const int64_t* ids, const float* score, cons
         return IISAN_EWORKSPACE;
     }
     const int64_t T = bs * S, M = bs * (S + 1);
-    const bool split16 = fwd_token == ce_token(bs, S, 2);
-    const bool fused = split16 || fwd_token == ce_token(bs, S, 1);
-    if (split16) {            // whatever the dev switch says by now: the images this route needs are in the workspace
-        hipLaunchKernelGGL(ce_scale_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(T * E / 4, 256), 1024)), dim3(256), 0, s, b.dprec, d_loss, d_prec, T * E / 4);
-        IISAN_LAUNCH_OK();
-        int ys = 1;
-        if (g_ce16_nsub == 2) IISAN_TRY(launch_ce16_col<2>(log_mask, b, b16, bs, S, s, &ys));
-        else IISAN_TRY(launch_ce16_col<1>(log_mask, b, b16, bs, S, s, &ys));
-        hipLaunchKernelGGL(ce16_col_combine_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(M * E / 4, 256), 2048)), dim3(256), 0, s, b, b16, M * E / 4, ys, d_loss, d_score);
-        IISAN_LAUNCH_OK();
-        return IISAN_OK;
-    }
-    if (!fused && fwd_token != ce_token(bs, S, 0)) {
+    const dim3 rows((unsigned)ceil_div(T, 16)), cols((unsigned)ceil_div(M, 16));
+    int route = -1;           // the forward's, whatever the dev switch says by now: what this route needs is in the workspace
+    for (int r = CE_ROUTE_GENERIC; r <= CE_ROUTE_SPLIT16; ++r)
+        if (fwd_token == ce_token(bs, S, r)) route = r;
+    if (route < 0) {
         iisan_set_error("inbatch_ce_bwd: fwd_token %llx is not what inbatch_ce_fwd returns for bs = %lld, S = %d", (unsigned long long)fwd_token, (long long)bs, S);
         return IISAN_EBADSHAPE;
     }
-    if (fused)        // d_prec for d_loss = 1 is in the workspace (whatever the dev switch ce_fast says by now)
+    // d_prec: scaled from the forward's d_prec for d_loss = 1, or its own row pass
+    if (route == CE_ROUTE_FUSED || route == CE_ROUTE_SPLIT16)
         hipLaunchKernelGGL(ce_scale_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(T * E / 4, 256), 1024)), dim3(256), 0, s, b.dprec, d_loss, d_prec, T * E / 4);
-    else if (rowpass_ok(bs, S) && S + 1 <= 11) hipLaunchKernelGGL((ce_rowpass_kernel<CE_DPREC, 11>), dim3((unsigned)ceil_div(T, 16)), dim3(256), 0, s, prec, score,
-                       log_mask, b, (int)bs, S, d_loss, d_prec);
-    else if (rowpass_ok(bs, S)) hipLaunchKernelGGL((ce_rowpass_kernel<CE_DPREC, MAXS1>), dim3((unsigned)ceil_div(T, 16)), dim3(256), 0, s, prec, score,
-                       log_mask, b, (int)bs, S, d_loss, d_prec);
-    else if (S + 1 <= 11) hipLaunchKernelGGL((ce_pass_kernel<CE_DPREC, 11>), dim3((unsigned)ceil_div(T, 16)), dim3(256), 0, s, prec, score, log_mask, b, bs, S,
-                       d_loss, d_prec);
-    else hipLaunchKernelGGL((ce_pass_kernel<CE_DPREC, MAXS1>), dim3((unsigned)ceil_div(T, 16)), dim3(256), 0, s, prec, score, log_mask, b, bs, S,
-                       d_loss, d_prec);
+    else if (route == CE_ROUTE_ROWPASS)
+        with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_DPREC, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, d_loss, d_prec); });
+    else
+        with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_pass_kernel<CE_DPREC, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_prec); });
     IISAN_LAUNCH_OK();
-    if (rowpass_ok(bs, S) && S + 1 <= 11) hipLaunchKernelGGL((ce_colpass_kernel<11>), dim3((unsigned)ceil_div(M, 16)), dim3(256), 0, s, prec, score,
-                       log_mask, b, (int)bs, S, d_loss, d_score);
-    else if (rowpass_ok(bs, S)) hipLaunchKernelGGL((ce_colpass_kernel<MAXS1>), dim3((unsigned)ceil_div(M, 16)), dim3(256), 0, s, prec, score,
-                       log_mask, b, (int)bs, S, d_loss, d_score);
-    else if (S + 1 == 11) hipLaunchKernelGGL((ce_pass_kernel<CE_DSCORE, 11>), dim3((unsigned)ceil_div(M, 16)), dim3(256), 0, s, prec, score, log_mask, b, bs, S,
-                       d_loss, d_score);
-    else hipLaunchKernelGGL((ce_pass_kernel<CE_DSCORE, MAXS1>), dim3((unsigned)ceil_div(M, 16)), dim3(256), 0, s, prec, score, log_mask, b, bs, S,
-                       d_loss, d_score);
+    // d_score: the column pass
+    if (route == CE_ROUTE_SPLIT16) {
+        int ys = 1;
+        IISAN_TRY(launch_ce16_pass<true>(log_mask, b, b16, bs, S, s, &ys));
+        hipLaunchKernelGGL(ce16_col_combine_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(M * E / 4, 256), 2048)), dim3(256), 0, s, b, b16, M * E / 4, ys, d_loss, d_score);
+    } else if (route != CE_ROUTE_GENERIC) {
+        with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_colpass_kernel<CE_RS1>), cols, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, d_loss, d_score); });
+    } else if (S + 1 == 11) {
+        // == 11, not <= 11: in its CE_DSCORE mode ce_pass_kernel holds no ids in registers (RS1 sizes only the unused `rid`) and RS1 = 11 selects
+        // the id scan with compile-time indices, which that kernel takes for S + 1 == 11 alone — for a shorter sequence the instantiation would
+        // run the very loop of the MAXS1 one, so those stay there
+        hipLaunchKernelGGL((ce_pass_kernel<CE_DSCORE, 11>), cols, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_score);
+    } else {
+        hipLaunchKernelGGL((ce_pass_kernel<CE_DSCORE, MAXS1>), cols, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_score);
+    }
     IISAN_LAUNCH_OK();
     return IISAN_OK;
 }

@@ -394,6 +394,16 @@ int x3p_tile_n(int64_t M, int64_t N);          // gemm16_x3.hip: 128 or 192 colu
 struct AmaxBatch { const float* x[16]; int64_t rows[16], cols[16], ld[16]; uint32_t* out[16]; };
 int launch_amax_batch(const AmaxBatch& b, int n, hipStream_t s);
 
+// The fusion operands of one tower at one SANB step, as the executor of sidenet.hip (Ctx::fuse_operands) hands them to whichever
+// launcher forms F or its backward: the fusion kernels, the fused SANB step, the fusion-fed down projection and the gate-fused dF product.
+// Host side only — every kernel-argument struct keeps its own layout and is filled from this.
+//   type 0: F = g·a + (1-g)·prev ;  type 1: F = prev + g·a + (1-g)·b   (not gated: plain sums)
+struct FuseOperands {
+    const float* a; const float* b; const float* prev;      // row r at a + r*lda (floats); prev null = zeros
+    int64_t lda, ldb, ldp;
+    const float* gate;                                       // device scalar theta, null = not gated
+    int32_t D, type;
+};
 struct Gemm32Prob {
     const float* A; const float* B; const float* bias; const float* resid; const float* act_src; float* C;
     int64_t M; int32_t N; int64_t K;
@@ -417,7 +427,7 @@ struct Gemm32Prob {
 // fusion-fed down projection of the separate SANB launches (gemm32.hip: gemm32_n64f_kernel):  F = fuse(a, b, prev) is formed in the
 // registers that feed the product, written out once, and  U = F·W^T + bias,  A = act(U)  leave together
 struct N64FDesc {
-    const float* a; const float* b; const float* prev; int64_t lda, ldb, ldp; const float* gate; int32_t type;   // as FuseTower (sidenet.hip)
+    FuseOperands f;                // what F is made of (f.D is not read: K below is the width)
     float* F;                      // [M, K] (ld K)
     const float* W; int32_t ldw;   // [64, K]
     const float* bias;             // [64]
@@ -454,7 +464,7 @@ int launch_colsum(const float* const* X, float* const* out, const int64_t* M, co
 
 // fused SANB step (sanb.hip): one tower of one launch, as plain pointers (the executor of sidenet.hip fills it)
 struct SanbTowerDesc {
-    const float* a; const float* b; const float* prev; int64_t lda, ldb, ldp; const float* gate; int32_t D, type;
+    FuseOperands f;
     const float* Wd; const float* bd; const float* Wu; const float* bu;
     float* F; float* U; float* A; float* O;
     const float* dO; const float* Upre; float* dU; float* dprev; float* da; float* db; float* dgate; float* dbu; float* dbd;

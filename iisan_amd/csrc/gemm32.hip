@@ -861,28 +861,41 @@ __global__ __launch_bounds__(256) void gemm32_reduce_kernel(ReduceBatch rb, int 
 thread_local float* g_scratch = nullptr;
 thread_local size_t g_scratch_floats = 0;
 
-// launch-shape heuristics (constants since round 5; tools/step_ab.py measured them): workgroups wanted before the row tile shrinks /
-// before split-K stops adding slices
-static constexpr int g_tm_thresh = 512, g_splitk_target = 1024;   // tools/step_ab.py (MI355X): row tiles shrink below 512 workgroups: Versa 9.88 -> 9.55 ms, Cached unchanged; split-K target 512 or 2048: no gain
-
+template <int FLAGS, bool FAST, int DEPTH>
+void launch_tiled(const Gemm32Batch& b, dim3 grid, int tm, int epi, hipStream_t s) {
+    if (tm == 64) hipLaunchKernelGGL((gemm32_kernel<FLAGS, 64, FAST, DEPTH>), grid, dim3(256), 0, s, b, epi);
+    else if (tm == 32) hipLaunchKernelGGL((gemm32_kernel<FLAGS, 32, FAST, DEPTH>), grid, dim3(256), 0, s, b, epi);
+    else hipLaunchKernelGGL((gemm32_kernel<FLAGS, 16, FAST, DEPTH>), grid, dim3(256), 0, s, b, epi);
+}
 template <int FLAGS>
 int launch_flags(const Gemm32Batch& b, dim3 grid, int tm, int epi, bool fast, bool deep, hipStream_t s) {
-    if constexpr ((FLAGS & (G32_TA | G32_TB)) == (G32_TA | G32_TB)) {
-        if (deep && fast) {          // long-K weight gradients: three K-tiles in flight
-            if (tm == 64) hipLaunchKernelGGL((gemm32_kernel<FLAGS, 64, true, 3>), grid, dim3(256), 0, s, b, epi);
-            else if (tm == 32) hipLaunchKernelGGL((gemm32_kernel<FLAGS, 32, true, 3>), grid, dim3(256), 0, s, b, epi);
-            else hipLaunchKernelGGL((gemm32_kernel<FLAGS, 16, true, 3>), grid, dim3(256), 0, s, b, epi);
-            IISAN_LAUNCH_OK();
-            return IISAN_OK;
-        }
+    constexpr bool DW = (FLAGS & (G32_TA | G32_TB)) == (G32_TA | G32_TB);      // the only layout with a three-deep instantiation
+    if (DW && deep) launch_tiled<FLAGS, true, DW ? 3 : 2>(b, grid, tm, epi, s);
+    else if (fast) launch_tiled<FLAGS, true, 2>(b, grid, tm, epi, s);
+    else launch_tiled<FLAGS, false, 2>(b, grid, tm, epi, s);
+    IISAN_LAUNCH_OK();
+    return IISAN_OK;
+}
+// indexed by the structural flags: TA | TB << 1 | ACCUM << 2
+constexpr int (*g_tiled[8])(const Gemm32Batch&, dim3, int, int, bool, bool, hipStream_t) = {
+    launch_flags<0>, launch_flags<G32_TA>, launch_flags<G32_TB>, launch_flags<G32_TA | G32_TB>,
+    launch_flags<G32_ACCUM>, launch_flags<G32_TA | G32_ACCUM>, launch_flags<G32_TB | G32_ACCUM>, launch_flags<G32_TA | G32_TB | G32_ACCUM>};
+
+// The K-splits that own a non-empty K range: the kernels give split y the K-tiles [y, y + 1) * ceil(ktiles / splits) and a split whose
+// range is empty writes nothing — its partial would be read uninitialised by the reducer.
+int nonempty_splits(int64_t ktiles, int splits) { return (int)ceil_div(ktiles, ceil_div(ktiles, (int64_t)splits)); }
+
+// Split-K partials -> C.  The caller has filled rb.p (the problem as the reducer sees it: C, bias, residual, act_src), rb.P, rb.stride
+// and rb.cs; `splitk` is the launch's split count (a problem with a shorter K than its launch mates owns fewer of them).
+int launch_reduce(ReduceBatch& rb, int n, int splitk, int epi, hipStream_t s) {
+    int64_t max_mn = 0;
+    for (int i = 0; i < n; ++i) {
+        rb.ns[i] = nonempty_splits(ceil_div(rb.p[i].K, (int64_t)TK), splitk);
+        if (rb.p[i].M * rb.p[i].N > max_mn) max_mn = rb.p[i].M * rb.p[i].N;
     }
-    if (fast) {
-        if (tm == 64) hipLaunchKernelGGL((gemm32_kernel<FLAGS, 64, true>), grid, dim3(256), 0, s, b, epi);
-        else if (tm == 32) hipLaunchKernelGGL((gemm32_kernel<FLAGS, 32, true>), grid, dim3(256), 0, s, b, epi);
-        else hipLaunchKernelGGL((gemm32_kernel<FLAGS, 16, true>), grid, dim3(256), 0, s, b, epi);
-    } else if (tm == 64) hipLaunchKernelGGL((gemm32_kernel<FLAGS, 64, false>), grid, dim3(256), 0, s, b, epi);
-    else if (tm == 32) hipLaunchKernelGGL((gemm32_kernel<FLAGS, 32, false>), grid, dim3(256), 0, s, b, epi);
-    else hipLaunchKernelGGL((gemm32_kernel<FLAGS, 16, false>), grid, dim3(256), 0, s, b, epi);
+    int64_t blocks = ceil_div(max_mn, 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(gemm32_reduce_kernel, dim3((unsigned)blocks, 1, (unsigned)n), dim3(256), 0, s, rb, splitk, epi);
     IISAN_LAUNCH_OK();
     return IISAN_OK;
 }
@@ -908,11 +921,16 @@ bool gemm32_n64f_ok(const N64FDesc* d, int n) {
     if (!g_use_n64f || n < 1 || n > 3) return false;
     for (int i = 0; i < n; ++i) {
         const N64FDesc& q = d[i];
-        if (q.K < 256 || (q.K & 63) || (q.lda & 3) || (q.ldw & 3) || (q.prev && (q.ldp & 3)) || (q.type == 1 && (!q.b || (q.ldb & 3))) || !q.a || !q.bias ||
-            (((uintptr_t)q.a | (uintptr_t)q.b | (uintptr_t)q.prev | (uintptr_t)q.F | (uintptr_t)q.W | (uintptr_t)q.bias | (uintptr_t)q.U | (uintptr_t)q.A) & 15))
+        const FuseOperands& f = q.f;
+        if (q.K < 256 || (q.K & 63) || (f.lda & 3) || (q.ldw & 3) || (f.prev && (f.ldp & 3)) || (f.type == 1 && (!f.b || (f.ldb & 3))) || !f.a || !q.bias ||
+            (((uintptr_t)f.a | (uintptr_t)f.b | (uintptr_t)f.prev | (uintptr_t)q.F | (uintptr_t)q.W | (uintptr_t)q.bias | (uintptr_t)q.U | (uintptr_t)q.A) & 15))
             return false;
     }
     return true;
+}
+static void fill(N64FProb& q, const N64FDesc& d) {
+    q.a = d.f.a; q.b = d.f.b; q.prev = d.f.prev; q.lda = d.f.lda; q.ldb = d.f.ldb; q.ldp = d.f.ldp; q.gate = d.f.gate; q.type = d.f.type;
+    q.F = d.F; q.W = d.W; q.ldw = d.ldw; q.bias = d.bias; q.U = d.U; q.A = d.A; q.M = d.M; q.K = d.K;
 }
 static int launch_gemm32_n64f_impl(const N64FDesc* d, int n, int gelu, hipStream_t s) {
     IISAN_CHECK_SHAPE(gemm32_n64f_ok(d, n), "gemm32_n64f: unsupported problem");
@@ -921,9 +939,7 @@ static int launch_gemm32_n64f_impl(const N64FDesc* d, int n, int gelu, hipStream
     int64_t maxM = 0;
     int max_k = 0;
     for (int i = 0; i < n; ++i) {
-        N64FProb& q = nb.p[i];
-        q.a = d[i].a; q.b = d[i].b; q.prev = d[i].prev; q.lda = d[i].lda; q.ldb = d[i].ldb; q.ldp = d[i].ldp; q.gate = d[i].gate; q.type = d[i].type;
-        q.F = d[i].F; q.W = d[i].W; q.ldw = d[i].ldw; q.bias = d[i].bias; q.U = d[i].U; q.A = d[i].A; q.M = d[i].M; q.K = d[i].K;
+        fill(nb.p[i], d[i]);
         if (d[i].M > maxM) maxM = d[i].M;
         if (d[i].K > max_k) max_k = d[i].K;
     }
@@ -962,29 +978,48 @@ static int launch_gemm32_n64f_impl(const N64FDesc* d, int n, int gelu, hipStream
     IISAN_LAUNCH_OK();
     if (ks < 2) return IISAN_OK;
     ReduceBatch rb{};
-    int64_t max_mn = 0;
     for (int i = 0; i < n; ++i) {
-        Gemm32Prob q{};
+        Gemm32Prob& q = rb.p[i];
         q.C = d[i].A; q.ldc = 64; q.bias = d[i].bias; q.act_src = d[i].U; q.M = d[i].M; q.N = 64; q.K = d[i].K; q.ldr = 64;
-        rb.p[i] = q;
         rb.P[i] = nb.p[i].P;
         rb.stride[i] = nb.p[i].pstride;
-        const int64_t ktiles = d[i].K / TK, per = ceil_div(ktiles, (int64_t)ks);
-        rb.ns[i] = (int32_t)ceil_div(ktiles, per);
-        if (d[i].M * 64 > max_mn) max_mn = d[i].M * 64;
     }
-    int64_t blocks = ceil_div(max_mn, 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(gemm32_reduce_kernel, dim3((unsigned)blocks, 1, (unsigned)n), dim3(256), 0, s, rb, ks, (gelu ? G32_GELU : G32_RELU) | G32_PREACT);
-    IISAN_LAUNCH_OK();
-    return IISAN_OK;
+    return launch_reduce(rb, n, ks, (gelu ? G32_GELU : G32_RELU) | G32_PREACT, s);
 }
 
-// Shapes the K = 64 kernel takes (shared by launch_gemm32's own dispatch test and the gate-fused entry below)
+// ---- K = 64 kernel: the shapes it takes, its launch geometry and its kernel arguments — shared by launch_gemm32's plan and the
+// gate-fused entry below
 static bool k64_shape_ok(const Gemm32Prob& q) {
     return q.K == 64 && q.N >= 256 && (q.N & 63) == 0 && !q.act_src && q.ksplit_stride == 0 &&
            (q.lda & 3) == 0 && (q.ldb & 3) == 0 && (q.ldc & 3) == 0 && (!q.resid || (q.ldr & 3) == 0) &&
            (((uintptr_t)q.A | (uintptr_t)q.B | (uintptr_t)q.C | (uintptr_t)q.resid | (uintptr_t)q.bias) & 15) == 0;
+}
+struct K64Grid { int64_t rt; int nblk, ny; };      // 64-row tiles, 64-column blocks per workgroup, column slices
+static K64Grid k64_grid(const Gemm32Prob* probs, int nprob) {
+    int64_t maxM = 0;
+    int maxnb = 0;
+    for (int i = 0; i < nprob; ++i) {
+        if (probs[i].M > maxM) maxM = probs[i].M;
+        if ((probs[i].N >> 6) > maxnb) maxnb = probs[i].N >> 6;
+    }
+    K64Grid g;
+    g.rt = ceil_div(maxM, 64);
+    g.nblk = 4;                                      // 64-column blocks per workgroup: fewer while the launch is small
+    while (g.nblk > 1 && g.rt * ceil_div(maxnb, g.nblk) * nprob < 1024) g.nblk >>= 1;
+    // One 64-row tile per workgroup.  (Persistent workgroups that keep their W slice and walk several row tiles were
+    // slower at every size tried — Versa 5.86 vs 5.65 ms per step, Cached on this route 6.41 vs 6.25: a tile's operand
+    // and first residual round trips are exposed once per tile and the hardware's own workgroup dispatch balances better.)
+    g.ny = (int)ceil_div(maxnb, g.nblk);
+    return g;
+}
+static void fill_k64(K64Batch& kb, const Gemm32Prob* probs, int nprob) {
+    for (int i = 0; i < nprob; ++i) {
+        const Gemm32Prob& q = probs[i];
+        K64Prob& k = kb.p[i];
+        k = K64Prob{};
+        k.A = q.A; k.W = q.B; k.bias = q.bias; k.resid = q.resid; k.C = q.C; k.M = q.M; k.N = q.N;
+        k.lda = q.lda; k.ldw = q.ldb; k.ldc = q.ldc; k.ldr = q.ldr;
+    }
 }
 static int g_use_k64_gate = 1;
 IISAN_DEV_KNOB(gemm32_k64_gate, g_use_k64_gate);
@@ -1004,94 +1039,87 @@ bool gemm32_k64_gate_ok(const Gemm32Prob* probs, const K64Gate* gates, int nprob
 static int launch_gemm32_k64_gate_impl(const Gemm32Prob* probs, const K64Gate* gates, int nprob, hipStream_t s) {
     IISAN_CHECK_SHAPE(gemm32_k64_gate_ok(probs, gates, nprob), "gemm32_k64_gate: unsupported problem");
     K64Batch kb{};
-    int64_t maxM = 0;
-    int maxnb = 0;
+    fill_k64(kb, probs, nprob);
     for (int i = 0; i < nprob; ++i) {
-        const Gemm32Prob& q = probs[i];
         K64Prob& k = kb.p[i];
-        k.A = q.A; k.W = q.B; k.bias = q.bias; k.resid = q.resid; k.C = q.C; k.M = q.M; k.N = q.N;
-        k.lda = q.lda; k.ldw = q.ldb; k.ldc = q.ldc; k.ldr = q.ldr;
         k.gate = gates[i].gate; k.ga = gates[i].ga; k.go = gates[i].go; k.ldga = gates[i].ldga; k.ldgo = gates[i].ldgo;
         k.dgate = gates[i].dgate; k.scale_prev = gates[i].scale_prev; k.store = gates[i].store;
         k.d2 = gates[i].d2; k.ldd2 = gates[i].ldd2; k.d2_is_b = gates[i].d2_is_b;
-        if (q.M > maxM) maxM = q.M;
-        if ((q.N >> 6) > maxnb) maxnb = q.N >> 6;
     }
-    const int64_t rt = ceil_div(maxM, 64);
-    int nblk = 4;
-    while (nblk > 1 && rt * ceil_div(maxnb, nblk) * nprob < 1024) nblk >>= 1;
-    IISAN_CHECK_SHAPE(rt < (1ll << 31), "gemm32: grid too large");
-    const dim3 grid((unsigned)rt, (unsigned)ceil_div(maxnb, nblk), (unsigned)nprob);
-    const size_t lds = (size_t)64 * (64 * nblk + 4) * sizeof(float);
+    const K64Grid g = k64_grid(probs, nprob);
+    IISAN_CHECK_SHAPE(g.rt < (1ll << 31), "gemm32: grid too large");
+    const dim3 grid((unsigned)g.rt, (unsigned)g.ny, (unsigned)nprob);
+    const size_t lds = (size_t)64 * (64 * g.nblk + 4) * sizeof(float);
     static OncePerDevice attr;
     if (attr.first())
         IISAN_HIP_OK(hipFuncSetAttribute((const void*)gemm32_k64_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 68 * 4));
     ++g_cnt_k64;
-    hipLaunchKernelGGL((gemm32_k64_kernel<true, true>), grid, dim3(256), lds, s, kb, nblk);
+    hipLaunchKernelGGL((gemm32_k64_kernel<true, true>), grid, dim3(256), lds, s, kb, g.nblk);
     IISAN_LAUNCH_OK();
     return IISAN_OK;
 }
 
-static int launch_gemm32_impl(const Gemm32Prob* probs, int nprob, int flags, hipStream_t s) {
-    IISAN_CHECK_SHAPE(nprob >= 1 && nprob <= G32_MAXP, "gemm32: 1..%d problems per launch (got %d)", G32_MAXP, nprob);
-    Gemm32Batch b{};
-    int64_t min_k = INT64_MAX;
+// ---- launch_gemm32: plan, then run ---------------------------------------------------------------------------------------------
+// What one call does, decided before anything is launched.  plan_gemm32 is pure host logic: it touches no device memory, allocates
+// nothing and reads only the shapes, leading dimensions and alignments of the problems, the dev switches and iisan_cu_count().
+enum { G32K_REJECTED = -1, G32K_TILED = 0, G32K_K64 = 1, G32K_DW = 2,      // gemm32_kernel / gemm32_k64_kernel / gemm32_dw_kernel
+       G32K_SPLIT_K64 = 3 };    // a mixed group: its nk64 K = 64 members as one launch_gemm32 call, the rest as another
+enum { G32S_NONE = 0,           // the product writes (or atomically adds to) C itself
+       G32S_EPILOGUE = 1,       // raw split-K partials in the scratch; the reducer applies bias / activation / residual to the sums
+       G32S_ADD_C = 2 };        // raw split-K partials in the scratch; the reducer adds them to C ("+=" in a fixed order)
+enum { G32C_NONE = 0, G32C_FOLDED = 1, G32C_OWN_LAUNCH = 2 };      // the column sums of A (Gemm32Prob::colsum_a)
+struct Gemm32Plan {
+    int kernel;
+    int tm, splitk;             // row-tile height; K ranges of the grid (with G32S_ADD_C: non-empty ones only)
+    int scratch;
+    bool fast, deep;            // tiled kernel: the unconditional fetch; three K-tiles in flight
+    int colsum;
+    int nblk;                   // G32K_K64: 64-column blocks per workgroup
+    int64_t gx; int gy, gz;     // the product launch's grid
+    int nk64;                   // G32K_SPLIT_K64: members of the K = 64 launch
+};
+
+// launch-shape heuristics (constants since round 5; tools/step_ab.py measured them): workgroups wanted before the row tile shrinks /
+// before split-K stops adding slices
+static constexpr int g_tm_thresh = 512, g_splitk_target = 1024;   // tools/step_ab.py (MI355X): row tiles shrink below 512 workgroups: Versa 9.88 -> 9.55 ms, Cached unchanged; split-K target 512 or 2048: no gain
+
+// floats of one split-K partial of problem q in the scratch (+ M floats behind the C partial for the A operand's column sums, where
+// gemm32_dw_kernel computes them)
+static int64_t partial_floats(const Gemm32Prob& q, bool with_colsum) {
+    return (int64_t)align_up((size_t)(q.M * q.N + (with_colsum && q.colsum_a ? q.M : 0)), 64);
+}
+static bool partials_fit(const Gemm32Prob* probs, int nprob, int splitk, bool with_colsum, size_t scratch_floats) {
+    int64_t need = 0;
+    for (int i = 0; i < nprob; ++i) need += (int64_t)splitk * partial_floats(probs[i], with_colsum);
+    return (size_t)need <= scratch_floats;
+}
+
+static Gemm32Plan plan_gemm32(const Gemm32Prob* probs, int nprob, int flags, size_t scratch_floats) {
+    Gemm32Plan pl{};
+    pl.kernel = G32K_REJECTED;
+    if (nprob < 1 || nprob > G32_MAXP) { iisan_set_error("gemm32: 1..%d problems per launch (got %d)", G32_MAXP, nprob); return pl; }
+    int64_t min_k = INT64_MAX, max_k = 0;
+    bool any_colsum = false;
     for (int i = 0; i < nprob; ++i) {
-        b.p[i] = probs[i];
-        IISAN_CHECK_SHAPE(probs[i].M > 0 && probs[i].N > 0 && probs[i].K > 0, "gemm32: empty problem %d", i);
+        if (!(probs[i].M > 0 && probs[i].N > 0 && probs[i].K > 0)) { iisan_set_error("gemm32: empty problem %d", i); return pl; }
         if (probs[i].K < min_k) min_k = probs[i].K;
+        if (probs[i].K > max_k) max_k = probs[i].K;
+        any_colsum = any_colsum || probs[i].colsum_a;
     }
+    const bool have_scratch = scratch_floats > 0;
     // K = 64 products with a wide N and a plain epilogue (bias / residual): gemm32_k64_kernel
-    if ((flags & ~G32_TB) == 0 && g_use_k64 && nprob > 1) {
+    if ((flags & ~G32_TB) == 0 && g_use_k64) {
+        int nk64 = 0;
+        for (int i = 0; i < nprob; ++i) nk64 += k64_shape_ok(probs[i]) ? 1 : 0;
         // a group that mixes K = 64 products with others (Versa's fc backward: dO = dY Wf is [1408, 64] x [64 -> 1024 | 8192] for the two
         // towers and [1408, 1024] x [1024 -> 1024] for the inter-modal one) used to go to the tiled kernel as a whole — one K-tile per
         // workgroup for the K = 64 members: 68.6 us for 46 MB of output (round 6).  The K = 64 members get their own launch.
-        Gemm32Prob yes[G32_MAXP], no[G32_MAXP];
-        int ny = 0, nn = 0;
-        for (int i = 0; i < nprob; ++i) { if (k64_shape_ok(probs[i])) yes[ny++] = probs[i]; else no[nn++] = probs[i]; }
-        if (ny > 0 && nn > 0) {
-            IISAN_TRY(launch_gemm32_impl(yes, ny, flags, s));
-            return launch_gemm32_impl(no, nn, flags, s);
-        }
-    }
-    if ((flags & ~G32_TB) == 0 && g_use_k64 && nprob <= 4) {      // (K64Batch holds four)
-        bool ok = true;
-        int64_t maxM = 0;
-        int maxnb = 0;
-        K64Batch kb{};
-        for (int i = 0; i < nprob && ok; ++i) {
-            const Gemm32Prob& q = probs[i];
-            ok = q.K == 64 && q.N >= 256 && (q.N & 63) == 0 && !q.act_src && q.ksplit_stride == 0 &&
-                 (q.lda & 3) == 0 && (q.ldb & 3) == 0 && (q.ldc & 3) == 0 && (!q.resid || (q.ldr & 3) == 0) &&
-                 (((uintptr_t)q.A | (uintptr_t)q.B | (uintptr_t)q.C | (uintptr_t)q.resid | (uintptr_t)q.bias) & 15) == 0;
-            kb.p[i] = K64Prob{};
-            kb.p[i].A = q.A; kb.p[i].W = q.B; kb.p[i].bias = q.bias; kb.p[i].resid = q.resid; kb.p[i].C = q.C; kb.p[i].M = q.M; kb.p[i].N = q.N;
-            kb.p[i].lda = q.lda; kb.p[i].ldw = q.ldb; kb.p[i].ldc = q.ldc; kb.p[i].ldr = q.ldr;
-            if (q.M > maxM) maxM = q.M;
-            if ((q.N >> 6) > maxnb) maxnb = q.N >> 6;
-        }
-        if (ok) {
-            const int64_t rt = ceil_div(maxM, 64);
-            int nblk = 4;                                    // 64-column blocks per workgroup: fewer while the launch is small
-            while (nblk > 1 && rt * ceil_div(maxnb, nblk) * nprob < 1024) nblk >>= 1;
-            // One 64-row tile per workgroup.  (Persistent workgroups that keep their W slice and walk several row tiles were
-            // slower at every size tried — Versa 5.86 vs 5.65 ms per step, Cached on this route 6.41 vs 6.25: a tile's operand
-            // and first residual round trips are exposed once per tile and the hardware's own workgroup dispatch balances better.)
-            const int64_t ny = ceil_div(maxnb, nblk);
-            IISAN_CHECK_SHAPE(rt < (1ll << 31), "gemm32: grid too large");
-            const dim3 grid((unsigned)rt, (unsigned)ny, (unsigned)nprob);
-            const size_t lds = (size_t)64 * (64 * nblk + 4) * sizeof(float) > (size_t)64 * nblk * 68 * sizeof(float)
-                                   ? (size_t)64 * (64 * nblk + 4) * sizeof(float) : (size_t)64 * nblk * 68 * sizeof(float);
-            static OncePerDevice attr;
-            if (attr.first()) {
-                IISAN_HIP_OK(hipFuncSetAttribute((const void*)gemm32_k64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 68 * 4));
-                IISAN_HIP_OK(hipFuncSetAttribute((const void*)gemm32_k64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 68 * 4));
-            }
-            ++g_cnt_k64;
-            if (flags & G32_TB) hipLaunchKernelGGL(gemm32_k64_kernel<true>, grid, dim3(256), lds, s, kb, nblk);
-            else hipLaunchKernelGGL(gemm32_k64_kernel<false>, grid, dim3(256), lds, s, kb, nblk);
-            IISAN_LAUNCH_OK();
-            return IISAN_OK;
+        if (nk64 > 0 && nk64 < nprob) { pl.kernel = G32K_SPLIT_K64; pl.nk64 = nk64; return pl; }
+        if (nk64 == nprob && nprob <= 4) {       // (K64Batch holds four)
+            const K64Grid g = k64_grid(probs, nprob);
+            if (g.rt >= (1ll << 31)) { iisan_set_error("gemm32: grid too large"); return pl; }
+            pl.kernel = G32K_K64; pl.nblk = g.nblk; pl.gx = g.rt; pl.gy = g.ny; pl.gz = nprob;
+            return pl;
         }
     }
     auto tiles_for = [&](int tm) {
@@ -1104,21 +1132,19 @@ static int launch_gemm32_impl(const Gemm32Prob* probs, int nprob, int flags, hip
     };
     // row-tile height: the tallest that still gives the chip ~one workgroup per CU (weight-gradient launches spread
     // K instead and keep 64)
-    int TM = 64;
-    if (!(flags & G32_ACCUM)) {
-        if (tiles_for(64) * nprob < g_tm_thresh) TM = tiles_for(32) * nprob >= g_tm_thresh ? 32 : 16;
-    }
-    const int64_t max_tiles = tiles_for(TM);
-    IISAN_CHECK_SHAPE(max_tiles < (1ll << 31), "gemm32: grid too large");
+    pl.tm = 64;
+    if (!(flags & G32_ACCUM) && tiles_for(64) * nprob < g_tm_thresh) pl.tm = tiles_for(32) * nprob >= g_tm_thresh ? 32 : 16;
+    const int64_t max_tiles = tiles_for(pl.tm);
+    if (max_tiles >= (1ll << 31)) { iisan_set_error("gemm32: grid too large"); return pl; }
+    pl.gx = max_tiles; pl.gz = nprob;
     // weight-gradient shape on whole 64-tiles: gemm32_dw_kernel (needs the scratch route for its raw split-K partials)
-    bool dw_ok = g_use_dw && (flags & (G32_TA | G32_TB | G32_ACCUM)) == (G32_TA | G32_TB | G32_ACCUM) && (flags & ~(G32_TA | G32_TB | G32_ACCUM)) == 0 &&
-                 g_scratch;
+    bool dw_ok = g_use_dw && flags == (G32_TA | G32_TB | G32_ACCUM) && have_scratch;
     for (int i = 0; i < nprob && dw_ok; ++i) {
         const Gemm32Prob& q = probs[i];
         dw_ok = (q.M & 63) == 0 && (q.N & 63) == 0 && (q.K & 63) == 0 && q.K >= 4 * TK && (q.lda & 3) == 0 && (q.ldb & 3) == 0 &&
                 (((uintptr_t)q.A | (uintptr_t)q.B) & 15) == 0;
     }
-    int splitk = 1;
+    pl.splitk = 1;
     if (flags & G32_ACCUM) {   // weight-gradient shape: few tiles, long K -> spread K over the chip
         int64_t want = ceil_div(g_splitk_target, max_tiles * nprob);
         if (dw_ok) {
@@ -1138,123 +1164,138 @@ static int launch_gemm32_impl(const Gemm32Prob* probs, int nprob, int flags, hip
             if (g_dw_splits > 0 && nprob > 3) want = g_dw_splits;          // (sweeps of the merged SANB launches)
         }
         const int64_t maxs = ceil_div(min_k, 2 * TK);
-        splitk = (int)(want < 1 ? 1 : (want > maxs ? maxs : want));
-        if (splitk < 1) splitk = 1;
-    }
-    // Skinny long-K products that are not "+=" (the [M, 8192] -> 64 projections of Versa's text tower: 88 workgroups, each a
-    // serial chain of 128 K-tiles — 77 us for 1.5 GFLOP): spread K over the chip through the executor's scratch buffer and
-    // let a reducer apply the epilogue to the complete sums.
-    Gemm32Batch orig = b;
-    bool via_scratch = false;
-    if (!(flags & G32_ACCUM) && g_scratch && max_tiles <= 192) {
-        int64_t max_k = 0, need = 0;
-        for (int i = 0; i < nprob; ++i) if (probs[i].K > max_k) max_k = probs[i].K;
+        pl.splitk = (int)(want < 1 ? 1 : (want > maxs ? maxs : want));
+        // Weight-gradient products ("+=", K = number of item slots): the split-K partial products used to be added with fp32
+        // atomics — 29 splits x 49k outputs x 3 towers = 4.3 M atomics per launch, which is what the launch took (45 us at
+        // K = 11264 and 48 us at K = 4373: independent of K; rocprofv3, Cached step).  Through the scratch buffer instead: plain
+        // 16-byte stores of the partials and a reducer that adds them to C in a fixed order — faster, and the weight gradients
+        // become bit-reproducible.  Falls back to atomics when the scratch buffer is missing or too small.
+        // (round 6: gemm32_dw_kernel also when ONE split is wanted — a group whose tiles already fill the chip, like Versa's fc weight
+        //  gradients (400 tiles), fell back to the tiled kernel: 22 K-tiles in a row per workgroup, 77 us; the raw partial costs one more pass
+        //  of the reducer over the output and is still the faster route)
+        if (have_scratch && (pl.splitk >= 2 || dw_ok)) {
+            pl.splitk = nonempty_splits(ceil_div(min_k, (int64_t)TK), pl.splitk);
+            if (partials_fit(probs, nprob, pl.splitk, dw_ok, scratch_floats)) pl.scratch = G32S_ADD_C;
+        }
+    } else if (have_scratch && max_tiles <= 192) {
+        // Skinny long-K products that are not "+=" (the [M, 8192] -> 64 projections of Versa's text tower: 88 workgroups, each a
+        // serial chain of 128 K-tiles — 77 us for 1.5 GFLOP): spread K over the chip through the executor's scratch buffer and
+        // let a reducer apply the epilogue to the complete sums.
         int ks = (int)(max_k / (8 * TK));
         if (ks > 8) ks = 8;
-        for (int i = 0; i < nprob; ++i) need += (int64_t)ks * (int64_t)align_up((size_t)(probs[i].M * probs[i].N), 64);
-        if (ks >= 2 && (size_t)need <= g_scratch_floats) {
-            int64_t off = 0;
-            for (int i = 0; i < nprob; ++i) {
-                Gemm32Prob& q = b.p[i];
-                q.C = g_scratch + off; q.ldc = q.N; q.bias = nullptr; q.resid = nullptr; q.act_src = nullptr;
-                q.ksplit_stride = (int64_t)align_up((size_t)(q.M * q.N), 64);
-                off += ks * q.ksplit_stride;
-            }
-            splitk = ks;
-            via_scratch = true;
-        }
+        if (ks >= 2 && partials_fit(probs, nprob, ks, false, scratch_floats)) { pl.splitk = ks; pl.scratch = G32S_EPILOGUE; }
     }
-    // Weight-gradient products ("+=", K = number of item slots): the split-K partial products used to be added with fp32
-    // atomics — 29 splits x 49k outputs x 3 towers = 4.3 M atomics per launch, which is what the launch took (45 us at
-    // K = 11264 and 48 us at K = 4373: independent of K; rocprofv3, Cached step).  Through the scratch buffer instead: plain
-    // 16-byte stores of the partials and a reducer that adds them to C in a fixed order — faster, and the weight gradients
-    // become bit-reproducible.  Falls back to atomics when the scratch buffer is missing or too small.
-    int structural = flags & (G32_TA | G32_TB | G32_ACCUM);
-    // (round 6: gemm32_dw_kernel also when ONE split is wanted — a group whose tiles already fill the chip, like Versa's fc weight
-    //  gradients (400 tiles), fell back to the tiled kernel: 22 K-tiles in a row per workgroup, 77 us; the raw partial costs one more pass
-    //  of the reducer over the output and is still the faster route)
-    if ((flags & G32_ACCUM) && g_scratch && (splitk >= 2 || dw_ok)) {
-        {   // only NON-EMPTY K ranges: the kernel gives split y the K-tiles [y, y+1) * ceil(ktiles / splits) and a split whose
-            // range is empty writes nothing — its partial would be read uninitialised by the reducer
-            const int64_t ktiles = ceil_div(min_k, (int64_t)TK), per = ceil_div(ktiles, (int64_t)splitk);
-            splitk = (int)ceil_div(ktiles, per);
-        }
-        // (+ M floats behind every C partial for the A operand's column sums, where gemm32_dw_kernel computes them)
-        auto cs_floats = [&](const Gemm32Prob& q) { return (dw_ok && q.colsum_a) ? q.M : 0; };
-        int64_t need = 0;
-        for (int i = 0; i < nprob; ++i) need += (int64_t)splitk * (int64_t)align_up((size_t)(probs[i].M * probs[i].N + cs_floats(probs[i])), 64);
-        if ((size_t)need <= g_scratch_floats) {
-            int64_t off = 0;
-            for (int i = 0; i < nprob; ++i) {
-                Gemm32Prob& q = b.p[i];
-                q.C = g_scratch + off; q.ldc = q.N; q.bias = nullptr; q.resid = nullptr; q.act_src = nullptr;
-                q.ksplit_stride = (int64_t)align_up((size_t)(q.M * q.N + cs_floats(q)), 64);
-                off += splitk * q.ksplit_stride;
-                orig.p[i].resid = orig.p[i].C;          // the reducer adds the old C:  C = sum of partials + C
-                orig.p[i].ldr = orig.p[i].ldc;
-                orig.p[i].bias = nullptr;
-            }
-            via_scratch = true;
-            structural &= ~G32_ACCUM;
-        }
+    pl.gy = pl.splitk;
+    if (dw_ok && pl.scratch == G32S_ADD_C) {
+        pl.kernel = G32K_DW;
+        pl.colsum = any_colsum ? G32C_FOLDED : G32C_NONE;
+        return pl;
     }
-    dim3 grid((unsigned)max_tiles, (unsigned)splitk, (unsigned)nprob);
+    pl.kernel = G32K_TILED;
     // FAST fetch: full tiles, whole K-tiles per split, 16-byte aligned operand rows — for every problem of the launch
-    bool fast = true;
-    for (int i = 0; i < nprob && fast; ++i) {
+    pl.fast = true;
+    for (int i = 0; i < nprob && pl.fast; ++i) {
         const Gemm32Prob& q = probs[i];
-        fast = q.M % TM == 0 && q.N % TN == 0 && q.K % TK == 0 &&
-               (q.lda & 3) == 0 && (q.ldb & 3) == 0 && ((uintptr_t)q.A & 15) == 0 && ((uintptr_t)q.B & 15) == 0;
+        pl.fast = q.M % pl.tm == 0 && q.N % TN == 0 && q.K % TK == 0 &&
+                  (q.lda & 3) == 0 && (q.ldb & 3) == 0 && ((uintptr_t)q.A & 15) == 0 && ((uintptr_t)q.B & 15) == 0;
     }
-    const int epi = via_scratch ? 0 : (flags & ~(G32_TA | G32_TB | G32_ACCUM));
-    int rc;
-    bool cs_folded = false;          // the A operand's column sums came out of the product kernel
-    if (dw_ok && via_scratch && structural == (G32_TA | G32_TB)) {
+    // three K-tiles in flight: long-K weight-gradient layouts on the fast fetch only (gemm32_kernel: DEPTH)
+    pl.deep = pl.fast && (flags & (G32_TA | G32_TB)) == (G32_TA | G32_TB) && min_k >= 4096;
+    // every route but gemm32_dw_kernel: the column sums as a launch of their own
+    pl.colsum = (any_colsum && (flags & G32_TA)) ? G32C_OWN_LAUNCH : G32C_NONE;
+    return pl;
+}
+
+static int launch_gemm32_impl(const Gemm32Prob* probs, int nprob, int flags, hipStream_t s) {
+    const Gemm32Plan pl = plan_gemm32(probs, nprob, flags, g_scratch ? g_scratch_floats : 0);
+    if (pl.kernel == G32K_REJECTED) return IISAN_EBADSHAPE;
+    if (pl.kernel == G32K_SPLIT_K64) {
+        Gemm32Prob yes[G32_MAXP], no[G32_MAXP];
+        int ny = 0, nn = 0;
+        for (int i = 0; i < nprob; ++i) { if (k64_shape_ok(probs[i])) yes[ny++] = probs[i]; else no[nn++] = probs[i]; }
+        IISAN_TRY(launch_gemm32_impl(yes, ny, flags, s));
+        return launch_gemm32_impl(no, nn, flags, s);
+    }
+    const dim3 grid((unsigned)pl.gx, (unsigned)pl.gy, (unsigned)pl.gz);
+    if (pl.kernel == G32K_K64) {
+        K64Batch kb{};
+        fill_k64(kb, probs, nprob);
+        // the [N, 64] layout stages 64 nblk rows of 68 floats, the [64, N] layout 64 rows of 64 nblk + 4: four pad floats per 64
+        // against four per 64 nblk — the first is never the smaller, and both instantiations are launched with it
+        const size_t lds = (size_t)64 * pl.nblk * 68 * sizeof(float);
+        static OncePerDevice attr;
+        if (attr.first()) {
+            IISAN_HIP_OK(hipFuncSetAttribute((const void*)gemm32_k64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 68 * 4));
+            IISAN_HIP_OK(hipFuncSetAttribute((const void*)gemm32_k64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 68 * 4));
+        }
+        ++g_cnt_k64;
+        if (flags & G32_TB) hipLaunchKernelGGL(gemm32_k64_kernel<true>, grid, dim3(256), lds, s, kb, pl.nblk);
+        else hipLaunchKernelGGL(gemm32_k64_kernel<false>, grid, dim3(256), lds, s, kb, pl.nblk);
+        IISAN_LAUNCH_OK();
+        return IISAN_OK;
+    }
+    // place the partials: split y of problem i writes its raw product at C + y * ksplit_stride of the scratch
+    Gemm32Batch b{};
+    for (int i = 0; i < nprob; ++i) b.p[i] = probs[i];
+    if (pl.scratch != G32S_NONE) {
+        int64_t off = 0;
+        for (int i = 0; i < nprob; ++i) {
+            Gemm32Prob& q = b.p[i];
+            q.C = g_scratch + off; q.ldc = q.N; q.bias = nullptr; q.resid = nullptr; q.act_src = nullptr;
+            q.ksplit_stride = partial_floats(q, pl.kernel == G32K_DW);
+            off += pl.splitk * q.ksplit_stride;
+        }
+    }
+    const int epi = flags & ~(G32_TA | G32_TB | G32_ACCUM);
+    if (pl.kernel == G32K_DW) {
         ++g_cnt_dw;
         hipLaunchKernelGGL(gemm32_dw_kernel, grid, dim3(256), 0, s, b);
         IISAN_LAUNCH_OK();
-        rc = IISAN_OK;
-        cs_folded = true;
-    } else
-    switch (structural) {
-#define G32_CASE(F) case (F): rc = launch_flags<(F)>(b, grid, TM, epi, fast, min_k >= 4096, s); break
-        G32_CASE(0);
-        G32_CASE(G32_TA);
-        G32_CASE(G32_TB);
-        G32_CASE(G32_TA | G32_TB);
-        G32_CASE(G32_ACCUM);
-        G32_CASE(G32_TA | G32_ACCUM);
-        G32_CASE(G32_TB | G32_ACCUM);
-        G32_CASE(G32_TA | G32_TB | G32_ACCUM);
-#undef G32_CASE
-        default: iisan_set_error("gemm32: bad flags 0x%x", flags); return IISAN_EBADSHAPE;
+    } else {
+        // partials that meet in the reducer are plain stores: no atomics, no epilogue
+        const int structural = flags & (G32_TA | G32_TB | (pl.scratch == G32S_NONE ? G32_ACCUM : 0));
+        const int kepi = pl.scratch == G32S_NONE ? epi : 0;
+        IISAN_TRY(g_tiled[(structural & 3) | (structural & G32_ACCUM ? 4 : 0)](b, grid, pl.tm, kepi, pl.fast, pl.deep, s));
     }
-    if (rc == IISAN_OK && !cs_folded && (flags & G32_TA)) {          // every other route: the column sums as a launch of their own
+    if (pl.colsum == G32C_OWN_LAUNCH) {
         const float* X[G32_MAXP]; float* O[G32_MAXP]; int64_t Ms[G32_MAXP]; int32_t Ns[G32_MAXP], lds[G32_MAXP];
         int n = 0;
         for (int i = 0; i < nprob; ++i)
             if (probs[i].colsum_a) { X[n] = probs[i].A; O[n] = probs[i].colsum_a; Ms[n] = probs[i].K; Ns[n] = (int32_t)probs[i].M; lds[n] = probs[i].lda; ++n; }
         for (int i = 0; i < n; i += 4) IISAN_TRY(launch_colsum(X + i, O + i, Ms + i, Ns + i, lds + i, n - i < 4 ? n - i : 4, s));
     }
-    if (rc != IISAN_OK || !via_scratch) return rc;
+    if (pl.scratch == G32S_NONE) return IISAN_OK;
     ReduceBatch rb{};
-    int64_t max_mn = 0;
     for (int i = 0; i < nprob; ++i) {
-        rb.p[i] = orig.p[i];
+        rb.p[i] = probs[i];
+        if (pl.scratch == G32S_ADD_C) {         // the reducer adds the old C:  C = sum of partials + C
+            rb.p[i].resid = probs[i].C; rb.p[i].ldr = probs[i].ldc; rb.p[i].bias = nullptr;
+        }
         rb.P[i] = b.p[i].C;
         rb.stride[i] = b.p[i].ksplit_stride;
-        rb.cs[i] = cs_folded ? orig.p[i].colsum_a : nullptr;
-        {   // the kernel gives split y the K-tiles [y, y+1) * ceil(ktiles / splits)
-            const int64_t ktiles = ceil_div(orig.p[i].K, (int64_t)TK), per = ceil_div(ktiles, (int64_t)splitk);
-            rb.ns[i] = (int32_t)ceil_div(ktiles, per);
-        }
-        if (orig.p[i].M * orig.p[i].N > max_mn) max_mn = orig.p[i].M * orig.p[i].N;
+        rb.cs[i] = pl.colsum == G32C_FOLDED ? probs[i].colsum_a : nullptr;
     }
-    int64_t blocks = ceil_div(max_mn, 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(gemm32_reduce_kernel, dim3((unsigned)blocks, 1, (unsigned)nprob), dim3(256), 0, s, rb, splitk, flags & ~(G32_TA | G32_TB | G32_ACCUM));
-    IISAN_LAUNCH_OK();
-    return IISAN_OK;
+    return launch_reduce(rb, nprob, pl.splitk, epi, s);
+}
+
+// host-side query of the plan (tests/test_host_logic.py pins it as a literal table): problems with natural leading dimensions and aligned
+// operands, act_src present where the flags read or write it; the residual has no say in the plan
+extern "C" int32_t iisan_gemm32_plan(const int64_t* M, const int32_t* N, const int64_t* K, int32_t nprob, int32_t flags, int64_t scratch_floats,
+                                     int32_t with_colsum, int32_t* plan12) {
+    static float present[4];
+    Gemm32Prob p[G32_MAXP] = {};
+    for (int i = 0; i < nprob && i < G32_MAXP; ++i) {
+        p[i].M = M[i]; p[i].N = N[i]; p[i].K = K[i];
+        p[i].lda = (int32_t)((flags & G32_TA) ? M[i] : K[i]);
+        p[i].ldb = (int32_t)((flags & G32_TB) ? N[i] : K[i]);
+        p[i].ldc = N[i]; p[i].ldr = N[i];
+        if (flags & (G32_PREACT | G32_MUL_RELU_MASK | G32_MUL_GELU_GRAD)) p[i].act_src = present;
+        if (with_colsum) p[i].colsum_a = present;
+    }
+    const Gemm32Plan pl = plan_gemm32(p, nprob, flags, scratch_floats > 0 ? (size_t)scratch_floats : 0);
+    const int64_t v[12] = {pl.kernel, pl.tm, pl.splitk, pl.scratch, pl.fast, pl.deep, pl.colsum, pl.nblk, pl.gx, pl.gy, pl.gz, pl.nk64};
+    for (int i = 0; i < 12; ++i) plan12[i] = (int32_t)v[i];
+    return pl.kernel;
 }
 
 // ---- public launchers: the implementation above, bracketed by HIP events when bench.py times this kernel family (class 2).
@@ -1273,7 +1314,7 @@ int launch_gemm32_n64f(const N64FDesc* d, int n, int gelu, hipStream_t s) {
     double fl = 0, by = 0;
     for (int i = 0; i < n; ++i) {       // reads tap (+ second tap) + previous state, writes F, U, A; the product is [M, K] x [K, 64]
         fl += 2.0 * (double)d[i].M * 64.0 * d[i].K;
-        by += 4.0 * ((double)d[i].M * d[i].K * ((d[i].a ? 1 : 0) + (d[i].b ? 1 : 0) + (d[i].prev ? 1 : 0) + 1) + 64.0 * d[i].K + 2.0 * d[i].M * 64.0);
+        by += 4.0 * ((double)d[i].M * d[i].K * ((d[i].f.a ? 1 : 0) + (d[i].f.b ? 1 : 0) + (d[i].f.prev ? 1 : 0) + 1) + 64.0 * d[i].K + 2.0 * d[i].M * 64.0);
     }
     TimedLaunch t(2, s, fl, by);
     return launch_gemm32_n64f_impl(d, n, gelu, s);

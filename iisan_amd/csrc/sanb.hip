@@ -384,7 +384,7 @@ size_t lds_bytes(int D) { return (size_t)lds_floats(D) * sizeof(float); }
 bool sanb_fused_ok(int D, int down) { return down == RD && (D == 1024 || D == 768 || D == 512 || D == 256); }
 
 static void fill(SanbTower& t, const SanbTowerDesc& d) {
-    t.a = d.a; t.b = d.b; t.prev = d.prev; t.lda = d.lda; t.ldb = d.ldb; t.ldp = d.ldp; t.gate = d.gate; t.D = d.D; t.type = d.type;
+    t.a = d.f.a; t.b = d.f.b; t.prev = d.f.prev; t.lda = d.f.lda; t.ldb = d.f.ldb; t.ldp = d.f.ldp; t.gate = d.f.gate; t.D = d.f.D; t.type = d.f.type;
     t.Wd = d.Wd; t.bd = d.bd; t.Wu = d.Wu; t.bu = d.bu; t.F = d.F; t.U = d.U; t.A = d.A; t.O = d.O;
     t.dO = d.dO; t.Upre = d.Upre; t.dU = d.dU; t.dprev = d.dprev; t.da = d.da; t.db = d.db; t.dgate = d.dgate; t.dbu = d.dbu; t.dbd = d.dbd;
 }
@@ -394,9 +394,9 @@ static int launch_sanb(const SanbTowerDesc* towers, int n, int64_t M, int gelu, 
     IISAN_CHECK_SHAPE(n >= 1 && n <= 3 && M > 0, "sanb: 1..3 towers per launch");
     SanbArgs a{};
     a.M = M; a.gelu = gelu;
-    const int D = towers[0].D;
+    const int D = towers[0].f.D;
     for (int i = 0; i < n; ++i) {
-        IISAN_CHECK_SHAPE(towers[i].D == D && sanb_fused_ok(D, RD), "sanb: towers of one launch must share a supported width");
+        IISAN_CHECK_SHAPE(towers[i].f.D == D && sanb_fused_ok(D, RD), "sanb: towers of one launch must share a supported width");
         fill(a.t[i], towers[i]);
     }
     const int cus = iisan_cu_count();

@@ -387,17 +387,44 @@ struct ScratchGuard {       // registers the executor's split-K scratch with gem
     ~ScratchGuard() { gemm32_set_scratch(nullptr, 0); }
 };
 
+// the kernel-argument image of the operands (fuse_fwd_kernel / fuse_bwd_kernel); F, da, db, dgate: the caller
+void fill(FuseTower& t, const FuseOperands& f) {
+    t.a = f.a; t.b = f.b; t.prev = f.prev; t.lda = f.lda; t.ldb = f.ldb; t.ldp = f.ldp; t.gate = f.gate; t.D = f.D; t.type = f.type;
+}
+// ... and what the gate-fused dF product reads of them: the tap and the operand it is mixed with
+K64Gate k64_gate(const FuseOperands& f) {
+    K64Gate g{};
+    g.gate = f.gate; g.ga = f.a; g.ldga = f.lda;
+    if (f.type == 1) { g.go = f.b; g.ldgo = f.ldb; }
+    else { g.go = f.prev; g.ldgo = f.ldp; }
+    g.scale_prev = f.type == 0 ? 1 : 0;
+    return g;
+}
+
+// the active towers of a step can share one fused launch
+bool step_fusable(const Plan& p, const StepMap& sm, int64_t M) {
+    if (!g_use_sanb || (g_use_sanb == 1 && M >= SANB_FUSED_MAX_ROWS)) return false;
+    const int D = p.D[sm.z[0]];
+    for (int a = 0; a < sm.nact; ++a)
+        if (p.D[sm.z[a]] != D) return false;
+    return sanb_fused_ok(D, p.r);
+}
+
 struct Ctx {
     const iisan_side_cfg* cfg; Plan p; SideBufs b;
     const float* taps[2]; int64_t M;
     const void* const* params;
+    void* const* grads;            // backward only
+    hipStream_t s;
     const float* W(int i) const { return (const float*)params[i]; }
+    float* G(int i) const { return (float*)grads[i]; }
     int tap_idx(int z, int k) const { return (z == 1 && cfg->versa) ? cfg->tap_index_text[k] : cfg->tap_index[k]; }
     int64_t tap_ld(int z) const { return (int64_t)(z == 0 ? cfg->tap_stride_cv : cfg->tap_stride_text) * p.D[z]; }
     const float* tap(int z, int k) const { return taps[z] + (int64_t)tap_idx(z, k) * p.D[z]; }
     int first_idx(int z) const { return (z == 1 && cfg->versa) ? cfg->first_index_text : cfg->first_index; }
     // fusion operands of tower z at its block k (mm: k = i)
-    void fuse_operands(FuseTower& t, int z, int k, const StepMap& sm) const {
+    FuseOperands fuse_operands(int z, int k, const StepMap& sm) const {
+        FuseOperands t{};
         t.D = p.D[z];
         t.gate = cfg->gated ? W(p.gate(z, k)) : nullptr;
         t.prev = nullptr; t.ldp = p.D[z];
@@ -415,28 +442,262 @@ struct Ctx {
                 else { t.a = b.DP[k]; t.lda = p.D[2]; }
             }
         }
+        return t;
+    }
+    // the forward fc product of tower z / dim-align product of aligned step i: asked again by the backward call for "did it take the
+    // split-operand route (and leave its operands' amax)?"
+    Gemm32Prob fc_prob(int z) const { return prob(b.O[p.n[z] - 1][z], p.D[z], W(p.p_fc[z]), p.D[z], W(p.p_fc[z] + 1), b.Y[z], p.H[z], M, p.H[z], p.D[z]); }
+    Gemm32Prob align_prob(int i) const {
+        const int zw = p.text_wide ? 1 : 0, kw = step_map(p, p.diff_cv + p.diff_t + i).k[zw];
+        return prob(tap(zw, kw), (int)tap_ld(zw), W(p.dpw(i)), p.D[zw], W(p.dpw(i) + 1), b.DP[i], p.D[2], M, p.D[2], p.D[zw]);
+    }
+
+    // ---- forward: one function per launch list -------------------------------------------------------------------------------------
+    // dim-align the wider modality's taps (Code_Cached_Asym/model/model.py:404-411).  The products depend on taps and weights only, not on
+    // the chain: round 6 issues them as ONE group ahead of it (they used to sit in front of their steps, one amax launch per weight each)
+    int fwd_dim_align(bool taps_preset) const {
+        Gemm32Prob pd[IISAN_MAX_SIDE];
+        for (int i = 0; i < p.n[2]; ++i) {
+            pd[i] = align_prob(i);
+            pd[i].amax_a = b.amax + 9 + i;         // the tap's amax: read again by the weight-gradient product of this step
+            pd[i].amax_a_ready = taps_preset ? 1 : 0;
+            pd[i].exact16_a = taps_preset ? 1 : 0;
+        }
+        return gemm_group(pd, p.n[2], 0, b, s);
+    }
+
+    // fusion + down + activation + up of every active tower in one launch
+    int fwd_step_fused(const StepMap& sm) const {
+        SanbTowerDesc td[3];
+        for (int a = 0; a < sm.nact; ++a) {
+            const int z = sm.z[a], k = sm.k[a];
+            td[a] = SanbTowerDesc{};
+            td[a].f = fuse_operands(z, k, sm);
+            // both weights as stored: fc_down [64, D] and fc_up [D, 64] have the contraction index contiguous
+            td[a].Wd = W(p.wd(z, k)); td[a].bd = W(p.wd(z, k) + 1); td[a].Wu = W(p.wd(z, k) + 2); td[a].bu = W(p.wd(z, k) + 3);
+            td[a].F = b.F[k][z]; td[a].U = b.U[k][z]; td[a].A = b.A[k][z]; td[a].O = b.O[k][z];
+        }
+        return launch_sanb_fwd(td, sm.nact, M, cfg->gelu, s);
+    }
+
+    // fusion + down projection + activation in one launch where the shapes allow (gemm32_n64f_kernel: F is formed in the registers that
+    // feed the product and written once), else the fusion kernel, then the product; the up projection with the residual F behind either
+    int fwd_step_separate(const StepMap& sm) const {
+        const int na = sm.nact;
+        FuseOperands fo[3];
+        for (int a = 0; a < na; ++a) fo[a] = fuse_operands(sm.z[a], sm.k[a], sm);
+        Gemm32Prob pr[3];
+        bool fed = false;
+        if (p.r == 64) {
+            N64FDesc nd[3];
+            for (int a = 0; a < na; ++a) {
+                const int z = sm.z[a], k = sm.k[a];
+                nd[a] = N64FDesc{};
+                nd[a].f = fo[a];
+                nd[a].F = b.F[k][z]; nd[a].W = W(p.wd(z, k)); nd[a].ldw = p.D[z]; nd[a].bias = W(p.wd(z, k) + 1);
+                nd[a].U = b.U[k][z]; nd[a].A = b.A[k][z]; nd[a].M = M; nd[a].K = p.D[z];
+            }
+            if (gemm32_n64f_ok(nd, na)) {
+                IISAN_TRY(launch_gemm32_n64f(nd, na, cfg->gelu, s));
+                fed = true;
+            }
+        }
+        if (!fed) {
+            FuseArgs fa{};
+            fa.M = M;
+            int maxD = 0;
+            for (int a = 0; a < na; ++a) {
+                const int z = sm.z[a], k = sm.k[a];
+                fill(fa.t[a], fo[a]);
+                fa.t[a].F = b.F[k][z];
+                if (p.D[z] > maxD) maxD = p.D[z];
+                // U = F Wd^T + bd (saved), A = act(U)
+                pr[a] = prob(b.F[k][z], p.D[z], W(p.wd(z, k)), p.D[z], W(p.wd(z, k) + 1), b.A[k][z], p.r, M, p.r, p.D[z], nullptr, 0, b.U[k][z]);
+            }
+            hipLaunchKernelGGL(fuse_fwd_kernel, dim3(ew_grid(M, maxD), na), dim3(256), 0, s, fa);
+            IISAN_LAUNCH_OK();
+            IISAN_TRY(launch_gemm32(pr, na, (cfg->gelu ? G32_GELU : G32_RELU) | G32_PREACT, s));
+        }
+        for (int a = 0; a < na; ++a) {   // state = A Wu^T + bu + F
+            const int z = sm.z[a], k = sm.k[a];
+            pr[a] = prob(b.A[k][z], p.r, W(p.wd(z, k) + 2), p.r, W(p.wd(z, k) + 3), b.O[k][z], p.D[z], M, p.D[z], p.r, b.F[k][z], p.D[z]);
+        }
+        return launch_gemm32(pr, na, 0, s);
+    }
+
+    // Y_z = O_z Wf^T + bf, then E_z = Y_z Wh^T + bh into its third of item3
+    int fwd_fc_head(float* item3) const {
+        Gemm32Prob pr[3];
+        for (int z = 0; z < 3; ++z) {
+            pr[z] = fc_prob(z);
+            pr[z].amax_a = b.amax + z;                   // O_z and the fc weight: their amax is left for the backward products
+            pr[z].amax_b = b.amax + 3 + z;
+        }
+        IISAN_TRY(gemm_group(pr, 3, 0, b, s));
+        for (int z = 0; z < 3; ++z) pr[z] = prob(b.Y[z], p.H[z], W(p.p_head[z]), p.H[z], W(p.p_head[z] + 1), item3 + z * p.E, 3 * p.E, M, p.E, p.H[z]);
+        return launch_gemm32(pr, 3, 0, s);
+    }
+
+    // ---- backward ----------------------------------------------------------------------------------------------------------------
+    int bwd_fc_head(const float* d_item3) const {
+        const int E = p.E;
+        Gemm32Prob pr[3];
+        const float* cs_x[3]; float* cs_o[3]; int64_t cs_m[3] = {M, M, M}; int32_t cs_n[3], cs_ld[3];
+        // heads: E_z = Y_z Wh^T + bh
+        for (int z = 0; z < 3; ++z) pr[z] = prob(d_item3 + z * E, 3 * E, W(p.p_head[z]), p.H[z], nullptr, b.dY[z], p.H[z], M, p.H[z], E);
+        IISAN_TRY(launch_gemm32(pr, 3, G32_TB, s));                                   // dY = dE · Wh
+        for (int z = 0; z < 3; ++z) pr[z] = prob(d_item3 + z * E, 3 * E, b.Y[z], p.H[z], nullptr, G(p.p_head[z]), p.H[z], E, p.H[z], M);
+        IISAN_TRY(launch_gemm32(pr, 3, G32_TA | G32_TB | G32_ACCUM, s));              // dWh += dE^T · Y
+        for (int z = 0; z < 3; ++z) { cs_x[z] = d_item3 + z * E; cs_o[z] = G(p.p_head[z] + 1); cs_n[z] = E; cs_ld[z] = 3 * E; }
+        IISAN_TRY(launch_colsum(cs_x, cs_o, cs_m, cs_n, cs_ld, 3, s));
+        // fc: Y_z = O_z Wf^T + bf
+        IISAN_HIP_OK(hipMemsetAsync(b.zb, 0, (size_t)(ZB_HEAD + X3Z_WORDS * X3Z_SLOTS_B) * sizeof(uint32_t), s));
+        b.x3z_next = b.x3z_b; b.x3z_left = X3Z_SLOTS_B;
+        int fwd_x3[3];      // did the forward fc product of tower z take the split-operand route (and leave its operands' amax)?
+        for (int z = 0; z < 3; ++z) fwd_x3[z] = (b.x3 && gemm_x3_applicable(fc_prob(z), 0)) ? 1 : 0;
+        for (int z = 0; z < 3; ++z) {
+            pr[z] = prob(b.dY[z], p.H[z], W(p.p_fc[z]), p.D[z], nullptr, b.dO[z], p.D[z], M, p.D[z], p.H[z]);
+            pr[z].amax_a = b.zb + z;                                                  // dY_z: computed here, reused by dWf below
+            if (fwd_x3[z]) { pr[z].amax_b = b.amax + 3 + z; pr[z].amax_b_ready = 1; } // the fc weight: from the forward call
+        }
+        IISAN_TRY(gemm_group(pr, 3, G32_TB, b, s));                                   // dO = dY · Wf
+        int dy_ready[3];
+        for (int z = 0; z < 3; ++z) dy_ready[z] = (b.x3 && gemm_x3_applicable(pr[z], G32_TB)) ? 1 : 0;
+        for (int z = 0; z < 3; ++z) {
+            pr[z] = prob(b.dY[z], p.H[z], b.O[p.n[z] - 1][z], p.D[z], nullptr, G(p.p_fc[z]), p.D[z], p.H[z], p.D[z], M);
+            pr[z].amax_a = b.zb + z; pr[z].amax_a_ready = dy_ready[z];          // (zeroed above; filled by the dX product if it took this route)
+            if (fwd_x3[z]) { pr[z].amax_b = b.amax + z; pr[z].amax_b_ready = 1; }     // O_z: from the forward call
+        }
+        IISAN_TRY(gemm_group(pr, 3, G32_TA | G32_TB | G32_ACCUM, b, s));              // dWf += dY^T · O
+        for (int z = 0; z < 3; ++z) { cs_x[z] = b.dY[z]; cs_o[z] = G(p.p_fc[z] + 1); cs_n[z] = p.H[z]; cs_ld[z] = p.H[z]; }
+        return launch_colsum(cs_x, cs_o, cs_m, cs_n, cs_ld, 3, s);
+    }
+
+    // dWu += dO^T · A first (needs dO as it arrives), then ONE launch turns dO into dprev in place (tile-local: a workgroup reads its
+    // rows of dO into LDS before it writes them) and leaves dU, db_u, db_d, dθ; dWd += dU^T · F last
+    int bwd_step_fused(const StepMap& sm) const {
+        const int na = sm.nact, r = p.r;
+        Gemm32Prob pr[3];
+        for (int a = 0; a < na; ++a) {
+            const int z = sm.z[a], k = sm.k[a];
+            pr[a] = prob(b.dO[z], p.D[z], b.A[k][z], r, nullptr, G(p.wd(z, k) + 2), r, p.D[z], r, M);
+        }
+        IISAN_TRY(launch_gemm32(pr, na, G32_TA | G32_TB | G32_ACCUM, s));
+        SanbTowerDesc td[3];
+        const float* tin[6]; float* tout[6]; int32_t trows[6], tcols[6];
+        for (int a = 0; a < na; ++a) {
+            const int z = sm.z[a], k = sm.k[a];
+            tin[2 * a] = W(p.wd(z, k)); tout[2 * a] = b.WT[z][0]; trows[2 * a] = p.r; tcols[2 * a] = p.D[z];              // fc_down [64,D] -> [D,64]
+            tin[2 * a + 1] = W(p.wd(z, k) + 2); tout[2 * a + 1] = b.WT[z][1]; trows[2 * a + 1] = p.D[z]; tcols[2 * a + 1] = p.r;  // fc_up [D,64] -> [64,D]
+            td[a] = SanbTowerDesc{};
+            td[a].f = fuse_operands(z, k, sm);
+            td[a].Wd = b.WT[z][1]; td[a].Wu = b.WT[z][0];      // dA = dO · fc_up: fc_up^T [64, D];  dU · fc_down: fc_down^T [D, 64] (contraction index contiguous)
+            td[a].dO = b.dO[z]; td[a].Upre = b.U[k][z]; td[a].dU = b.dU[z];
+            td[a].dprev = k > 0 ? b.dO[z] : nullptr;     // block 0 starts from zeros / a tap: nobody reads that gradient
+            td[a].dgate = cfg->gated ? G(p.gate(z, k)) : nullptr;
+            td[a].dbu = G(p.wd(z, k) + 3); td[a].dbd = G(p.wd(z, k) + 1);
+        }
+        IISAN_TRY(launch_sanb_transpose(tin, tout, trows, tcols, 2 * na, s));
+        IISAN_TRY(launch_sanb_bwd(td, na, M, cfg->gelu, s));
+        for (int a = 0; a < na; ++a) {
+            const int z = sm.z[a], k = sm.k[a];
+            pr[a] = prob(b.dU[z], r, b.F[k][z], p.D[z], nullptr, G(p.wd(z, k)), p.D[z], r, p.D[z], M);
+        }
+        return launch_gemm32(pr, na, G32_TA | G32_TB | G32_ACCUM, s);               // dWd += dU^T · F
+    }
+
+    // state = A Wu^T + bu + F ; A = act(U) ; U = F Wd^T + bd, product by product: dU, both weight gradients, dF (in place over dO) and the
+    // fusion's backward — in the epilogue of the dF product where the step is gated and the shapes allow, else as fuse_bwd_kernel
+    int bwd_step_separate(const StepMap& sm) const {
+        const int na = sm.nact, r = p.r;
+        Gemm32Prob pr[3];
+        for (int a = 0; a < na; ++a) {
+            const int z = sm.z[a], k = sm.k[a];
+            pr[a] = prob(b.dO[z], p.D[z], W(p.wd(z, k) + 2), r, nullptr, b.dU[z], r, M, r, p.D[z], nullptr, 0, b.U[k][z]);
+        }
+        IISAN_TRY(launch_gemm32(pr, na, G32_TB | (cfg->gelu ? G32_MUL_GELU_GRAD : G32_MUL_RELU_MASK), s));  // dU
+        {   // both weight gradients of the step, every tower, in ONE launch (round 6: they were two launches + two reducers; dO is still
+            // whole here — the dF product below overwrites it in place)
+            Gemm32Prob pw[6];
+            for (int a = 0; a < na; ++a) {
+                const int z = sm.z[a], k = sm.k[a];
+                pw[a] = prob(b.dO[z], p.D[z], b.A[k][z], r, nullptr, G(p.wd(z, k) + 2), r, p.D[z], r, M);             // dWu += dO^T · A
+                pw[a].colsum_a = G(p.wd(z, k) + 3);                             // dbu += column sums of dO: out of the same product
+                pw[na + a] = prob(b.dU[z], r, b.F[k][z], p.D[z], nullptr, G(p.wd(z, k)), p.D[z], r, p.D[z], M);       // dWd += dU^T · F
+                pw[na + a].colsum_a = G(p.wd(z, k) + 1);                        // dbd += column sums of dU
+            }
+            if (g_dw_merge) IISAN_TRY(launch_gemm32(pw, 2 * na, G32_TA | G32_TB | G32_ACCUM, s));
+            else {
+                IISAN_TRY(launch_gemm32(pw, na, G32_TA | G32_TB | G32_ACCUM, s));
+                IISAN_TRY(launch_gemm32(pw + na, na, G32_TA | G32_TB | G32_ACCUM, s));
+            }
+        }
+        const bool need_dp = sm.mm_i >= 0 && p.align;      // the mm tower also owes the gradient wrt its dim-aligned tap
+        FuseOperands fo[3];
+        for (int a = 0; a < na; ++a) {
+            const int z = sm.z[a], k = sm.k[a];
+            fo[a] = fuse_operands(z, k, sm);
+            pr[a] = prob(b.dU[z], r, W(p.wd(z, k)), p.D[z], nullptr, b.dO[z], p.D[z], M, p.D[z], r, b.dO[z], p.D[z]);
+        }
+        // gated fusion: its backward rides in the epilogue of the dF product (gemm32_k64_kernel<true,
+        // true>: gate gradient and the (1 - g) scaling while dF is in registers) — no separate pass over dF
+        if (cfg->gated) {
+            K64Gate kg[3];
+            for (int a = 0; a < na; ++a) {
+                const int z = sm.z[a], k = sm.k[a];
+                kg[a] = k64_gate(fo[a]);
+                kg[a].dgate = G(p.gate(z, k));
+                kg[a].store = k > 0 ? 1 : 0;          // block 0 starts from zeros / a tap: nobody reads that gradient
+                if (z == 2 && need_dp) { kg[a].d2 = b.dDP[sm.mm_i]; kg[a].ldd2 = p.D[2]; kg[a].d2_is_b = p.text_wide ? 1 : 0; }
+            }
+            if (gemm32_k64_gate_ok(pr, kg, na))
+                return launch_gemm32_k64_gate(pr, kg, na, s);                     // dprev = (1 - g | 1) · (dO + dU · Wd), dθ (in place)
+        }
+        IISAN_TRY(launch_gemm32(pr, na, G32_TB, s));                                  // dF = dO + dU · Wd (in place)
+        if (!cfg->gated && !need_dp) return IISAN_OK;                                 // not gated: dprev_z = dF_z, already in dO
+        FuseArgs fa{};
+        fa.M = M;
+        int maxD = 0;
+        for (int a = 0; a < na; ++a) {
+            const int z = sm.z[a], k = sm.k[a];
+            fill(fa.t[a], fo[a]);
+            fa.t[a].F = b.dO[z];
+            fa.t[a].dgate = cfg->gated ? G(p.gate(z, k)) : nullptr;
+            if (z == 2 && need_dp) { if (p.text_wide) fa.t[a].db = b.dDP[sm.mm_i]; else fa.t[a].da = b.dDP[sm.mm_i]; }
+            if (p.D[z] > maxD) maxD = p.D[z];
+        }
+        // every workgroup ends with ONE atomic on its tower's gate gradient and same-address atomics serialise (~12 ns
+        // each): 4096 workgroups spent ~50 us there (Versa: 130 us for 230 MB).  768 workgroups, more rows each.
+        unsigned gb = ew_grid(M, maxD);
+        if (gb > 768) gb = 768;
+        hipLaunchKernelGGL(fuse_bwd_kernel, dim3(gb, na), dim3(256), 0, s, fa);
+        IISAN_LAUNCH_OK();
+        return IISAN_OK;
+    }
+
+    // DP_i = tap_wide · Pd_i^T + bd_i: the weight gradients of every aligned step as ONE group behind the chain (round 6: they sat
+    // inside their steps — an amax launch and a column-sum launch each; nothing in the chain reads them)
+    int bwd_dim_align() const {
+        Gemm32Prob pd[IISAN_MAX_SIDE];
+        const float* X[IISAN_MAX_SIDE]; float* O[IISAN_MAX_SIDE]; int64_t Ms[IISAN_MAX_SIDE]; int32_t Ns[IISAN_MAX_SIDE], lds[IISAN_MAX_SIDE];
+        const int zw = p.text_wide ? 1 : 0;
+        for (int i = 0; i < p.n[2]; ++i) {
+            const Gemm32Prob f = align_prob(i);
+            pd[i] = prob(b.dDP[i], p.D[2], f.A, f.lda, nullptr, G(p.dpw(i)), p.D[zw], p.D[2], p.D[zw], M);
+            if (b.x3 && gemm_x3_applicable(f, 0)) {       // the tap: from the forward dim-align product
+                pd[i].amax_b = b.amax + 9 + i; pd[i].amax_b_ready = 1;
+                pd[i].exact16_b = cfg->taps_exact16 ? 1 : 0;     // (side_net_fwd preset the slot: scale 1)
+            }
+            X[i] = b.dDP[i]; O[i] = G(p.dpw(i) + 1); Ms[i] = M; Ns[i] = p.D[2]; lds[i] = p.D[2];
+        }
+        IISAN_TRY(gemm_group(pd, p.n[2], G32_TA | G32_TB | G32_ACCUM | G32_HINT_B_EXACT16, b, s));     // dPd_i += dDP_i^T · tap
+        for (int i = 0; i < p.n[2]; i += 4) IISAN_TRY(launch_colsum(X + i, O + i, Ms + i, Ns + i, lds + i, p.n[2] - i < 4 ? p.n[2] - i : 4, s));
+        return IISAN_OK;
     }
 };
 
-// the active towers of a step can share one fused launch
-bool step_fusable(const Plan& p, const StepMap& sm, int64_t M) {
-    if (!g_use_sanb || (g_use_sanb == 1 && M >= SANB_FUSED_MAX_ROWS)) return false;
-    const int D = p.D[sm.z[0]];
-    for (int a = 0; a < sm.nact; ++a)
-        if (p.D[sm.z[a]] != D) return false;
-    return sanb_fused_ok(D, p.r);
-}
-
-void tower_desc(SanbTowerDesc& d, const Ctx& c, int z, int k, const StepMap& sm) {
-    FuseTower ft{};
-    c.fuse_operands(ft, z, k, sm);
-    d = SanbTowerDesc{};
-    d.a = ft.a; d.b = ft.b; d.prev = ft.prev; d.lda = ft.lda; d.ldb = ft.ldb; d.ldp = ft.ldp; d.gate = ft.gate;
-    d.D = ft.D; d.type = ft.type;
-}
-
 int setup(Ctx& c, const iisan_side_cfg* cfg, const float* taps_cv, const float* taps_text, int64_t M,
-          const void* const* params, void* ws, size_t ws_bytes, const char* who) {
+          const void* const* params, void* ws, size_t ws_bytes, hipStream_t s, const char* who) {
     IISAN_CHECK_SHAPE(M > 0, "side_net: M must be positive");
     c.cfg = cfg;
     IISAN_TRY(make_plan(cfg, c.p));
@@ -446,7 +707,7 @@ int setup(Ctx& c, const iisan_side_cfg* cfg, const float* taps_cv, const float* 
         iisan_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, w.off);
         return IISAN_EWORKSPACE;
     }
-    c.taps[0] = taps_cv; c.taps[1] = taps_text; c.M = M; c.params = params;
+    c.taps[0] = taps_cv; c.taps[1] = taps_text; c.M = M; c.params = params; c.grads = nullptr; c.s = s;
     return IISAN_OK;
 }
 
@@ -480,12 +741,10 @@ extern "C" int iisan_side_net_fwd(const iisan_side_cfg* cfg, const float* taps_c
                                   void* stream) {
     hipStream_t s = (hipStream_t)stream;
     Ctx c;
-    IISAN_TRY(setup(c, cfg, taps_cv, taps_text, M, params, ws, ws_bytes, "side_net_fwd"));
+    IISAN_TRY(setup(c, cfg, taps_cv, taps_text, M, params, ws, ws_bytes, s, "side_net_fwd"));
     const Plan& p = c.p;
     SideBufs& b = c.b;
     ScratchGuard guard(b.skws, b.skws_floats);
-    const int act_flag = cfg->gelu ? G32_GELU : G32_RELU;
-    const int nsteps = p.diff_cv + p.diff_t + p.n[2];
     IISAN_CHECK_SHAPE(fwd_token != nullptr, "side_net_fwd: fwd_token must not be null");
     *fwd_token = 0x51DE000000000000ull ^ x3_route_word();     // the backward call must see the same split-operand routing
     IISAN_HIP_OK(hipMemsetAsync(b.amax, 0, (size_t)(16 + IISAN_MAX_SIDE + X3Z_WORDS * X3Z_SLOTS_F) * sizeof(uint32_t), s));
@@ -495,271 +754,39 @@ extern "C" int iisan_side_net_fwd(const iisan_side_cfg* cfg, const float* taps_c
     // the dim-align products skip the tap's amax pass (15 us each at Versa's [1408, 8192]), forward and weight gradient.
     const bool taps_preset = cfg->taps_exact16 && p.align && p.n[2] > 0;
     if (taps_preset) IISAN_HIP_OK(hipMemsetD32Async((hipDeviceptr_t)(b.amax + 9), 0x46000000, (size_t)p.n[2], s));
-    if (p.align && p.n[2] > 0) {
-        // dim-align the wider modality's taps (Code_Cached_Asym/model/model.py:404-411).  The products depend on taps and weights only, not on
-        // the chain: round 6 issues them as ONE group ahead of it (they used to sit in front of their steps, one amax launch per weight each)
-        Gemm32Prob pd[IISAN_MAX_SIDE];
-        const int zw = p.text_wide ? 1 : 0;
-        for (int i = 0; i < p.n[2]; ++i) {
-            const StepMap sm = step_map(p, p.diff_cv + p.diff_t + i);
-            pd[i] = prob(c.tap(zw, sm.k[zw]), (int)c.tap_ld(zw), c.W(p.dpw(i)), p.D[zw], c.W(p.dpw(i) + 1), b.DP[i], p.D[2], M, p.D[2], p.D[zw]);
-            pd[i].amax_a = b.amax + 9 + i;           // the tap's amax: read again by the weight-gradient product of this step
-            pd[i].amax_a_ready = taps_preset ? 1 : 0;
-            pd[i].exact16_a = taps_preset ? 1 : 0;
-        }
-        IISAN_TRY(gemm_group(pd, p.n[2], 0, b, s));
-    }
+    if (p.align && p.n[2] > 0) IISAN_TRY(c.fwd_dim_align(taps_preset));
+    const int nsteps = p.diff_cv + p.diff_t + p.n[2];
     for (int g = 0; g < nsteps; ++g) {
         const StepMap sm = step_map(p, g);
-        if (step_fusable(p, sm, M)) {         // fusion + down + activation + up of every active tower in one launch
-            SanbTowerDesc td[3];
-            for (int a = 0; a < sm.nact; ++a) {
-                const int z = sm.z[a], k = sm.k[a];
-                tower_desc(td[a], c, z, k, sm);
-                // both weights as stored: fc_down [64, D] and fc_up [D, 64] have the contraction index contiguous
-                td[a].Wd = c.W(p.wd(z, k)); td[a].bd = c.W(p.wd(z, k) + 1); td[a].Wu = c.W(p.wd(z, k) + 2); td[a].bu = c.W(p.wd(z, k) + 3);
-                td[a].F = b.F[k][z]; td[a].U = b.U[k][z]; td[a].A = b.A[k][z]; td[a].O = b.O[k][z];
-            }
-            IISAN_TRY(launch_sanb_fwd(td, sm.nact, M, cfg->gelu, s));
-            continue;
-        }
-        FuseArgs fa{};
-        fa.M = M;
-        int maxD = 0;
-        for (int a = 0; a < sm.nact; ++a) {
-            c.fuse_operands(fa.t[a], sm.z[a], sm.k[a], sm);
-            fa.t[a].F = b.F[sm.k[a]][sm.z[a]];
-            if (p.D[sm.z[a]] > maxD) maxD = p.D[sm.z[a]];
-        }
-        Gemm32Prob pr[3];
-        // fusion + down projection + activation in one launch where the shapes allow (gemm32_n64f_kernel: F is formed in the
-        // registers that feed the product and written once); else the fusion kernel, then the product
-        bool fed = false;
-        if (p.r == 64) {
-            N64FDesc nd[3];
-            for (int a = 0; a < sm.nact; ++a) {
-                const int z = sm.z[a], k = sm.k[a];
-                const FuseTower& ft = fa.t[a];
-                nd[a] = N64FDesc{};
-                nd[a].a = ft.a; nd[a].b = ft.b; nd[a].prev = ft.prev; nd[a].lda = ft.lda; nd[a].ldb = ft.ldb; nd[a].ldp = ft.ldp;
-                nd[a].gate = ft.gate; nd[a].type = ft.type;
-                nd[a].F = b.F[k][z]; nd[a].W = c.W(p.wd(z, k)); nd[a].ldw = p.D[z]; nd[a].bias = c.W(p.wd(z, k) + 1);
-                nd[a].U = b.U[k][z]; nd[a].A = b.A[k][z]; nd[a].M = M; nd[a].K = p.D[z];
-            }
-            if (gemm32_n64f_ok(nd, sm.nact)) {
-                IISAN_TRY(launch_gemm32_n64f(nd, sm.nact, cfg->gelu, s));
-                fed = true;
-            }
-        }
-        if (!fed) {
-            hipLaunchKernelGGL(fuse_fwd_kernel, dim3(ew_grid(M, maxD), sm.nact), dim3(256), 0, s, fa);
-            IISAN_LAUNCH_OK();
-            for (int a = 0; a < sm.nact; ++a) {   // U = F Wd^T + bd (saved), A = act(U)
-                const int z = sm.z[a], k = sm.k[a];
-                pr[a] = prob(b.F[k][z], p.D[z], c.W(p.wd(z, k)), p.D[z], c.W(p.wd(z, k) + 1), b.A[k][z], p.r, M, p.r, p.D[z], nullptr, 0, b.U[k][z]);
-            }
-            IISAN_TRY(launch_gemm32(pr, sm.nact, act_flag | G32_PREACT, s));
-        }
-        for (int a = 0; a < sm.nact; ++a) {   // state = A Wu^T + bu + F
-            const int z = sm.z[a], k = sm.k[a];
-            pr[a] = prob(b.A[k][z], p.r, c.W(p.wd(z, k) + 2), p.r, c.W(p.wd(z, k) + 3), b.O[k][z], p.D[z], M, p.D[z], p.r, b.F[k][z], p.D[z]);
-        }
-        IISAN_TRY(launch_gemm32(pr, sm.nact, 0, s));
+        IISAN_TRY(step_fusable(p, sm, M) ? c.fwd_step_fused(sm) : c.fwd_step_separate(sm));
     }
-    Gemm32Prob pr[3];
-    for (int z = 0; z < 3; ++z) {
-        pr[z] = prob(b.O[p.n[z] - 1][z], p.D[z], c.W(p.p_fc[z]), p.D[z], c.W(p.p_fc[z] + 1), b.Y[z], p.H[z], M, p.H[z], p.D[z]);
-        pr[z].amax_a = b.amax + z;                   // O_z and the fc weight: their amax is left for the backward products
-        pr[z].amax_b = b.amax + 3 + z;
-    }
-    IISAN_TRY(gemm_group(pr, 3, 0, b, s));
-    for (int z = 0; z < 3; ++z) pr[z] = prob(b.Y[z], p.H[z], c.W(p.p_head[z]), p.H[z], c.W(p.p_head[z] + 1), item3 + z * p.E, 3 * p.E, M, p.E, p.H[z]);
-    IISAN_TRY(launch_gemm32(pr, 3, 0, s));
-    return IISAN_OK;
+    return c.fwd_fc_head(item3);
 }
 
 extern "C" int iisan_side_net_bwd(const iisan_side_cfg* cfg, const float* taps_cv, const float* taps_text, int64_t M,
                                   const void* const* params, const float* d_item3, void* const* grads, void* ws,
                                   size_t ws_bytes, uint64_t fwd_token, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
     Ctx c;
-    {   // (before setup(): a changed routing also changes the workspace layout.)  The amax slots this call marks "ready" were filled by the forward call only on the routes IT took
-        if ((fwd_token >> 48) != 0x51DE) {
-            iisan_set_error("side_net_bwd: fwd_token %llx did not come from side_net_fwd", (unsigned long long)fwd_token);
-            return IISAN_EBADSHAPE;
-        }
-        if ((fwd_token ^ 0x51DE000000000000ull) != x3_route_word()) {
-            iisan_set_error("side_net_bwd: the split-operand routing (iisan_set_x3) changed since side_net_fwd filled this workspace");
-            return IISAN_EBADSHAPE;
-        }
+    // (before setup(): a changed routing also changes the workspace layout.)  The amax slots this call marks "ready" were filled by the forward call only on the routes IT took
+    if ((fwd_token >> 48) != 0x51DE) {
+        iisan_set_error("side_net_bwd: fwd_token %llx did not come from side_net_fwd", (unsigned long long)fwd_token);
+        return IISAN_EBADSHAPE;
     }
-    IISAN_TRY(setup(c, cfg, taps_cv, taps_text, M, params, ws, ws_bytes, "side_net_bwd"));
+    if ((fwd_token ^ 0x51DE000000000000ull) != x3_route_word()) {
+        iisan_set_error("side_net_bwd: the split-operand routing (the x3 switch) changed since side_net_fwd filled this workspace");
+        return IISAN_EBADSHAPE;
+    }
+    IISAN_TRY(setup(c, cfg, taps_cv, taps_text, M, params, ws, ws_bytes, (hipStream_t)stream, "side_net_bwd"));
+    c.grads = grads;
     const Plan& p = c.p;
-    SideBufs& b = c.b;
-    ScratchGuard guard(b.skws, b.skws_floats);
-    const int E = p.E, r = p.r;
-    auto G = [&](int i) { return (float*)grads[i]; };
-    Gemm32Prob pr[3];
-    const float* cs_x[3]; float* cs_o[3]; int64_t cs_m[3] = {M, M, M}; int32_t cs_n[3], cs_ld[3];
-
-    // heads: E_z = Y_z Wh^T + bh
-    for (int z = 0; z < 3; ++z) pr[z] = prob(d_item3 + z * E, 3 * E, c.W(p.p_head[z]), p.H[z], nullptr, b.dY[z], p.H[z], M, p.H[z], E);
-    IISAN_TRY(launch_gemm32(pr, 3, G32_TB, s));                                   // dY = dE · Wh
-    for (int z = 0; z < 3; ++z) pr[z] = prob(d_item3 + z * E, 3 * E, b.Y[z], p.H[z], nullptr, G(p.p_head[z]), p.H[z], E, p.H[z], M);
-    IISAN_TRY(launch_gemm32(pr, 3, G32_TA | G32_TB | G32_ACCUM, s));              // dWh += dE^T · Y
-    for (int z = 0; z < 3; ++z) { cs_x[z] = d_item3 + z * E; cs_o[z] = G(p.p_head[z] + 1); cs_n[z] = E; cs_ld[z] = 3 * E; }
-    IISAN_TRY(launch_colsum(cs_x, cs_o, cs_m, cs_n, cs_ld, 3, s));
-    // fc: Y_z = O_z Wf^T + bf
-    IISAN_HIP_OK(hipMemsetAsync(b.zb, 0, (size_t)(ZB_HEAD + X3Z_WORDS * X3Z_SLOTS_B) * sizeof(uint32_t), s));
-    b.x3z_next = b.x3z_b; b.x3z_left = X3Z_SLOTS_B;
-    int fwd_x3[3];      // did the forward fc product of tower z take the split-operand route (and leave its operands' amax)?
-    for (int z = 0; z < 3; ++z) {
-        const Gemm32Prob f = prob(b.O[p.n[z] - 1][z], p.D[z], c.W(p.p_fc[z]), p.D[z], c.W(p.p_fc[z] + 1), b.Y[z], p.H[z], M, p.H[z], p.D[z]);
-        fwd_x3[z] = (b.x3 && gemm_x3_applicable(f, 0)) ? 1 : 0;
-    }
-    for (int z = 0; z < 3; ++z) {
-        pr[z] = prob(b.dY[z], p.H[z], c.W(p.p_fc[z]), p.D[z], nullptr, b.dO[z], p.D[z], M, p.D[z], p.H[z]);
-        pr[z].amax_a = b.zb + z;                                                  // dY_z: computed here, reused by dWf below
-        if (fwd_x3[z]) { pr[z].amax_b = b.amax + 3 + z; pr[z].amax_b_ready = 1; } // the fc weight: from the forward call
-    }
-    IISAN_TRY(gemm_group(pr, 3, G32_TB, b, s));                                   // dO = dY · Wf
-    int dy_ready[3];
-    for (int z = 0; z < 3; ++z) dy_ready[z] = (b.x3 && gemm_x3_applicable(pr[z], G32_TB)) ? 1 : 0;
-    for (int z = 0; z < 3; ++z) {
-        pr[z] = prob(b.dY[z], p.H[z], b.O[p.n[z] - 1][z], p.D[z], nullptr, G(p.p_fc[z]), p.D[z], p.H[z], p.D[z], M);
-        pr[z].amax_a = b.zb + z; pr[z].amax_a_ready = dy_ready[z];          // (zeroed above; filled by the dX product if it took this route)
-        if (fwd_x3[z]) { pr[z].amax_b = b.amax + z; pr[z].amax_b_ready = 1; }     // O_z: from the forward call
-    }
-    IISAN_TRY(gemm_group(pr, 3, G32_TA | G32_TB | G32_ACCUM, b, s));              // dWf += dY^T · O
-    for (int z = 0; z < 3; ++z) { cs_x[z] = b.dY[z]; cs_o[z] = G(p.p_fc[z] + 1); cs_n[z] = p.H[z]; cs_ld[z] = p.H[z]; }
-    IISAN_TRY(launch_colsum(cs_x, cs_o, cs_m, cs_n, cs_ld, 3, s));
-
-    const int nsteps = p.diff_cv + p.diff_t + p.n[2];
-    for (int g = nsteps - 1; g >= 0; --g) {
+    ScratchGuard guard(c.b.skws, c.b.skws_floats);
+    IISAN_TRY(c.bwd_fc_head(d_item3));
+    for (int g = p.diff_cv + p.diff_t + p.n[2] - 1; g >= 0; --g) {
         const StepMap sm = step_map(p, g);
-        const int na = sm.nact;
-        if (step_fusable(p, sm, M) && !(sm.mm_i >= 0 && p.align)) {
-            // dWu += dO^T · A first (needs dO as it arrives), then ONE launch turns dO into dprev in place (tile-local:
-            // a workgroup reads its rows of dO into LDS before it writes them) and leaves dU, db_u, db_d, dθ; dWd += dU^T · F last
-            for (int a = 0; a < na; ++a) {
-                const int z = sm.z[a], k = sm.k[a];
-                pr[a] = prob(b.dO[z], p.D[z], b.A[k][z], r, nullptr, G(p.wd(z, k) + 2), r, p.D[z], r, M);
-            }
-            IISAN_TRY(launch_gemm32(pr, na, G32_TA | G32_TB | G32_ACCUM, s));
-            SanbTowerDesc td[3];
-            const float* tin[6]; float* tout[6]; int32_t trows[6], tcols[6];
-            for (int a = 0; a < na; ++a) {
-                const int z = sm.z[a], k = sm.k[a];
-                tin[2 * a] = c.W(p.wd(z, k)); tout[2 * a] = b.WT[z][0]; trows[2 * a] = p.r; tcols[2 * a] = p.D[z];              // fc_down [64,D] -> [D,64]
-                tin[2 * a + 1] = c.W(p.wd(z, k) + 2); tout[2 * a + 1] = b.WT[z][1]; trows[2 * a + 1] = p.D[z]; tcols[2 * a + 1] = p.r;  // fc_up [D,64] -> [64,D]
-                tower_desc(td[a], c, z, k, sm);
-                td[a].Wd = b.WT[z][1]; td[a].Wu = b.WT[z][0];      // dA = dO · fc_up: fc_up^T [64, D];  dU · fc_down: fc_down^T [D, 64] (contraction index contiguous)
-                td[a].dO = b.dO[z]; td[a].Upre = b.U[k][z]; td[a].dU = b.dU[z];
-                td[a].dprev = k > 0 ? b.dO[z] : nullptr;     // block 0 starts from zeros / a tap: nobody reads that gradient
-                td[a].dgate = cfg->gated ? G(p.gate(z, k)) : nullptr;
-                td[a].dbu = G(p.wd(z, k) + 3); td[a].dbd = G(p.wd(z, k) + 1);
-            }
-            IISAN_TRY(launch_sanb_transpose(tin, tout, trows, tcols, 2 * na, s));
-            IISAN_TRY(launch_sanb_bwd(td, na, M, cfg->gelu, s));
-            for (int a = 0; a < na; ++a) {
-                const int z = sm.z[a], k = sm.k[a];
-                pr[a] = prob(b.dU[z], r, b.F[k][z], p.D[z], nullptr, G(p.wd(z, k)), p.D[z], r, p.D[z], M);
-            }
-            IISAN_TRY(launch_gemm32(pr, na, G32_TA | G32_TB | G32_ACCUM, s));         // dWd += dU^T · F
-            continue;
-        }
-        // state = A Wu^T + bu + F ; A = act(U) ; U = F Wd^T + bd
-        for (int a = 0; a < na; ++a) {
-            const int z = sm.z[a], k = sm.k[a];
-            pr[a] = prob(b.dO[z], p.D[z], c.W(p.wd(z, k) + 2), r, nullptr, b.dU[z], r, M, r, p.D[z], nullptr, 0, b.U[k][z]);
-        }
-        IISAN_TRY(launch_gemm32(pr, na, G32_TB | (cfg->gelu ? G32_MUL_GELU_GRAD : G32_MUL_RELU_MASK), s));  // dU
-        {   // both weight gradients of the step, every tower, in ONE launch (round 6: they were two launches + two reducers; dO is still
-            // whole here — the dF product below overwrites it in place)
-            Gemm32Prob pw[6];
-            for (int a = 0; a < na; ++a) {
-                const int z = sm.z[a], k = sm.k[a];
-                pw[a] = prob(b.dO[z], p.D[z], b.A[k][z], r, nullptr, G(p.wd(z, k) + 2), r, p.D[z], r, M);             // dWu += dO^T · A
-                pw[a].colsum_a = G(p.wd(z, k) + 3);                               // dbu += column sums of dO: out of the same product
-                pw[na + a] = prob(b.dU[z], r, b.F[k][z], p.D[z], nullptr, G(p.wd(z, k)), p.D[z], r, p.D[z], M);       // dWd += dU^T · F
-                pw[na + a].colsum_a = G(p.wd(z, k) + 1);                          // dbd += column sums of dU
-            }
-            if (g_dw_merge) IISAN_TRY(launch_gemm32(pw, 2 * na, G32_TA | G32_TB | G32_ACCUM, s));
-            else {
-                IISAN_TRY(launch_gemm32(pw, na, G32_TA | G32_TB | G32_ACCUM, s));
-                IISAN_TRY(launch_gemm32(pw + na, na, G32_TA | G32_TB | G32_ACCUM, s));
-            }
-        }
-        for (int a = 0; a < na; ++a) {
-            const int z = sm.z[a], k = sm.k[a];
-            pr[a] = prob(b.dU[z], r, c.W(p.wd(z, k)), p.D[z], nullptr, b.dO[z], p.D[z], M, p.D[z], r, b.dO[z], p.D[z]);
-        }
-        const bool need_dp = sm.mm_i >= 0 && p.align;
-        // gated fusion: its backward rides in the epilogue of the dF product (gemm32_k64_kernel<true,
-        // true>: gate gradient and the (1 - g) scaling while dF is in registers) — no separate pass over dF
-        bool gate_folded = false;
-        if (cfg->gated) {
-            K64Gate kg[3];
-            for (int a = 0; a < na; ++a) {
-                const int z = sm.z[a], k = sm.k[a];
-                FuseTower ft{};
-                c.fuse_operands(ft, z, k, sm);
-                kg[a] = K64Gate{};
-                kg[a].gate = ft.gate; kg[a].ga = ft.a; kg[a].ldga = ft.lda;
-                if (ft.type == 1) { kg[a].go = ft.b; kg[a].ldgo = ft.ldb; }
-                else { kg[a].go = ft.prev; kg[a].ldgo = ft.ldp; }
-                kg[a].dgate = G(p.gate(z, k));
-                kg[a].scale_prev = ft.type == 0 ? 1 : 0;
-                kg[a].store = k > 0 ? 1 : 0;          // block 0 starts from zeros / a tap: nobody reads that gradient
-                if (z == 2 && need_dp) { kg[a].d2 = b.dDP[sm.mm_i]; kg[a].ldd2 = p.D[2]; kg[a].d2_is_b = p.text_wide ? 1 : 0; }      // gradient wrt the dim-aligned tap
-            }
-            if (gemm32_k64_gate_ok(pr, kg, na)) {
-                IISAN_TRY(launch_gemm32_k64_gate(pr, kg, na, s));                 // dprev = (1 - g | 1) · (dO + dU · Wd), dθ (in place)
-                gate_folded = true;
-            }
-        }
-        if (!gate_folded) IISAN_TRY(launch_gemm32(pr, na, G32_TB, s));            // dF = dO + dU · Wd (in place)
-
-        if (!gate_folded && (cfg->gated || need_dp)) {
-            FuseArgs fa{};
-            fa.M = M;
-            int maxD = 0;
-            for (int a = 0; a < na; ++a) {
-                const int z = sm.z[a], k = sm.k[a];
-                c.fuse_operands(fa.t[a], z, k, sm);
-                fa.t[a].F = b.dO[z];
-                fa.t[a].dgate = cfg->gated ? G(p.gate(z, k)) : nullptr;
-                fa.t[a].da = nullptr; fa.t[a].db = nullptr;
-                if (z == 2 && need_dp) { if (p.text_wide) fa.t[a].db = b.dDP[sm.mm_i]; else fa.t[a].da = b.dDP[sm.mm_i]; }
-                if (p.D[z] > maxD) maxD = p.D[z];
-            }
-            // every workgroup ends with ONE atomic on its tower's gate gradient and same-address atomics serialise (~12 ns
-            // each): 4096 workgroups spent ~50 us there (Versa: 130 us for 230 MB).  768 workgroups, more rows each.
-            unsigned gb = ew_grid(M, maxD);
-            if (gb > 768) gb = 768;
-            hipLaunchKernelGGL(fuse_bwd_kernel, dim3(gb, na), dim3(256), 0, s, fa);
-            IISAN_LAUNCH_OK();
-        }
-        // not gated: dprev_z = dF_z, already in dO
+        // (an aligned step of a dim-aligned configuration owes the gradient wrt the aligned tap, which the fused launch does not produce)
+        const bool fused = step_fusable(p, sm, M) && !(sm.mm_i >= 0 && p.align);
+        IISAN_TRY(fused ? c.bwd_step_fused(sm) : c.bwd_step_separate(sm));
     }
-    if (p.align && p.n[2] > 0) {
-        // DP_i = tap_wide · Pd_i^T + bd_i: the weight gradients of every aligned step as ONE group behind the chain (round 6: they sat
-        // inside their steps — an amax launch and a column-sum launch each; nothing in the chain reads them)
-        Gemm32Prob pd[IISAN_MAX_SIDE];
-        const float* X[IISAN_MAX_SIDE]; float* O[IISAN_MAX_SIDE]; int64_t Ms[IISAN_MAX_SIDE]; int32_t Ns[IISAN_MAX_SIDE], lds[IISAN_MAX_SIDE];
-        const int zw = p.text_wide ? 1 : 0;
-        for (int i = 0; i < p.n[2]; ++i) {
-            const StepMap sm = step_map(p, p.diff_cv + p.diff_t + i);
-            pd[i] = prob(b.dDP[i], p.D[2], c.tap(zw, sm.k[zw]), (int)c.tap_ld(zw), nullptr, G(p.dpw(i)), p.D[zw], p.D[2], p.D[zw], M);
-            const Gemm32Prob f = prob(c.tap(zw, sm.k[zw]), (int)c.tap_ld(zw), c.W(p.dpw(i)), p.D[zw], c.W(p.dpw(i) + 1), b.DP[i], p.D[2], M, p.D[2], p.D[zw]);
-            if (b.x3 && gemm_x3_applicable(f, 0)) {       // the tap: from the forward dim-align product
-                pd[i].amax_b = b.amax + 9 + i; pd[i].amax_b_ready = 1;
-                pd[i].exact16_b = cfg->taps_exact16 ? 1 : 0;     // (side_net_fwd preset the slot: scale 1)
-            }
-            X[i] = b.dDP[i]; O[i] = G(p.dpw(i) + 1); Ms[i] = M; Ns[i] = p.D[2]; lds[i] = p.D[2];
-        }
-        IISAN_TRY(gemm_group(pd, p.n[2], G32_TA | G32_TB | G32_ACCUM | G32_HINT_B_EXACT16, b, s));     // dPd_i += dDP_i^T · tap
-        for (int i = 0; i < p.n[2]; i += 4) IISAN_TRY(launch_colsum(X + i, O + i, Ms + i, Ns + i, lds + i, p.n[2] - i < 4 ? p.n[2] - i : 4, s));
-    }
+    if (p.align && p.n[2] > 0) IISAN_TRY(c.bwd_dim_align());
     return IISAN_OK;
 }

@@ -343,6 +343,18 @@ int32_t iisan_gemm16_h256_applicable(int32_t mode, int64_t M, int32_t N, int32_t
  * Operands with natural leading dimensions; qkv_S is the patch count of the patch modes; with_rowstat: LayerNorm in the epilogue. */
 int32_t iisan_gemm16_route(int32_t dtype16, int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t qkv_heads,
                            int32_t qkv_which0, int32_t with_rowstat);
+/* host-side query of the launch iisan_gemm32 / the side network makes for a group of nprob fp32 products C[M,N] = op(A) op(B) under `flags`
+ * (csrc/common.h: G32_*) with scratch_floats of split-K scratch registered (no device memory touched; the plan depends on the compute-unit
+ * count of the current device, 256 without one).  Natural leading dimensions, aligned operands; with_colsum: every problem wants the column
+ * sums of A.  plan12 = kernel (0 tiled, 1 K = 64, 2 weight-gradient, 3 split into a K = 64 launch and a rest launch), row-tile height, K
+ * splits, scratch use (0 none, 1 partials + epilogue reducer, 2 partials added to C), fast fetch, three K-tiles in flight, column sums (0 none,
+ * 1 out of the product, 2 own launch), 64-column blocks per workgroup (K = 64 kernel), grid x / y / z, members of the K = 64 launch of a split.
+ * Returns the kernel, negative = rejected (iisan_last_error). */
+int32_t iisan_gemm32_plan(const int64_t* M, const int32_t* N, const int64_t* K, int32_t nprob, int32_t flags, int64_t scratch_floats,
+                          int32_t with_colsum, int32_t* plan12);
+/* host-side query: the route iisan_inbatch_ce_fwd takes for this shape under the current ce_fast — 0 generic kernel, 1 separate row passes,
+ * 2 fused f32 row pass, 3 split-operand passes; negative = the shape is rejected (iisan_last_error) */
+int32_t iisan_inbatch_ce_route(int64_t bs, int32_t S);
 
 /* ------------------------------------------------------------------------------------------------------------
  * DEV section — process-wide development switches and measurement hooks.  NOT part of the product contract: a

@@ -362,6 +362,97 @@ def test_gemm16_route_table_under_every_variant():
                 assert (got if got >= 0 else -1) == want[variant], (variant, args, got, want[variant])
 
 
+def test_inbatch_ce_route_table_under_every_ce_fast():
+    """The route of one loss call (ce.hip: ce_route, the ONE place that decides; the forward call's token carries it to the backward call),
+    as a literal table under ce_fast 0..4: G = generic kernel, R = separate row passes, F = fused f32 row pass, X = split-operand passes.
+    The row-fixed kernels take 5 <= S <= 15; the default (1) goes to the split-operand route from 2^24 logits on; shapes `check()` rejects
+    are negative.  Pure host logic: no device is touched."""
+    from iisan_amd import _lib
+    lib = _lib.load()
+    G, R, F, X = 0, 1, 2, 3
+    table = [
+        ((3, 10), (G, F, R, X, F)),
+        ((128, 10), (G, F, R, X, F)),
+        ((64, 15), (G, F, R, X, F)),                 # RS1 = 16
+        ((1024, 10), (G, X, R, X, F)),
+        ((390, 10), (G, F, R, X, F)),                # 390^2 * 110 = 16,731,000 < 2^24
+        ((391, 10), (G, X, R, X, F)),                # 391^2 * 110 = 16,816,910 >= 2^24
+        ((64, 4), (G, G, G, G, G)),                  # S too small: a 16-row tile would span more than four sequences
+        ((64, 16), (G, G, G, G, G)),                 # S + 1 > 16 ids per sequence
+        ((0, 10), None),
+        ((64, 64), None),
+    ]
+    for ce_fast in range(5):
+        with _lib.dev(ce_fast=ce_fast):
+            for (bs, S), want in table:
+                got = lib.iisan_inbatch_ce_route(bs, S)
+                if want is None:
+                    assert got < 0, (ce_fast, bs, S, got)
+                else:
+                    assert got == want[ce_fast], (ce_fast, bs, S, got, want[ce_fast])
+
+
+def test_gemm32_plan_table():
+    """What `launch_gemm32` does with a group of fp32 products (gemm32.hip: plan_gemm32, decided before anything is launched), as a literal
+    table.  THE PLAN DEPENDS ON `iisan_cu_count`: the weight-gradient split counts below are those of 256 compute units — an MI355X, and the
+    value the library assumes where no device is visible, so the table holds on a CPU.  Expected values: recorded from the launcher this
+    plan replaced (its decisions at each launch, on the same inputs), which agreed with every hand-derived anchor (#1 - #8: the side
+    network's launches at the bench shapes).  Fields: kernel (0 tiled, 1 K = 64, 2 weight-gradient, 3 split into a K = 64 launch and a rest
+    launch), row-tile height, K splits, scratch (0 none, 1 partials + epilogue reducer, 2 partials added to C), fast fetch, three K-tiles in
+    flight, column sums (0 none, 1 out of the product, 2 own launch), column blocks (K = 64 kernel), grid x / y / z, K = 64 members of a split."""
+    import ctypes as C
+    from iisan_amd import _lib
+    lib = _lib.load()
+    TA, TB, RELU, GELU, ACCUM, MASK, PREACT = 1, 2, 4, 8, 16, 32, 128
+    DW = TA | TB | ACCUM
+    AMPLE = 1 << 28
+    cached6 = [(768, 64, 11264)] * 3 + [(64, 768, 11264)] * 3      # dWu and dWd of a Cached SANB step (bs = 1024), three towers
+    versa6 = [(1024, 64, 1408), (8192, 64, 1408), (1024, 64, 1408), (64, 1024, 1408), (64, 8192, 1408), (64, 1024, 1408)]
+    k64 = [(11264, 768, 64)] * 3
+    # (problems (M, N, K), flags, scratch floats, with column sums, dev switches) -> plan
+    table = [
+        (cached6, DW, AMPLE, 1, {}, (2, 64, 7, 2, 0, 0, 1, 0, 12, 7, 6, 0)),                        # 1: 72 tiles x 7 = two workgroups per CU
+        (cached6[:3], DW, AMPLE, 1, {}, (2, 64, 7, 2, 0, 0, 1, 0, 12, 7, 3, 0)),                    # 2: 36 tiles x 7 = one per CU
+        (versa6, DW, AMPLE, 1, {}, (2, 64, 2, 2, 0, 0, 1, 0, 128, 2, 6, 0)),                        # 3
+        (k64, 0, AMPLE, 0, {}, (1, 0, 0, 0, 0, 0, 0, 4, 176, 3, 3, 0)),                             # 4: up projection + residual
+        ([(1408, 64, 8192)], 0, AMPLE, 0, {}, (0, 16, 8, 1, 1, 0, 0, 0, 88, 8, 1, 0)),              # 5: Versa's skinny long-K projection
+        ([(11264, 64, 768)] * 3, TB | MASK, AMPLE, 0, {}, (0, 64, 1, 0, 1, 0, 0, 0, 176, 1, 3, 0)), # 6: dU
+        ([(1408, 64, 768)] * 3, 0, AMPLE, 0, {}, (0, 16, 1, 0, 1, 0, 0, 0, 88, 1, 3, 0)),           # 7
+        ([(1408, 1024, 64), (1408, 1024, 1024)], TB, AMPLE, 0, {}, (3, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1)),   # 8: a mixed group
+        (cached6, DW, 0, 1, {}, (0, 64, 15, 0, 1, 1, 2, 0, 12, 15, 6, 0)),                          # 1 without scratch: tiled, atomics
+        (cached6, DW, AMPLE, 1, {"gemm32_dw": 0}, (0, 64, 15, 2, 1, 1, 2, 0, 12, 15, 6, 0)),        # 1 with the weight-gradient kernel off
+        (k64, 0, AMPLE, 0, {"gemm32_k64": 0}, (0, 64, 1, 0, 1, 0, 0, 0, 2112, 1, 3, 0)),            # 4 with the K = 64 kernel off
+        # beyond the anchors
+        (cached6, DW, 100000, 1, {}, (0, 64, 7, 0, 1, 1, 2, 0, 12, 7, 6, 0)),                       # scratch too small for the partials
+        (cached6, DW, AMPLE, 1, {"gemm32_dw_splits": 5}, (2, 64, 5, 2, 0, 0, 1, 0, 12, 5, 6, 0)),
+        ([(64, 768, 11264)] * 3, DW, AMPLE, 0, {}, (2, 64, 7, 2, 0, 0, 0, 0, 12, 7, 3, 0)),         # no column sums wanted
+        ([(1024, 1024, 1408)], DW, AMPLE, 0, {}, (2, 64, 1, 2, 0, 0, 0, 0, 256, 1, 1, 0)),          # tiles fill the chip: ONE split, still gemm32_dw
+        ([(64, 64, 1408), (64, 64, 11264)], DW, AMPLE, 1, {}, (2, 64, 11, 2, 0, 0, 1, 0, 1, 11, 2, 0)),     # splits follow the shortest K
+        ([(100, 64, 1408)], DW, AMPLE, 0, {}, (0, 64, 11, 2, 0, 0, 0, 0, 2, 11, 1, 0)),             # M % 64: tiled, partials through the scratch
+        ([(64, 768, 1408)], DW, 0, 0, {}, (0, 64, 11, 0, 1, 0, 0, 0, 12, 11, 1, 0)),                # iisan_linear_bwd: no executor, no scratch
+        ([(64, 64, 1408)], TA | TB, 0, 1, {}, (0, 16, 1, 0, 1, 0, 2, 0, 4, 1, 1, 0)),
+        ([(1408, 64, 8192)], 0, 0, 0, {}, (0, 16, 1, 0, 1, 0, 0, 0, 88, 1, 1, 0)),                  # 5 without scratch: never split
+        (k64, TB, AMPLE, 0, {}, (1, 0, 0, 0, 0, 0, 0, 4, 176, 3, 3, 0)),
+        ([(130, 768, 64)], TB, 0, 0, {}, (1, 0, 0, 0, 0, 0, 0, 1, 3, 12, 1, 0)),                    # a small launch: one column block per workgroup
+        ([(1408, 256, 64)] * 5, 0, AMPLE, 0, {}, (0, 32, 1, 0, 1, 0, 0, 0, 176, 1, 5, 0)),          # the K = 64 kernel takes four problems
+        ([(1408, 256, 768)] * 3, GELU | PREACT, AMPLE, 0, {}, (0, 32, 1, 0, 1, 0, 0, 0, 176, 1, 3, 0)),
+        ([(70, 64, 48)], 0, 0, 0, {}, (0, 16, 1, 0, 0, 0, 0, 0, 5, 1, 1, 0)),                       # ragged: the generic fetch
+        ([(64, 64, 64)] * 7, 0, 0, 0, {}, None),                                                    # more than six problems: rejected
+    ]
+    for probs, flags, scratch, colsum, knobs, want in table:
+        n = len(probs)
+        M = (C.c_int64 * n)(*[q[0] for q in probs])
+        N = (C.c_int32 * n)(*[q[1] for q in probs])
+        K = (C.c_int64 * n)(*[q[2] for q in probs])
+        out = (C.c_int32 * 12)()
+        with _lib.dev(**knobs):
+            rc = lib.iisan_gemm32_plan(M, N, K, n, flags, scratch, colsum, out)
+        if want is None:
+            assert rc < 0, (probs, flags, rc)
+        else:
+            assert rc == want[0] and tuple(out) == want, (probs, flags, scratch, colsum, knobs, rc, tuple(out), want)
+
+
 def test_tools_compile_and_name_only_declared_entry_points():
     """a development tool that still iterated a table the ABI clean-up had removed died silently in every child process.  Every
     script under tools/ must byte-compile, and every `iisan_*` entry point it names must be one the loader binds (`_lib.SIGNATURES` =
@@ -371,12 +462,11 @@ def test_tools_compile_and_name_only_declared_entry_points():
     import re
     from iisan_amd import _lib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    retired = {"iisan_set_x3"}                       # named in prose (error messages / docstrings) only
     for path in sorted(glob.glob(os.path.join(root, "tools", "*.py"))):
         py_compile.compile(path, doraise=True)
         src = open(path).read()
         for name in set(re.findall(r"\biisan_[a-z0-9_]+\b", src)):
-            if name in ("iisan_amd", "iisan_hip", "iisan_oracle") or name in retired:
+            if name in ("iisan_amd", "iisan_hip", "iisan_oracle"):
                 continue
             assert name in _lib.SIGNATURES, f"{os.path.basename(path)} names {name}, which the library does not export"
         for attr in set(re.findall(r"\b_lib\.([A-Za-z_]+)\b", src)):
