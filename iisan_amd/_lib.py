@@ -57,8 +57,10 @@ SIGNATURES = {
     "iisan_vit_fold_layernorm": (i32, [C.POINTER(VitWeights), vp, sz, vp]),
     "iisan_vit_forward_taps": (i32, [C.POINTER(VitWeights), vp, i64, C.POINTER(i32), i32, vp, i64, vp, sz, vp]),
     "iisan_vit_forward_taps_u8": (i32, [C.POINTER(VitWeights), vp, i64, C.POINTER(i32), i32, vp, i64, vp, sz, vp]),
+    "iisan_vit_forward_taps_u8_indexed": (i32, [C.POINTER(VitWeights), vp, i64, vp, i64, C.POINTER(i32), i32, vp, i64, vp, sz, vp]),
     "iisan_bert_forward_taps_ws_bytes": (sz, [C.POINTER(BertWeights), i64, i32, i64]),
     "iisan_bert_forward_taps": (i32, [C.POINTER(BertWeights), vp, i64, i32, C.POINTER(i32), i32, vp, i64, vp, sz, vp]),
+    "iisan_bert_forward_taps_indexed": (i32, [C.POINTER(BertWeights), vp, i64, vp, i64, i32, C.POINTER(i32), i32, vp, i64, vp, sz, vp]),
     "iisan_side_net_ws_bytes": (sz, [C.POINTER(SideCfg), i64]),
     "iisan_side_net_num_params": (i32, [C.POINTER(SideCfg)]),
     "iisan_side_net_fwd": (i32, [C.POINTER(SideCfg), vp, vp, i64, C.POINTER(vp), vp, vp, sz, C.POINTER(u64), vp]),

@@ -358,10 +358,17 @@ int launch_attention_cls16(int dtype16, const void* qkv, const float* key_bias, 
                            int heads, hipStream_t s, const void* q_cls = nullptr);   // q_cls: [items, heads*64] 16-bit CLS queries
 // embedding and tap steps of the encoder executors (rowops.hip)
 int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64_t M, int C, int R, int p, hipStream_t s);
+// item m = row index[m] of a resident uint8 catalogue [rows, C, R, R]; values outside [0, rows) = padding (zero fragment, no read)
+int launch_vit_im2col_indexed(int dtype16, const uint8_t* catalogue, int64_t rows, const int64_t* index, void* out, int64_t M, int C,
+                              int R, int p, hipStream_t s);
 int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M, int T, int D, hipStream_t s);
 int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, const float* pos, const float* type0,
                          const float* g, const float* b, float eps, float* X, void* H, float* key_bias, int64_t M,
                          int W, int vocab, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
+// item m = row index[m] of a resident table [rows, 2W]; values outside [0, rows) = padding (zero ids and mask, no read)
+int launch_bert_embed_ln_indexed(int dtype16, const int64_t* table, int64_t rows, const int64_t* index, const float* word, const float* pos,
+                                 const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
+                                 int64_t M, int W, int vocab, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
 int launch_gather_cls(const float* X, float* taps, int64_t M, int T, int D, int n_taps, int k, hipStream_t s);
 int launch_gather_rows16(const void* H, void* out, int64_t M, int T, int D, hipStream_t s);   // out[m] = H[m*T] (16-bit rows)
 

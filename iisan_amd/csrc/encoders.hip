@@ -230,9 +230,11 @@ struct VitChunk {
     float* bf_qkv(int l) const { return b.Bf + (size_t)l * (3 * D + F); }
     float* bf_fc1(int l) const { return bf_qkv(l) + 3 * D; }
 
-    int embed(const void* img, int img_u8) const {
+    // index != null: `img` is a resident uint8 catalogue of `rows` images and item m of the chunk is its row index[m]
+    int embed(const void* img, int img_u8, const int64_t* index = nullptr, int64_t rows = 0) const {
         const int P = T - 1, pd = w->channels * w->patch * w->patch;
-        IISAN_TRY(launch_vit_im2col(dt, img, img_u8, b.F1, mc, w->channels, w->image, w->patch, s));
+        if (index) IISAN_TRY(launch_vit_im2col_indexed(dt, (const uint8_t*)img, rows, index, b.F1, mc, w->channels, w->image, w->patch, s));
+        else IISAN_TRY(launch_vit_im2col(dt, img, img_u8, b.F1, mc, w->channels, w->image, w->patch, s));
         // patch embedding: resid32 = fp32 token rows with the position embedding added (128x128 kernel); mixed = 16-bit rows on the
         // production GEMM (gemm16_h256, 0.40 against 0.59 ms at bs = 128), the position table is added by block 0's open step
         if (mixed()) IISAN_TRY(gemm(dt, EPI_PATCH16, b.F1, pd, w->patch_w, w->patch_b, b.D16b, D, nullptr, mc * P, s, nullptr, P));
@@ -363,9 +365,11 @@ const struct { int (VitChunk::*open)(int) const; int (VitChunk::*full)(int) cons
 
 }  // namespace
 
+// index != null: `images` is a resident uint8 catalogue [rows, C, R, R] and slot m reads row index[m] (the chunk loop offsets the
+// index, never the catalogue)
 static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images, int img_u8, int64_t M,
                                  const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
-                                 void* ws, size_t ws_bytes, void* stream) {
+                                 void* ws, size_t ws_bytes, void* stream, const int64_t* index = nullptr, int64_t rows = 0) {
     hipStream_t s = (hipStream_t)stream;
     IISAN_CHECK_SHAPE(M > 0, "vit_forward_taps: M must be positive");
     IISAN_TRY(check_common(w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
@@ -396,7 +400,8 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
     for (int64_t m0 = 0; m0 < M; m0 += Mc) {
         const int64_t mc = (M - m0 < Mc) ? M - m0 : Mc;
         const VitChunk ch{w, b, st, s, w->dtype16, D, F, T, w->heads, w->eps, mc, mc * T, taps + m0 * n_taps * D, n_taps};
-        IISAN_TRY(ch.embed(img_u8 ? (const void*)((const uint8_t*)images + m0 * img_elems) : (const void*)((const float*)images + m0 * img_elems), img_u8));
+        if (index) IISAN_TRY(ch.embed(images, 1, index + m0, rows));
+        else IISAN_TRY(ch.embed(img_u8 ? (const void*)((const uint8_t*)images + m0 * img_elems) : (const void*)((const float*)images + m0 * img_elems), img_u8));
         int k = tap_index(tap_layers, n_taps, 0);
         if (k >= 0) IISAN_TRY(ch.tap(k));
         for (int l = 0; l < live; ++l) {
@@ -428,6 +433,16 @@ extern "C" int iisan_vit_forward_taps_u8(const iisan_vit_weights* w, const uint8
     return vit_forward_taps_impl(w, images, 1, M, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream);
 }
 
+extern "C" int iisan_vit_forward_taps_u8_indexed(const iisan_vit_weights* w, const uint8_t* catalogue, int64_t rows,
+                                                 const int64_t* index, int64_t M, const int32_t* tap_layers, int32_t n_taps,
+                                                 float* taps, int64_t chunk_items, void* ws, size_t ws_bytes, void* stream) {
+    IISAN_CHECK_SHAPE(rows > 0, "vit u8 indexed: the catalogue needs at least one row (rows = %lld)", (long long)rows);
+    IISAN_CHECK_SHAPE(catalogue != nullptr && index != nullptr, "vit u8 indexed: null %s", catalogue ? "index" : "catalogue");
+    IISAN_CHECK_SHAPE(w->image % 8 == 0, "vit u8 indexed: image side %d must be a multiple of 8", w->image);
+    IISAN_CHECK_SHAPE(M > 0, "vit u8 indexed: M must be positive");
+    return vit_forward_taps_impl(w, catalogue, 1, M, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream, index, rows);
+}
+
 extern "C" size_t iisan_bert_forward_taps_ws_bytes(const iisan_bert_weights* w, int64_t M, int32_t words, int64_t chunk_items) {
     const int64_t Mc = (chunk_items > 0 && chunk_items < M) ? chunk_items : M;
     WsCarver c(nullptr, 0);
@@ -435,9 +450,10 @@ extern "C" size_t iisan_bert_forward_taps_ws_bytes(const iisan_bert_weights* w, 
     return carve(c, b, Mc * words, Mc, w->hidden, w->mlp, Mc * words);
 }
 
-extern "C" int iisan_bert_forward_taps(const iisan_bert_weights* w, const int64_t* text, int64_t M, int32_t words,
-                                       const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
-                                       void* ws, size_t ws_bytes, void* stream) {
+// index != null: `text` is a resident table [rows, 2W] and slot m reads row index[m] (the chunk loop offsets the index, never the table)
+static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* text, int64_t M, int32_t words,
+                                  const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
+                                  void* ws, size_t ws_bytes, void* stream, const int64_t* index = nullptr, int64_t rows = 0) {
     hipStream_t s = (hipStream_t)stream;
     IISAN_CHECK_SHAPE(M > 0, "bert_forward_taps: M must be positive");
     IISAN_TRY(check_common(w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
@@ -462,8 +478,10 @@ extern "C" int iisan_bert_forward_taps(const iisan_bert_weights* w, const int64_
         // LayerNorm kernels move 6 instead of 8 bytes per element)
         const bool alias = mixed && dt == IISAN_F16 && g_ln_fold;
         void* IMG = alias ? b.X16 : b.H;
-        IISAN_TRY(launch_bert_embed_ln(dt, text + m0 * 2 * words, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w,
-                                       w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, s, b.X16, b.Xc));
+        if (index) IISAN_TRY(launch_bert_embed_ln_indexed(dt, text, rows, index + m0, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w,
+                                                          w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, s, b.X16, b.Xc));
+        else IISAN_TRY(launch_bert_embed_ln(dt, text + m0 * 2 * words, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w,
+                                            w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, s, b.X16, b.Xc));
         auto tap = [&](int k) { return mixed ? launch_gather_cls(b.Xc, tp, mc, 1, D, n_taps, k, s) : launch_gather_cls(b.X, tp, mc, T, D, n_taps, k, s); };
         // x = LN(x + delta): stream and 16-bit image out
         auto add_ln = [&](const float* g, const float* be) {
@@ -508,4 +526,20 @@ extern "C" int iisan_bert_forward_taps(const iisan_bert_weights* w, const int64_
         }
     }
     return IISAN_OK;
+}
+
+extern "C" int iisan_bert_forward_taps(const iisan_bert_weights* w, const int64_t* text, int64_t M, int32_t words,
+                                       const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
+                                       void* ws, size_t ws_bytes, void* stream) {
+    return bert_forward_taps_impl(w, text, M, words, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream);
+}
+
+extern "C" int iisan_bert_forward_taps_indexed(const iisan_bert_weights* w, const int64_t* table, int64_t rows,
+                                               const int64_t* index, int64_t M, int32_t words, const int32_t* tap_layers,
+                                               int32_t n_taps, float* taps, int64_t chunk_items, void* ws, size_t ws_bytes,
+                                               void* stream) {
+    IISAN_CHECK_SHAPE(rows > 0, "bert indexed: the table needs at least one row (rows = %lld)", (long long)rows);
+    IISAN_CHECK_SHAPE(table != nullptr && index != nullptr, "bert indexed: null %s", table ? "index" : "table");
+    IISAN_CHECK_SHAPE(M > 0, "bert indexed: M must be positive");
+    return bert_forward_taps_impl(w, table, M, words, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream, index, rows);
 }

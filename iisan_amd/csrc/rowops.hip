@@ -229,9 +229,13 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
 // SRC = float: already normalised pixels; SRC = uint8_t: raw pixels, normalised here exactly as the reference's
 // transform does in fp32 — ToTensor (x/255) then Normalize(mean .5, std .5) (`Code_Uncached/data_utils/dataset.py:46-50`)
 // — so the 16-bit patch matrix is bit-identical to the fp32 route while the image crosses PCIe/HBM at a quarter the size.
-template <typename T, typename SRC>
+// IDX (uint8 only): `img` is a resident catalogue [rows, C, R, R] and item m reads row index[m]; any value outside [0, rows) is a
+// padding slot — never dereferenced, its fragment is the all-zero NORMALISED image the reference ships for pad slots
+// (`Code_Uncached/data_utils/dataset.py:73`; no uint8 pixel normalises to 0).  The plain instantiations compile as before.
+template <typename T, typename SRC, bool IDX = false>
 __global__ __launch_bounds__(256) void vit_im2col_kernel(const SRC* __restrict__ img, typename T::elem* __restrict__ out,
-                                                         int64_t M, int C, int R, int p) {
+                                                         int64_t M, int C, int R, int p,
+                                                         const int64_t* __restrict__ index = nullptr, int64_t rows = 0) {
     const int per_row = C * p * p / 8;        // threads per patch row
     const int gp = R / p;                      // patches per image side
     const int64_t total = M * gp * gp * per_row;
@@ -242,9 +246,19 @@ __global__ __launch_bounds__(256) void vit_im2col_kernel(const SRC* __restrict__
         const int c = col / (p * p), rem = col % (p * p), iy = rem / p, ix = rem % p;
         const int64_t m = pr / (gp * gp);
         const int pp = (int)(pr % (gp * gp)), py = pp / gp, px = pp % gp;
-        const SRC* src = img + ((m * C + c) * R + (py * p + iy)) * (int64_t)R + px * p + ix;
+        int64_t sm = m;
+        bool pad = false;
+        if constexpr (IDX) {
+            sm = index[m];
+            pad = (uint64_t)sm >= (uint64_t)rows;       // negative or >= rows
+            if (pad) sm = 0;                            // keeps the address arithmetic below in range; never loaded
+        }
+        const SRC* src = img + ((sm * C + c) * R + (py * p + iy)) * (int64_t)R + px * p + ix;
         f4 a, b2;
-        if constexpr (sizeof(SRC) == 4) {
+        if (IDX && pad) {
+            a = f4{0.f, 0.f, 0.f, 0.f};
+            b2 = a;
+        } else if constexpr (sizeof(SRC) == 4) {
             a = *(const f4*)src;
             b2 = *(const f4*)(src + 4);
         } else {
@@ -277,21 +291,33 @@ __global__ void vit_cls_rows_kernel(float* __restrict__ X, const float* __restri
 }
 
 // ---- BERT embeddings: LN(word[id] + pos[t] + type[0]) -> X fp32 + H 16-bit; key bias from the attention mask ------
-template <typename T>
+// IDX: `text` is a resident table [rows, 2W] and item m reads row index[m]; a value outside [0, rows) is a padding slot — never
+// dereferenced, all-zero ids and mask (what `dataset.py:79-84` ships for pad slots).
+template <typename T, bool IDX = false>
 __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __restrict__ text, const float* __restrict__ word,
                                                             const float* __restrict__ pos, const float* __restrict__ type0,
                                                             const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                             float* __restrict__ X, typename T::elem* __restrict__ H,
                                                             float* __restrict__ key_bias, int64_t M, int W, int vocab,
-                                                            _Float16* __restrict__ X16, float* __restrict__ Xc) {
+                                                            _Float16* __restrict__ X16, float* __restrict__ Xc,
+                                                            const int64_t* __restrict__ index = nullptr, int64_t rows = 0) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M * W) return;
     const int64_t m = row / W;
     const int t = (int)(row % W);
-    int64_t id = text[m * 2 * W + t];
+    int64_t id, msk;
+    if constexpr (IDX) {
+        const int64_t sm = index[m];
+        const bool pad = (uint64_t)sm >= (uint64_t)rows;
+        id = pad ? 0 : text[sm * 2 * W + t];
+        msk = pad ? 0 : text[sm * 2 * W + W + t];
+    } else {
+        id = text[m * 2 * W + t];
+        msk = text[m * 2 * W + W + t];
+    }
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    if (lane == 0) key_bias[row] = text[m * 2 * W + W + t] != 0 ? 0.0f : -1.0f;
+    if (lane == 0) key_bias[row] = msk != 0 ? 0.0f : -1.0f;
     const float* wr = word + id * 768;
     const float* pr = pos + (int64_t)t * 768;
     f4 v[3];
@@ -453,6 +479,18 @@ int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64
     return IISAN_OK;
 }
 
+int launch_vit_im2col_indexed(int dtype16, const uint8_t* catalogue, int64_t rows, const int64_t* index, void* out, int64_t M, int C,
+                              int R, int p, hipStream_t s) {
+    const int64_t total = M * (R / p) * (R / p) * (C * p * p / 8);
+    const unsigned grid = (unsigned)(ceil_div(total, 256) < 262144 ? ceil_div(total, 256) : 262144);
+    if (dtype16 == IISAN_BF16)
+        hipLaunchKernelGGL((vit_im2col_kernel<BF16, uint8_t, true>), dim3(grid), dim3(256), 0, s, catalogue, (__bf16*)out, M, C, R, p, index, rows);
+    else
+        hipLaunchKernelGGL((vit_im2col_kernel<F16, uint8_t, true>), dim3(grid), dim3(256), 0, s, catalogue, (_Float16*)out, M, C, R, p, index, rows);
+    IISAN_LAUNCH_OK();
+    return IISAN_OK;
+}
+
 int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M, int T, int D, hipStream_t s) {
     hipLaunchKernelGGL(vit_cls_rows_kernel, dim3((unsigned)ceil_div(M * D, 256)), dim3(256), 0, s, X, cls, pos, M, T, D);
     IISAN_LAUNCH_OK();
@@ -467,6 +505,18 @@ int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, co
         hipLaunchKernelGGL(bert_embed_ln_kernel<BF16>, grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (__bf16*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc);
     else
         hipLaunchKernelGGL(bert_embed_ln_kernel<F16>, grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (_Float16*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc);
+    IISAN_LAUNCH_OK();
+    return IISAN_OK;
+}
+
+int launch_bert_embed_ln_indexed(int dtype16, const int64_t* table, int64_t rows, const int64_t* index, const float* word, const float* pos,
+                                 const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
+                                 int64_t M, int W, int vocab, hipStream_t s, void* X16, float* Xc) {
+    dim3 grid((unsigned)ceil_div(M * W, 4)), block(256);
+    if (dtype16 == IISAN_BF16)
+        hipLaunchKernelGGL((bert_embed_ln_kernel<BF16, true>), grid, block, 0, s, table, word, pos, type0, g, b, eps, X, (__bf16*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows);
+    else
+        hipLaunchKernelGGL((bert_embed_ln_kernel<F16, true>), grid, block, 0, s, table, word, pos, type0, g, b, eps, X, (_Float16*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows);
     IISAN_LAUNCH_OK();
     return IISAN_OK;
 }

@@ -135,6 +135,28 @@ class PackedVit(_PackedEncoder):
         return taps
 
 
+    def forward_taps_indexed(self, catalogue_u8: torch.Tensor, index: torch.Tensor, tap_layers: Sequence[int],
+                             chunk_items: int = 0) -> torch.Tensor:
+        """catalogue uint8 [rows,C,R,R] resident on the device, index int64 [M] on the device -> fp32 [M, len(tap_layers), D]: slot m
+        encodes row index[m]; a value outside [0, rows) is a padding slot (the zero normalised image, `dataset.py:73`).  No
+        [M,C,R,R] tensor is built (`iisan_vit_forward_taps_u8_indexed`)."""
+        lib = _lib.load()
+        cfg = self.cfg
+        assert catalogue_u8.is_cuda and catalogue_u8.dtype == torch.uint8 and catalogue_u8.is_contiguous()
+        assert catalogue_u8.dim() == 4 and catalogue_u8.shape[1:] == (cfg.channels, cfg.image, cfg.image), catalogue_u8.shape
+        assert index.is_cuda and index.device == catalogue_u8.device and index.dtype == torch.int64
+        assert index.dim() == 1 and index.is_contiguous(), index.shape
+        M = index.shape[0]
+        taps = torch.empty((M, len(tap_layers), cfg.hidden), dtype=torch.float32, device=index.device)
+        tl = (C.c_int32 * len(tap_layers))(*tap_layers)
+        nbytes = lib.iisan_vit_forward_taps_ws_bytes(C.byref(self.struct), M, chunk_items)
+        ws = self.ws.get(nbytes, index.device)
+        _lib.check(lib.iisan_vit_forward_taps_u8_indexed(C.byref(self.struct), _ptr(catalogue_u8), catalogue_u8.shape[0], _ptr(index), M,
+                                                         tl, len(tap_layers), _ptr(taps), chunk_items, _ptr(ws), ws.numel(),
+                                                         _stream()), "iisan_vit_forward_taps_u8_indexed")
+        return taps
+
+
 class PackedBert(_PackedEncoder):
     def __init__(self, w: Dict[str, torch.Tensor], cfg: BertConfig, device="cuda", dtype16: int = _lib.IISAN_F16):
         super().__init__(w, device, dtype16)
@@ -160,4 +182,23 @@ class PackedBert(_PackedEncoder):
         _lib.check(lib.iisan_bert_forward_taps(C.byref(self.struct), _ptr(text), M, words, tl, len(tap_layers),
                                                _ptr(taps), chunk_items, _ptr(ws), ws.numel(), _stream()),
                    "iisan_bert_forward_taps")
+        return taps
+
+    def forward_taps_indexed(self, table: torch.Tensor, index: torch.Tensor, tap_layers: Sequence[int],
+                             chunk_items: int = 0) -> torch.Tensor:
+        """table int64 [rows, 2W] resident on the device, index int64 [M] on the device -> fp32 [M, len(tap_layers), D]: slot m
+        encodes row index[m]; a value outside [0, rows) is a padding slot (all-zero ids and mask, `dataset.py:79-84`)."""
+        lib = _lib.load()
+        assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
+        assert table.dim() == 2 and table.shape[1] % 2 == 0, table.shape
+        assert index.is_cuda and index.device == table.device and index.dtype == torch.int64
+        assert index.dim() == 1 and index.is_contiguous(), index.shape
+        M, words = index.shape[0], table.shape[1] // 2
+        taps = torch.empty((M, len(tap_layers), self.cfg.hidden), dtype=torch.float32, device=index.device)
+        tl = (C.c_int32 * len(tap_layers))(*tap_layers)
+        nbytes = lib.iisan_bert_forward_taps_ws_bytes(C.byref(self.struct), M, words, chunk_items)
+        ws = self.ws.get(nbytes, index.device)
+        _lib.check(lib.iisan_bert_forward_taps_indexed(C.byref(self.struct), _ptr(table), table.shape[0], _ptr(index), M, words, tl,
+                                                       len(tap_layers), _ptr(taps), chunk_items, _ptr(ws), ws.numel(), _stream()),
+                   "iisan_bert_forward_taps_indexed")
         return taps

@@ -11,6 +11,8 @@
   encoded redundantly by every rank.
 * `build_tap_cache`  is what `Code_Cached/preprocess_vectors.py:68-112` does with HuggingFace models: the per-layer CLS
   taps `[N, L+1, 768]` of a catalogue, from the same encoder kernels as the Uncached path.
+* `item_table_from_store` / `build_tap_cache_from_store`  the same two over an item store (`iisan_amd.itemstore`): id ranges
+  through the indexed encoder entries, no image batch on the host or the device.
 """
 from __future__ import annotations
 
@@ -51,6 +53,58 @@ def item_table(model, images_or_taps: torch.Tensor, text_or_taps: torch.Tensor, 
         rows.append(model.fuse_item3(item3))
     emb = model.com_dense.weight.shape[0]
     mine = torch.cat(rows) if rows else torch.empty(0, emb, device=images_or_taps.device)
+    if world == 1:
+        return mine
+    pad = torch.zeros(per, emb, device=mine.device)
+    pad[:mine.shape[0]] = mine
+    return dp.gather_concat(pad, per * world)[:N]
+
+
+def _store_batches(model, store, lo: int, hi: int, batch: int):
+    """(catalogue_u8, title table, index) of item ids lo..hi-1 in id ranges of `batch`, through `store.lookup`.  A streaming source
+    (one with `submit`: `ItemFeed`) is sent each range right before it is looked up — nothing is copied ahead here, the catalogue pass
+    is bound by the encoders — so its `capacity` AND its index buffers must cover `batch`: the index buffers are sized by
+    `batch_slots` or, without it, by the FIRST batch the feed ever saw, so a feed that trained on smaller batches needs
+    `batch_slots >= batch` at construction (`submit` raises otherwise)."""
+    store = model.prepare_item_store(store)
+    for i in range(lo, hi, batch):
+        j = min(i + batch, hi)
+        if hasattr(store, "submit"):
+            store.submit(np.arange(i, j, dtype=np.int64))
+        yield store.lookup(torch.arange(i, j, dtype=torch.int64, device=store.device))
+
+
+@torch.no_grad()
+def build_tap_cache_from_store(model, store, batch: int = 256) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`build_tap_cache` over the catalogue of an item store (`iisan_amd.itemstore`): the encoders read the store's rows by index,
+    no image batch is materialised.  Row 0 = the padding item (zero image, zero title)."""
+    enc = model.mm_encoder
+    cvs, txs = [], []
+    for cat, txt, index in _store_batches(model, store, 0, store.rows, batch):
+        Lc = enc.cv_encoder.packed(index.device).cfg.layers
+        Lt = enc.bert_encoder.text_encoders["title"].packed(index.device).cfg.layers
+        cvs.append(enc.cv_encoder.forward_taps_indexed(cat, index, range(Lc + 1)))
+        txs.append(enc.bert_encoder.forward_taps_indexed(txt, index, range(Lt + 1)))
+    if hasattr(store, "release"):
+        store.release()
+    return torch.cat(cvs), torch.cat(txs)
+
+
+@torch.no_grad()
+def item_table_from_store(model, store, batch: int = 512, rank: int = 0, world: int = 1) -> torch.Tensor:
+    """`item_table` over the catalogue of an item store: [N+1, emb] for item ids 0..N (row 0 = the padding item), the same values
+    as `item_table` on the materialised catalogue at the same `batch`."""
+    N = store.rows
+    per = (N + world - 1) // world
+    lo, hi = min(rank * per, N), min((rank + 1) * per, N)
+    rows = []
+    for cat, txt, index in _store_batches(model, store, lo, hi, batch):
+        item3, _ = model.mm_encoder.forward_item3_indexed(cat, txt, index)
+        rows.append(model.fuse_item3(item3))
+    if hasattr(store, "release"):
+        store.release()
+    emb = model.com_dense.weight.shape[0]
+    mine = torch.cat(rows) if rows else torch.empty(0, emb, device=store.device)
     if world == 1:
         return mine
     pad = torch.zeros(per, emb, device=mine.device)

@@ -95,6 +95,14 @@ class Vit_Encoder(nn.Module):                      # encoders.py:23-31
             pk.full_blocks = getattr(self, "full_blocks", False)      # True: every block on every token, like HF (bench.py)
             return pk.forward_taps(item_content.contiguous(), list(tap_layers), self.chunk_items)
 
+    def forward_taps_indexed(self, catalogue_u8, index, tap_layers):
+        """The same for slots that name rows of a device-resident uint8 catalogue (`iisan_amd.itemstore`); index values
+        outside the catalogue are padding slots."""
+        with torch.no_grad():
+            pk = self.packed(index.device)
+            pk.full_blocks = getattr(self, "full_blocks", False)
+            return pk.forward_taps_indexed(catalogue_u8, index, list(tap_layers), self.chunk_items)
+
     def forward(self, item_content):
         """Reference signature (`encoders.py:29-31`).  Returns `(None, hidden_states)` where each hidden state is the
         [M,1,768] CLS row (`h[:,0]` is what IISAN reads, `model.py:212`); the dead GELU(classifier(...)) output of
@@ -147,6 +155,12 @@ class Text_Encoder(nn.Module):                     # encoders.py:68-91
             pk.full_blocks = getattr(self, "full_blocks", False)
             return pk.forward_taps(text.contiguous().to(torch.int64), list(tap_layers), self.chunk_items)
 
+    def forward_taps_indexed(self, table, index, tap_layers):
+        with torch.no_grad():
+            pk = self.packed(index.device)
+            pk.full_blocks = getattr(self, "full_blocks", False)
+            return pk.forward_taps_indexed(table, index, list(tap_layers), self.chunk_items)
+
     def forward(self, text):
         L = self.packed(text.device).cfg.layers
         taps = self.forward_taps(text, range(L + 1))
@@ -173,6 +187,18 @@ class Bert_Encoder(nn.Module):                     # encoders.py:116-159
 
     def forward_taps(self, news, tap_layers):
         return self.text_encoders['title'].forward_taps(self._title(news), tap_layers)
+
+    def title_columns(self):
+        """(start, length) of the title columns in an item-content row.  An item store narrows a wider table to them ONCE and keeps
+        that contiguous copy (`iisan_amd.itemstore`: `narrow_text`), so that no step narrows or copies text."""
+        return self.attributes2start['title'], self.attributes2length['title']
+
+    def forward_taps_indexed(self, title_table, index, tap_layers):
+        """`title_table` [rows, 2W]: the title columns only (see `title_columns`)."""
+        if title_table.shape[1] != self.attributes2length['title']:
+            raise ValueError(f"Bert_Encoder.forward_taps_indexed: the table is {title_table.shape[1]} columns wide, the title "
+                             f"{self.attributes2length['title']}: narrow it once with the store's narrow_text(*title_columns())")
+        return self.text_encoders['title'].forward_taps_indexed(title_table, index, tap_layers)
 
     def forward(self, news):
         return self.text_encoders['title'](self._title(news))

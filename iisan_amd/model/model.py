@@ -102,9 +102,7 @@ class IISANAdaptedMModel(_SideNetBase):
         self._build(args)
 
     def forward_item3(self, sample_items_images, sample_items_text, item_ids=None):
-        layers = self.side_cv_adapter_num_list
-        need = ([0] if self.remove_first else []) + list(layers)        # model.py:215-218 seeds states with tap 0
-        need = sorted(set(need))
+        layers, need = self._need()
         if item_ids is not None:
             # encode every distinct item of the batch once.  Item content is a function of the item id
             # (`Build_MM_Dataset.__getitem__`, dataset.py:73-84; id 0 = the all-zero padding content), encoder rows are
@@ -117,30 +115,59 @@ class IISANAdaptedMModel(_SideNetBase):
             taps_cv = self.cv_encoder.forward_taps(sample_items_images.index_select(0, first), need).index_select(0, inverse)
             taps_text = self.bert_encoder.forward_taps(sample_items_text.index_select(0, first), need).index_select(0, inverse)
         else:
-            if self.overlap_towers and sample_items_images.is_cuda:
-                # the two towers on two HIP streams of their own — the image tower on a HIGH-priority stream, the text tower on a
-                # normal one — so that the text tower's kernels only fill what the image tower's persistent GEMMs leave free (their
-                # partial last rounds).  Same kernels, same results (tests/test_gpu_trainable.py: bit-identical embeddings).
-                # profiles/r5_overlap.md (same box, three interleaved rounds of 20 steps): -0.33 / -0.41 ms per step, every round; with
-                # BOTH towers at normal priority the step is bimodal (-0.5 ms or +1.2 .. +4.3 ms: a text-tower GEMM that wins a CU keeps
-                # it for its whole static tile list and the image tower's kernel waits for it).  Round 6: the default
-                # (`overlap_towers = False` / `bench.py --no-overlap-towers` for profiling runs: per-kernel durations of an overlapped
-                # run — HIP events and rocprofv3 alike — are inflated by the sharing, profiles/r4_overlap_by_stream.md).
-                cur = torch.cuda.current_stream()
-                hi, side = self.tower_streams()
-                side.wait_stream(cur)
-                hi.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    taps_text = self.bert_encoder.forward_taps(sample_items_text, need)
-                with torch.cuda.stream(hi):
-                    taps_cv = self.cv_encoder.forward_taps(sample_items_images, need)
-                cur.wait_stream(side)
-                cur.wait_stream(hi)
-                taps_text.record_stream(cur)
-                taps_cv.record_stream(cur)
-            else:
-                taps_cv = self.cv_encoder.forward_taps(sample_items_images, need)
-                taps_text = self.bert_encoder.forward_taps(sample_items_text, need)
+            taps_cv, taps_text = self._towers(lambda: self.cv_encoder.forward_taps(sample_items_images, need),
+                                              lambda: self.bert_encoder.forward_taps(sample_items_text, need),
+                                              sample_items_images.is_cuda)
+        return self._side(taps_cv, taps_text, [need.index(l) for l in layers], need.index(0) if self.remove_first else 0)
+
+    def _need(self):
+        """Tap layers the side network reads: its list, preceded by layer 0 when `remove_first` (model.py:215-218 seeds states with it)."""
+        layers = self.side_cv_adapter_num_list
+        return layers, sorted(set(([0] if self.remove_first else []) + list(layers)))
+
+    def _towers(self, run_cv, run_text, on_device):
+        """(taps_cv, taps_text) of the two frozen towers, each given as a callable — on two HIP streams when `overlap_towers`."""
+        if self.overlap_towers and on_device:
+            # the two towers on two HIP streams of their own — the image tower on a HIGH-priority stream, the text tower on a
+            # normal one — so that the text tower's kernels only fill what the image tower's persistent GEMMs leave free (their
+            # partial last rounds).  Same kernels, same results (tests/test_gpu_trainable.py: bit-identical embeddings).
+            # profiles/r5_overlap.md (same box, three interleaved rounds of 20 steps): -0.33 / -0.41 ms per step, every round; with
+            # BOTH towers at normal priority the step is bimodal (-0.5 ms or +1.2 .. +4.3 ms: a text-tower GEMM that wins a CU keeps
+            # it for its whole static tile list and the image tower's kernel waits for it).  Round 6: the default
+            # (`overlap_towers = False` / `bench.py --no-overlap-towers` for profiling runs: per-kernel durations of an overlapped
+            # run — HIP events and rocprofv3 alike — are inflated by the sharing, profiles/r4_overlap_by_stream.md).
+            cur = torch.cuda.current_stream()
+            hi, side = self.tower_streams()
+            side.wait_stream(cur)
+            hi.wait_stream(cur)
+            with torch.cuda.stream(side):
+                taps_text = run_text()
+            with torch.cuda.stream(hi):
+                taps_cv = run_cv()
+            cur.wait_stream(side)
+            cur.wait_stream(hi)
+            taps_text.record_stream(cur)
+            taps_cv.record_stream(cur)
+        else:
+            taps_cv = run_cv()
+            taps_text = run_text()
+        return taps_cv, taps_text
+
+    def forward_item3_indexed(self, catalogue_u8, text_table, index, dedup=False):
+        """`forward_item3` for slots that name rows of device-resident item content (`iisan_amd.itemstore`): slot m is row index[m] of
+        the uint8 catalogue and of the title table, a value outside them a padding slot.  No [M,3,R,R] tensor exists.  `dedup`: the
+        encoders run once per DISTINCT index value and their taps are gathered back to the slots — same taps (rows are independent and
+        bit-reproducible), no image copy."""
+        layers, need = self._need()
+        index = index.reshape(-1)
+        inverse = None
+        if dedup:
+            index, inverse = torch.unique(index, return_inverse=True)
+        taps_cv, taps_text = self._towers(lambda: self.cv_encoder.forward_taps_indexed(catalogue_u8, index, need),
+                                          lambda: self.bert_encoder.forward_taps_indexed(text_table, index, need),
+                                          index.is_cuda)
+        if inverse is not None:
+            taps_cv, taps_text = taps_cv.index_select(0, inverse), taps_text.index_select(0, inverse)
         return self._side(taps_cv, taps_text, [need.index(l) for l in layers], need.index(0) if self.remove_first else 0)
 
     def tower_streams(self):
@@ -216,6 +243,9 @@ class ModelMM(nn.Module):                          # model.py:14-105
         # Cached path only: packed device tap stores (iisan_amd.tapstore.TapStore) for image / text taps.
         # When set, forward() ignores the `sample_items_images/text` arguments and gathers the taps by item id.
         self.tap_stores = None
+        # Uncached path only: a device item source (iisan_amd.itemstore.ItemStore / ItemFeed).  When set, forward()
+        # ignores the `sample_items_images/text` arguments and the encoders read item content by row index, looked up by item id.
+        self._item_stores = None
 
     def score_embs(self, sample_items_images, sample_items_text, sample_items_id=None):
         enc = self.mm_encoder
@@ -234,6 +264,8 @@ class ModelMM(nn.Module):                          # model.py:14-105
                 item3, _ = enc.forward_item3_packed(st_cv.gather(uniq), st_tx.gather(uniq), exact16=ex16)
                 return self.fuse_item3(item3).index_select(0, inverse)
             item3, _ = enc.forward_item3_packed(st_cv.gather(sample_items_id), st_tx.gather(sample_items_id), exact16=ex16)
+        elif self.item_stores is not None and hasattr(enc, "forward_item3_indexed") and sample_items_id is not None:
+            item3, _ = enc.forward_item3_indexed(*self.item_stores.lookup(sample_items_id), dedup=self.dedup_items)
         elif hasattr(enc, "forward_item3"):
             if self.dedup_items and sample_items_id is not None and not getattr(enc, "cached", False):
                 item3, _ = enc.forward_item3(sample_items_images, sample_items_text, sample_items_id)
@@ -242,6 +274,29 @@ class ModelMM(nn.Module):                          # model.py:14-105
         else:
             raise NotImplementedError("mm_encoder must be wrapped by IISANAdaptedMModel (run.py:214-216)")
         return self.fuse_item3(item3)
+
+    @property
+    def item_stores(self):
+        return self._item_stores
+
+    @item_stores.setter
+    def item_stores(self, store):
+        self._item_stores = None if store is None else self.prepare_item_store(store)
+
+    def prepare_item_store(self, store):
+        """What has to hold before a store feeds this model, done ONCE (when the store is assigned, or by the eval hooks for a store
+        passed to them) and never on a step: the catalogue has a row for every item id of the model — an id beyond it would silently
+        be a padding slot to the kernels — and the text table holds the title columns only (`Bert_Encoder.title_columns`; a wider
+        `item_content` table is narrowed by the store, which keeps that one contiguous copy)."""
+        n_items = self.pop_prob_list.numel()            # item_num + 1
+        if store.rows < n_items:
+            raise ValueError(f"item store: the catalogue has {store.rows} rows, the model {n_items} item ids (item_num + 1)")
+        cols = tuple(int(c) for c in self.mm_encoder.bert_encoder.title_columns())
+        if store.text_columns is None and cols != (0, store.text_width):
+            store.narrow_text(*cols)
+        elif store.text_columns is not None and store.text_columns != cols:
+            raise ValueError(f"item store: its text table holds columns {store.text_columns}, the title is {cols}")
+        return store
 
     def fuse_item3(self, item3):
         """`com_dense` over the towers' outputs `[M, 3E] = cv | text | mm` (model.py:67-72)."""

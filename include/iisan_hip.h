@@ -113,6 +113,18 @@ int iisan_vit_forward_taps(const iisan_vit_weights* w, const float* images, int6
 int iisan_vit_forward_taps_u8(const iisan_vit_weights* w, const uint8_t* images, int64_t M,
                               const int32_t* tap_layers, int32_t n_taps, float* taps,
                               int64_t chunk_items, void* ws, size_t ws_bytes, void* stream);
+/* The same from a DEVICE-RESIDENT raw catalogue uint8 [rows, C, R, R]: the image of slot m is row index[m] (index int64 [M] on the
+ * device), read inside the patch-extraction kernel — no [M,C,R,R] tensor exists.  This is the per-slot lookup of
+ * Build_MM_Dataset.__getitem__ (Code_Uncached/data_utils/dataset.py:56-86) moved onto the device.  Any index value outside
+ * [0, rows) — negative or >= rows — is a PADDING slot: never dereferenced, the tower sees the all-zero normalised image the
+ * reference ships for pad slots (dataset.py:73; no uint8 pixel normalises to 0, so the zero is not a catalogue row).  A bad
+ * index therefore cannot fault and needs no synchronisation to report.  Patch matrices, hence taps, are bit-identical to
+ * iisan_vit_forward_taps fed with normalise(catalogue[index]) and zeros on pad slots.  Workspace: iisan_vit_forward_taps_ws_bytes.
+ * IISAN_EBADSHAPE before any launch: rows <= 0, null catalogue / index, image % 8 != 0, M <= 0. */
+int iisan_vit_forward_taps_u8_indexed(const iisan_vit_weights* w, const uint8_t* catalogue, int64_t rows,
+                                      const int64_t* index, int64_t M,
+                                      const int32_t* tap_layers, int32_t n_taps, float* taps,
+                                      int64_t chunk_items, void* ws, size_t ws_bytes, void* stream);
 
 /* Replaces Text_Encoder/Bert_Encoder.forward + tap selection (encoders.py:81-91,148-159, model.py:211,213):
  * text int64 [M, 2W] (W ids then W attention-mask values) -> taps fp32 [M, n_taps, D]. */
@@ -120,6 +132,15 @@ size_t iisan_bert_forward_taps_ws_bytes(const iisan_bert_weights* w, int64_t M, 
 int iisan_bert_forward_taps(const iisan_bert_weights* w, const int64_t* text, int64_t M, int32_t words,
                             const int32_t* tap_layers, int32_t n_taps, float* taps,
                             int64_t chunk_items, void* ws, size_t ws_bytes, void* stream);
+/* The same from a DEVICE-RESIDENT table int64 [rows, 2W]: the text of slot m is row index[m] (the title lookup of
+ * Build_MM_Dataset.__getitem__, Code_Uncached/data_utils/dataset.py:56-86, on the device).  An index value outside [0, rows) is a
+ * padding slot: never dereferenced, all-zero ids and mask (dataset.py:79-84).  Taps bit-identical to iisan_bert_forward_taps fed
+ * with table[index] and zero rows on pad slots.  Workspace: iisan_bert_forward_taps_ws_bytes.
+ * IISAN_EBADSHAPE before any launch: rows <= 0, null table / index, M <= 0. */
+int iisan_bert_forward_taps_indexed(const iisan_bert_weights* w, const int64_t* table, int64_t rows,
+                                    const int64_t* index, int64_t M, int32_t words,
+                                    const int32_t* tap_layers, int32_t n_taps, float* taps,
+                                    int64_t chunk_items, void* ws, size_t ws_bytes, void* stream);
 
 /* Dead-work policy of the two executors above (`full_blocks` of the weights struct — part of the call, not process state).
  * 0 (default): blocks deeper than the deepest tapped hidden state are not run, and in the last live block attention / O /
