@@ -47,6 +47,10 @@ class SasrecCfg(C.Structure):
     _fields_ = [("seq", i32), ("emb", i32), ("heads", i32), ("blocks", i32), ("dropout", f32), ("seed", u64)]
 
 
+class BertDropout(C.Structure):       # iisan_bert_dropout: sites and index formulas in include/iisan_hip.h
+    _fields_ = [("hidden_p", f32), ("attn_p", f32), ("seed", u64)]
+
+
 # name -> (restype, argtypes); must list EVERY symbol include/iisan_hip.h declares (tests/test_abi.py checks)
 SIGNATURES = {
     "iisan_version": (C.c_char_p, []),
@@ -61,6 +65,8 @@ SIGNATURES = {
     "iisan_bert_forward_taps_ws_bytes": (sz, [C.POINTER(BertWeights), i64, i32, i64]),
     "iisan_bert_forward_taps": (i32, [C.POINTER(BertWeights), vp, i64, i32, C.POINTER(i32), i32, vp, i64, vp, sz, vp]),
     "iisan_bert_forward_taps_indexed": (i32, [C.POINTER(BertWeights), vp, i64, vp, i64, i32, C.POINTER(i32), i32, vp, i64, vp, sz, vp]),
+    "iisan_bert_forward_taps_dropout": (i32, [C.POINTER(BertWeights), vp, i64, vp, i64, i32, C.POINTER(i32), i32, vp, i64,
+                                              C.POINTER(BertDropout), vp, sz, vp]),
     "iisan_side_net_ws_bytes": (sz, [C.POINTER(SideCfg), i64]),
     "iisan_side_net_num_params": (i32, [C.POINTER(SideCfg)]),
     "iisan_side_net_fwd": (i32, [C.POINTER(SideCfg), vp, vp, i64, C.POINTER(vp), vp, vp, sz, C.POINTER(u64), vp]),
@@ -81,6 +87,7 @@ SIGNATURES = {
     "iisan_layernorm768": (i32, [i32, vp, vp, vp, f32, vp, vp, i64, vp]),
     "iisan_attention16": (i32, [i32, vp, vp, vp, i64, i32, i32, vp]),
     "iisan_attention_cls16": (i32, [i32, vp, vp, vp, i64, i32, i32, vp]),
+    "iisan_attention16_dropout": (i32, [i32, vp, vp, vp, i64, i32, i32, f32, u64, i32, i32, vp]),
     "iisan_gemm32": (i32, [vp, vp, vp, vp, i64, i32, i64, i32, i32, i32, i32, vp]),
     "iisan_gemm_x3_ws_bytes": (sz, [i64, i32, i64]),
     "iisan_gemm_x3": (i32, [vp, vp, vp, vp, i64, i32, i64, i32, i32, i32, vp, sz, vp]),

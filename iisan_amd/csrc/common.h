@@ -369,6 +369,20 @@ int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, co
 int launch_bert_embed_ln_indexed(int dtype16, const int64_t* table, int64_t rows, const int64_t* index, const float* word, const float* pos,
                                  const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
                                  int64_t M, int W, int vocab, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
+// train-mode dropout of the BERT tower (bert_drop.hip; DropCfg above): variants of the four steps above that apply a counter-based keep
+// factor — slot0 / row0 / item0 / m0 place the chunk in the whole call, so the masks do not depend on the chunking
+int launch_attention16_drop(int dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int S, int heads,
+                            const DropCfg& drop, int64_t slot0, bool cls_only, const void* q_cls, hipStream_t s);
+// x = LN(x + drop(delta16)) on the mixed stream (launch_layernorm768_mixed with MX_D1 | MX_LN | MX_RESY [| MX_ALIAS])
+int launch_add_ln_drop_mixed(int dtype16, bool alias, void* x16, float* xc, const void* delta16, const float* g, const float* b, float eps,
+                             void* out16, int64_t items, int Ttok, const DropCfg& drop, int64_t row0, hipStream_t s);
+// ... on compact fp32 CLS rows, in place (row r = token row (item0 + r) * Ttok of the all-token execution); out16 may be null
+int launch_add_ln_drop_rows(int dtype16, float* x, const void* delta16, const float* g, const float* b, float eps, void* out16,
+                            int64_t rows, const DropCfg& drop, int64_t item0, int Ttok, hipStream_t s);
+// drop(LN(embeddings)) for the mixed stream; index != null: the indexed form
+int launch_bert_embed_ln_drop(int dtype16, const int64_t* text, int64_t rows, const int64_t* index, const float* word, const float* pos,
+                              const float* type0, const float* g, const float* b, float eps, void* H, float* key_bias, int64_t M, int W,
+                              int vocab, void* X16, float* Xc, const DropCfg& drop, int64_t m0, hipStream_t s);
 int launch_gather_cls(const float* X, float* taps, int64_t M, int T, int D, int n_taps, int k, hipStream_t s);
 int launch_gather_rows16(const void* H, void* out, int64_t M, int T, int D, hipStream_t s);   // out[m] = H[m*T] (16-bit rows)
 

@@ -451,10 +451,22 @@ extern "C" size_t iisan_bert_forward_taps_ws_bytes(const iisan_bert_weights* w, 
 }
 
 // index != null: `text` is a resident table [rows, 2W] and slot m reads row index[m] (the chunk loop offsets the index, never the table)
+// drop: null or both probabilities 0 = eval mode, the launch sequence below unchanged; otherwise the train-mode variants of bert_drop.hip
+// take the place of the embedding, attention and add + LayerNorm steps (sites and indices: include/iisan_hip.h, iisan_bert_dropout)
 static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* text, int64_t M, int32_t words,
                                   const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
-                                  void* ws, size_t ws_bytes, void* stream, const int64_t* index = nullptr, int64_t rows = 0) {
+                                  void* ws, size_t ws_bytes, void* stream, const int64_t* index = nullptr, int64_t rows = 0,
+                                  const iisan_bert_dropout* drop = nullptr) {
     hipStream_t s = (hipStream_t)stream;
+    if (drop) {
+        IISAN_CHECK_SHAPE(drop->hidden_p >= 0.f && drop->hidden_p < 1.f, "bert dropout: hidden_p %.3f out of range", drop->hidden_p);
+        IISAN_CHECK_SHAPE(drop->attn_p >= 0.f && drop->attn_p < 1.f, "bert dropout: attn_p %.3f out of range", drop->attn_p);
+    }
+    const bool dropping = drop && (drop->hidden_p > 0.f || drop->attn_p > 0.f);
+    // never a silent fall-back to eval mode: the variants exist for the mixed stream only
+    IISAN_CHECK_SHAPE(!(dropping && g_resid32), "bert dropout: not built for the fp32 residual stream of the dev switch resid32 = 1");
+    const float hp = dropping ? drop->hidden_p : 0.f, ap = dropping ? drop->attn_p : 0.f;
+    const uint64_t seed = dropping ? drop->seed : 0;
     IISAN_CHECK_SHAPE(M > 0, "bert_forward_taps: M must be positive");
     IISAN_TRY(check_common(w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
     IISAN_CHECK_SHAPE(words >= 1 && words <= w->max_pos && words <= 224, "bert: %d words unsupported", words);
@@ -478,13 +490,17 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
         // LayerNorm kernels move 6 instead of 8 bytes per element)
         const bool alias = mixed && dt == IISAN_F16 && g_ln_fold;
         void* IMG = alias ? b.X16 : b.H;
-        if (index) IISAN_TRY(launch_bert_embed_ln_indexed(dt, text, rows, index + m0, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w,
+        if (dropping) IISAN_TRY(launch_bert_embed_ln_drop(dt, index ? text : text + m0 * 2 * words, rows, index ? index + m0 : nullptr, w->word_emb,
+                                                          w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b, w->eps, IMG, b.KB, mc, T, w->vocab,
+                                                          b.X16, b.Xc, make_drop(seed, 0, hp), m0, s));
+        else if (index) IISAN_TRY(launch_bert_embed_ln_indexed(dt, text, rows, index + m0, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w,
                                                           w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, s, b.X16, b.Xc));
         else IISAN_TRY(launch_bert_embed_ln(dt, text + m0 * 2 * words, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w,
                                             w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, s, b.X16, b.Xc));
         auto tap = [&](int k) { return mixed ? launch_gather_cls(b.Xc, tp, mc, 1, D, n_taps, k, s) : launch_gather_cls(b.X, tp, mc, T, D, n_taps, k, s); };
         // x = LN(x + delta): stream and 16-bit image out
-        auto add_ln = [&](const float* g, const float* be) {
+        auto add_ln = [&](const float* g, const float* be, int site) {
+            if (dropping) return launch_add_ln_drop_mixed(dt, alias, b.X16, b.Xc, b.D16, g, be, w->eps, IMG, mc, T, make_drop(seed, site, hp), m0 * T, s);
             return mixed ? launch_layernorm768_mixed(dt, MX_D1 | MX_LN | MX_RESY | (alias ? MX_ALIAS : 0), nullptr, b.X16, b.Xc, b.D16, nullptr, g, be, w->eps, IMG, mc, T, s)
                          : launch_add_layernorm768(dt, b.X, b.D16, g, be, w->eps, nullptr, b.H, b.X, tok, s);
         };
@@ -497,13 +513,14 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
             // a = LN(x + O(attn(x)))
             if (l + 1 < live || full_blocks) {
                 IISAN_TRY(gemm(dt, EPI_QKVH16, IMG, D, L.qkv_w, L.qkv_b, b.QKV, 3 * D, nullptr, tok, s, nullptr, 0, T, w->heads));
-                IISAN_TRY(launch_attention16(dt, b.QKV, b.KB, b.H, mc, T, w->heads, s));
+                if (dropping) IISAN_TRY(launch_attention16_drop(dt, b.QKV, b.KB, b.H, mc, T, w->heads, make_drop(seed, 1 + 3 * l, ap), m0, false, nullptr, s));
+                else IISAN_TRY(launch_attention16(dt, b.QKV, b.KB, b.H, mc, T, w->heads, s));
                 IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
-                IISAN_TRY(add_ln(L.ln1_w, L.ln1_b));
+                IISAN_TRY(add_ln(L.ln1_w, L.ln1_b, 2 + 3 * l));
                 // x = LN(a + FC2(gelu(FC1 a)))
                 IISAN_TRY(gemm(dt, EPI_GELU16, IMG, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, tok, s));
                 IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, nullptr, tok, s));
-                IISAN_TRY(add_ln(L.ln2_w, L.ln2_b));
+                IISAN_TRY(add_ln(L.ln2_w, L.ln2_b, 3 + 3 * l));
                 k = tap_index(tap_layers, n_taps, l + 1);
                 if (k >= 0) IISAN_TRY(tap(k));
             } else {
@@ -513,13 +530,17 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
                 IISAN_TRY(launch_gather_rows16(IMG, Hc, mc, T, D, s));
                 IISAN_TRY(kv_all_q_cls(dt, L, IMG, b.QKV, Hc, Qc, tok, mc, T, w->heads, D, s));
                 float* Xc = (float*)b.QKV;
-                IISAN_TRY(launch_attention_cls16(dt, b.QKV, b.KB, b.H, mc, T, w->heads, s, Qc));
+                if (dropping) IISAN_TRY(launch_attention16_drop(dt, b.QKV, b.KB, b.H, mc, T, w->heads, make_drop(seed, 1 + 3 * l, ap), m0, true, Qc, s));
+                else IISAN_TRY(launch_attention_cls16(dt, b.QKV, b.KB, b.H, mc, T, w->heads, s, Qc));
                 IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, mc, s));
                 if (mixed) IISAN_TRY(launch_gather_cls(b.Xc, Xc, mc, 1, D, 1, 0, s)); else IISAN_TRY(launch_gather_cls(b.X, Xc, mc, T, D, 1, 0, s));
-                IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln1_w, L.ln1_b, w->eps, nullptr, b.H, Xc, mc, s));
+                // (dropping: the masks of token row t = 0 of the all-token execution)
+                if (dropping) IISAN_TRY(launch_add_ln_drop_rows(dt, Xc, b.D16, L.ln1_w, L.ln1_b, w->eps, b.H, mc, make_drop(seed, 2 + 3 * l, hp), m0, T, s));
+                else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln1_w, L.ln1_b, w->eps, nullptr, b.H, Xc, mc, s));
                 IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, mc, s));
                 IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, nullptr, mc, s));
-                IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, nullptr, Xc, mc, s));
+                if (dropping) IISAN_TRY(launch_add_ln_drop_rows(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, mc, make_drop(seed, 3 + 3 * l, hp), m0, T, s));
+                else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, nullptr, Xc, mc, s));
                 k = tap_index(tap_layers, n_taps, live);
                 IISAN_TRY(launch_gather_cls(Xc, tp, mc, 1, D, n_taps, k, s));
             }
@@ -542,4 +563,15 @@ extern "C" int iisan_bert_forward_taps_indexed(const iisan_bert_weights* w, cons
     IISAN_CHECK_SHAPE(table != nullptr && index != nullptr, "bert indexed: null %s", table ? "index" : "table");
     IISAN_CHECK_SHAPE(M > 0, "bert indexed: M must be positive");
     return bert_forward_taps_impl(w, table, M, words, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream, index, rows);
+}
+
+extern "C" int iisan_bert_forward_taps_dropout(const iisan_bert_weights* w, const int64_t* text_or_table, int64_t rows,
+                                               const int64_t* index, int64_t M, int32_t words, const int32_t* tap_layers,
+                                               int32_t n_taps, float* taps, int64_t chunk_items, const iisan_bert_dropout* drop,
+                                               void* ws, size_t ws_bytes, void* stream) {
+    IISAN_CHECK_SHAPE(text_or_table != nullptr, "bert dropout: null text");
+    IISAN_CHECK_SHAPE(!index || rows > 0, "bert dropout, indexed: the table needs at least one row (rows = %lld)", (long long)rows);
+    IISAN_CHECK_SHAPE(M > 0, "bert dropout: M must be positive");
+    return bert_forward_taps_impl(w, text_or_table, M, words, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream, index,
+                                  index ? rows : 0, drop);
 }

@@ -170,8 +170,15 @@ class PackedBert(_PackedEncoder):
         self.struct = s
         self._w = None
 
-    def forward_taps(self, text: torch.Tensor, tap_layers: Sequence[int], chunk_items: int = 0) -> torch.Tensor:
-        """text int64 [M, 2W] -> fp32 [M, len(tap_layers), D] (`encoders.py:81-91` + `model.py:213`)."""
+    @staticmethod
+    def _drop_struct(dropout):
+        """`(hidden_p, attn_p, seed)` -> `iisan_bert_dropout` (sites and index formulas: include/iisan_hip.h)."""
+        hidden_p, attn_p, seed = dropout
+        return _lib.BertDropout(float(hidden_p), float(attn_p), int(seed))
+
+    def forward_taps(self, text: torch.Tensor, tap_layers: Sequence[int], chunk_items: int = 0, dropout=None) -> torch.Tensor:
+        """text int64 [M, 2W] -> fp32 [M, len(tap_layers), D] (`encoders.py:81-91` + `model.py:213`).
+        dropout: None = eval mode; `(hidden_p, attn_p, seed)` = the tower as HF runs it under `train()`, one seed per call."""
         lib = _lib.load()
         assert text.is_cuda and text.dtype == torch.int64 and text.is_contiguous() and text.shape[1] % 2 == 0
         M, words = text.shape[0], text.shape[1] // 2
@@ -179,15 +186,21 @@ class PackedBert(_PackedEncoder):
         tl = (C.c_int32 * len(tap_layers))(*tap_layers)
         nbytes = lib.iisan_bert_forward_taps_ws_bytes(C.byref(self.struct), M, words, chunk_items)
         ws = self.ws.get(nbytes, text.device)
+        if dropout is not None:
+            _lib.check(lib.iisan_bert_forward_taps_dropout(C.byref(self.struct), _ptr(text), 0, None, M, words, tl, len(tap_layers),
+                                                           _ptr(taps), chunk_items, C.byref(self._drop_struct(dropout)), _ptr(ws),
+                                                           ws.numel(), _stream()), "iisan_bert_forward_taps_dropout")
+            return taps
         _lib.check(lib.iisan_bert_forward_taps(C.byref(self.struct), _ptr(text), M, words, tl, len(tap_layers),
                                                _ptr(taps), chunk_items, _ptr(ws), ws.numel(), _stream()),
                    "iisan_bert_forward_taps")
         return taps
 
     def forward_taps_indexed(self, table: torch.Tensor, index: torch.Tensor, tap_layers: Sequence[int],
-                             chunk_items: int = 0) -> torch.Tensor:
+                             chunk_items: int = 0, dropout=None) -> torch.Tensor:
         """table int64 [rows, 2W] resident on the device, index int64 [M] on the device -> fp32 [M, len(tap_layers), D]: slot m
-        encodes row index[m]; a value outside [0, rows) is a padding slot (all-zero ids and mask, `dataset.py:79-84`)."""
+        encodes row index[m]; a value outside [0, rows) is a padding slot (all-zero ids and mask, `dataset.py:79-84`).
+        dropout: as in `forward_taps`; the masks follow the SLOT m, not the table row."""
         lib = _lib.load()
         assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
         assert table.dim() == 2 and table.shape[1] % 2 == 0, table.shape
@@ -198,6 +211,11 @@ class PackedBert(_PackedEncoder):
         tl = (C.c_int32 * len(tap_layers))(*tap_layers)
         nbytes = lib.iisan_bert_forward_taps_ws_bytes(C.byref(self.struct), M, words, chunk_items)
         ws = self.ws.get(nbytes, index.device)
+        if dropout is not None:
+            _lib.check(lib.iisan_bert_forward_taps_dropout(C.byref(self.struct), _ptr(table), table.shape[0], _ptr(index), M, words, tl,
+                                                           len(tap_layers), _ptr(taps), chunk_items, C.byref(self._drop_struct(dropout)),
+                                                           _ptr(ws), ws.numel(), _stream()), "iisan_bert_forward_taps_dropout")
+            return taps
         _lib.check(lib.iisan_bert_forward_taps_indexed(C.byref(self.struct), _ptr(table), table.shape[0], _ptr(index), M, words, tl,
                                                        len(tap_layers), _ptr(taps), chunk_items, _ptr(ws), ws.numel(), _stream()),
                    "iisan_bert_forward_taps_indexed")

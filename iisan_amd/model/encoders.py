@@ -59,7 +59,8 @@ def _bert_canonical(bert_model):
     c = bert_model.config
     cfg = weights.BertConfig(hidden=c.hidden_size, layers=c.num_hidden_layers, heads=c.num_attention_heads,
                              mlp=c.intermediate_size, vocab=c.vocab_size, max_pos=c.max_position_embeddings,
-                             eps=c.layer_norm_eps)
+                             eps=c.layer_norm_eps, hidden_dropout=float(c.hidden_dropout_prob),
+                             attn_dropout=float(c.attention_probs_dropout_prob))
     return weights.bert_from_hf(bert_model.state_dict()), cfg
 
 
@@ -141,7 +142,33 @@ class Text_Encoder(nn.Module):                     # encoders.py:68-91
         self.dtype16 = dtype16
         self.chunk_items = 0
         self._packed = None
+        # opt-in: the frozen tower's own dropout on the TRAINING forward, as HF's BertModel applies it under model.train()
+        # (Code_Uncached/run.py:394).  Off (the default): the tower always runs in eval mode.  INTEGRATION.md, "Numeric deviations".
+        self.train_dropout = False
         self.register_load_state_dict_post_hook(_drop_packed)
+
+    def dropout_probs(self):
+        """(hidden_dropout_prob, attention_probs_dropout_prob) of the wrapped tower: the HF config's, or the `BertConfig` fields of a
+        `FrozenBert` container."""
+        if hasattr(self.bert_model, "canonical_weights"):
+            cfg = self.bert_model.canonical_weights()[1]
+            return float(cfg.hidden_dropout), float(cfg.attn_dropout)
+        c = self.bert_model.config
+        return float(c.hidden_dropout_prob), float(c.attention_probs_dropout_prob)
+
+    def step_dropout(self):
+        """The `dropout` argument of one training forward: None unless `train_dropout and self.training`, else `(hidden_p, attn_p,
+        seed)` with a fresh seed.  Only the training forward (`IISANAdaptedMModel.forward_item3[_indexed]`) asks for it: a bare
+        `forward_taps(...)` is deterministic whatever the module's mode (evaluate.py builds its tap caches through it).  A forward
+        under `torch.no_grad()` is not a training step either: `evaluate.item_table` goes through `forward_item3` that way, without
+        `model.eval()`, and must give the same table whatever the switch says."""
+        if not (self.train_dropout and self.training and torch.is_grad_enabled()):
+            return None
+        hidden_p, attn_p = self.dropout_probs()
+        if hidden_p <= 0.0 and attn_p <= 0.0:
+            return None
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # CPU generator: no device sync (modules.TransformerEncoder.forward)
+        return hidden_p, attn_p, seed
 
     def packed(self, device) -> enc.PackedBert:
         if self._packed is None or self._packed.device != torch.device(device):
@@ -149,17 +176,17 @@ class Text_Encoder(nn.Module):                     # encoders.py:68-91
             self._packed = enc.PackedBert(w, cfg, device, self.dtype16)
         return self._packed
 
-    def forward_taps(self, text, tap_layers):
+    def forward_taps(self, text, tap_layers, dropout=None):
         with torch.no_grad():
             pk = self.packed(text.device)
             pk.full_blocks = getattr(self, "full_blocks", False)
-            return pk.forward_taps(text.contiguous().to(torch.int64), list(tap_layers), self.chunk_items)
+            return pk.forward_taps(text.contiguous().to(torch.int64), list(tap_layers), self.chunk_items, dropout=dropout)
 
-    def forward_taps_indexed(self, table, index, tap_layers):
+    def forward_taps_indexed(self, table, index, tap_layers, dropout=None):
         with torch.no_grad():
             pk = self.packed(index.device)
             pk.full_blocks = getattr(self, "full_blocks", False)
-            return pk.forward_taps_indexed(table, index, list(tap_layers), self.chunk_items)
+            return pk.forward_taps_indexed(table, index, list(tap_layers), self.chunk_items, dropout=dropout)
 
     def forward(self, text):
         L = self.packed(text.device).cfg.layers
@@ -185,20 +212,24 @@ class Bert_Encoder(nn.Module):                     # encoders.py:116-159
     def _title(self, news):
         return torch.narrow(news, 1, self.attributes2start['title'], self.attributes2length['title'])
 
-    def forward_taps(self, news, tap_layers):
-        return self.text_encoders['title'].forward_taps(self._title(news), tap_layers)
+    def forward_taps(self, news, tap_layers, dropout=None):
+        return self.text_encoders['title'].forward_taps(self._title(news), tap_layers, dropout=dropout)
+
+    def step_dropout(self):
+        """`Text_Encoder.step_dropout` of the title encoder (None: eval mode)."""
+        return self.text_encoders['title'].step_dropout()
 
     def title_columns(self):
         """(start, length) of the title columns in an item-content row.  An item store narrows a wider table to them ONCE and keeps
         that contiguous copy (`iisan_amd.itemstore`: `narrow_text`), so that no step narrows or copies text."""
         return self.attributes2start['title'], self.attributes2length['title']
 
-    def forward_taps_indexed(self, title_table, index, tap_layers):
+    def forward_taps_indexed(self, title_table, index, tap_layers, dropout=None):
         """`title_table` [rows, 2W]: the title columns only (see `title_columns`)."""
         if title_table.shape[1] != self.attributes2length['title']:
             raise ValueError(f"Bert_Encoder.forward_taps_indexed: the table is {title_table.shape[1]} columns wide, the title "
                              f"{self.attributes2length['title']}: narrow it once with the store's narrow_text(*title_columns())")
-        return self.text_encoders['title'].forward_taps_indexed(title_table, index, tap_layers)
+        return self.text_encoders['title'].forward_taps_indexed(title_table, index, tap_layers, dropout=dropout)
 
     def forward(self, news):
         return self.text_encoders['title'](self._title(news))

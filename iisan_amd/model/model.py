@@ -103,7 +103,9 @@ class IISANAdaptedMModel(_SideNetBase):
 
     def forward_item3(self, sample_items_images, sample_items_text, item_ids=None):
         layers, need = self._need()
+        drop = self.bert_encoder.step_dropout()       # None unless Text_Encoder.train_dropout and train()
         if item_ids is not None:
+            self._refuse_dedup(drop)
             # encode every distinct item of the batch once.  Item content is a function of the item id
             # (`Build_MM_Dataset.__getitem__`, dataset.py:73-84; id 0 = the all-zero padding content), encoder rows are
             # independent and bit-reproducible, so scattering the unique taps back gives exactly the [M, ...] taps the
@@ -116,9 +118,15 @@ class IISANAdaptedMModel(_SideNetBase):
             taps_text = self.bert_encoder.forward_taps(sample_items_text.index_select(0, first), need).index_select(0, inverse)
         else:
             taps_cv, taps_text = self._towers(lambda: self.cv_encoder.forward_taps(sample_items_images, need),
-                                              lambda: self.bert_encoder.forward_taps(sample_items_text, need),
+                                              lambda: self.bert_encoder.forward_taps(sample_items_text, need, dropout=drop),
                                               sample_items_images.is_cuda)
         return self._side(taps_cv, taps_text, [need.index(l) for l in layers], need.index(0) if self.remove_first else 0)
+
+    @staticmethod
+    def _refuse_dedup(drop):
+        if drop is not None:
+            raise ValueError("dedup_items / dedup=True with Text_Encoder.train_dropout: the reference draws independent dropout masks for "
+                             "two slots that hold the same item; one encoding per distinct id cannot reproduce that")
 
     def _need(self):
         """Tap layers the side network reads: its list, preceded by layer 0 when `remove_first` (model.py:215-218 seeds states with it)."""
@@ -161,10 +169,12 @@ class IISANAdaptedMModel(_SideNetBase):
         layers, need = self._need()
         index = index.reshape(-1)
         inverse = None
+        drop = self.bert_encoder.step_dropout()
         if dedup:
+            self._refuse_dedup(drop)
             index, inverse = torch.unique(index, return_inverse=True)
         taps_cv, taps_text = self._towers(lambda: self.cv_encoder.forward_taps_indexed(catalogue_u8, index, need),
-                                          lambda: self.bert_encoder.forward_taps_indexed(text_table, index, need),
+                                          lambda: self.bert_encoder.forward_taps_indexed(text_table, index, need, dropout=drop),
                                           index.is_cuda)
         if inverse is not None:
             taps_cv, taps_text = taps_cv.index_select(0, inverse), taps_text.index_select(0, inverse)

@@ -63,6 +63,10 @@ class BertConfig:
     vocab: int = 30522
     max_pos: int = 512
     eps: float = 1e-12
+    # hidden_dropout_prob / attention_probs_dropout_prob of the same config: read only by the opt-in train-mode dropout of the tower
+    # (`Text_Encoder.train_dropout`); the eval-mode path never looks at them
+    hidden_dropout: float = 0.1
+    attn_dropout: float = 0.1
 
 
 VIT_BASE = VitConfig()

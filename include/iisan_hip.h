@@ -142,6 +142,30 @@ int iisan_bert_forward_taps_indexed(const iisan_bert_weights* w, const int64_t* 
                                     const int32_t* tap_layers, int32_t n_taps, float* taps,
                                     int64_t chunk_items, void* ws, size_t ws_bytes, void* stream);
 
+/* TRAIN-MODE DROPOUT of the frozen BERT tower (opt-in).  The reference trains with model.train() (Code_Uncached/run.py:394), so HF's
+ * BertModel applies hidden_dropout_prob / attention_probs_dropout_prob on every training step; the entry points above are eval mode.
+ * Masks are counter-based: the keep factor (0 or 1 / (1 - p)) of an element is a pure function of (seed, site, index) — the same
+ * generator as iisan_sasrec_cfg's — with one 64-bit seed per forward call and
+ *   site 0        embeddings:                    drop(LayerNorm(word + pos + type)) — this IS hidden state 0           (hidden_p)
+ *   site 1 + 3l   block l, attention:            drop(softmax(Q K^T / 8 + key_bias)) V, no renormalisation             (attn_p)
+ *   site 2 + 3l   block l, attention output:     LayerNorm(drop(dense(ctx)) + x)                                       (hidden_p)
+ *   site 3 + 3l   block l, FFN output:           LayerNorm(drop(dense(gelu(..))) + a)                                  (hidden_p)
+ *   hidden sites:     index = (m T + t) D + c                   (T = words, D = hidden, c = column)
+ *   attention sites:  index = ((m H + h) T + q) T + k           (H = heads, q / k = query / key token)
+ * where m = 0 .. M-1 is the slot's position in the WHOLE call — not within a chunk of `chunk_items`, and on the indexed route not the
+ * row of the table.  Chunked and unchunked, indexed and direct calls therefore draw the same masks, and the CLS-only last live block
+ * draws the masks of row t = 0 / query q = 0.  Padding slots are dropped like any other (the reference does not exempt them). */
+typedef struct { float hidden_p; float attn_p; uint64_t seed; } iisan_bert_dropout;
+/* iisan_bert_forward_taps (index == NULL: text_or_table is the text [M, 2W], `rows` is ignored) or iisan_bert_forward_taps_indexed
+ * (index != NULL) with dropout.  drop == NULL or both probabilities 0: exactly the launches and the bits of those two.  Otherwise
+ * the variants of csrc/bert_drop.hip run, for both operand types; dead-work pruning is unchanged.  Workspace:
+ * iisan_bert_forward_taps_ws_bytes is sufficient.  IISAN_EBADSHAPE before any launch: a probability outside [0, 1); dropout asked for
+ * under the development switch resid32 = 1 (never a silent fall-back to eval mode). */
+int iisan_bert_forward_taps_dropout(const iisan_bert_weights* w, const int64_t* text_or_table, int64_t rows,
+                                    const int64_t* index, int64_t M, int32_t words,
+                                    const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
+                                    const iisan_bert_dropout* drop, void* ws, size_t ws_bytes, void* stream);
+
 /* Dead-work policy of the two executors above (`full_blocks` of the weights struct — part of the call, not process state).
  * 0 (default): blocks deeper than the deepest tapped hidden state are not run, and in the last live block attention / O /
  * MLP / LayerNorm run for the CLS row of every item only (K and V still for all tokens): the path consumes nothing but
@@ -311,6 +335,10 @@ int iisan_attention16(int32_t dtype16, const void* qkv, const float* key_bias, v
  * in the last live block, where only `hidden_states[i][:, 0]` is consumed (Code_Uncached/model/model.py:210-213) */
 int iisan_attention_cls16(int32_t dtype16, const void* qkv, const float* key_bias, void* ctx_cls, int64_t items,
                           int32_t S, int32_t heads, void* stream);
+/* iisan_attention16 (cls_only == 0) / iisan_attention_cls16 (cls_only != 0; the query is token 0 of the q block) with the
+ * probabilities dropped at `site` (iisan_bert_dropout; slot m = item); p = 0 gives the bits of iisan_attention16.  S <= 224. */
+int iisan_attention16_dropout(int32_t dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int32_t S,
+                              int32_t heads, float p, uint64_t seed, int32_t site, int32_t cls_only, void* stream);
 /* fp32 MFMA GEMM: C[M,N] = op(A) op(B) (+bias)(+relu); ta: A stored [K,M]; tb: B stored [K,N] (else [N,K]);
  * accumulate != 0: C += (atomic, split-K capable) */
 int iisan_gemm32(const float* A, const float* B, const float* bias, float* C, int64_t M, int32_t N, int64_t K,
