@@ -487,6 +487,8 @@ int launch_attention16(int dtype16, const void* qkv, const float* key_bias, void
     IISAN_CHECK_SHAPE(items > 0 && S > 0 && heads > 0, "attention16: empty problem");
     IISAN_CHECK_SHAPE(items * heads < (1ll << 31), "attention16: grid too large");
     IISAN_CHECK_SHAPE((int64_t)S * heads * 64 < (1ll << 31), "attention16: item of %d x %d elements too large", S, heads * 64);
+    // ViT (no key_bias, 13 key tiles): K / V staged by LDS-DMA, V read transposed (attn16_dma.hip; dev switch attn_route)
+    if (attention16_dma_routed(key_bias, S)) return launch_attention16_dma(dtype16, qkv, ctx, items, S, heads, s);
     return dtype16 == IISAN_BF16 ? launch_t<BF16>(qkv, key_bias, ctx, items, S, heads, s)
                                  : launch_t<F16>(qkv, key_bias, ctx, items, S, heads, s);
 }

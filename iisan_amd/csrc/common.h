@@ -353,6 +353,10 @@ int launch_stream_stats_finalize(const float* rowpart, int nslots, int64_t Mpad,
                                  int64_t items, int Ttok, hipStream_t s);
 int launch_attention16(int dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int S,
                        int heads, hipStream_t s);
+// attn16_dma.hip: the ViT shape (no key_bias, 192 < S <= 208) with K / V staged by LDS-DMA; `routed` = launch_attention16 sends this
+// problem there under the dev switch attn_route
+bool attention16_dma_routed(const float* key_bias, int S);
+int launch_attention16_dma(int dtype16, const void* qkv, void* ctx, int64_t items, int S, int heads, hipStream_t s);
 // CLS query only: ctx_cls [items, heads*64] (last executed encoder block)
 int launch_attention_cls16(int dtype16, const void* qkv, const float* key_bias, void* ctx_cls, int64_t items, int S,
                            int heads, hipStream_t s, const void* q_cls = nullptr);   // q_cls: [items, heads*64] 16-bit CLS queries
