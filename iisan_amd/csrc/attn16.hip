@@ -16,7 +16,7 @@
 //   * K rows are 128 bytes, 16-byte slots XOR-swizzled with (row&7): conflict-free ds_read_b128;
 //   * fp32 softmax statistics; masked keys (BERT attention_mask == 0) take the constant fp32-min score exactly like
 //     HF's additive mask, so an all-masked padding item attends uniformly; structural pad keys get -inf.
-#include "common.h"
+#include "attn16_block.h"
 #ifndef ATTN_KBATCH
 #define ATTN_KBATCH 4
 #endif
@@ -30,41 +30,22 @@ static constexpr int g_attn_dbg = 0;
 
 namespace {
 
-// masked keys carry this RAW score (before the log2(e)/8 scaling): every real score is absorbed by it, like HF's
-// additive fp32-min mask, and MASK_RAW * c2 stays finite
-constexpr float MASK_RAW = -0x1p126f;      // a power of two: MASK_RAW * c2 is exact, so the fused scale-and-shift below is exactly 0 on all-masked rows
-
 // One workgroup = one item x HPW consecutive heads, software-pipelined: while head h is being computed out of LDS,
 // the Q/K/V registers for head h+1 are already being filled from HBM (measured on the unpipelined version: the load
-// phase and the compute phase of a workgroup did not overlap at all and the kernel ran at 2.4 TB/s).
-// 16-key tail product of an odd tile count (ViT: 13 tiles): v_mfma_f32_16x16x16 with 4 contraction slots per lane (key base + 4 g + e)
-template <typename T> struct Mfma16k16;
-template <> struct Mfma16k16<F16> {
-    static __device__ __forceinline__ f4 run(h4 a, h4 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mfma16k16<BF16> {
-    typedef short s4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ f4 run(b4 a, b4 b, f4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s4, a), __builtin_bit_cast(s4, b), c, 0, 0, 0);
-    }
-};
-
-// PF (prefetch): true (the product) — the next head's Q / K / V registers fill from HBM during this head's compute (92 registers held
-// across it: 227 VGPRs, two waves per SIMD, two workgroups per CU); false (round 4 experiment, no longer instantiated) =
-// no register prefetch, 136 VGPRs and 54.6 KB of LDS so that THREE workgroups share a CU: one loads and stages while two compute.
-// Measured 4 % SLOWER (415-421 against 398-411 us per ViT layer): a third wave per SIMD does not make up for the load phase a
-// workgroup now waits out.
+// phase and the compute phase of a workgroup did not overlap at all and the kernel ran at 2.4 TB/s).  92 registers are held
+// across a head's compute for it: 227 VGPRs, two waves per SIMD, two workgroups per CU.
 // MASKALL (round 5): true = the per-key limit is applied to every key tile (key_bias present, or a sequence that leaves more than the last
 // tile padded); false = compile-time knowledge that only the LAST tile can hold pad slots (no key_bias and S > 16 (NT16 - 1): ViT) — the
 // run-time test per tile made every tile its own basic block (~100 branches in the unrolled block loop).
-template <typename T, int NT16, bool PF, bool MASKALL>
-__global__ __launch_bounds__(256, PF ? 2 : 3) void attention16_kernel(const typename T::elem* __restrict__ qkv,
+template <typename T, int NT16, bool MASKALL>
+__global__ __launch_bounds__(256, 2) void attention16_kernel(const typename T::elem* __restrict__ qkv,
                                                              const float* __restrict__ key_bias,
                                                              typename T::elem* __restrict__ ctx, int S, int heads, int hpw,
                                                              int dbg_arg) {
     typedef typename T::elem E;
     typedef typename T::v8 V8;
     typedef typename T::v4 V4;
+    typedef AttnLds<NT16> L;
 #ifndef ATTN_DEBUG_BITS
     // the ablation bits of tools/attn_time.py (dev switch attn_debug: 1 = no V^T write, 8 = no store, 16 = no K write, 32 = no global loads, 64 = no
     // query blocks) are compiled in
@@ -74,21 +55,12 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void attention16_kernel(const type
 #else
     const int dbg = dbg_arg;
 #endif
-    constexpr int SP = NT16 * 16;
-    // V^T[d][slot] in LDS, keys PERMUTED inside every group of 32 so that the eight contraction values a lane needs for one P.V step — keys
-    // 32 kb + 4 g + (0..3) of score tile 2 kb and 32 kb + 16 + 4 g + (0..3) of tile 2 kb + 1 — are contiguous: key 16 t + 4 g' + r sits at slot
-    // 32 (t >> 1) + 8 g' + 4 (t & 1) + r, and a fragment is ONE ds_read_b128 (round 6; before: two 8-byte pieces 32 bytes apart, read as a
-    // ds_read2_b64 — 8 LDS cycles per wave-instruction instead of 4, MI355X_MICROARCH.md LDS table; the reads were a third of the kernel's LDS time).
-    // Row stride: the slots an odd tile count leaves half-filled count, + 16 elements: rows 16 (mod 32) elements apart put the 16 rows of a
-    // ds_read_b128 lane group on 16 distinct bank quads (208 -> 240: K + V^T + key limits = 58,176 B, two workgroups per CU as the registers allow).
-    constexpr int VT_LD = 32 * ((NT16 + 1) / 2) + 16;
+    constexpr int SP = L::SP, KP = L::KP, VP = L::VP;
     constexpr int MAXQB = (NT16 + 3) / 4;            // 16-query blocks per wave
-    constexpr int KP = (SP + 31) / 32;                // K passes: 32 rows per pass (the last may be partial: NT16 odd)
-    constexpr int VP = (SP / 4 + 31) / 32;            // V passes: 32 four-key groups per pass
-    __shared__ __attribute__((aligned(16))) char smem[SP * 128 + 64 * VT_LD * 2 + SP * 4];
+    __shared__ __attribute__((aligned(16))) char smem[L::BYTES];
     char* sK = smem;
-    E* sVt = (E*)(smem + SP * 128);
-    float* sKB = (float*)(smem + SP * 128 + 64 * VT_LD * 2);
+    E* sVt = (E*)(smem + L::VT_OFF);
+    float* sKB = (float*)(smem + L::KB_OFF);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int groups = heads / hpw;
@@ -117,7 +89,7 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void attention16_kernel(const type
             sq = sq < S ? sq : S - 1;
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) qnext[i][kk] = *(const V8*)(qb_ + (unsigned)(sq * 64 + kk * 32 + g * 8));   // 32-bit lane offsets from a uniform base: as
-                                                                                              // 64-bit addresses they were spilled (see the store below)
+                                                                                              // 64-bit addresses they were spilled (see attn_store_ctx)
         }
 #pragma unroll
         for (int p = 0; p < KP; ++p) {
@@ -140,36 +112,20 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void attention16_kernel(const type
             }
     };
 
-    if (PF) load_head(h0);
-    for (int r = tid; r < SP; r += 256)
-        sKB[r] = r >= S ? -INFINITY : ((key_bias && key_bias[(int64_t)item * S + r] < 0.f) ? MASK_RAW : INFINITY);   // per-key upper limit of the score
+    load_head(h0);
+    for (int r = tid; r < SP; r += 256) sKB[r] = attn_key_limit(key_bias, item, S, r);
 
-    // exp(s/8 - m) = exp2(acc * c2 - m2),  c2 = log2(e) / 8
-    // (an odd tile count ends with a 16-key product of its own, Mfma16k16: no zero-filled half step, no LDS for it)
-    const float c2 = 0.18033688011112042f;
 #pragma unroll 1
     for (int hi = 0; hi < hpw; ++hi) {
         const int h = h0 + hi;
-        if (!PF) load_head(h);                // (the other workgroups of the CU compute meanwhile)
         if (hi > 0) __syncthreads();          // every wave is done reading the previous head's K / V^T
 #pragma unroll
-        for (int p = 0; p < KP; ++p) {
-            const int r = r0 + 32 * p;
-            if ((SP % 32 == 0 || r < SP) && !(dbg & 16)) *(V8*)(sK + r * 128 + ((c ^ (r & 7)) << 4)) = kreg[p];
-        }
-        // V^T: a thread owns 4 consecutive keys x 8 head dims -> eight 8-byte LDS writes per pass
+        for (int p = 0; p < KP; ++p)
+            if (!(dbg & 16)) L::stage_k_row(sK, r0 + 32 * p, c, kreg[p]);
 #pragma unroll
         for (int p = 0; p < VP; ++p) {
             const int kg = r0 + 32 * p;
-            if (kg < SP / 4) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    V4 t;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) t[r] = vreg[p][r][e];
-                    if (!(dbg & 1)) *(V4*)(sVt + (c * 8 + e) * VT_LD + 32 * (kg >> 3) + 8 * (kg & 3) + 4 * ((kg >> 2) & 1)) = t;
-                }
-            }
+            if (kg < SP / 4 && !(dbg & 1)) L::template stage_v_group<T>(sVt, tid, p, vreg[p]);
         }
         V8 qf[MAXQB][2];
 #pragma unroll
@@ -177,7 +133,7 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void attention16_kernel(const type
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) qf[i][kk] = qnext[i][kk];
         __syncthreads();
-        if (PF && hi + 1 < hpw) load_head(h + 1);   // in flight during this head's compute
+        if (hi + 1 < hpw) load_head(h + 1);   // in flight during this head's compute
 
 #pragma unroll
         for (int i = 0; i < MAXQB; ++i) {
@@ -185,10 +141,7 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void attention16_kernel(const type
             if (qb >= nqb || (dbg & 64)) break;  // (ablation bit 64, debug builds: loads and staging alone)
             const int sq = qb * 16 + j;
 
-            // S^T tiles: lane holds query j, keys 16t + 4g + r (raw dot products; the 1/8 scale is folded into exp2)
-            // VALU diet (PMC: this kernel is VALU-bound, 1088 VALU instructions per 16-query block before): the
-            // mask select runs only on tiles that can contain masked/padded keys, scale+subtract is one fma, and
-            // exp2 is the bare v_exp_f32 (arguments <= 0, results in [0,1]: no range fix-up needed).
+            // S^T tiles: lane holds query j, keys 16t + 4g + r (raw dot products; the 1/8 scale is folded into exp2).
             // The K fragments of tile t+1 are requested before the MFMAs of tile t (no branch inside this loop: with the
             // per-tile `if`s of the first version every tile was its own basic block and each pair of MFMAs waited a
             // full LDS round trip — the ISA showed read, s_waitcnt, mfma, read, s_waitcnt, mfma ... and PMC 49 % of
@@ -203,7 +156,7 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void attention16_kernel(const type
                     for (int u = 0; u < KBATCH; ++u)
 #pragma unroll
                         for (int kk = 0; kk < 2; ++kk)
-                            if (t0 + u < NT16) kf[u][kk] = *(const V8*)(sK + ((t0 + u) * 16 + j) * 128 + (((kk * 4 + g) ^ (j & 7)) << 4));
+                            if (t0 + u < NT16) kf[u][kk] = *(const V8*)(sK + L::k_off((t0 + u) * 16 + j, kk * 4 + g));
                     __builtin_amdgcn_sched_barrier(0);      // unfenced, hipcc sinks the reads back to one or two MFMAs before their use
 #pragma unroll
                     for (int u = 0; u < KBATCH; ++u) {
@@ -215,66 +168,31 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void attention16_kernel(const type
                     }
                 }
             }
-            // masks afterwards, only on the tiles that can hold masked / padded keys (wave-uniform conditions)
-#pragma unroll
-            for (int t = 0; t < NT16; ++t) {
-                if (MASKALL || t == NT16 - 1) {
-                    const f4 kb = *(const f4*)(sKB + t * 16 + g * 4);
-#pragma unroll
-                    // +inf keeps, MASK_RAW replaces (every real score is above it), -inf removes a pad slot: min(score, limit) as ONE
-                    // instruction the compiler can see — med3(score, limit, -inf).  (fminf() adds two canonicalising v_max; rounds 2-4 used an
-                    // inline-asm v_min_f32 here, which was only safe because a branch stood between it and the MFMAs: the hazard recognizer
-                    // does not look inside inline asm, and with the per-tile branches gone (round 5) the v_min read its MFMA result before
-                    // the matrix pipe had written it — 12 of 18 attention cases wrong.)
-                    for (int r = 0; r < 4; ++r) sc[t][r] = __builtin_amdgcn_fmed3f(sc[t][r], kb[r], -INFINITY);
-                }
-            }
-            // (round 5: two independent max chains and four independent sum chains instead of one 26-deep v_max3 chain and one 52-deep
-            //  v_add chain — the dependent-issue latency of those chains was exposed time, not arithmetic)
-            float mx0 = -INFINITY, mx1 = -INFINITY;
-#pragma unroll
-            for (int t = 0; t < NT16; ++t) {
-                if (t & 1) mx1 = fmaxf(fmaxf(mx1, sc[t][0]), fmaxf(sc[t][1], fmaxf(sc[t][2], sc[t][3])));
-                else mx0 = fmaxf(fmaxf(mx0, sc[t][0]), fmaxf(sc[t][1], fmaxf(sc[t][2], sc[t][3])));
-            }
-            float mx = fmaxf(mx0, mx1);
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            f4 sum4 = {0.f, 0.f, 0.f, 0.f};
-            const float mxs = -(mx * c2);
+            // limits afterwards, only on the tiles that can hold masked / padded keys (wave-uniform conditions)
 #pragma unroll
             for (int t = 0; t < NT16; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float a = fmaf(sc[t][r], c2, mxs);    // one instruction; mxs = -(mx * c2).  At the maximum the result is the
-                                                                  // rounding residue of mx*c2 (<= 1e-6 in magnitude: exp2 = 1 +- 7e-7), and it
-                                                                  // is exactly 0 on all-masked rows because MASK_RAW is a power of two
-                    const float p = __builtin_amdgcn_exp2f(a);          // (a run-time debug select here cost one v_cndmask per score)
-                    sc[t][r] = p;
-                    sum4[r] += p;
-                }
-            float sum = (sum4[0] + sum4[1]) + (sum4[2] + sum4[3]);
-            sum += __shfl_xor(sum, 16, 64);
-            sum += __shfl_xor(sum, 32, 64);
-            const float inv = 1.0f / sum;
+                if (MASKALL || t == NT16 - 1) attn_apply_key_limit(sc[t], *(const f4*)(sKB + t * 16 + g * 4));
+            const float inv = attn_row_softmax(sc, AttnKeepAll());
 
-            // O^T = V^T · P^T
             f4 o[4];
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) o[dt] = (f4){0.f, 0.f, 0.f, 0.f};
             {
+                // O^T = V^T · P^T: 32-key steps, the next step's V^T fragments in flight during the MFMAs.  The loop and its P rounding stay
+                // written out in this file: with either behind a function boundary hipcc lays out the text tower's launch (NT16 = 2)
+                // differently (profiles/attention_shared_block.md)
                 auto vload = [&](int kb, V8 (&vf)[4]) {
 #pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) vf[dt] = *(const V8*)(sVt + (dt * 16 + j) * VT_LD + kb * 32 + g * 8);
+                    for (int dt = 0; dt < 4; ++dt) vf[dt] = L::template vt_frag<V8>(sVt, dt, j, g, kb);
                 };
                 V8 vc[4];
                 vload(0, vc);
-                constexpr int NPV = NT16 / 2;                  // 32-key steps of P.V (an odd tile count: + one 16-key step below)
+                constexpr int NPV = NT16 / 2;                  // (an odd tile count: + one 16-key step below)
 #pragma unroll
                 for (int kb = 0; kb < NPV; ++kb) {
                     V8 vn[4];
-                    if (kb + 1 < NPV) vload(kb + 1, vn);          // next step's V^T fragments: in flight during the MFMAs
-                    V8 pf;
+                    if (kb + 1 < NPV) vload(kb + 1, vn);
+                    V8 pf;                                        // (attn_round_p, written out: see above)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         pf[e] = T::from_f32(sc[2 * kb][e]);
@@ -288,47 +206,15 @@ __global__ __launch_bounds__(256, PF ? 2 : 3) void attention16_kernel(const type
                     }
                 }
                 if constexpr (NT16 % 2 == 1) {                 // keys SP-16 .. SP-1
-                    V4 pt;
+                    const V4 pt = attn_round_p_tail<T>(sc[NT16 - 1]);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) pt[e] = T::from_f32(sc[NT16 - 1][e]);
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt)
-                        o[dt] = Mfma16k16<T>::run(*(const V4*)(sVt + (dt * 16 + j) * VT_LD + (NT16 / 2) * 32 + g * 8), pt, o[dt]);
+                    for (int dt = 0; dt < 4; ++dt) o[dt] = Mfma16k16<T>::run(L::template vt_frag<V4>(sVt, dt, j, g, NT16 / 2), pt, o[dt]);
                 }
             }
-            // A lane holds 4 consecutive head dims (8 B) of its query per 16-dim tile; lanes 16 apart (g, g+1) hold the
-            // neighbouring 8 B.  `v_permlane16_swap` trades the odd lane's piece of tile 2q for the even lane's piece of
-            // tile 2q+1, so every lane owns 16 contiguous bytes and a store instruction writes 16 rows x 64 contiguous
-            // bytes (two 16-byte stores per block instead of four 8-byte ones).
-            typedef unsigned u2 __attribute__((ext_vector_type(2)));
-            u2 pk[4];
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                V4 ov;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ov[r] = T::from_f32(o[dt][r] * inv);
-                pk[dt] = __builtin_bit_cast(u2, ov);
-            }
-#pragma unroll
-            for (int q2 = 0; q2 < 2; ++q2)
-#pragma unroll
-                for (int w = 0; w < 2; ++w) {
-                    const auto sw = __builtin_amdgcn_permlane16_swap(pk[2 * q2][w], pk[2 * q2 + 1][w], false, false);
-                    pk[2 * q2][w] = sw[0];
-                    pk[2 * q2 + 1][w] = sw[1];
-                }
-            if (sq < S && !(dbg & 8)) {
-                // 32-bit element offset from a wave-uniform base (the launcher checks the tensor is < 2^31 elements): as 64-bit
-                // per-lane addresses these were spilled, and every scratch reload is an `s_waitcnt vmcnt(0)` — which also waits
-                // for the next head's prefetch loads and for every earlier store
-                int g2 = g;
-                asm volatile("" : "+v"(g2));              // (recomputed per block for the same reason as in load_head)
-                E* op = ctx + (size_t)item * S * D + (unsigned)(sq * D + h * 64 + g2 * 4 + ((g2 & 1) ? 12 : 0));
-                typedef unsigned u4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-                for (int q2 = 0; q2 < 2; ++q2)
-                    *(u4*)(op + q2 * 32) = (u4){pk[2 * q2][0], pk[2 * q2][1], pk[2 * q2 + 1][0], pk[2 * q2 + 1][1]};
-            }
+            // g is RECOMPUTED per block behind a laundering asm, for the same reason as in load_head: the store offset must not live across
+            // the head loop — a spill's reload also waits for the next head's prefetch loads and for every earlier store
+            attn_store_ctx<T>(ctx + (size_t)item * S * D, sq * D + h * 64, [&] { int g2 = g; asm volatile("" : "+v"(g2)); return g2; }, o, inv,
+                              sq < S && !(dbg & 8));
         }
     }
 }
@@ -450,7 +336,8 @@ template <typename T>
 int launch_t(const void* qkv, const float* key_bias, void* ctx, int64_t items, int S, int heads, hipStream_t s) {
     typedef typename T::elem E;
     // heads per workgroup: 2 (one head computing, the next one's Q/K/V in flight).  On the spill-free kernel 1 / 2 / 4 / 6
-    // heads measured 420 / 421 / 428 / 437 us per ViT layer in isolation and 68.55 / 68.58 / 68.78 ms per step
+    // heads measured 420 / 421 / 428 / 437 us per ViT layer in isolation and 68.55 / 68.58 / 68.78 ms per step.  (Without the register
+    // prefetch, three workgroups per CU instead: 415-421 against 398-411 us per ViT layer — removed.)
     int hpw = heads % 2 == 0 ? 2 : 1;
 #ifdef ATTN_DEBUG_BITS
     {   // ablation builds (tools/attn_pf_ab.py): bits 8..11 of dev switch attn_debug = heads per workgroup, when it divides the head count
@@ -459,13 +346,11 @@ int launch_t(const void* qkv, const float* key_bias, void* ctx, int64_t items, i
     }
 #endif
     dim3 grid((unsigned)(items * (heads / hpw))), block(256);
-    // (round 4 measured a three-workgroups-per-CU instantiation without register prefetch, PF = false: 415-421 us against 398-411 us per
-    //  ViT layer for this one; it is no longer instantiated — round 5 route retirement)
 #define IISAN_ATTN_CASE(NT)                                                                                                       \
     if (key_bias == nullptr && S > 16 * (NT - 1))                                                                                 \
-        hipLaunchKernelGGL((attention16_kernel<T, NT, true, false>), grid, block, 0, s, (const E*)qkv, key_bias, (E*)ctx, S, heads, hpw, g_attn_dbg & 127); \
+        hipLaunchKernelGGL((attention16_kernel<T, NT, false>), grid, block, 0, s, (const E*)qkv, key_bias, (E*)ctx, S, heads, hpw, g_attn_dbg & 127); \
     else                                                                                                                          \
-        hipLaunchKernelGGL((attention16_kernel<T, NT, true, true>), grid, block, 0, s, (const E*)qkv, key_bias, (E*)ctx, S, heads, hpw, g_attn_dbg & 127)
+        hipLaunchKernelGGL((attention16_kernel<T, NT, true>), grid, block, 0, s, (const E*)qkv, key_bias, (E*)ctx, S, heads, hpw, g_attn_dbg & 127)
     if (S <= 32) { IISAN_ATTN_CASE(2); }
     else if (S <= 64) { IISAN_ATTN_CASE(4); }
     else if (S <= 128) { IISAN_ATTN_CASE(8); }

@@ -20,7 +20,7 @@
 // vmcnt retires in order and DMA pieces, Q loads and context stores share it; every wait below is `vmcnt(n)` with n = the number of
 // vector-memory instructions the wave has issued BEHIND the one it needs (a lower bound where waves differ), so that the two context
 // stores of the previous block stay in flight over it.  The counts are written next to each wait.
-#include "common.h"
+#include "attn16_block.h"
 
 static int g_attn_route = 0;            // 0 = this kernel where it applies by default, 1 = always attention16_kernel, 2 = this kernel wherever it applies
 IISAN_DEV_KNOB(attn_route, g_attn_route);
@@ -33,17 +33,6 @@ constexpr int DMA_NT16 = 13, DMA_SP = DMA_NT16 * 16;       // 208 key slots
 constexpr int DMA_BUF = DMA_SP * 128;                        // one head's K or V: 26,624 B = 26 pieces of 1 KiB
 constexpr int DMA_PIECES = DMA_BUF / 1024;
 constexpr int DMA_LDS = 2 * DMA_BUF;                         // K, then V
-
-template <typename T> struct Mfma16k16d;
-template <> struct Mfma16k16d<F16> {
-    static __device__ __forceinline__ f4 run(h4 a, h4 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mfma16k16d<BF16> {
-    typedef short s4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ f4 run(b4 a, b4 b, f4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s4, a), __builtin_bit_cast(s4, b), c, 0, 0, 0);
-    }
-};
 
 #define DMA_FENCE() __builtin_amdgcn_sched_barrier(0)
 // vmcnt(n) as the builtin (gfx9 encoding: vmcnt[3:0] | expcnt << 4 | lgkmcnt << 8 | vmcnt[5:4] << 14)
@@ -74,7 +63,6 @@ __device__ __forceinline__ void dma16(unsigned lane_off, const void* base, unsig
 template <typename T>
 __global__ __launch_bounds__(256, 3) void attention16_dma_kernel(const typename T::elem* __restrict__ qkv, typename T::elem* __restrict__ ctx,
                                                                  int S, int heads) {
-    typedef typename T::elem E;
     typedef typename T::v8 V8;
     typedef typename T::v4 V4;
     typedef short s4 __attribute__((ext_vector_type(4)));
@@ -156,7 +144,6 @@ __global__ __launch_bounds__(256, 3) void attention16_dma_kernel(const typename 
     const char* sK = smem;
     const char* sV = smem + DMA_BUF;
 
-    const float c2 = 0.18033688011112042f;      // exp(s/8 - m) = exp2(acc * c2 - m2),  c2 = log2(e) / 8
     DMA_VMCNT(6);                               // K and Q: behind them, at least 6 V pieces
     DMA_BARRIER();                              // every wave's K pieces are in LDS
 #pragma unroll
@@ -193,31 +180,8 @@ __global__ __launch_bounds__(256, 3) void attention16_dma_kernel(const typename 
                 }
             }
         }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sc[NT16 - 1][r] = __builtin_amdgcn_fmed3f(sc[NT16 - 1][r], lim[r], -INFINITY);
-        float mx0 = -INFINITY, mx1 = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NT16; ++t) {
-            if (t & 1) mx1 = fmaxf(fmaxf(mx1, sc[t][0]), fmaxf(sc[t][1], fmaxf(sc[t][2], sc[t][3])));
-            else mx0 = fmaxf(fmaxf(mx0, sc[t][0]), fmaxf(sc[t][1], fmaxf(sc[t][2], sc[t][3])));
-        }
-        float mx = fmaxf(mx0, mx1);
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        f4 sum4 = {0.f, 0.f, 0.f, 0.f};
-        const float mxs = -(mx * c2);
-#pragma unroll
-        for (int t = 0; t < NT16; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float p = __builtin_amdgcn_exp2f(fmaf(sc[t][r], c2, mxs));
-                sc[t][r] = p;
-                sum4[r] += p;
-            }
-        float sum = (sum4[0] + sum4[1]) + (sum4[2] + sum4[3]);
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = 1.0f / sum;
+        attn_apply_key_limit(sc[NT16 - 1], lim);
+        const float inv = attn_row_softmax(sc, AttnKeepAll());
 
         if (i == 0) {
             // V: own pieces landed, then everybody's.  Behind the wave's V pieces: the two Q loads of block 1.
@@ -246,12 +210,7 @@ __global__ __launch_bounds__(256, 3) void attention16_dma_kernel(const typename 
             for (int kb = 0; kb < NPV; ++kb) {
                 V8 vn[4];
                 if (kb + 1 < NPV) vload(kb + 1, vn);
-                V8 pf;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    pf[e] = T::from_f32(sc[2 * kb][e]);
-                    pf[4 + e] = T::from_f32(sc[2 * kb + 1][e]);
-                }
+                const V8 pf = attn_round_p<T>(sc[2 * kb], sc[2 * kb + 1]);
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) o[dt] = T::mfma(vc[dt], pf, o[dt]);
                 if (kb + 1 < NPV) {
@@ -259,36 +218,12 @@ __global__ __launch_bounds__(256, 3) void attention16_dma_kernel(const typename 
                     for (int dt = 0; dt < 4; ++dt) vc[dt] = vn[dt];
                 }
             }
-            V4 pt;                          // keys 192 .. 207
+            const V4 pt = attn_round_p_tail<T>(sc[NT16 - 1]);      // keys 192 .. 207
 #pragma unroll
-            for (int e = 0; e < 4; ++e) pt[e] = T::from_f32(sc[NT16 - 1][e]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[dt] = Mfma16k16d<T>::run(vtr(dt, (NT16 / 2) * 4096), pt, o[dt]);
+            for (int dt = 0; dt < 4; ++dt) o[dt] = Mfma16k16<T>::run(vtr(dt, (NT16 / 2) * 4096), pt, o[dt]);
         }
-        // `v_permlane16_swap` gives every lane 16 contiguous bytes of its query's context row (attn16.hip)
-        u2 pk[4];
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            V4 ov;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ov[r] = T::from_f32(o[dt][r] * inv);
-            pk[dt] = __builtin_bit_cast(u2, ov);
-        }
-#pragma unroll
-        for (int q2 = 0; q2 < 2; ++q2)
-#pragma unroll
-            for (int w = 0; w < 2; ++w) {
-                const auto sw = __builtin_amdgcn_permlane16_swap(pk[2 * q2][w], pk[2 * q2 + 1][w], false, false);
-                pk[2 * q2][w] = sw[0];
-                pk[2 * q2 + 1][w] = sw[1];
-            }
         // exactly two store instructions per block (every block of 192 < S <= 208 has a real query): the waits above count them
-        if (sq < S) {
-            E* op = ctx + (size_t)item * S * D + (unsigned)(sq * D + h * 64 + g * 4 + ((g & 1) ? 12 : 0));
-#pragma unroll
-            for (int q2 = 0; q2 < 2; ++q2)
-                *(u4*)(op + q2 * 32) = (u4){pk[2 * q2][0], pk[2 * q2][1], pk[2 * q2 + 1][0], pk[2 * q2 + 1][1]};
-        }
+        attn_store_ctx<T>(ctx + (size_t)item * S * D, sq * D + h * 64, [&] { return g; }, o, inv, sq < S);
         DMA_FENCE();
     }
 }

@@ -7,7 +7,7 @@
 // where m is the slot's position in the WHOLE call — so chunked and unchunked, indexed and direct calls, and the CLS-only last block
 // and the all-token execution draw the same masks.  The eval-mode kernels (attn16.hip, rowops.hip) are not touched: every kernel here is
 // a variant of its own, launched only when a dropout description with a non-zero probability is given.
-#include "common.h"
+#include "attn16_block.h"
 
 // launches of this file's kernels: with the switch off a step leaves it at 0 — it runs the eval-mode launch sequence (tests, tools/bert_dropout_time.py)
 static int64_t g_cnt_bert_drop = 0;
@@ -15,25 +15,12 @@ IISAN_DEV_COUNTER(bert_drop, g_cnt_bert_drop);
 
 namespace {
 
-constexpr float MASK_RAW = -0x1p126f;      // raw score of a masked key (attn16.hip)
-
-template <typename T> struct Mfma16k16;
-template <> struct Mfma16k16<F16> {
-    static __device__ __forceinline__ f4 run(h4 a, h4 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mfma16k16<BF16> {
-    typedef short s4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ f4 run(b4 a, b4 b, f4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s4, a), __builtin_bit_cast(s4, b), c, 0, 0, 0);
-    }
-};
-
 // ---- attention with dropped probabilities -----------------------------------------------------------------------------------------
 // ctx = (drop(P) V) with P = softmax(Q K^T / 8 + key_bias): the keep factor multiplies the exponentials that go into the P.V product,
 // the row sum that normalises them is taken BEFORE it.  One workgroup = one (item, head): K (XOR-swizzled rows) and V^T (keys permuted
 // inside groups of 32) of that head in LDS, one wave per 16-query block, scores of a whole row in registers (S <= 224: at most 14
-// tiles) — the layouts, the MFMA mapping and the ORDER of every fp32 operation are those of attention16_kernel (attn16.hip), so that
-// with the identity mask (p = 0) the result equals that kernel's bit for bit.  No register prefetch of the next head, one head per
+// tiles) — the layouts, the MFMA mapping and the ORDER of every fp32 operation are those of attention16_kernel (attn16.hip): both are
+// built from attn16_block.h, so that with the identity mask (p = 0) the result equals that kernel's bit for bit.  No register prefetch of the next head, one head per
 // workgroup: the text tower's attention is a few per cent of its time (S = 30: two key tiles).
 // CLS: only query 0 of every item (the last live block of the executor): q from `q_cls` [items, heads * 64] when given (the QKV
 // product of that block wrote K and V only), ctx [items, heads * 64].  The mask is that of row q = 0 of the all-token form.
@@ -45,14 +32,11 @@ __global__ __launch_bounds__(256) void attention16_drop_kernel(const typename T:
     typedef typename T::elem E;
     typedef typename T::v8 V8;
     typedef typename T::v4 V4;
-    constexpr int SP = NT16 * 16;
-    constexpr int VT_LD = 32 * ((NT16 + 1) / 2) + 16;
-    constexpr int KP = (SP + 31) / 32;
-    constexpr int VP = (SP / 4 + 31) / 32;
-    __shared__ __attribute__((aligned(16))) char smem[SP * 128 + 64 * VT_LD * 2 + SP * 4];
+    typedef AttnLds<NT16> L;
+    __shared__ __attribute__((aligned(16))) char smem[L::BYTES];
     char* sK = smem;
-    E* sVt = (E*)(smem + SP * 128);
-    float* sKB = (float*)(smem + SP * 128 + 64 * VT_LD * 2);
+    E* sVt = (E*)(smem + L::VT_OFF);
+    float* sKB = (float*)(smem + L::KB_OFF);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int item = blockIdx.x / heads, h = blockIdx.x - item * heads;
@@ -65,34 +49,26 @@ __global__ __launch_bounds__(256) void attention16_drop_kernel(const typename T:
 
     // pad slots (row >= S) re-read the last real row: their scores are forced to -inf below, their P is exactly 0
 #pragma unroll
-    for (int p = 0; p < KP; ++p) {
+    for (int p = 0; p < L::KP; ++p) {
         const int r = r0 + 32 * p;
-        if (SP % 32 == 0 || r < SP) *(V8*)(sK + r * 128 + ((c ^ (r & 7)) << 4)) = *(const V8*)(kb_ + (unsigned)((r < S ? r : S - 1) * 64 + c * 8));
+        L::stage_k_row(sK, r, c, *(const V8*)(kb_ + (unsigned)((r < S ? r : S - 1) * 64 + c * 8)));
     }
 #pragma unroll
-    for (int p = 0; p < VP; ++p) {
+    for (int p = 0; p < L::VP; ++p) {
         const int kg = r0 + 32 * p;
-        if (kg < SP / 4) {
+        if (kg < L::SP / 4) {
             V8 v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int key = kg * 4 + r;
                 v[r] = *(const V8*)(vb_ + (unsigned)((key < S ? key : S - 1) * 64 + c * 8));
             }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                V4 t;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) t[r] = v[r][e];
-                *(V4*)(sVt + (c * 8 + e) * VT_LD + 32 * (kg >> 3) + 8 * (kg & 3) + 4 * ((kg >> 2) & 1)) = t;
-            }
+            L::template stage_v_group<T>(sVt, tid, p, v);
         }
     }
-    for (int r = tid; r < SP; r += 256)
-        sKB[r] = r >= S ? -INFINITY : ((key_bias && key_bias[(int64_t)item * S + r] < 0.f) ? MASK_RAW : INFINITY);   // per-key upper limit of the score
+    for (int r = tid; r < L::SP; r += 256) sKB[r] = attn_key_limit(key_bias, item, S, r);
     __syncthreads();
 
-    const float c2 = 0.18033688011112042f;      // log2(e) / 8
     const int nqb = CLS ? 1 : (S + 15) >> 4;
     const uint64_t pair = (uint64_t)(slot0 + item) * (uint64_t)heads + (uint64_t)h;
 #pragma unroll 1
@@ -111,69 +87,36 @@ __global__ __launch_bounds__(256) void attention16_drop_kernel(const typename T:
         for (int t = 0; t < NT16; ++t) {
             V8 kf[2];
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) kf[kk] = *(const V8*)(sK + (t * 16 + j) * 128 + (((kk * 4 + g) ^ (j & 7)) << 4));
+            for (int kk = 0; kk < 2; ++kk) kf[kk] = *(const V8*)(sK + L::k_off(t * 16 + j, kk * 4 + g));
             f4 acc = {0.f, 0.f, 0.f, 0.f};
             acc = T::mfma(kf[0], qf[0], acc);
             acc = T::mfma(kf[1], qf[1], acc);
             sc[t] = acc;
         }
 #pragma unroll
-        for (int t = 0; t < NT16; ++t) {
-            const f4 kb = *(const f4*)(sKB + t * 16 + g * 4);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sc[t][r] = __builtin_amdgcn_fmed3f(sc[t][r], kb[r], -INFINITY);     // min(score, limit)
-        }
-        float mx0 = -INFINITY, mx1 = -INFINITY;
-#pragma unroll
-        for (int t = 0; t < NT16; ++t) {
-            if (t & 1) mx1 = fmaxf(fmaxf(mx1, sc[t][0]), fmaxf(sc[t][1], fmaxf(sc[t][2], sc[t][3])));
-            else mx0 = fmaxf(fmaxf(mx0, sc[t][0]), fmaxf(sc[t][1], fmaxf(sc[t][2], sc[t][3])));
-        }
-        float mx = fmaxf(mx0, mx1);
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        f4 sum4 = {0.f, 0.f, 0.f, 0.f};
-        const float mxs = -(mx * c2);
+        for (int t = 0; t < NT16; ++t) attn_apply_key_limit(sc[t], *(const f4*)(sKB + t * 16 + g * 4));
         // index of (query sq, key 0) at this site; pad queries (sq >= S) are never stored, pad keys have P = 0
         const uint64_t base = (pair * (uint64_t)S + (uint64_t)sq) * (uint64_t)S;
-#pragma unroll
-        for (int t = 0; t < NT16; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float p = __builtin_amdgcn_exp2f(fmaf(sc[t][r], c2, mxs));
-                sum4[r] += p;       // the UNDROPPED denominator
-                sc[t][r] = p * drop_scale(drop.seed, drop.site, base + (uint64_t)(16 * t + 4 * g + r), drop.thr24, drop.inv_keep);
-            }
-        float sum = (sum4[0] + sum4[1]) + (sum4[2] + sum4[3]);
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = 1.0f / sum;
+        const float inv = attn_row_softmax(sc, [&](int t, int r) {
+            return drop_scale(drop.seed, drop.site, base + (uint64_t)(16 * t + 4 * g + r), drop.thr24, drop.inv_keep);
+        });
 
-        // O^T = V^T · drop(P)^T
+        // O^T = V^T · drop(P)^T: the lane holds head dims 16 dt + 4 g + (0..3) of its query
         f4 o[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) o[dt] = (f4){0.f, 0.f, 0.f, 0.f};
         constexpr int NPV = NT16 / 2;
 #pragma unroll
         for (int kb = 0; kb < NPV; ++kb) {
-            V8 pf;
+            const V8 pf = attn_round_p<T>(sc[2 * kb], sc[2 * kb + 1]);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                pf[e] = T::from_f32(sc[2 * kb][e]);
-                pf[4 + e] = T::from_f32(sc[2 * kb + 1][e]);
-            }
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[dt] = T::mfma(*(const V8*)(sVt + (dt * 16 + j) * VT_LD + kb * 32 + g * 8), pf, o[dt]);
+            for (int dt = 0; dt < 4; ++dt) o[dt] = T::mfma(L::template vt_frag<V8>(sVt, dt, j, g, kb), pf, o[dt]);
         }
         if constexpr (NT16 % 2 == 1) {                 // keys SP-16 .. SP-1
-            V4 pt;
+            const V4 pt = attn_round_p_tail<T>(sc[NT16 - 1]);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) pt[e] = T::from_f32(sc[NT16 - 1][e]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-                o[dt] = Mfma16k16<T>::run(*(const V4*)(sVt + (dt * 16 + j) * VT_LD + (NT16 / 2) * 32 + g * 8), pt, o[dt]);
+            for (int dt = 0; dt < 4; ++dt) o[dt] = Mfma16k16<T>::run(L::template vt_frag<V4>(sVt, dt, j, g, NT16 / 2), pt, o[dt]);
         }
-        // the lane holds head dims 16 dt + 4 g + (0..3) of its query
         if (CLS) {
             if (j == 0) {
 #pragma unroll
@@ -185,31 +128,7 @@ __global__ __launch_bounds__(256) void attention16_drop_kernel(const typename T:
                 }
             }
         } else {
-            // `v_permlane16_swap` trades the odd lane group's piece of tile 2q for the even group's piece of tile 2q + 1: every lane owns 16
-            // contiguous bytes (attn16.hip)
-            u2 pk[4];
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                V4 ov;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ov[r] = T::from_f32(o[dt][r] * inv);
-                pk[dt] = __builtin_bit_cast(u2, ov);
-            }
-#pragma unroll
-            for (int q2 = 0; q2 < 2; ++q2)
-#pragma unroll
-                for (int w = 0; w < 2; ++w) {
-                    const auto sw = __builtin_amdgcn_permlane16_swap(pk[2 * q2][w], pk[2 * q2 + 1][w], false, false);
-                    pk[2 * q2][w] = sw[0];
-                    pk[2 * q2 + 1][w] = sw[1];
-                }
-            if (sq < S) {
-                // (the launcher checks that an item's context is < 2^31 elements)
-                E* op = ctx + (size_t)item * S * D + (unsigned)(sq * D + h * 64 + g * 4 + ((g & 1) ? 12 : 0));
-#pragma unroll
-                for (int q2 = 0; q2 < 2; ++q2)
-                    *(u4*)(op + q2 * 32) = (u4){pk[2 * q2][0], pk[2 * q2][1], pk[2 * q2 + 1][0], pk[2 * q2 + 1][1]};
-            }
+            attn_store_ctx<T>(ctx + (size_t)item * S * D, sq * D + h * 64, [&] { return g; }, o, inv, sq < S);
         }
     }
 }

@@ -65,8 +65,10 @@ def test_dma_route_against_fp64(lib, dt, case):
 
 @pytest.mark.parametrize("dt", [0, 1])
 def test_old_route_against_new_route(lib, dt):
-    """One input through attn_route 1 (attention16_kernel) and 2 (the DMA kernel): both within the bound; the P·V contraction order differs
-    between the two (k-slots of the transposed read), so the last bit of a 16-bit output may."""
+    """One input through attn_route 1 (attention16_kernel) and 2 (the DMA kernel): both within the bound, and within one unit in the last
+    place of each other.  Observed on MI355X at this shape, fp16 and bf16: max |route 1 - route 2| = 0, not one of the 453,888 output words
+    differs (profiles/attention_shared_block.md) — the transposed read delivers P·V's contraction values in the k-slots the V^T image has
+    them in, and the limit, the softmax, the P rounding and the store are one piece of code for both (csrc/attn16_block.h)."""
     items, S, heads = 3, 197, 12
     qkv = _input(items, S, heads, dt, 77)
     ref = _attn_ref64(qkv)
@@ -86,8 +88,9 @@ def test_old_route_against_new_route(lib, dt):
           f"new err {(out[2] - ref).abs().max().item():.3e}, bound {tol:.3e}")
     for route in (1, 2):
         assert (out[route] - ref).abs().max().item() <= tol, route
-    # The two kernels differ in the fp32 summation order of P·V alone (relative 1e-7), which can move an output across a rounding boundary
-    # of its 16-bit type: one unit in the last place of that output, at most the unit of the largest one (2^-10 / 2^-7 relative).
+    # Bit-equality is what is observed, not what is asserted: how the matrix cores order the fp32 sums of a 32-key and of a 16-key product is
+    # not documented, and a difference there (relative 1e-7) could move an output across a rounding boundary of its 16-bit type: one unit in
+    # the last place of that output, at most the unit of the largest one (2^-10 / 2^-7 relative).
     ulp = {0: 2.0 ** -10, 1: 2.0 ** -7}[dt]
     assert diff <= ulp * max(out[1].abs().max().item(), out[2].abs().max().item())
 
@@ -119,9 +122,10 @@ def test_guard_arena(lib, dt):
 
 
 def test_buffer_reuse_over_more_workgroups_than_the_chip_holds(lib):
-    """96 items x 12 heads: every CU runs several workgroups one after the other and every workgroup rotates its three LDS buffers over
-    its heads.  Twice: bit-equal outputs (a piece that lands after its first read, or a buffer overwritten while a slow wave still reads it,
-    shows as a run-to-run difference); first, middle and last item against fp32 on the device."""
+    """96 items x 12 heads = 1,152 workgroups of one head each, three to a CU: every CU runs several one after the other, and a workgroup's
+    single K / V image is written by LDS-DMA into LDS the previous workgroup has just left.  Twice: bit-equal outputs (a piece that is read
+    before it has landed, or a Q register taken before its load, shows as a run-to-run difference); first, middle and last item against
+    fp32 on the device."""
     items, S, heads = 96, 197, 12
     D = heads * 64
     g = torch.Generator(device="cuda").manual_seed(9)

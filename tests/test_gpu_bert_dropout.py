@@ -45,7 +45,8 @@ def _attn_ref(qkv, key_bias, items, S, heads, keep):
 
 
 ATTN_CASES = [(3, 1, 2, False, 0.1), (2, 7, 12, True, 0.1), (5, 30, 12, True, 0.1), (2, 16, 2, False, 0.1), (2, 17, 2, True, 0.1),
-              (2, 33, 3, True, 0.1), (2, 64, 2, False, 0.1), (1, 100, 2, True, 0.1), (1, 224, 2, False, 0.1), (5, 30, 12, True, 0.5)]
+              (2, 33, 3, True, 0.1), (2, 64, 2, False, 0.1), (1, 100, 2, True, 0.1), (1, 224, 2, False, 0.1), (5, 30, 12, True, 0.5),
+              (1, 200, 2, True, 0.1)]          # 13 key tiles: the 16-key tail product (the key bias keeps the p = 0 comparison on attention16_kernel)
 
 
 @pytest.mark.parametrize("dt", [0, 1])

@@ -1,7 +1,7 @@
 """CPU-side code-object screen of the LDS-DMA ViT attention kernel (csrc/attn16_dma.hip), in the style of test_isa_screen.py: hipcc
-cross-compiles gfx950, no GPU needed.  The kernel is designed for two workgroups of four waves per CU (79,872 B of LDS each), i.e. two
-waves per SIMD: at most 256 VGPRs, no scratch, no spilled VGPR — a scratch reload is followed by `s_waitcnt vmcnt(0)`, which would
-drain the LDS-DMA pieces of the next head in the middle of a block."""
+cross-compiles gfx950, no GPU needed.  The kernel is designed for three workgroups of four waves per CU (one head per workgroup, K and V
+single-buffered: 53,248 B of LDS each), i.e. three waves per SIMD: at most 168 VGPRs, no scratch, no spilled VGPR — a scratch reload is
+followed by `s_waitcnt vmcnt(0)`, which would drain the LDS-DMA pieces and the Q loads in flight in the middle of a block."""
 import os
 import re
 
