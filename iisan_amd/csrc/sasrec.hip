@@ -268,7 +268,9 @@ int check_cfg(const iisan_sasrec_cfg* cfg, int64_t B) {
     IISAN_CHECK_SHAPE(B > 0, "sasrec: empty batch");
     IISAN_CHECK_SHAPE(cfg->emb % 64 == 0 && cfg->emb <= MAXE, "sasrec: d_model %d must be a multiple of 64 and <= %d", cfg->emb, MAXE);
     IISAN_CHECK_SHAPE(cfg->heads > 0 && cfg->emb % cfg->heads == 0, "sasrec: heads %d does not divide d_model %d", cfg->heads, cfg->emb);
-    IISAN_CHECK_SHAPE(cfg->seq >= 1 && cfg->seq <= 32 && cfg->seq * cfg->heads <= 64, "sasrec: seq %d x heads %d unsupported", cfg->seq, cfg->heads);
+    // (seq x heads is not limited: the per-operator attention kernels run one workgroup per (sequence, head) over S <= 32 positions of
+    //  dh <= 64 columns whatever the head count; the one-launch kernels have their own rule, sasrec_fused_shape_ok)
+    IISAN_CHECK_SHAPE(cfg->seq >= 1 && cfg->seq <= 32, "sasrec: seq %d unsupported (1 .. 32)", cfg->seq);
     IISAN_CHECK_SHAPE(cfg->emb / cfg->heads <= 64, "sasrec: head width %d > 64 unsupported", cfg->emb / cfg->heads);
     IISAN_CHECK_SHAPE(cfg->blocks >= 1 && cfg->blocks <= 8, "sasrec: %d blocks unsupported", cfg->blocks);
     IISAN_CHECK_SHAPE(cfg->dropout >= 0.f && cfg->dropout < 1.f, "sasrec: dropout %.3f out of range", cfg->dropout);

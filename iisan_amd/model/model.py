@@ -31,6 +31,10 @@ class _SideNetBase(nn.Module):
             raise NotImplementedError(f"modality {args.modality!r}: the IISAN wrapper serves 'intra_inter' and 'inter'")
         if self.side_bert_adapter_num_list != self.side_cv_adapter_num_list:
             raise NotImplementedError("different tap lists per tower are the Versa variant (Code_Cached_Asym)")
+        if args.cv_adapter_down_size != args.bert_adapter_down_size:
+            # the reference builds the cv adapters with one width and the text / mm adapters with the other (model.py:178-189);
+            # iisan_side_cfg has ONE `down`, so the kernels would index the cv adapters by the wrong shape
+            raise NotImplementedError("the HIP side network uses one bottleneck width for all towers")
         n = len(self.side_cv_adapter_num_list)
         # model.py:178-205: the intra-modal towers (cv, text) exist with "intra" in the modality, the inter-modal tower (mm)
         # with "inter".  With modality "inter" only the mm tower has parameters (and state-dict keys); the fused HIP side

@@ -5,6 +5,7 @@ library.  There is no fallback: a missing library raises at first use (`_lib.loa
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import List, Sequence
 
 import torch
@@ -144,6 +145,59 @@ def versa_param_order(n_cv: int, n_text: int, align: bool) -> List[str]:
     return names
 
 
+def _side_param_slots(cfg):
+    """(label, shape) of every slot of the side network's parameter table, in ABI order (include/iisan_hip.h)."""
+    return _side_slots(bool(cfg.versa), cfg.n_side, cfg.n_side_text, cfg.dim_cv, cfg.dim_text, cfg.down, cfg.emb)
+
+
+@functools.lru_cache(maxsize=64)          # (a training step asks for the same table every time)
+def _side_slots(versa, n_cv, n_t, Dc, Dt, r, E):
+    if versa:
+        d = min(Dc, Dt)
+        n_mm = min(n_cv, n_t)
+    else:
+        Dt = d = Dc
+        n_t = n_mm = n_cv
+    towers = (("cv", n_cv, Dc), ("bert", n_t, Dt), ("mm", n_mm, d))
+    slots = []
+    for tower, n, D in towers:
+        for k in range(n):
+            p = f"{tower}_adapter_list.{k}."
+            slots += [(p + "fc_down.weight", (r, D)), (p + "fc_down.bias", (r,)), (p + "fc_up.weight", (D, r)), (p + "fc_up.bias", (D,))]
+    for g, n in (("cv", n_cv), ("text", n_t), ("mm", n_mm)):
+        slots += [(f"side_gate_params_{g}.{k}", (1,)) for k in range(n)]
+    if versa:
+        if Dc != Dt:                                   # dim-align: the wider modality's tap is projected to the narrower width
+            for i in range(n_mm):
+                slots += [(f"down_project_list.{i}.weight", (d, max(Dc, Dt))), (f"down_project_list.{i}.bias", (d,))]
+        slots += [("fc_cv.weight", (E, Dc)), ("fc_cv.bias", (E,)), ("fc_bert.weight", (E, Dt)), ("fc_bert.bias", (E,)),
+                  ("fc_mm.weight", (d, d)), ("fc_mm.bias", (d,)), ("cv_pre_fc.weight", (E, E)), ("cv_pre_fc.bias", (E,)),
+                  ("bert_pre_fc.weight", (E, E)), ("bert_pre_fc.bias", (E,))]
+    else:
+        slots += [("fc_cv.weight", (d, d)), ("fc_cv.bias", (d,)), ("fc_bert.weight", (d, d)), ("fc_bert.bias", (d,)),
+                  ("fc_mm.weight", (d, d)), ("fc_mm.bias", (d,)), ("head_cv.weight", (E, d)), ("head_cv.bias", (E,)),
+                  ("head_text.weight", (E, d)), ("head_text.bias", (E,))]
+    slots += [("fc_mm_down.weight", (E, d)), ("fc_mm_down.bias", (E,))]
+    return tuple(slots)
+
+
+def side_param_shapes(cfg) -> List[tuple]:
+    """The tensor shape the library ASSUMES for every slot of the side network's parameter table, in ABI order
+    (`side_param_order` / `versa_param_order`; gate slots are `(1,)`, Versa's dim-align pairs included).  Pure host arithmetic
+    on `cfg`: the kernels receive bare pointers and index them by these shapes, so `SideNetFn` refuses any other tensor."""
+    return [shape for _, shape in _side_param_slots(cfg)]
+
+
+def _check_shapes(what: str, slots, params):
+    """IisanHipError naming the first slot whose tensor is not the shape the kernels will index it by."""
+    if len(slots) != len(params):
+        raise _lib.IisanHipError(f"{what} expects {len(slots)} parameter tensors, got {len(params)}")
+    for i, ((label, shape), p) in enumerate(zip(slots, params)):
+        if p.shape != shape and not (callable(shape) and shape(tuple(p.shape))):       # (a callable: a rule instead of one shape)
+            want = shape if not callable(shape) else shape.__doc__
+            raise _lib.IisanHipError(f"{what}: parameter slot {i} ({label}) has shape {tuple(p.shape)}, the kernels assume {want}")
+
+
 class SideNetFn(torch.autograd.Function):
     """(taps_cv [M,Lc,D], taps_text [M,Lt,D], *params) -> item3 [M, 3*emb] = cat[cv, text, mm]."""
 
@@ -159,6 +213,12 @@ class SideNetFn(torch.autograd.Function):
         if need != len(params):
             raise _lib.IisanHipError(f"side network expects {need} parameter tensors, got {len(params)}: "
                                      f"{lib.iisan_last_error().decode()}")
+        # the kernels index bare pointers by the shapes `cfg` implies: a tensor of another shape would be read and `+=`-written out
+        # of bounds, so it is refused here — before the workspace query and before any launch
+        _check_shapes("side network", _side_param_slots(cfg), params)
+        for name, t, D, stride in (("taps_cv", taps_cv, cfg.dim_cv, cfg.tap_stride_cv), ("taps_text", taps_text, cfg.dim_text, cfg.tap_stride_text)):
+            if t.dim() != 3 or t.shape[0] != M or t.shape[1] != stride or t.shape[2] != D:
+                raise _lib.IisanHipError(f"side network: {name} has shape {tuple(t.shape)}, the kernels assume ({M}, {stride}, {D})")
         item3 = torch.empty((M, 3 * cfg.emb), dtype=torch.float32, device=taps_cv.device)
         ws = torch.empty(lib.iisan_side_net_ws_bytes(C.byref(cfg), M), dtype=torch.uint8, device=taps_cv.device)
         tab = _ptr_table(params)
@@ -237,6 +297,27 @@ def make_sasrec_cfg(seq: int, emb: int, heads: int, blocks: int, dropout: float 
     return cfg
 
 
+def _sasrec_param_slots(cfg):
+    """(label, shape) per slot of the SASRec parameter table (`sasrec_param_order`).  The position table may hold more rows than
+    `seq` (the kernels read, and write the gradient of, its first `seq` rows)."""
+    return _sasrec_slots(cfg.seq, cfg.emb, cfg.blocks)
+
+
+@functools.lru_cache(maxsize=64)
+def _sasrec_slots(S, E, blocks):
+
+    def pos_ok(shape):
+        return len(shape) == 2 and shape[0] >= S and shape[1] == E
+    pos_ok.__doc__ = f"(>= {S}, {E})"
+    slots = [("position_embedding.weight", pos_ok), ("layer_norm.weight", (E,)), ("layer_norm.bias", (E,))]
+    for l in range(blocks):
+        a, f = f"transformer_blocks.{l}.multi_head_attention.", f"transformer_blocks.{l}.feed_forward."
+        slots += [(a + "w_Q.weight", (E, E)), (a + "w_K.weight", (E, E)), (a + "w_V.weight", (E, E)), (a + "fc.weight", (E, E)),
+                  (a + "layer_norm.weight", (E,)), (a + "layer_norm.bias", (E,)), (f + "w_1.weight", (4 * E, E)), (f + "w_1.bias", (4 * E,)),
+                  (f + "w_2.weight", (E, 4 * E)), (f + "w_2.bias", (E,)), (f + "layer_norm.weight", (E,)), (f + "layer_norm.bias", (E,))]
+    return tuple(slots)
+
+
 class SasrecFn(torch.autograd.Function):
     """(x [B,S,E], log_mask [B,S], *params) -> [B,S,E]."""
 
@@ -248,7 +329,12 @@ class SasrecFn(torch.autograd.Function):
         ctx.orig = list(params)
         params = [_f32c(p.detach()) for p in params]
         B = x.shape[0]
-        assert x.shape[1] == cfg.seq and x.shape[2] == cfg.emb, (x.shape, cfg.seq, cfg.emb)
+        # bare pointers again: every tensor must be what `cfg` implies before the workspace query and the first launch
+        if x.dim() != 3 or x.shape[1] != cfg.seq or x.shape[2] != cfg.emb:
+            raise _lib.IisanHipError(f"sasrec: x has shape {tuple(x.shape)}, the kernels assume (B, {cfg.seq}, {cfg.emb})")
+        if tuple(log_mask.shape) != (B, cfg.seq):
+            raise _lib.IisanHipError(f"sasrec: log_mask has shape {tuple(log_mask.shape)}, the kernels assume ({B}, {cfg.seq})")
+        _check_shapes("sasrec", _sasrec_param_slots(cfg), params)
         y = torch.empty_like(x)
         ws = torch.empty(lib.iisan_sasrec_ws_bytes(C.byref(cfg), B), dtype=torch.uint8, device=x.device)
         _lib.check(lib.iisan_sasrec_fwd(C.byref(cfg), x.data_ptr(), log_mask.data_ptr(), B, _ptr_table(params),

@@ -242,7 +242,8 @@ int iisan_linear_bwd(const float* x, const float* w, const float* dy, float* dx,
  * ffn layer_norm.{weight,bias}.   x: [B,S,E]; log_mask: [B,S]; y: [B,S,E].
  * With emb == 64, seq <= 16 and 1, 2 or 4 heads (the reference configuration is 64 / 10 / 2) each direction is ONE launch
  * (+ a fixed-order reducer of per-workgroup parameter-gradient partial sums in the backward: bit-reproducible, no atomics);
- * other shapes take one launch per operator.  Either way the forward keeps every intermediate the backward needs in `ws`
+ * other shapes (seq <= 32, emb a multiple of 64 up to 256, emb / heads <= 64, 1 .. 8 blocks; anything else is IISAN_EBADSHAPE)
+ * take one launch per operator.  Either way the forward keeps every intermediate the backward needs in `ws`
  * (same slots), and gradients ACCUMULATE (+=) into the caller's tensors.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct {

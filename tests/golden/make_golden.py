@@ -9,6 +9,8 @@ inputs from `iisan_amd.synth` through, and stores INPUT CHECKSUMS + EXPECTED OUT
   encoders_full.npz   HF ViT-B / BERT-B (repo config.json shapes, eager attention) -> CLS taps [4,13,768] x2
   sidenet_full.npz    Cached IISANAdaptedMModel + ModelMM at full width on synthetic taps: cv/text/mm, score,
                       prec, loss, gradients (small tensors whole, large ones strided), one Adam step; variants
+  sidenet_hparams.npz the same model at NON-default launcher arguments (bottleneck width, max_seq_len / heads / blocks,
+                      side-adapter lists): cv/text/mm, score, prec, loss, gradients per variant
   e2e_small.npz       Uncached ModelMM end to end with 2-layer ViT/BERT (hidden 768): loss + gradients
   e2e_bs8.npz         the same on 8 sequences (88 item slots)
   e2e_inter.npz       the same as e2e_small with --modality inter (mm tower only)
@@ -90,11 +92,11 @@ def hf_models(vcfg: weights.VitConfig, bcfg: weights.BertConfig, vw, bw):
     return vit.eval(), bert.eval()
 
 
-def pack_grads(named_grads):
+def pack_grads(named_grads, sample=None):
     out = {}
     for n, g in named_grads.items():
         g = g.detach().reshape(-1)
-        out["g/" + n] = (g if g.numel() <= GRAD_FULL_MAX else g[::GRAD_STRIDE]).numpy().copy()
+        out["g/" + n] = (sample(g) if sample else (g if g.numel() <= GRAD_FULL_MAX else g[::GRAD_STRIDE])).numpy().copy()
         out["gn/" + n] = np.array([float(g.double().norm()), float(g.double().sum())])
     return out
 
@@ -204,6 +206,69 @@ def gen_sidenet_full():
                                              if nm[n].numel() > GRAD_FULL_MAX else (nm[n].detach() - before[n]).reshape(-1)).numpy()
                         for n in names})
     np.savez_compressed(os.path.join(HERE, "sidenet_full.npz"), **out)
+
+
+ALL_LAYERS = ",".join(str(i) for i in range(12))
+HPARAM_ITEMS = 100
+
+
+def hparam_sample(g):
+    """Coarser sampling than sidenet_full's (seven variants in one file under 1 MiB): tensors up to 256 elements whole, up to 5000
+    (the 768-wide biases, the 64 x 64 SASRec matrices) every 37th element, larger ones every 389th; norm and sum of every tensor whole."""
+    return g if g.numel() <= 256 else g[::37] if g.numel() <= 5000 else g[::389]
+
+
+HPARAM_VARIANTS = {
+    # name: (launcher arguments off their defaults, sequence lengths incl. the target)
+    "down32": (dict(cv_adapter_down_size=32, bert_adapter_down_size=32), [4, 11, 7]),
+    "down128_gelu": (dict(cv_adapter_down_size=128, bert_adapter_down_size=128, adapter_activation="GELU"), [4, 11, 7]),
+    "s20_l3_h4": (dict(max_seq_len=20, transformer_block=3, num_attention_heads=4), [21, 3, 12, 16, 17]),
+    "s32_l1_h1": (dict(max_seq_len=32, transformer_block=1, num_attention_heads=1), [33, 2, 17]),
+    "s5_h1": (dict(max_seq_len=5, num_attention_heads=1), [6, 2, 4]),
+    "layers12": (dict(side_adapter_vit_list=ALL_LAYERS, side_adapter_bert_list=ALL_LAYERS), [4, 11, 7]),
+    "one_layer_rmfirst": (dict(side_adapter_vit_list="11", side_adapter_bert_list="11", remove_first="TRUE"), [4, 11, 7]),
+}
+
+
+def gen_sidenet_hparams():
+    """The Cached reference model at launcher arguments other than the defaults every other fixture uses.  Per variant: tensor
+    shapes from the PRODUCT's module tree (the reference must accept that state dict without a missing or unexpected key), values
+    from `weights.fill_params_seeded`, taps from `synth.cached_taps`."""
+    from iisan_amd import factory
+    out = {}
+    for vname, (kw, lengths) in HPARAM_VARIANTS.items():
+        args = ref_args(**kw)
+        bs, S = len(lengths), args.max_seq_len
+        b = synth.scientific_batch(bs=bs, seed=79, seq_len=S, lengths=lengths, dup_items=True, res=2, words=2, item_num=HPARAM_ITEMS)
+        taps_cv = synth.cached_taps(b.ids, 12, 768, seed=25)
+        taps_tx = synth.cached_taps(b.ids, 12, 768, seed=26)
+        product = factory.build_model(factory.make_args(**kw), HPARAM_ITEMS, b.pop_prob, cached=True, device="cpu")
+        shapes = {n: tuple(p.shape) for n, p in product.named_parameters() if p.requires_grad}
+        P = weights.fill_params_seeded(shapes, seed=557)
+        model = build_cached_ref(P, args, HPARAM_ITEMS, b.pop_prob)
+        ref_names = {n for n, _ in model.named_parameters()
+                     if n.startswith("mm_encoder.") or n.startswith("user_encoder.") or n.startswith("com_dense.")}
+        assert ref_names == set(P), (sorted(ref_names - set(P))[:4], sorted(set(P) - ref_names)[:4])
+        with torch.no_grad():
+            cv, (text, mm) = model.mm_encoder(taps_cv, taps_tx)
+            score = model.com_dense(torch.cat([cv, text, mm], 1))
+            prec = model.user_encoder(score.view(bs, S + 1, 64)[:, :-1], b.log_mask, "cpu").reshape(-1, 64)
+        loss, grads = run_ref_loss(model, b.ids, taps_cv.view(bs, S + 1, 13, 768), taps_tx.view(bs, S + 1, 13, 768), b.log_mask, set(P))
+        assert set(grads) == set(P)
+        pre = vname + "/"
+        out.update({pre + "ids": b.ids.numpy(), pre + "log_mask": b.log_mask.numpy(), pre + "pop": b.pop_prob.numpy(),
+                    pre + "taps_sha": np.array([sha(taps_cv), sha(taps_tx)]),
+                    pre + "names_sha": np.array(hashlib.sha256("\n".join(sorted(P)).encode()).hexdigest()[:16]),
+                    pre + "cv": cv.numpy(), pre + "text": text.numpy(), pre + "mm": mm.numpy(),
+                    pre + "score": score.numpy(), pre + "prec": prec.numpy(), pre + "loss": loss.numpy()})
+        # sidenet_full's "g/<name>" / "gn/<name>" pairs, stored as ONE array each in sorted-name order (an .npz member costs ~300 bytes of
+        # zip headers: 2,100 members were half of the file): g = the samples back to back, g_end = where each tensor's end, gn = [n, 2]
+        pk = pack_grads(grads, hparam_sample)
+        out.update({pre + "g": np.concatenate([pk["g/" + n] for n in sorted(P)]),
+                    pre + "g_end": np.cumsum([pk["g/" + n].size for n in sorted(P)]),
+                    pre + "gn": np.stack([pk["gn/" + n] for n in sorted(P)])})
+        print(f"sidenet_hparams[{vname}]: loss {loss.item():.6f}, {len(P)} tensors")
+    np.savez_compressed(os.path.join(HERE, "sidenet_hparams.npz"), **out)
 
 
 def group_rule():
@@ -395,7 +460,7 @@ def gen_e2e_inter():
     gen_e2e_small("e2e_inter", write_groups=False, modality="inter")
 
 
-GENS = dict(versa=gen_versa, encoders_full=gen_encoders_full, sidenet_full=gen_sidenet_full, e2e_small=gen_e2e_small,
+GENS = dict(versa=gen_versa, encoders_full=gen_encoders_full, sidenet_full=gen_sidenet_full, sidenet_hparams=gen_sidenet_hparams, e2e_small=gen_e2e_small,
             e2e_bs8=gen_e2e_bs8, e2e_inter=gen_e2e_inter, eval=gen_eval)
 
 if __name__ == "__main__":

@@ -28,6 +28,12 @@ def sample_like_golden(t: torch.Tensor) -> np.ndarray:
     return (g if g.numel() <= GRAD_FULL_MAX else g[::GRAD_STRIDE]).numpy()
 
 
+def sample_like_hparams(t: torch.Tensor) -> np.ndarray:
+    """`hparam_sample` of tests/golden/make_golden.py (sidenet_hparams.npz)."""
+    g = t.detach().cpu().reshape(-1)
+    return (g if g.numel() <= 256 else g[::37] if g.numel() <= 5000 else g[::389]).numpy()
+
+
 def encoders_full_inputs():
     z = load("encoders_full.npz")
     vw = weights.make_vit_weights(weights.VIT_BASE, seed=int(z["vit_seed"]))
@@ -50,6 +56,56 @@ def sidenet_full_inputs(variant: str = "default"):
     P = weights.make_trainable_params(seed=99, cached=True, n_side=6 if variant == "rmfirst" else 7)
     kw = dict(default={}, gelu=dict(activation="GELU"), rmfirst=dict(remove_first=True))[variant]
     return z, b, taps_cv, taps_tx, P, kw
+
+
+ALL_LAYERS = ",".join(str(i) for i in range(12))
+HPARAM_ITEMS = 100
+HPARAM_VARIANTS = {
+    # name: (launcher arguments off their defaults, sequence lengths incl. the target) - as in tests/golden/make_golden.py
+    "down32": (dict(cv_adapter_down_size=32, bert_adapter_down_size=32), [4, 11, 7]),
+    "down128_gelu": (dict(cv_adapter_down_size=128, bert_adapter_down_size=128, adapter_activation="GELU"), [4, 11, 7]),
+    "s20_l3_h4": (dict(max_seq_len=20, transformer_block=3, num_attention_heads=4), [21, 3, 12, 16, 17]),
+    "s32_l1_h1": (dict(max_seq_len=32, transformer_block=1, num_attention_heads=1), [33, 2, 17]),
+    "s5_h1": (dict(max_seq_len=5, num_attention_heads=1), [6, 2, 4]),
+    "layers12": (dict(side_adapter_vit_list=ALL_LAYERS, side_adapter_bert_list=ALL_LAYERS), [4, 11, 7]),
+    "one_layer_rmfirst": (dict(side_adapter_vit_list="11", side_adapter_bert_list="11", remove_first="TRUE"), [4, 11, 7]),
+}
+
+
+def sidenet_hparams_inputs(variant: str):
+    """Batch, taps, seeded parameters (shapes from the product's module tree) and the oracle's keyword arguments of one
+    `sidenet_hparams.npz` variant."""
+    import helpers
+    z = load("sidenet_hparams.npz")
+    kw, lengths = HPARAM_VARIANTS[variant]
+    args = helpers.make_args(**kw)
+    pre = variant + "/"
+    b = synth.scientific_batch(bs=len(lengths), seed=79, seq_len=args.max_seq_len, lengths=lengths, dup_items=True, res=2, words=2,
+                               item_num=HPARAM_ITEMS)
+    assert np.array_equal(b.ids.numpy(), z[pre + "ids"]) and np.array_equal(b.pop_prob.numpy(), z[pre + "pop"])
+    assert np.array_equal(b.log_mask.numpy(), z[pre + "log_mask"])
+    taps_cv = synth.cached_taps(b.ids, 12, 768, seed=25)
+    taps_tx = synth.cached_taps(b.ids, 12, 768, seed=26)
+    assert sha(taps_cv) == str(z[pre + "taps_sha"][0]) and sha(taps_tx) == str(z[pre + "taps_sha"][1])
+    model = helpers.build_model(args, HPARAM_ITEMS, b.pop_prob, cached=True, device="cpu")
+    shapes = {n: tuple(p.shape) for n, p in model.named_parameters() if p.requires_grad}
+    assert hashlib.sha256("\n".join(sorted(shapes)).encode()).hexdigest()[:16] == str(z[pre + "names_sha"]), \
+        "the module tree differs from the reference's"
+    P = weights.fill_params_seeded(shapes, seed=557)
+    rm = args.remove_first == "TRUE"
+    okw = dict(heads=args.num_attention_heads, n_layers=args.transformer_block, activation=args.adapter_activation, remove_first=rm,
+               cv_head="mm_encoder.cv_pre_fc.", text_head="mm_encoder.bert_pre_fc.")
+    layers = [int(i) + 1 for i in args.side_adapter_vit_list.split(",")]
+    return z, b, taps_cv, taps_tx, P, (layers if rm else [0] + layers), okw
+
+
+def hparams_grads(z, variant: str, names):
+    """{name: (sampled gradient, [norm, sum])} of one `sidenet_hparams.npz` variant (stored back to back in sorted-name order)."""
+    pre = variant + "/"
+    names = sorted(names)
+    g, end, gn = z[pre + "g"], z[pre + "g_end"], z[pre + "gn"]
+    assert len(names) == len(end) == len(gn)
+    return {n: (g[(end[i - 1] if i else 0):end[i]], gn[i]) for i, n in enumerate(names)}
 
 
 E2E_VIT = weights.VitConfig(hidden=768, layers=2, heads=12, mlp=512, image=32, patch=16)

@@ -4,6 +4,7 @@ import json
 import os
 
 import numpy as np
+import pytest
 import torch
 
 import golden_io as gio
@@ -57,6 +58,83 @@ def test_abi_parameter_tables_resolve():
     te = dict(model.user_encoder.transformer_encoder.named_parameters())
     order = ops.sasrec_param_order(2)
     assert len(order) == 27 and set(order) == set(te)
+
+
+@pytest.mark.parametrize("cached", [False, True])
+def test_unequal_adapter_widths_are_refused_at_construction(cached):
+    """The reference builds the cv adapters with `cv_adapter_down_size` and the text / mm adapters with `bert_adapter_down_size`
+    (`model.py:178-189`); `iisan_side_cfg` has ONE `down`, so a model with two widths would hand the kernels `[16, 768]` tensors
+    they index as `[64, 768]`.  Both IISAN wrappers refuse it like the Versa wrapper does; equal widths of any value build."""
+    args = helpers.make_args(cv_adapter_down_size=16, bert_adapter_down_size=64)
+    with pytest.raises(NotImplementedError, match="one bottleneck width for all towers"):
+        helpers.build_model(args, 100, torch.ones(101), cached=cached, device="cpu")
+    model = helpers.build_model(helpers.make_args(cv_adapter_down_size=16, bert_adapter_down_size=16), 100, torch.ones(101),
+                                cached=cached, device="cpu")
+    assert model.mm_encoder.cv_adapter_list[0].fc_down.out_features == 16
+
+
+def _iisan_side_cfg(enc, n_taps=13):
+    """The `iisan_side_cfg` `_SideNetBase._side` builds for taps [M, n_taps, 768] (Cached: the layer list indexes the tap axis)."""
+    return ops.make_side_cfg(enc.n_side, 768, enc.mm_adapter_list[0].fc_down.out_features, enc.fc_mm_down.out_features, enc.gated,
+                             enc.mm_adapter_list[0].gelu, enc.remove_first, n_taps, n_taps, list(enc.side_cv_adapter_num_list), 0)
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(remove_first="TRUE"), dict(cv_adapter_down_size=32, bert_adapter_down_size=32),
+                                dict(fusion_method="sum"), dict(modality="inter")], ids=["default", "rmfirst", "down32", "sum", "inter"])
+@pytest.mark.parametrize("cached", [False, True])
+def test_side_param_shapes_equal_the_module_tree(kw, cached):
+    """`ops.side_param_shapes(cfg)` - what `SideNetFn` holds every tensor to before a launch - is the shape of every tensor the
+    wrapper hands over, in ABI order, placeholders (absent gates / towers) included."""
+    model = helpers.build_model(helpers.make_args(**kw), 100, torch.ones(101), cached=cached, device="cpu")
+    enc = model.mm_encoder
+    got = [tuple(t.shape) for t in enc._abi_params(torch.device("cpu"))]
+    want = ops.side_param_shapes(_iisan_side_cfg(enc))
+    assert len(want) == 15 * enc.n_side + 12
+    assert got == want, [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w][:4]
+    r = 32 if "cv_adapter_down_size" in kw else 64
+    assert want[0] == (r, 768) and want[2] == (768, r) and want[12 * enc.n_side] == (1,) and want[-2] == (64, 768)
+
+
+@pytest.mark.parametrize("variant", sorted(gio.VERSA_VARIANTS))
+def test_side_param_shapes_equal_the_versa_module_tree(variant):
+    """The same for the Versa wrapper: towers of different depth and width, the dim-align pairs where the widths differ."""
+    Di, Dt, Lc, Lt, vlist, blist, extra = gio.VERSA_VARIANTS[variant]
+    args = helpers.make_args(text_embedding_dim=Dt, image_embedding_dim=Di, side_adapter_vit_list=vlist, side_adapter_bert_list=blist,
+                             image_layers=Lc - 1, text_layers=Lt - 1, **extra)
+    enc = helpers.build_model(args, 50, torch.ones(51), cached="versa", device="cpu").mm_encoder
+    cfg = ops.make_versa_cfg(Di, Dt, args.cv_adapter_down_size, args.embedding_dim, enc.gated, args.adapter_activation == "GELU",
+                             enc.remove_first, Lc, Lt, enc.side_cv_adapter_num_list, enc.side_bert_adapter_num_list)
+    got = [tuple(t.shape) for t in enc._abi_params(torch.device("cpu"))]
+    want = ops.side_param_shapes(cfg)
+    n_mm = min(enc.n_cv, enc.n_t)
+    assert len(want) == 5 * (enc.n_cv + enc.n_t + n_mm) + (2 * n_mm if Di != Dt else 0) + 12
+    assert got == want, [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w][:4]
+
+
+def test_mis_shaped_parameter_tables_are_named_before_anything_runs():
+    """`ops._check_shapes` (the comparison `SideNetFn.forward` / `SasrecFn.forward` make before the workspace query): the first
+    offending slot is named with both shapes; the SASRec position table may be longer than `seq`, never shorter or narrower."""
+    from iisan_amd import _lib
+    model = helpers.build_model(helpers.make_args(), 100, torch.ones(101), cached=True, device="cpu")
+    enc = model.mm_encoder
+    cfg = _iisan_side_cfg(enc)
+    params = enc._abi_params(torch.device("cpu"))
+    ops._check_shapes("side network", ops._side_param_slots(cfg), params)
+    bad = list(params)
+    bad[4] = torch.zeros(16, 768)                               # cv_adapter_list.1.fc_down.weight
+    with pytest.raises(_lib.IisanHipError, match=r"slot 4 \(cv_adapter_list.1.fc_down.weight\) has shape \(16, 768\).*\(64, 768\)"):
+        ops._check_shapes("side network", ops._side_param_slots(cfg), bad)
+    with pytest.raises(_lib.IisanHipError, match="expects 117 parameter tensors, got 116"):
+        ops._check_shapes("side network", ops._side_param_slots(cfg), params[:-1])
+    te = model.user_encoder.transformer_encoder
+    sp = te.abi_params()
+    for seq in (10, 7):                                         # a window shorter than the table is served
+        ops._check_shapes("sasrec", ops._sasrec_param_slots(ops.make_sasrec_cfg(seq, 64, 2, 2)), sp)
+    with pytest.raises(_lib.IisanHipError, match=r"slot 0 \(position_embedding.weight\) has shape \(10, 64\).*\(>= 11, 64\)"):
+        ops._check_shapes("sasrec", ops._sasrec_param_slots(ops.make_sasrec_cfg(11, 64, 2, 2)), sp)
+    with pytest.raises(_lib.IisanHipError, match=r"w_1.weight\) has shape \(256, 64\).*\(512, 128\)"):
+        ops._check_shapes("sasrec", ops._sasrec_param_slots(ops.make_sasrec_cfg(10, 128, 2, 2)), [torch.zeros(10, 128)] + [torch.zeros(128)] * 2
+                          + [torch.zeros(128, 128)] * 4 + [torch.zeros(128)] * 2 + sp[9:])
 
 
 def test_flat_trainer_storage_is_contiguous_by_group():

@@ -68,6 +68,29 @@ def test_sidenet_sasrec_loss_and_grads_match_reference(variant):
         assert abs(norm - gn) <= 2e-4 * gn + 1e-7, what
 
 
+@pytest.mark.parametrize("variant", list(gio.HPARAM_VARIANTS))
+def test_sidenet_at_non_default_hyperparameters_matches_reference(variant):
+    """The oracle against the real Cached reference at launcher arguments off their defaults - bottleneck 32 and 128 (GELU), 20 / 32 / 5
+    positions with 4 / 1 / 1 heads and 3 / 1 / 2 blocks, all twelve layers (13 SANBs), one layer with `remove_first`
+    (`tests/golden/sidenet_hparams.npz`): the yardstick of `tests/test_gpu_hparams.py` is valid where those tests use it.  Bounds of
+    `test_sidenet_sasrec_loss_and_grads_match_reference`."""
+    z, b, taps_cv, taps_tx, P, layers, okw = gio.sidenet_hparams_inputs(variant)
+    P = {k: v.clone().requires_grad_(True) for k, v in P.items()}
+    loss, aux = O.model_loss_from_taps(b.ids, taps_cv, taps_tx, b.log_mask, b.pop_prob, P, layers, **okw)
+    pre = variant + "/"
+    for k in ("cv", "text", "mm", "score", "prec"):
+        _close(aux[k].detach(), z[pre + k], 1e-5, 1e-5, f"{variant}:{k}")
+    _close(loss.detach(), z[pre + "loss"], 1e-5, 0, f"{variant}:loss")
+    loss.backward()
+    ref = gio.hparams_grads(z, variant, P)
+    for ns, what in _grads_by_tower(P):
+        g = np.concatenate([gio.sample_like_hparams(P[n].grad) for n in ns])
+        _close(g, np.concatenate([ref[n][0] for n in ns]), 2e-4, 1e-7, f"{variant}:grad {what}")
+        gn = float(np.sqrt(sum(ref[n][1][0] ** 2 for n in ns)))
+        norm = float(torch.cat([P[n].grad.double().reshape(-1) for n in ns]).norm())
+        assert abs(norm - gn) <= 2e-4 * gn + 1e-7, what
+
+
 def test_adam_step_matches_reference():
     """The first Adam step of the five groups on the reference's own gradients (stored at the same elements as its step): a
     first step is lr * g / (|g| + eps), which turns the last fp32 bits of a gradient near eps into 1e-3 of lr, so the oracle's
