@@ -113,6 +113,11 @@ SIGNATURES = {
     "iisan_timing_only_stream": (None, [vp, i32]),
     "iisan_timing_collect": (i64, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "iisan_timing_last_bytes": (C.c_double, []),
+    "iisan_gemm16_blk32": (i32, [i32, i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "iisan_gemm16_stream_blk32": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp]),
+    "iisan_stream_stats_finalize_blk32": (i32, [vp, i32, i64, vp, vp, vp, f32, i64, i32, i32, vp]),
+    "iisan_gemm16_h256_applicable_blk32": (i32, [i32, i64, i32, i32, i32, i32, i32, i32]),
+    "iisan_gemm16_route_blk32": (i32, [i32, i32, i64, i32, i32, i32, i32, i32, i32, i32, i32]),
 }
 
 _lib = None

@@ -297,9 +297,22 @@ struct Gemm16Args {
     // EPI_F32 (split-operand GEMM of the trainable path, split.hip): out fp32 = acc * inv_a[0] * inv_b[0] (+ bias) (+ resid)
     const float* inv_a; const float* inv_b;     // device scalars (reciprocal operand scales), null = 1
     int32_t atomic;     // 1: accumulate into out with fp32 atomics (bench knob only: ~20 G atomics/s chip-wide, far too slow)
+    int16_t a_blk32, out_blk32;       // block-major A operand / output (gemm16_h256; described at the end of the struct)
     int64_t split_stride;   // EPI_F32 split-K: K-split y writes its partial product to out + y*split_stride (bias / resid: reducer)
     const int32_t* skip_last_third;   // EPI_F32: device flag; when it reads 0 the last third of K is all zeros and is not multiplied
+    // Block-major ("blk32") 16-bit intermediates of gemm16_h256: a [Mpad, C] matrix (C % 32 == 0, leading dimension C) as
+    // 32 x 32 blocks of 2 KiB, element (m, c) at byte blk32_byte(m, c, C) below — the order in which the epilogue's lanes hold a block, so
+    // that every store instruction writes one whole KiB.  Only a launch of the same kernel reads such a buffer (its A-operand loader
+    // stages it block by block).  a_blk32: A is block-major (F1 into EPI_OUT16 / EPI_STREAM16, the ViT stream into the rowstat forms of
+    // EPI_QKVH16 / EPI_GELU16); out_blk32: out is (F1 from EPI_GELU16, the stream of EPI_STREAM16).  Every other route and mode rejects
+    // the flags (gemm16_route, gemm16_h256_applicable).  The two 16-bit fields sit in what
+    // was padding behind `atomic`: the struct is the kernels' argument, and a larger one moves their scalar loads.
 };
+// byte offset of element (m, c) of a block-major [Mpad, C] 16-bit matrix: block (m / 32, c / 32) row-major over blocks; inside a block the
+// first KiB holds the columns with (c / 8) even, the second those with (c / 8) odd, 16 bytes per (c / 16 % 2, m % 32)
+__host__ __device__ static inline int64_t blk32_byte(int64_t m, int64_t c, int64_t C) {
+    return ((m >> 5) * (C >> 5) + (c >> 5)) * 2048 + ((c >> 3) & 1) * 1024 + (((c >> 4) & 1) * 32 + (m & 31)) * 16 + (c & 7) * 2;
+}
 enum { EPI_OUT16 = 0, EPI_GELU16 = 1, EPI_RESID32 = 2, EPI_PATCH32 = 3, EPI_QKVH16 = 4, EPI_F32 = 5, EPI_PATCH16 = 6, EPI_STREAM16 = 7 };
 // EPI_STREAM16 (gemm16_h256 only, fp16, N = ldo): the residual add of a pre-LN tower in the epilogue — out IS the fp16 stream x [Mpad, N],
 // read and written in place: x[m] = fp16(x[m] + acc[m] + bias), and `rowpart` [N / 64][Mpad] (sum, sum of squares) receives every
@@ -331,7 +344,8 @@ int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, c
                              const float* b, float eps, float* sum32, void* out16, float* out32, int64_t rows, hipStream_t s);
 // mixed-precision residual stream (rowops.hip: layernorm768_mixed_kernel): CLS rows fp32 in `xc` [items, 768], every other token
 // row fp16 in `x16` [items * Ttok, 768]; V = which operands exist
-enum { MX_D1 = 1, MX_D2 = 2, MX_LN = 4, MX_RESV = 8, MX_RESY = 16, MX_SRC32 = 32, MX_CLSONLY = 64, MX_POSROW = 128, MX_STAT = 256, MX_ALIAS = 512 };
+enum { MX_D1 = 1, MX_D2 = 2, MX_LN = 4, MX_RESV = 8, MX_RESY = 16, MX_SRC32 = 32, MX_CLSONLY = 64, MX_POSROW = 128, MX_STAT = 256, MX_ALIAS = 512, MX_BLK32 = 1024 };
+// MX_BLK32 (with MX_SRC32 | MX_STAT): x16 is written block-major (blk32_byte above) — the ViT stream under the dev switch blk32 = 2
 // MX_ALIAS (with MX_RESY, fp16 operands): out16 IS x16 — the post-LN tower's stream and its LayerNorm image are the same fp16 values, written
 // once (every row, the CLS rows too; their fp32 copy still goes to xc)
 // MX_STAT (with MX_RESV, without MX_LN): no LayerNorm image; every row's sum goes to the fp16 stream (the CLS rows as well: the stream
@@ -350,7 +364,7 @@ int launch_fold_ln_weights(const LnFoldJob* jobs, int n, hipStream_t s);
 // after an EPI_STREAM16 product: rstat[m] = rstd of row m from the `nslots` partial sums of rowpart [nslots][Mpad][2]; the CLS rows
 // (m = item * Ttok): xc[item] += the fp16 delta the product left in x16[m]; x16[m] = fp16(xc[item]); rstat[m] from the rounded row
 int launch_stream_stats_finalize(const float* rowpart, int nslots, int64_t Mpad, void* x16, float* xc, float* rstat, float eps,
-                                 int64_t items, int Ttok, hipStream_t s);
+                                 int64_t items, int Ttok, hipStream_t s, bool x16_blk32 = false);     // x16_blk32: the stream is block-major
 int launch_attention16(int dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int S,
                        int heads, hipStream_t s);
 // attn16_dma.hip: the ViT shape (no key_bias, 192 < S <= 208) with K / V staged by LDS-DMA; `routed` = launch_attention16 sends this

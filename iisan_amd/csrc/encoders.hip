@@ -37,6 +37,14 @@ int g_resid32 = 0;
 // per-slice row sums, a small kernel turns those into rstd and folds the CLS rows' deltas into their fp32 stream.
 // 0: the LayerNorm image of rounds 1-4.  Bench / test knob.
 int g_ln_fold = 2;
+// Block-major ("blk32") intermediates of the persistent 256x256 GEMM.  1: F1, the FC1 -> FC2 intermediate of every
+// all-token block of both towers, is written by the FC1 epilogue in accumulator order — every store instruction one whole KiB instead of
+// 32 cache lines — and copied as it is into the LDS tile of the FC2 product.  2 (default): ... and the ViT residual stream X16 of the
+// product route (VS_STREAM) as well: patches_to_stream writes it block-major, the O / FC2 stream epilogues read-modify-write it, the
+// QKV / FC1 products (and the K/V product of the CLS-only last block) stage it, stream_stats_finalize addresses the CLS rows through the
+// formula.  0: row-major everywhere (the A/B handle and the tests' reference route: the same kernels, the same arithmetic, bit-equal
+// results).
+int g_blk32 = 2;
 
 size_t carve(WsCarver& c, EncBufs& b, int64_t tokens, int64_t items, int D, int F, int64_t kb_elems, int fold_layers = 0, bool fold_ws = true) {
     const int64_t Tp = ceil_div(tokens, 256) * 256;     // GEMM A operands are read in 256-row tiles
@@ -74,6 +82,54 @@ Gemm16Args gemm_args(int mode, const void* A, int K, const void* W, const float*
     return a;
 }
 
+// F1 block-major?  Decided once per call: only when BOTH products — FC1 (GELU, `rowstat`: LayerNorm in its epilogue) and FC2 (`fc2_mode`:
+// EPI_OUT16 or EPI_STREAM16) — run on gemm16_h256 with the flag for every chunk size of the call (the last chunk may be shorter)
+bool f1_blk32(int dt, int D, int F, int64_t M, int64_t Mc, int T, const float* rowstat, int fc2_mode, float* rowpart) {
+    if (g_blk32 < 1) return false;
+    for (int64_t mc : {Mc, M % Mc == 0 ? Mc : M % Mc}) {
+        const int64_t tok = mc * T;
+        Gemm16Args f1 = gemm_args(EPI_GELU16, nullptr, D, nullptr, nullptr, nullptr, F, tok, 0, 0, 0, rowstat);
+        Gemm16Args f2 = gemm_args(fc2_mode, nullptr, F, nullptr, nullptr, nullptr, D, tok, fc2_mode == EPI_STREAM16 ? T : 0);
+        f1.out_blk32 = 1;
+        f2.a_blk32 = 1; f2.rowpart = rowpart;
+        if (gemm16_route(dt, EPI_GELU16, f1) != G16_H256 || gemm16_route(dt, fc2_mode, f2) != G16_H256) return false;
+    }
+    return true;
+}
+
+// The ViT stream block-major?  Only on the product route (VS_STREAM) with F1 block-major, and only when every product that touches the
+// stream takes the flags for every chunk size of the call: QKV and FC1 (A), O and FC2 (read-modify-write), the K/V product of a CLS-only
+// last block (A)
+bool x16_blk32(int dt, int D, int F, int heads, int64_t M, int64_t Mc, int T, bool full_blocks, const float* rowstat, float* rowpart) {
+    if (g_blk32 < 2) return false;
+    for (int64_t mc : {Mc, M % Mc == 0 ? Mc : M % Mc}) {
+        const int64_t tok = mc * T;
+        Gemm16Args q = gemm_args(EPI_QKVH16, nullptr, D, nullptr, nullptr, nullptr, 3 * D, tok, T, heads, 0, rowstat);
+        Gemm16Args kv = gemm_args(EPI_QKVH16, nullptr, D, nullptr, nullptr, nullptr, 2 * D, tok, T, heads, 1, rowstat);
+        Gemm16Args f1 = gemm_args(EPI_GELU16, nullptr, D, nullptr, nullptr, nullptr, F, tok, 0, 0, 0, rowstat);
+        Gemm16Args o = gemm_args(EPI_STREAM16, nullptr, D, nullptr, nullptr, nullptr, D, tok, T), f2 = gemm_args(EPI_STREAM16, nullptr, F, nullptr, nullptr, nullptr, D, tok, T);
+        q.a_blk32 = kv.a_blk32 = f1.a_blk32 = f1.out_blk32 = o.out_blk32 = f2.a_blk32 = f2.out_blk32 = 1;
+        o.rowpart = f2.rowpart = rowpart;
+        auto h256 = [&](int mode, const Gemm16Args& a) { return gemm16_route(dt, mode, a) == G16_H256; };
+        if (!(h256(EPI_QKVH16, q) && h256(EPI_GELU16, f1) && h256(EPI_STREAM16, o) && h256(EPI_STREAM16, f2) && (full_blocks || h256(EPI_QKVH16, kv))))
+            return false;
+    }
+    return true;
+}
+
+// the FC1 -> FC2 pair of an all-token block: F1 = GELU(A W1^T + b1) (rowstat: LayerNorm in the epilogue), out = F1 W2^T + b2
+int gemm_fc1(int dt, const void* A, int D, const void* W, const float* bias, const float* rowstat, void* F1, int F, int64_t M, bool f1blk, hipStream_t s,
+             bool a_blk = false) {
+    Gemm16Args a = gemm_args(EPI_GELU16, A, D, W, bias, F1, F, M, 0, 0, 0, rowstat);
+    a.out_blk32 = f1blk; a.a_blk32 = a_blk;
+    return launch_gemm16(dt, EPI_GELU16, a, s);
+}
+int gemm_fc2(int dt, const void* F1, int F, const void* W, const float* bias, void* out, int D, int64_t M, bool f1blk, hipStream_t s) {
+    Gemm16Args a = gemm_args(EPI_OUT16, F1, F, W, bias, out, D, M);
+    a.a_blk32 = f1blk;
+    return launch_gemm16(dt, EPI_OUT16, a, s);
+}
+
 int gemm(int dt, int mode, const void* A, int K, const void* W, const float* bias, void* out, int N, const float* resid,
          int64_t M, hipStream_t s, const float* pos = nullptr, int patch_P = 0, int qkv_S = 0, int qkv_heads = 0,
          int qkv_which0 = 0) {
@@ -84,8 +140,10 @@ int gemm(int dt, int mode, const void* A, int K, const void* W, const float* bia
 
 // LN(x) W^T + b with the LayerNorm in the epilogue: A = the stream, W / bias = the folded set, rowstat = the rows' rstd
 int gemm_ln(int dt, int mode, const void* X16, int K, const void* Wf, const float* bf, const float* rs, void* out, int N,
-            int64_t M, hipStream_t s, int qkv_S = 0, int qkv_heads = 0, int qkv_which0 = 0) {
-    return launch_gemm16(dt, mode, gemm_args(mode, X16, K, Wf, bf, out, N, M, qkv_S, qkv_heads, qkv_which0, rs), s);
+            int64_t M, hipStream_t s, int qkv_S = 0, int qkv_heads = 0, int qkv_which0 = 0, bool x_blk = false) {
+    Gemm16Args a = gemm_args(mode, X16, K, Wf, bf, out, N, M, qkv_S, qkv_heads, qkv_which0, rs);
+    a.a_blk32 = x_blk;       // the stream is block-major
+    return launch_gemm16(dt, mode, a, s);
 }
 
 // Last live block: K and V for every token (head-major; the q third of the buffer is left untouched), Q for the CLS rows
@@ -132,6 +190,7 @@ int check_common(int hidden, int layers, int heads, int mlp, int n_taps, const i
 IISAN_DEV_KNOB(full_blocks, g_full_blocks);
 IISAN_DEV_KNOB(resid32, g_resid32);
 IISAN_DEV_KNOB(ln_fold, g_ln_fold);
+IISAN_DEV_KNOB(blk32, g_blk32);
 static int vit_fold_layers(const iisan_vit_weights* w) {
     return (!g_resid32 && g_ln_fold && w->dtype16 == IISAN_F16) ? w->layers : 0;
 }
@@ -221,6 +280,8 @@ struct VitChunk {
     const iisan_vit_weights* w; const EncBufs& b; VitStrategy st; hipStream_t s;
     int dt, D, F, T, heads; float eps;
     int64_t mc, tok; float* tp; int n_taps;
+    bool f1blk;     // F1 of the full blocks is block-major (f1_blk32, decided once per call)
+    bool xblk;      // ... and so is the stream X16 (x16_blk32; VS_STREAM only)
 
     bool mixed() const { return st != VS_RESID32; }
     const iisan_layer_weights& layer(int l) const { return w->layer[l]; }
@@ -277,15 +338,15 @@ struct VitChunk {
         IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
         // h = LN2(x + dO)   (x itself is updated by the next open step)
         IISAN_TRY(launch_layernorm768_mixed(dt, MX_D1 | MX_LN, nullptr, b.X16, b.Xc, b.D16, nullptr, L.ln2_w, L.ln2_b, eps, b.H, mc, T, s));
-        IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, tok, s));
-        return gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, nullptr, tok, s);
+        IISAN_TRY(gemm_fc1(dt, b.H, D, L.fc1_w, L.fc1_b, nullptr, b.F1, F, tok, f1blk, s));
+        return gemm_fc2(dt, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, tok, f1blk, s);
     }
     // only the CLS rows of the last hidden state are consumed
     int close_image() const { return launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, b.D16, b.D16b, nullptr, nullptr, eps, nullptr, mc, T, s); }
 
     // ---- VS_FOLD: the stream + rstd per row; LN1 / LN2 are applied by the epilogues of the QKV / FC1 products -------------------------
     int patches_to_stream() const {     // position table + 16-bit patch embedding -> fp16 stream of the patch rows (the CLS rows are in Xc already)
-        return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_ADD_STAT, w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s, b.RS);
+        return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_ADD_STAT | (xblk ? MX_BLK32 : 0), w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s, b.RS);
     }
     int open_fold(int l) const {
         if (l == 0) return patches_to_stream();
@@ -299,19 +360,19 @@ struct VitChunk {
         IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
         // x += dO (written: the FC1 product reads the stream); LN2 in the FC1 product's epilogue
         IISAN_TRY(launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, b.D16, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s, b.RS));
-        IISAN_TRY(gemm_ln(dt, EPI_GELU16, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, s));
-        return gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, nullptr, tok, s);
+        IISAN_TRY(gemm_fc1(dt, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, f1blk, s));
+        return gemm_fc2(dt, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, tok, f1blk, s);
     }
     // x + dO is in the stream: the CLS rows take dF
     int close_fold() const { return launch_layernorm768_mixed(dt, MX_D1 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s); }
 
     // ---- VS_STREAM: ... and the O / FC2 products add into the stream and leave its row statistics --------------------------------------
     // x += A W^T + bias in the stream (fp16 rows in place, the CLS rows' fp32 stream through the finalize step); rstd of the new rows
-    int gemm_stream(const void* A, int K, const void* W, const float* bias) const {
+    int gemm_stream(const void* A, int K, const void* W, const float* bias, bool a_blk = false) const {
         Gemm16Args a = gemm_args(EPI_STREAM16, A, K, W, bias, b.X16, D, tok, T);
-        a.rowpart = b.RP;
+        a.rowpart = b.RP; a.a_blk32 = a_blk; a.out_blk32 = xblk;
         IISAN_TRY(launch_gemm16(dt, EPI_STREAM16, a, s));
-        return launch_stream_stats_finalize(b.RP, D / 64, ceil_div(tok, 256) * 256, b.X16, b.Xc, b.RS, eps, mc, T, s);
+        return launch_stream_stats_finalize(b.RP, D / 64, ceil_div(tok, 256) * 256, b.X16, b.Xc, b.RS, eps, mc, T, s, xblk);
     }
     int open_stream(int l) const {
         if (l == 0) return patches_to_stream();
@@ -319,11 +380,11 @@ struct VitChunk {
     }
     int full_stream(int l) const {
         const iisan_layer_weights& L = layer(l);
-        IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l), bf_qkv(l), b.RS, b.QKV, 3 * D, tok, s, T, heads));
+        IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l), bf_qkv(l), b.RS, b.QKV, 3 * D, tok, s, T, heads, 0, xblk));
         IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
         IISAN_TRY(gemm_stream(b.H, D, L.o_w, L.o_b));
-        IISAN_TRY(gemm_ln(dt, EPI_GELU16, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, s));
-        return gemm_stream(b.F1, F, L.fc2_w, L.fc2_b);
+        IISAN_TRY(gemm_fc1(dt, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, f1blk, s, xblk));
+        return gemm_stream(b.F1, F, L.fc2_w, L.fc2_b, f1blk);
     }
     int close_stream() const { return IISAN_OK; }       // the stream is the last hidden state already
 
@@ -337,7 +398,7 @@ struct VitChunk {
         if (st == VS_FOLD || st == VS_STREAM) {
             // K / V of every token from the stream (LN1 in the epilogue); the CLS rows' LN1 image from their fp32 stream
             IISAN_TRY(launch_layernorm768(dt, b.Xc, L.ln1_w, L.ln1_b, eps, Hc, nullptr, mc, s));
-            IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l) + (size_t)D * D * 2, bf_qkv(l) + D, b.RS, b.QKV, 2 * D, tok, s, T, heads, 1));
+            IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l) + (size_t)D * D * 2, bf_qkv(l) + D, b.RS, b.QKV, 2 * D, tok, s, T, heads, 1, xblk));
             IISAN_TRY(gemm(dt, EPI_OUT16, Hc, D, L.qkv_w, L.qkv_b, Qc, D, nullptr, mc, s));
         } else {
             IISAN_TRY(launch_gather_rows16(b.H, Hc, mc, T, D, s));            // CLS rows of LN1(x)
@@ -395,11 +456,13 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
     const int live = full_blocks ? w->layers : max_tap(tap_layers, n_taps);
     const VitStrategy st = vit_strategy(w, b, live, full_blocks, M, Mc, T);
     const auto& step = VIT_STEPS[st];
+    const bool xblk = st == VS_STREAM && x16_blk32(w->dtype16, D, F, w->heads, M, Mc, T, full_blocks, b.RS, b.RP);
+    const bool f1blk = xblk || (st != VS_RESID32 && f1_blk32(w->dtype16, D, F, M, Mc, T, st >= VS_FOLD ? b.RS : nullptr, st == VS_STREAM ? EPI_STREAM16 : EPI_OUT16, b.RP));
     if (st >= VS_FOLD && !w->folded) IISAN_TRY(vit_fold_all(w, live, full_blocks, (char*)b.Wf, b.Bf, s));
     const int64_t img_elems = (int64_t)w->channels * w->image * w->image;
     for (int64_t m0 = 0; m0 < M; m0 += Mc) {
         const int64_t mc = (M - m0 < Mc) ? M - m0 : Mc;
-        const VitChunk ch{w, b, st, s, w->dtype16, D, F, T, w->heads, w->eps, mc, mc * T, taps + m0 * n_taps * D, n_taps};
+        const VitChunk ch{w, b, st, s, w->dtype16, D, F, T, w->heads, w->eps, mc, mc * T, taps + m0 * n_taps * D, n_taps, f1blk, xblk};
         if (index) IISAN_TRY(ch.embed(images, 1, index + m0, rows));
         else IISAN_TRY(ch.embed(img_u8 ? (const void*)((const uint8_t*)images + m0 * img_elems) : (const void*)((const float*)images + m0 * img_elems), img_u8));
         int k = tap_index(tap_layers, n_taps, 0);
@@ -480,6 +543,7 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
         return IISAN_EWORKSPACE;
     }
     const int dt = w->dtype16;
+    const bool f1blk = f1_blk32(dt, D, F, M, Mc, T, nullptr, EPI_OUT16, nullptr);      // F1 of the all-token blocks block-major
     for (int64_t m0 = 0; m0 < M; m0 += Mc) {
         const int64_t mc = (M - m0 < Mc) ? M - m0 : Mc;
         const int64_t tok = mc * T;
@@ -518,8 +582,8 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
                 IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
                 IISAN_TRY(add_ln(L.ln1_w, L.ln1_b, 2 + 3 * l));
                 // x = LN(a + FC2(gelu(FC1 a)))
-                IISAN_TRY(gemm(dt, EPI_GELU16, IMG, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, tok, s));
-                IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, nullptr, tok, s));
+                IISAN_TRY(gemm_fc1(dt, IMG, D, L.fc1_w, L.fc1_b, nullptr, b.F1, F, tok, f1blk, s));
+                IISAN_TRY(gemm_fc2(dt, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, tok, f1blk, s));
                 IISAN_TRY(add_ln(L.ln2_w, L.ln2_b, 3 + 3 * l));
                 k = tap_index(tap_layers, n_taps, l + 1);
                 if (k >= 0) IISAN_TRY(tap(k));

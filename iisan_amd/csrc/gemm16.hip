@@ -228,6 +228,7 @@ int launch_t(int mode, const Gemm16Args& a, hipStream_t s) {
 int launch_gemm16_f32(const Gemm16Args& a, int ksplit, hipStream_t s) {
     IISAN_CHECK_SHAPE(a.M > 0 && a.N > 0 && a.K > 0 && a.K % BK == 0 && a.N % 8 == 0 && a.ldo % 4 == 0, "gemm16_f32: bad shape");
     IISAN_CHECK_SHAPE(ksplit >= 1 && (ksplit == 1 || a.atomic || a.split_stride > 0), "gemm16_f32: split-K needs a partial-product buffer");
+    IISAN_CHECK_SHAPE(!a.a_blk32 && !a.out_blk32, "gemm16_f32: block-major (blk32) operands run on gemm16_h256 only");
     const int64_t tiles = ceil_div(a.M, BM) * ceil_div(a.N, BN);
     IISAN_CHECK_SHAPE(tiles < (1ll << 31), "gemm16_f32: grid too large");
     hipLaunchKernelGGL((gemm16_kernel<F16, EPI_F32>), dim3((unsigned)tiles, (unsigned)ksplit), dim3(256), 0, s, a);
@@ -257,6 +258,8 @@ static int64_t g_cnt_h256 = 0, g_cnt_s256 = 0, g_cnt_v1 = 0;      // launches of
 IISAN_DEV_COUNTER(gemm16_h256, g_cnt_h256);
 IISAN_DEV_COUNTER(gemm16_s256, g_cnt_s256);
 IISAN_DEV_COUNTER(gemm16_v1, g_cnt_v1);
+static int64_t g_cnt_blk32 = 0;       // ... of them, gemm16_h256 launches with a block-major operand or output (Gemm16Args::a_blk32 / out_blk32)
+IISAN_DEV_COUNTER(gemm16_blk32, g_cnt_blk32);
 // tile walk of gemm16_h256 (bench knob): c = -1 auto policy, 0 = row-major tile list, > 0 = panels of c column tiles walked down
 // sub-slabs of h row tiles (h <= 0: the XCD's whole slab)
 static int g_walk_c = -1, g_walk_h = 0;
@@ -288,6 +291,8 @@ int gemm16_route(int dtype16, int mode, const Gemm16Args& a) {
         if (!h256) return reject(a.rowstat ? "a product with LayerNorm row statistics runs on gemm16_h256 only" : "the stream epilogue runs on gemm16_h256 only", mode, a);
         if (dtype16 != IISAN_F16) return reject("row statistics and the stream epilogue need fp16 operands", mode, a);
     }
+    // block-major intermediates (Gemm16Args::a_blk32 / out_blk32) exist on gemm16_h256 alone: never read or written row-major by mistake
+    if ((a.a_blk32 || a.out_blk32) && !h256) return reject("block-major (blk32) operands run on gemm16_h256 only, FC1 output / FC2 A operand", mode, a);
     if (h256) return G16_H256;
     // the staggered kernel without the half-slot boundary: variant 3 (the race-screen reference of gemm16_h256) and the shapes
     // gemm16_h256_applicable() turns down
@@ -318,6 +323,7 @@ int launch_gemm16(int dtype16, int mode, const Gemm16Args& a, hipStream_t s) {
                 b.walk_h = g_walk_c < 0 ? 16 : g_walk_h;
             }
             ++g_cnt_h256;
+            if (a.a_blk32 || a.out_blk32) ++g_cnt_blk32;
             return launch_gemm16_h256(dtype16, mode, b, s);
         case G16_S256:
             b.debug = g_variant >> 8;
@@ -365,6 +371,46 @@ extern "C" int iisan_gemm16_lna(int32_t mode, const void* A, const void* W, cons
     a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N;
     if (mode == EPI_QKVH16) { a.qkv_S = S; a.qkv_heads = N / 192; }
     return launch_gemm16(IISAN_F16, mode, a, (hipStream_t)stream);
+}
+
+// DEV-section entries of the block-major ("blk32") intermediates (tests/test_gpu_blk32.py, tools/gemm_blk32_ab.py): the product of
+// iisan_gemm16 (modes 0 / 1; rowstat != null: LayerNorm in the epilogue, fp16), of iisan_gemm16_stream and the finalize step behind it
+// with the two layout flags of Gemm16Args — in the product only the encoder executors set them (encoders.hip, dev switch blk32)
+extern "C" int iisan_gemm16_blk32(int32_t dtype16, int32_t mode, const void* A, const void* W, const float* bias, void* out,
+                                  const float* rowstat, int64_t M, int32_t N, int32_t K, int32_t a_blk32, int32_t out_blk32, void* stream) {
+    IISAN_CHECK_SHAPE(mode == EPI_OUT16 || mode == EPI_GELU16, "iisan_gemm16_blk32: mode must be 0 or 1");
+    Gemm16Args a{};
+    a.A = A; a.W = W; a.bias = bias; a.out = out; a.rowstat = rowstat;
+    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N;
+    a.a_blk32 = a_blk32 != 0; a.out_blk32 = out_blk32 != 0;
+    return launch_gemm16(dtype16, mode, a, (hipStream_t)stream);
+}
+
+extern "C" int iisan_gemm16_stream_blk32(const void* A, const void* W, const float* bias, void* x16, float* rowpart, int64_t M, int32_t N,
+                                         int32_t K, int32_t S, int32_t a_blk32, int32_t x_blk32, void* stream) {
+    Gemm16Args a{};
+    a.A = A; a.W = W; a.bias = bias; a.out = x16; a.rowpart = rowpart; a.qkv_S = S;
+    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N;
+    a.a_blk32 = a_blk32 != 0; a.out_blk32 = x_blk32 != 0;
+    return launch_gemm16(IISAN_F16, EPI_STREAM16, a, (hipStream_t)stream);
+}
+
+extern "C" int iisan_stream_stats_finalize_blk32(const float* rowpart, int32_t nslots, int64_t Mpad, void* x16, float* xc, float* rstat, float eps,
+                                                 int64_t items, int32_t Ttok, int32_t x_blk32, void* stream) {
+    return launch_stream_stats_finalize(rowpart, nslots, Mpad, x16, xc, rstat, eps, items, Ttok, (hipStream_t)stream, x_blk32 != 0);
+}
+
+// iisan_gemm16_route with the two layout flags (host side, no device touched)
+extern "C" int32_t iisan_gemm16_route_blk32(int32_t dtype16, int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t qkv_heads,
+                                            int32_t qkv_which0, int32_t with_rowstat, int32_t a_blk32, int32_t out_blk32) {
+    static float dummy = 0.f;
+    Gemm16Args a{};
+    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N; a.qkv_S = qkv_S; a.qkv_heads = qkv_heads; a.qkv_which0 = qkv_which0;
+    a.patch_P = mode == EPI_PATCH16 || mode == EPI_PATCH32 ? qkv_S : 0;
+    a.rowstat = with_rowstat ? &dummy : nullptr;
+    a.rowpart = &dummy; a.resid = &dummy; a.pos = &dummy;
+    a.a_blk32 = a_blk32 != 0; a.out_blk32 = out_blk32 != 0;
+    return gemm16_route(dtype16, mode, a);
 }
 
 // bench / test entry: the weight fold of one LayerNorm + product pair (rowops.hip)

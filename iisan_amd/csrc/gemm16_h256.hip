@@ -44,6 +44,11 @@
 //   EPI_STREAM16 (fp16, N <= 1024): the O / FC2 products add into the fp16 stream in place (x = fp16(x + acc + b)) and leave per-slice
 //        row sums for stream_stats_finalize (rowops.hip).  The old stream values of a half-epilogue are requested two slots ahead
 //        (stream_load: inline-asm loads, waits by hand — `vmcnt` is in order and the LDS-DMA pieces queue behind them).
+//
+// Block-major intermediates (template flag pair BLK; DESIGN §4 / 6k, profiles/blk32_layout.md): where an output is read by another launch of this
+// kernel alone — F1 between FC1 and FC2, the ViT stream of EPI_STREAM16 — it is stored as 32 x 32 blocks of 2 KiB in the order the epilogue's lanes
+// hold them: every store (and stream_load) instruction covers one contiguous KiB instead of 32 cache lines, and the consumer's LDS-DMA pieces copy
+// a wave's 4-KiB run per K-step into LDS as it is.  Same arithmetic, same summation order: bit-equal to the row-major instantiations.
 #include "common.h"
 #include <type_traits>
 
@@ -90,9 +95,17 @@ __device__ __forceinline__ int nperm32s(int q) { return (q & ~31) + 16 * ((q >> 
 // the stores of a half-epilogue that may stay in flight over the wait at the end of its slot: 8 per wave, 9 with the row statistics
 #define S256_VMCNT_EPI() do { if constexpr (EPI == EPI_STREAM16) S256_VMCNT(9); else S256_VMCNT(8); } while (0)
 
-template <typename T, int EPI, bool LNA>
+// BLK (compile time; Gemm16Args::a_blk32 / out_blk32): bit 0 = the A operand is block-major, bit 1 = the output is.  A 32-row
+// run of a tile starts a block row, so every wave-uniform ROW term of an address is the row-major one (lda == K, ldo == N); what changes
+// is the K-step / column term (4 KiB per 64-element K-step, 2 KiB per 32 columns) and the lane's offset inside a block.
+enum { BLK_A = 1, BLK_OUT = 2 };
+template <typename T, int EPI, bool LNA, int BLK>
 __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int tiles_m, int tiles_n, uint32_t qkv_magic) {
     typedef typename T::v8 V8;
+    constexpr bool A_BLK = (BLK & BLK_A) != 0, OUT_BLK = (BLK & BLK_OUT) != 0;
+    static_assert(!OUT_BLK || EPI == EPI_GELU16 || EPI == EPI_STREAM16, "block-major output: F1 (FC1 epilogue) and the ViT stream only");
+    static_assert(!A_BLK || EPI != EPI_PATCH16, "block-major A operand: F1 and the ViT stream only");
+    constexpr int A_KSTEP_BYTES = A_BLK ? 4096 : SBK * 2;      // bytes between two K-steps of a 32-row run of A
     // Ablation / experiment bits (Gemm16Args::debug, set through the dev switch gemm16_variant = 4 | bits << 8; tools/gemm_walk.py, gemm_stream.py):
     // compiled in only with -DGEMM16_DEBUG_BITS (`make EXTRA=-DGEMM16_DEBUG_BITS`).  The product build folds every test away: each
     // run-time bit test in the epilogue costs scalar registers the kernel does not have (round 5: SGPR spills 17 / 18 -> 11 / 16 in the
@@ -173,6 +186,14 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
     const int s0 = (lane & 7) ^ (lane >> 4);
     const int slotx0 = s0 * 16, slotx1 = (s0 ^ 4) * 16;
     const int rowA = r8 * p.lda * 2;                                             // A-operand: LDS row == global row
+    // Block-major A operand: the 32 rows x 64 K-elements a wave stages per K-step are ONE 4-KiB run of the matrix (two blocks), and
+    // they go into the wave's 4 KiB of the LDS tile AS THEY ARE — piece j = KiB j of the run, lane l its 16 bytes l: the LDS image of
+    // those rows is block-major too, and the fragment reads address it (read_step: granule 2 ks + fh of row frow sits at
+    // (ks / 2) * 2048 + fh * 1024 + (ks & 1) * 512 + frow * 16: each half-wave reads 512 contiguous bytes, no swizzle needed).
+    // (First built with the row-major LDS image kept and the GATHER on the global side — lane (r8, slot) fetching its granule from
+    //  wherever the block holds it: 8 complete lines per piece as in the row-major matrix, but adjacent lanes in 8 different lines;
+    //  the FC2 products lost 12 - 14 % in isolation, profiles/blk32_layout.md.)
+    auto a_lane_blk = [&](int j) { return j * 1024 + lane * 16; };
     const int rowW = (16 * ((r8 >> 2) & 1) + (r8 & 3)) * p.ldw * 2;              // W: permuted rows (nperm32s)
     const char* Abase = (const char*)p.A;
     const char* Wbase = (const char*)p.W;
@@ -182,8 +203,13 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
     auto piece_A = [&](int s, int h, int j) {      // prologue only: s = 0, 1 lie in the first tile (nk >= 2)
         const int kt = s, tm = cur_tm;
         const int q0 = h * 128 + wq * 32;
-        const char* Ag = Abase + (((int64_t)tm * SBM + q0 + 8 * j) * p.lda + (int64_t)kt * SBK) * 2 + rowA;
-        glds16(Ag + ((j & 1) ? slotx1 : slotx0), smem + (s & 1) * S_STAGE_BYTES + (q0 + 8 * j) * 128);
+        if constexpr (A_BLK) {
+            const char* Ag = Abase + ((int64_t)tm * SBM + q0) * p.lda * 2 + (int64_t)kt * A_KSTEP_BYTES;
+            glds16(Ag + a_lane_blk(j), smem + (s & 1) * S_STAGE_BYTES + (q0 + 8 * j) * 128);
+        } else {
+            const char* Ag = Abase + (((int64_t)tm * SBM + q0 + 8 * j) * p.lda + (int64_t)kt * SBK) * 2 + rowA;
+            glds16(Ag + ((j & 1) ? slotx1 : slotx0), smem + (s & 1) * S_STAGE_BYTES + (q0 + 8 * j) * 128);
+        }
     };
     auto piece_W = [&](int s, int h, int j) {   // LDS rows q0+8j.. hold W rows q0 + 4j + {0,16} + {0..3} (nperm32s)
         const int kt = s, tn = cur_tn;
@@ -204,7 +230,10 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
     const int fsw = (frow >> 1) & 7;
     int xoff[4], woff2[2];
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) xoff[mi] = (grp * 128 + mi * 32 + frow) * 128;   // group g reads only its A-half
+    for (int mi = 0; mi < 4; ++mi)      // group g reads only its A-half (block-major LDS image: see a_lane_blk)
+        xoff[mi] = A_BLK ? (grp * 128 + mi * 32) * 128 + fh * 1024 + frow * 16 : (grp * 128 + mi * 32 + frow) * 128;
+    // byte offset of K-slice ks inside a 32-row run of the A tile, added to xoff: the swizzled slot, or a constant (block-major)
+#define S256_ASLOT(ks, slot) (A_BLK ? ((ks) >> 1) * 2048 + ((ks) & 1) * 512 : (slot))
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) woff2[ni] = (wq * 64 + ni * 32 + frow) * 128;
 
@@ -218,7 +247,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) wf[ni][ks] = *(const V8*)(sW + woff2[ni] + slot);
 #pragma unroll
-            for (int mi = 0; mi < 4; ++mi) xf[mi][ks] = *(const V8*)(sA + xoff[mi] + slot);
+            for (int mi = 0; mi < 4; ++mi) xf[mi][ks] = *(const V8*)(sA + xoff[mi] + S256_ASLOT(ks, slot));
         }
     };
     // half-steps of a tile's last / first K-step: Rlo = every W fragment of the step + the A-operand rows 0..63 of the
@@ -232,7 +261,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) wf[ni][ks] = *(const V8*)(sW + woff2[ni] + slot);
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) xf[mi][ks] = *(const V8*)(sA + xoff[mi] + slot);
+            for (int mi = 0; mi < 2; ++mi) xf[mi][ks] = *(const V8*)(sA + xoff[mi] + S256_ASLOT(ks, slot));
         }
     };
     auto read_hi = [&](int s) {
@@ -241,7 +270,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
         for (int ks = 0; ks < 4; ++ks) {
             const int slot = ((2 * ks + fh) ^ fsw) << 4;
 #pragma unroll
-            for (int mi = 2; mi < 4; ++mi) xf[mi][ks] = *(const V8*)(sA + xoff[mi] + slot);
+            for (int mi = 2; mi < 4; ++mi) xf[mi][ks] = *(const V8*)(sA + xoff[mi] + S256_ASLOT(ks, slot));
         }
     };
     // ---- DMA plan of one MFMA slot: 8 wave-uniform (global address, LDS offset) pairs, computed in the preceding READ
@@ -259,7 +288,8 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
     uint32_t vj[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-        vj[j] = (uint32_t)((grp == 0 ? rowA : rowW) + ((j & 1) ? slotx1 : slotx0)) + (uint32_t)j * (grp == 0 ? 8u * p.lda * 2u : 4u * p.ldw * 2u);
+        if (A_BLK && grp == 0) vj[j] = (uint32_t)a_lane_blk(j);
+        else vj[j] = (uint32_t)((grp == 0 ? rowA : rowW) + ((j & 1) ? slotx1 : slotx0)) + (uint32_t)j * (grp == 0 ? 8u * p.lda * 2u : 4u * p.ldw * 2u);
     auto sgpr = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
     // Group A: pieces 0..3 = B's A-operand half of step s+1, 4..7 = A's own half of step s+2;
     // group B: the W tile of step s+2 (pieces 0..3 rows 0..127, 4..7 rows 128..255).
@@ -271,8 +301,9 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
         if (grp == 0) {
             int tm1, tn1, kt1;
             step_at(kt, 1, tm1, tn1, kt1);
-            g1 = (uint64_t)Abase + (((int64_t)tm1 * SBM + 128 + wq * 32) * p.lda + (int64_t)kt1 * SBK) * 2;
-            g2 = (uint64_t)Abase + (((int64_t)tm2 * SBM + wq * 32) * p.lda + (int64_t)kt2 * SBK) * 2;
+            // (block-major: the K-step term alone differs — 4 KiB instead of 128 bytes — since lda == K)
+            g1 = (uint64_t)Abase + (((int64_t)tm1 * SBM + 128 + wq * 32) * p.lda + (int64_t)kt1 * (A_KSTEP_BYTES / 2)) * 2;
+            g2 = (uint64_t)Abase + (((int64_t)tm2 * SBM + wq * 32) * p.lda + (int64_t)kt2 * (A_KSTEP_BYTES / 2)) * 2;
             q.l1 = ((s + 1) & 1) * S_STAGE_BYTES + (128 + wq * 32) * 128;
             q.l2 = (s & 1) * S_STAGE_BYTES + (wq * 32) * 128;
         } else {
@@ -387,16 +418,22 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
             }
             int l2 = lane;
             asm volatile("" : "+v"(l2));
-            const uint32_t lane_off = (uint32_t)((l2 & 31) * p.ldo * 2 + (l2 >> 5) * 32);
-            const char* base = (const char*)p.out + ((int64_t)(tm * SBM + grp * 128 + half * 64) * p.ldo + tn * SBN + wq * 64) * 2;
+            // (block-major stream: the lane's two granules of a block are its 16 bytes of either KiB, as in the epilogue's stores)
+            const uint32_t lane_off = OUT_BLK ? (uint32_t)(l2 * 16) : (uint32_t)((l2 & 31) * p.ldo * 2 + (l2 >> 5) * 32);
+            const char* base = OUT_BLK ? (const char*)p.out + ((int64_t)(tm * SBM + grp * 128 + half * 64) * p.ldo + (tn * SBN + wq * 64) * 32) * 2
+                                       : (const char*)p.out + ((int64_t)(tm * SBM + grp * 128 + half * 64) * p.ldo + tn * SBN + wq * 64) * 2;
             // (inline asm, waited for by hand in the epilogue: the compiler's own `s_waitcnt` for a plain load does not know the LDS-DMA
             //  pieces issued behind it and came out as `vmcnt(0)` at the top of the epilogue — a wait for the pieces of the MFMA slot
             //  that has just ended)
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                const char* bp = base + ((int64_t)((b & 1) * 32) * p.ldo + (b >> 1) * 32) * 2;      // wave-uniform
-                asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %3 offset:16"
-                             : "=v"(xo[b][0]), "=&v"(xo[b][1]) : "v"(lane_off), "s"(bp) : "memory");
+                const char* bp = base + ((int64_t)((b & 1) * 32) * p.ldo + (b >> 1) * (OUT_BLK ? 1024 : 32)) * 2;      // wave-uniform
+                if constexpr (OUT_BLK)
+                    asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %3 offset:1024"
+                                 : "=v"(xo[b][0]), "=&v"(xo[b][1]) : "v"(lane_off), "s"(bp) : "memory");
+                else
+                    asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %3 offset:16"
+                                 : "=v"(xo[b][0]), "=&v"(xo[b][1]) : "v"(lane_off), "s"(bp) : "memory");
             }
             S256_FENCE();
         }
@@ -448,6 +485,8 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
                     qk_rowadd = (((n64 - wq_ * Dm) >> 6) * 3u + wq_ + (uint32_t)p.qkv_which0) * qk_S;
                     lane_off = (uint32_t)(fh * 32);
                     (void)qk_item0;
+                } else if constexpr (OUT_BLK) {
+                    lane_off = (uint32_t)(l2 * 16);        // lane fh * 32 + frow of the block's two KiB (o0 | o1)
                 } else {
                     lane_off = (uint32_t)(frow * p.ldo * 2 + fh * 32);
                 }
@@ -463,7 +502,8 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
                     f2* sSum = (f2*)(sBias + 1024) + (wave * 4) * 64 + lane;
                     auto blk_ptr = [&](int b) {
                         const int mi = 2 * half + (b & 1), ni = b >> 1;
-                        return (char*)p.out + ((int64_t)(row0 + mi * 32) * p.ldo + col0 + ni * 32) * 2 + lane_off;
+                        if constexpr (OUT_BLK) return (char*)p.out + ((int64_t)(row0 + mi * 32) * p.ldo + (col0 + ni * 32) * 32) * 2 + lane_off;
+                        else return (char*)p.out + ((int64_t)(row0 + mi * 32) * p.ldo + col0 + ni * 32) * 2 + lane_off;
                     };
                     auto comp = [&](int b) {
                         const int mi = 2 * half + (b & 1), ni = b >> 1;
@@ -499,7 +539,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
                         char* op = blk_ptr(b);
                         if (FULL || (int64_t)(row0 + mi * 32 + frow) < p.M) {
                             *(V8*)op = oo[b][0];
-                            *(V8*)(op + 16) = oo[b][1];
+                            *(V8*)(op + (OUT_BLK ? 1024 : 16)) = oo[b][1];
                         }
                         S256_FENCE();
                     };
@@ -585,12 +625,13 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
                         op = (char*)p.out + ((uint32_t)(R * 128u) + (uint32_t)(ni * 64) + lane_off);
                         if (!FULL) ok = (int64_t)m < p.M;
                     } else {
-                        char* base = (char*)p.out + ((int64_t)mrow * p.ldo + col0 + ni * 32) * 2;      // wave-uniform
+                        // wave-uniform; block-major: block row mrow / 32 starts at the row-major byte of row mrow, 2 KiB per block
+                        char* base = (char*)p.out + ((int64_t)mrow * p.ldo + (col0 + ni * 32) * (OUT_BLK ? 32 : 1)) * 2;
                         op = base + lane_off;
                         if (!FULL) ok = (int64_t)(mrow + frow) < p.M;
                     }
                     if constexpr (EPI == EPI_OUT16 || EPI == EPI_GELU16) {
-                        if (FULL && (dbg_bits & 512)) {      // (full row tiles only: the re-addressed rows are not tested against M)
+                        if (!OUT_BLK && FULL && (dbg_bits & 512)) {      // (full row tiles only: the re-addressed rows are not tested against M)
                             // experiment (round 5, timing only — the DATA lands in the wrong places): the same two stores per block, but each
                             // instruction writes 8 complete 128-byte rows of the wave's 64-column slice (8 cache lines) instead of two 16-byte
                             // pieces in each of 32 rows (32 lines).  What would line-complete stores be worth if the rearrangement were free?
@@ -606,7 +647,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
                             __builtin_nontemporal_store(o1, (V8*)(op + 16));
                         } else {
                             *(V8*)op = o0;
-                            *(V8*)(op + 16) = o1;
+                            *(V8*)(op + (OUT_BLK ? 1024 : 16)) = o1;
                         }
                     }
                 }
@@ -783,10 +824,10 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
     }
 }
 
-template <typename T, int EPI, bool LNA = false>
+template <typename T, int EPI, bool LNA = false, int BLK = 0>
 int launch_epi(const Gemm16Args& a, hipStream_t s) {
     static OncePerDevice attr;
-    auto kern = gemm16_h256_kernel<T, EPI, LNA>;
+    auto kern = gemm16_h256_kernel<T, EPI, LNA, BLK>;
     constexpr int LDS = 2 * S_STAGE_BYTES + STG_BIAS_BYTES + STG_TILE_BYTES;       // 160 KiB: the whole LDS of a CU
     if (attr.first())
         IISAN_HIP_OK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
@@ -809,6 +850,25 @@ int launch_epi(const Gemm16Args& a, hipStream_t s) {
 
 template <typename T>
 int launch_t(int mode, const Gemm16Args& a, hipStream_t s) {
+    // block-major operands (gemm16_h256_applicable has turned every other combination down): F1 — FC1 writes, FC2 reads — and the ViT
+    // stream — the O / FC2 stream epilogues read-modify-write, the QKV / FC1 products with LayerNorm in the epilogue read
+    if (a.a_blk32 || a.out_blk32) {
+        constexpr bool f16 = std::is_same<T, F16>::value;
+        const bool ab = a.a_blk32, ob = a.out_blk32;
+        if (mode == EPI_GELU16 && ob && !a.rowstat && !ab) return launch_epi<T, EPI_GELU16, false, BLK_OUT>(a, s);
+        if (mode == EPI_OUT16 && ab && !ob && !a.rowstat) return launch_epi<T, EPI_OUT16, false, BLK_A>(a, s);
+        if constexpr (f16) {
+            if (mode == EPI_GELU16 && ob && a.rowstat)
+                return ab ? launch_epi<F16, EPI_GELU16, true, BLK_A | BLK_OUT>(a, s) : launch_epi<F16, EPI_GELU16, true, BLK_OUT>(a, s);
+            if (mode == EPI_QKVH16 && ab && !ob && a.rowstat) return launch_epi<F16, EPI_QKVH16, true, BLK_A>(a, s);
+            if (mode == EPI_STREAM16 && !a.rowstat)
+                return ab && ob ? launch_epi<F16, EPI_STREAM16, false, BLK_A | BLK_OUT>(a, s)
+                       : ab     ? launch_epi<F16, EPI_STREAM16, false, BLK_A>(a, s)
+                                : launch_epi<F16, EPI_STREAM16, false, BLK_OUT>(a, s);
+        }
+        iisan_set_error("gemm16_h256: block-major flags (A %d, out %d) not supported with epilogue mode %d", a.a_blk32, a.out_blk32, mode);
+        return IISAN_EBADSHAPE;
+    }
     if (a.rowstat) {         // LayerNorm in the epilogue: fp16 operands, the two products that follow a LayerNorm
         if constexpr (std::is_same<T, F16>::value) {
             if (mode == EPI_QKVH16) return launch_epi<F16, EPI_QKVH16, true>(a, s);
@@ -836,6 +896,13 @@ bool gemm16_h256_applicable(int mode, const Gemm16Args& a) {
           a.K / SBK >= 2 && (int64_t)a.lda * 2 * SBM < (1ll << 31) && (int64_t)a.ldw * 2 * SBN < (1ll << 31)))
         return false;
     if (a.rowstat && !((mode == EPI_QKVH16 || mode == EPI_GELU16) && a.N <= LNA_MAX_N)) return false;
+    // block-major intermediates (N % 32 == 0 and K % 32 == 0 hold: N % 256, K % 64 above): no leading dimension of their own, the FC1
+    // epilogue writes them, the A-operand loader of the FC2 products reads them
+    // (exactly the combinations launch_t instantiates: out — F1 from FC1, the stream from O / FC2; A — F1 into FC2, the stream into the
+    //  QKV / FC1 products with LayerNorm in the epilogue, FC1 then writing F1 block-major as well)
+    if (a.out_blk32 && !((mode == EPI_GELU16 || mode == EPI_STREAM16) && a.ldo == a.N)) return false;
+    if (a.a_blk32 && !(a.lda == a.K && (a.rowstat ? (mode == EPI_QKVH16 && !a.out_blk32) || (mode == EPI_GELU16 && a.out_blk32)
+                                                  : (mode == EPI_OUT16 || mode == EPI_STREAM16)))) return false;
     const int64_t rows = ceil_div(a.M, SBM) * SBM;
     if (mode == EPI_QKVH16)      // 32-bit byte offsets into the head-major tensor, exact reciprocal division.  The layout is always
                                  // [item][head][q|k|v][S][64]: element-row index R reaches rows * 3 * heads WHATEVER qkv_which0 is (a
@@ -858,5 +925,16 @@ extern "C" int32_t iisan_gemm16_h256_applicable(int32_t mode, int64_t M, int32_t
                                                 int32_t qkv_which0) {
     Gemm16Args a{};
     a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N; a.qkv_S = qkv_S; a.qkv_heads = qkv_heads; a.qkv_which0 = qkv_which0;
+    return gemm16_h256_applicable(mode, a) ? 1 : 0;
+}
+
+// ... with the layout flags of the block-major intermediates (DEV section; a non-null placeholder for the buffers the modes ask for)
+extern "C" int32_t iisan_gemm16_h256_applicable_blk32(int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t with_rowstat,
+                                                      int32_t a_blk32, int32_t out_blk32) {
+    static float dummy = 0.f;
+    Gemm16Args a{};
+    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N; a.qkv_S = qkv_S;
+    a.rowstat = with_rowstat ? &dummy : nullptr; a.rowpart = &dummy;
+    a.a_blk32 = a_blk32 != 0; a.out_blk32 = out_blk32 != 0;
     return gemm16_h256_applicable(mode, a) ? 1 : 0;
 }

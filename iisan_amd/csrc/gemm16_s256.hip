@@ -447,10 +447,12 @@ int launch_t(int mode, const Gemm16Args& a, hipStream_t s) {
 }  // namespace
 
 bool gemm16_s256_applicable(int mode, const Gemm16Args& a) {
+    if (a.a_blk32 || a.out_blk32) return false;      // block-major intermediates: gemm16_h256 only
     return (mode == EPI_OUT16 || mode == EPI_GELU16 || mode == EPI_QKVH16) && a.N % SBN == 0 && a.N <= 8192 && a.K % SBK == 0 &&
            a.K / SBK >= 2 && (int64_t)a.lda * 2 * SBM < (1ll << 31) && (int64_t)a.ldw * 2 * SBN < (1ll << 31);
 }
 
 int launch_gemm16_s256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s) {
+    IISAN_CHECK_SHAPE(!a.a_blk32 && !a.out_blk32, "gemm16_s256: block-major (blk32) operands run on gemm16_h256 only");
     return dtype16 == IISAN_BF16 ? launch_t<BF16>(mode, a, s) : launch_t<F16>(mode, a, s);
 }

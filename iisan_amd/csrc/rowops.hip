@@ -103,7 +103,8 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
                                                                  float* __restrict__ stat) {
     constexpr bool D1 = (V & MX_D1) != 0, D2 = (V & MX_D2) != 0, LN = (V & MX_LN) != 0, RESV = (V & MX_RESV) != 0,
                    RESY = (V & MX_RESY) != 0, SRC32 = (V & MX_SRC32) != 0, CLSONLY = (V & MX_CLSONLY) != 0, POSROW = (V & MX_POSROW) != 0,
-                   STAT = (V & MX_STAT) != 0, ALIAS = (V & MX_ALIAS) != 0;
+                   STAT = (V & MX_STAT) != 0, ALIAS = (V & MX_ALIAS) != 0, BLK32 = (V & MX_BLK32) != 0;
+    static_assert(!BLK32 || (STAT && SRC32), "block-major stream: written by the ViT's first add only (the products do the rest)");
     typedef typename T::v8 V8;
     const int lane = threadIdx.x & 31, half = threadIdx.x >> 5;          // 8 half-waves per workgroup
     int64_t item;
@@ -162,7 +163,8 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
             h8 o;
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (_Float16)val[e];
-            if (STAT) *(h8*)(x16 + row * 768 + i * 256 + lane * 8) = o;      // read again by the GEMM that follows
+            // read again by the GEMM that follows (MX_BLK32: block-major, common.h — the lane's 8 columns are one 16-byte granule of it)
+            if (STAT) *(h8*)(x16 + (BLK32 ? blk32_byte(row, i * 256 + lane * 8, 768) >> 1 : row * 768 + i * 256 + lane * 8)) = o;
             else __builtin_nontemporal_store(o, (h8*)(x16 + row * 768 + i * 256 + lane * 8));
             if (STAT) {
 #pragma unroll
@@ -442,6 +444,7 @@ int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, f
         MX_CASE(MX_D1 | MX_LN | MX_RESY | MX_ALIAS);       // BERT, fp16 operands: ... and the image IS the stream
         // LayerNorm applied by the consuming product (Gemm16Args::rowstat): the stream and the row statistics only
         MX_CASE(MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_STAT);   // ViT block 0
+        MX_CASE(MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_STAT | MX_BLK32);   // ... into a block-major stream
         MX_CASE(MX_D1 | MX_RESV | MX_STAT);                // ViT LN1 (x += dF) and LN2 (x += dO)
         MX_CASE(MX_D1 | MX_RESV | MX_CLSONLY);             // ViT closing add of the CLS rows when x + dO is in the stream already
         default: iisan_set_error("layernorm768_mixed: operand set %d not instantiated", V); return IISAN_EBADSHAPE;
@@ -736,7 +739,7 @@ int launch_fold_ln_weights(const LnFoldJob* jobs, int n, hipStream_t s) {
 // next product's A operand) and the rstd of the ROUNDED row, two-pass.
 __global__ __launch_bounds__(256) void stream_stats_finalize_kernel(const f2* __restrict__ part, int nslots, int64_t Mpad, _Float16* x16,
                                                                     float* xc, float* __restrict__ rstat, float eps, int64_t items,
-                                                                    int Ttok, unsigned row_blocks) {
+                                                                    int Ttok, unsigned row_blocks, int x16_blk32) {
     const int64_t rows = items * Ttok;
     if (blockIdx.x < row_blocks) {
         const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -770,7 +773,9 @@ __global__ __launch_bounds__(256) void stream_stats_finalize_kernel(const f2* __
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int c = i * 256 + lane * 8;
-        const h8 d = *(const h8*)(x16 + row * 768 + c);
+        // (block-major stream: the lane's 8 columns are one 16-byte granule of it, common.h)
+        _Float16* xp = x16 + (x16_blk32 ? blk32_byte(row, c, 768) >> 1 : row * 768 + c);
+        const h8 d = *(const h8*)xp;
         const f4 a = *(const f4*)(xc + item * 768 + c), b = *(const f4*)(xc + item * 768 + c + 4);
         h8 o;
 #pragma unroll
@@ -780,7 +785,7 @@ __global__ __launch_bounds__(256) void stream_stats_finalize_kernel(const f2* __
         }
         *(f4*)(xc + item * 768 + c) = (f4){v[i][0], v[i][1], v[i][2], v[i][3]};
         *(f4*)(xc + item * 768 + c + 4) = (f4){v[i][4], v[i][5], v[i][6], v[i][7]};
-        *(h8*)(x16 + row * 768 + c) = o;
+        *(h8*)xp = o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) { v[i][e] = (float)o[e]; s += v[i][e]; }
     }
@@ -800,12 +805,12 @@ __global__ __launch_bounds__(256) void stream_stats_finalize_kernel(const f2* __
 }
 
 int launch_stream_stats_finalize(const float* rowpart, int nslots, int64_t Mpad, void* x16, float* xc, float* rstat, float eps,
-                                 int64_t items, int Ttok, hipStream_t s) {
+                                 int64_t items, int Ttok, hipStream_t s, bool x16_blk32) {
     if (items <= 0) return IISAN_OK;
     const int64_t row_blocks = ceil_div(items * Ttok, 256), cls_blocks = ceil_div(items, 8);
     IISAN_CHECK_SHAPE(row_blocks + cls_blocks < (1ll << 31), "stream_stats_finalize: grid too large");
     hipLaunchKernelGGL(stream_stats_finalize_kernel, dim3((unsigned)(row_blocks + cls_blocks)), dim3(256), 0, s, (const f2*)rowpart, nslots, Mpad,
-                       (_Float16*)x16, xc, rstat, eps, items, Ttok, (unsigned)row_blocks);
+                       (_Float16*)x16, xc, rstat, eps, items, Ttok, (unsigned)row_blocks, x16_blk32 ? 1 : 0);
     IISAN_LAUNCH_OK();
     return IISAN_OK;
 }

@@ -430,6 +430,26 @@ void iisan_timing_enable(int32_t cls);
 void iisan_timing_only_stream(void* stream, int32_t on);
 int64_t iisan_timing_collect(double* total_ms, double* total_flops);
 double iisan_timing_last_bytes(void);
+/* Block-major ("blk32") 16-bit intermediates of the persistent 256x256 GEMM (tests, tools/gemm_blk32_ab.py): a [Mpad, C]
+ * matrix, Mpad % 32 == 0 and C % 32 == 0, as 32 x 32 blocks of 2 KiB; element (m, c) at byte
+ *   ((m >> 5) * (C >> 5) + (c >> 5)) * 2048 + ((c >> 3) & 1) * 1024 + (((c >> 4) & 1) * 32 + (m & 31)) * 16 + (c & 7) * 2.
+ * The executors' FC1 -> FC2 intermediate carries it (dev switch blk32 >= 1) and the ViT residual stream of the product route (blk32 = 2,
+ * the default; 0 = row-major everywhere).  iisan_gemm16_blk32: iisan_gemm16 (mode 0 / 1; rowstat != NULL: LayerNorm in the epilogue as
+ * iisan_gemm16_lna) with "A is block-major" (mode 0; mode 1 with rowstat and a block-major out: the stream into FC1) and "out is
+ * block-major" (mode 1); iisan_gemm16_stream_blk32 / iisan_stream_stats_finalize_blk32: iisan_gemm16_stream and its finalize step with
+ * a block-major A and / or a block-major stream x16.  Every combination or kernel route that does not carry a flag returns
+ * IISAN_EBADSHAPE. */
+int iisan_gemm16_blk32(int32_t dtype16, int32_t mode, const void* A, const void* W, const float* bias, void* out, const float* rowstat,
+                       int64_t M, int32_t N, int32_t K, int32_t a_blk32, int32_t out_blk32, void* stream);
+int iisan_gemm16_stream_blk32(const void* A, const void* W, const float* bias, void* x16, float* rowpart, int64_t M, int32_t N,
+                              int32_t K, int32_t S, int32_t a_blk32, int32_t x_blk32, void* stream);
+int iisan_stream_stats_finalize_blk32(const float* rowpart, int32_t nslots, int64_t Mpad, void* x16, float* xc, float* rstat, float eps,
+                                      int64_t items, int32_t Ttok, int32_t x_blk32, void* stream);
+/* iisan_gemm16_h256_applicable / iisan_gemm16_route with the two flags (host side, no device touched) */
+int32_t iisan_gemm16_h256_applicable_blk32(int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t with_rowstat,
+                                           int32_t a_blk32, int32_t out_blk32);
+int32_t iisan_gemm16_route_blk32(int32_t dtype16, int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t qkv_heads,
+                                 int32_t qkv_which0, int32_t with_rowstat, int32_t a_blk32, int32_t out_blk32);
 
 #ifdef __cplusplus
 }
