@@ -334,26 +334,27 @@ int launch_gemm16_s256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s
 bool gemm16_h256_applicable(int mode, const Gemm16Args& a);      // gemm16_h256.hip
 int launch_gemm16_h256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s);
 int launch_gemm16_f32(const Gemm16Args& a, int ksplit, hipStream_t s);      // gemm16.hip: fp32 output of the 128x128 kernel (split.hip)
+// `width` of the row kernels below: 768 or 1024 (the instantiated widths; anything else: IISAN_EBADSHAPE)
 int launch_layernorm768(int dtype16, const float* x, const float* g, const float* b, float eps, void* out16,
-                        float* out32, int64_t rows, hipStream_t s);
+                        float* out32, int64_t rows, int width, hipStream_t s);
 // x (+ delta16) -> [sum32 = x + delta] -> LayerNorm -> out16 / out32 (any output may be null; g == null: no LayerNorm)
 int launch_add_layernorm768(int dtype16, const float* x, const void* delta16, const float* g, const float* b, float eps,
-                            float* sum32, void* out16, float* out32, int64_t rows, hipStream_t s);
+                            float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s);
 // ... with a second 16-bit delta: v = (x + delta16) + delta16b (either may be null)
 int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, const void* delta16b, const float* g,
-                             const float* b, float eps, float* sum32, void* out16, float* out32, int64_t rows, hipStream_t s);
-// mixed-precision residual stream (rowops.hip: layernorm768_mixed_kernel): CLS rows fp32 in `xc` [items, 768], every other token
-// row fp16 in `x16` [items * Ttok, 768]; V = which operands exist
+                             const float* b, float eps, float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s);
+// mixed-precision residual stream (rowops.hip: layernorm768_mixed_kernel): CLS rows fp32 in `xc` [items, width], every other token
+// row fp16 in `x16` [items * Ttok, width]; V = which operands exist (MX_STAT / MX_BLK32 sets: width 768 only)
 enum { MX_D1 = 1, MX_D2 = 2, MX_LN = 4, MX_RESV = 8, MX_RESY = 16, MX_SRC32 = 32, MX_CLSONLY = 64, MX_POSROW = 128, MX_STAT = 256, MX_ALIAS = 512, MX_BLK32 = 1024 };
 // MX_BLK32 (with MX_SRC32 | MX_STAT): x16 is written block-major (blk32_byte above) — the ViT stream under the dev switch blk32 = 2
 // MX_ALIAS (with MX_RESY, fp16 operands): out16 IS x16 — the post-LN tower's stream and its LayerNorm image are the same fp16 values, written
 // once (every row, the CLS rows too; their fp32 copy still goes to xc)
 // MX_STAT (with MX_RESV, without MX_LN): no LayerNorm image; every row's sum goes to the fp16 stream (the CLS rows as well: the stream
 // is the next GEMM's A operand) and `stat` [rows] receives rstd of the ROUNDED row — Gemm16Args::rowstat
-// MX_POSROW (with MX_SRC32 | MX_D1): the fp32 source is a [Ttok, 768] table indexed by the TOKEN (the position embedding) and the delta is
+// MX_POSROW (with MX_SRC32 | MX_D1): the fp32 source is a [Ttok, width] table indexed by the TOKEN (the position embedding) and the delta is
 // the patch embedding of that token; CLS rows take neither (their stream holds cls + pos[0] already)
 int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, float* xc, const void* delta16, const void* delta16b,
-                              const float* g, const float* b, float eps, void* out16, int64_t items, int Ttok, hipStream_t s,
+                              const float* g, const float* b, float eps, void* out16, int64_t items, int Ttok, int width, hipStream_t s,
                               float* stat = nullptr);
 // LayerNorm folded into the weights of the product that consumes it (rowops.hip): Wf[n][k] = fp16(gamma[k] W[n][k] - mean_k(gamma W[n]))
 // with sum_k Wf[n][k] = 0 to the last bit that matters, bf[n] = bias[n] + sum_k beta[k] W[n][k]; K = 768, fp16 weights.  Up to 32 jobs in one launch.
@@ -382,11 +383,11 @@ int launch_vit_im2col_indexed(int dtype16, const uint8_t* catalogue, int64_t row
 int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M, int T, int D, hipStream_t s);
 int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, const float* pos, const float* type0,
                          const float* g, const float* b, float eps, float* X, void* H, float* key_bias, int64_t M,
-                         int W, int vocab, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
+                         int W, int vocab, int width, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
 // item m = row index[m] of a resident table [rows, 2W]; values outside [0, rows) = padding (zero ids and mask, no read)
 int launch_bert_embed_ln_indexed(int dtype16, const int64_t* table, int64_t rows, const int64_t* index, const float* word, const float* pos,
                                  const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
-                                 int64_t M, int W, int vocab, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
+                                 int64_t M, int W, int vocab, int width, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
 // train-mode dropout of the BERT tower (bert_drop.hip; DropCfg above): variants of the four steps above that apply a counter-based keep
 // factor — slot0 / row0 / item0 / m0 place the chunk in the whole call, so the masks do not depend on the chunking
 int launch_attention16_drop(int dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int S, int heads,

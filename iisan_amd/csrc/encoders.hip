@@ -174,9 +174,10 @@ int max_tap(const int32_t* tap_layers, int n) {
 }
 
 int check_common(int hidden, int layers, int heads, int mlp, int n_taps, const int32_t* tap_layers) {
-    IISAN_CHECK_SHAPE(hidden == 768, "encoder hidden size must be 768 (got %d): the side network is 768 wide "
-                      "(Code_Uncached/model/model.py:171)", hidden);
-    IISAN_CHECK_SHAPE(heads > 0 && hidden == heads * 64, "encoder head_dim must be 64 (hidden %d, heads %d)", hidden, heads);
+    // the widths the row kernels are instantiated at (rowops.hip): ViT-B / BERT-base and ViT-L / BERT-large
+    IISAN_CHECK_SHAPE(hidden == 768 || hidden == 1024, "encoder hidden size %d not supported: the supported widths are 768 (12 heads) "
+                      "and 1024 (16 heads)", hidden);
+    IISAN_CHECK_SHAPE(heads > 0 && hidden == heads * 64, "encoder head_dim must be 64 (hidden %d, heads %d; supported: 768 / 12 and 1024 / 16)", hidden, heads);
     IISAN_CHECK_SHAPE(layers >= 1 && layers <= IISAN_MAX_LAYERS, "encoder layers %d out of range", layers);
     IISAN_CHECK_SHAPE(mlp % 128 == 0, "encoder mlp size %d must be a multiple of 128", mlp);
     IISAN_CHECK_SHAPE(n_taps >= 1 && tap_layers, "need at least one tap layer");
@@ -191,8 +192,10 @@ IISAN_DEV_KNOB(full_blocks, g_full_blocks);
 IISAN_DEV_KNOB(resid32, g_resid32);
 IISAN_DEV_KNOB(ln_fold, g_ln_fold);
 IISAN_DEV_KNOB(blk32, g_blk32);
+// (the LayerNorm-folded routes — fold_ln_weights, the stream statistics, the block-major stream — are 768 wide: a 1024-wide tower runs
+//  on the LayerNorm-image route whatever ln_fold says, and asks for no folded set)
 static int vit_fold_layers(const iisan_vit_weights* w) {
-    return (!g_resid32 && g_ln_fold && w->dtype16 == IISAN_F16) ? w->layers : 0;
+    return (!g_resid32 && g_ln_fold && w->dtype16 == IISAN_F16 && w->hidden == 768) ? w->layers : 0;
 }
 // the folded set of one tower: [layers][(3D + F) x D] fp16, then [layers][3D + F] fp32 (the caller's `folded` buffer or the workspace)
 static size_t vit_fold_w_elems(const iisan_vit_weights* w) { return (size_t)(3 * w->hidden + w->mlp) * w->hidden; }
@@ -253,7 +256,7 @@ enum VitStrategy {
 // residual adds in the epilogues of the O / FC2 products likewise — for every chunk size of this call (the last chunk may be shorter)
 VitStrategy vit_strategy(const iisan_vit_weights* w, const EncBufs& b, int live, bool full_blocks, int64_t M, int64_t Mc, int T) {
     if (g_resid32) return VS_RESID32;
-    if (!b.Wf || live == 0) return VS_IMAGE;
+    if (!b.Wf || live == 0 || w->hidden != 768) return VS_IMAGE;       // (hidden 1024: b.Wf is null already — vit_fold_layers)
     const int dt = w->dtype16, D = w->hidden, F = w->mlp;
     bool fold = true, stream = g_ln_fold >= 2;
     for (int64_t mc : {Mc, M % Mc == 0 ? Mc : M % Mc}) {
@@ -309,8 +312,8 @@ struct VitChunk {
     // ---- VS_RESID32 ------------------------------------------------------------------------------------------------------------
     int open_resid32(int l) const {     // x += dO + dF of block l - 1 ; h = LN1(x)
         const iisan_layer_weights& L = layer(l);
-        if (l == 0) return launch_add2_layernorm768(dt, b.X, nullptr, nullptr, L.ln1_w, L.ln1_b, eps, nullptr, b.H, nullptr, tok, s);
-        return launch_add2_layernorm768(dt, b.X, b.D16, b.D16b, L.ln1_w, L.ln1_b, eps, b.X, b.H, nullptr, tok, s);
+        if (l == 0) return launch_add2_layernorm768(dt, b.X, nullptr, nullptr, L.ln1_w, L.ln1_b, eps, nullptr, b.H, nullptr, tok, D, s);
+        return launch_add2_layernorm768(dt, b.X, b.D16, b.D16b, L.ln1_w, L.ln1_b, eps, b.X, b.H, nullptr, tok, D, s);
     }
     int full_resid32(int l) const {
         const iisan_layer_weights& L = layer(l);
@@ -318,18 +321,18 @@ struct VitChunk {
         IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
         IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
         // h = LN2(x + dO)   (x itself is updated by the next open step)
-        IISAN_TRY(launch_add_layernorm768(dt, b.X, b.D16, L.ln2_w, L.ln2_b, eps, nullptr, b.H, nullptr, tok, s));
+        IISAN_TRY(launch_add_layernorm768(dt, b.X, b.D16, L.ln2_w, L.ln2_b, eps, nullptr, b.H, nullptr, tok, D, s));
         IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, tok, s));
         return gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, nullptr, tok, s);
     }
-    int close_resid32() const { return launch_add2_layernorm768(dt, b.X, b.D16, b.D16b, nullptr, nullptr, eps, b.X, nullptr, nullptr, tok, s); }
+    int close_resid32() const { return launch_add2_layernorm768(dt, b.X, b.D16, b.D16b, nullptr, nullptr, eps, b.X, nullptr, nullptr, tok, D, s); }
 
     // ---- VS_IMAGE ----------------------------------------------------------------------------------------------------------------
     int open_image(int l) const {
         const iisan_layer_weights& L = layer(l);
         if (l == 0)     // position table + 16-bit patch embedding -> fp16 stream of the patch rows (the CLS rows are in Xc already) + LN image
-            return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_LN, w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, L.ln1_w, L.ln1_b, eps, b.H, mc, T, s);
-        return launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_LN, nullptr, b.X16, b.Xc, b.D16, b.D16b, L.ln1_w, L.ln1_b, eps, b.H, mc, T, s);
+            return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_LN, w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, L.ln1_w, L.ln1_b, eps, b.H, mc, T, D, s);
+        return launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_LN, nullptr, b.X16, b.Xc, b.D16, b.D16b, L.ln1_w, L.ln1_b, eps, b.H, mc, T, D, s);
     }
     int full_image(int l) const {
         const iisan_layer_weights& L = layer(l);
@@ -337,21 +340,21 @@ struct VitChunk {
         IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
         IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
         // h = LN2(x + dO)   (x itself is updated by the next open step)
-        IISAN_TRY(launch_layernorm768_mixed(dt, MX_D1 | MX_LN, nullptr, b.X16, b.Xc, b.D16, nullptr, L.ln2_w, L.ln2_b, eps, b.H, mc, T, s));
+        IISAN_TRY(launch_layernorm768_mixed(dt, MX_D1 | MX_LN, nullptr, b.X16, b.Xc, b.D16, nullptr, L.ln2_w, L.ln2_b, eps, b.H, mc, T, D, s));
         IISAN_TRY(gemm_fc1(dt, b.H, D, L.fc1_w, L.fc1_b, nullptr, b.F1, F, tok, f1blk, s));
         return gemm_fc2(dt, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, tok, f1blk, s);
     }
     // only the CLS rows of the last hidden state are consumed
-    int close_image() const { return launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, b.D16, b.D16b, nullptr, nullptr, eps, nullptr, mc, T, s); }
+    int close_image() const { return launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, b.D16, b.D16b, nullptr, nullptr, eps, nullptr, mc, T, D, s); }
 
     // ---- VS_FOLD: the stream + rstd per row; LN1 / LN2 are applied by the epilogues of the QKV / FC1 products -------------------------
     int patches_to_stream() const {     // position table + 16-bit patch embedding -> fp16 stream of the patch rows (the CLS rows are in Xc already)
-        return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_ADD_STAT | (xblk ? MX_BLK32 : 0), w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s, b.RS);
+        return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_ADD_STAT | (xblk ? MX_BLK32 : 0), w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, D, s, b.RS);
     }
     int open_fold(int l) const {
         if (l == 0) return patches_to_stream();
         // x += dF of block l - 1 (x + dO is in the stream already: that block wrote it in its LN2 step)
-        return launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s, b.RS);
+        return launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, D, s, b.RS);
     }
     int full_fold(int l) const {
         const iisan_layer_weights& L = layer(l);
@@ -359,12 +362,12 @@ struct VitChunk {
         IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
         IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
         // x += dO (written: the FC1 product reads the stream); LN2 in the FC1 product's epilogue
-        IISAN_TRY(launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, b.D16, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s, b.RS));
+        IISAN_TRY(launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, b.D16, nullptr, nullptr, nullptr, eps, nullptr, mc, T, D, s, b.RS));
         IISAN_TRY(gemm_fc1(dt, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, f1blk, s));
         return gemm_fc2(dt, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, tok, f1blk, s);
     }
     // x + dO is in the stream: the CLS rows take dF
-    int close_fold() const { return launch_layernorm768_mixed(dt, MX_D1 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, s); }
+    int close_fold() const { return launch_layernorm768_mixed(dt, MX_D1 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, D, s); }
 
     // ---- VS_STREAM: ... and the O / FC2 products add into the stream and leave its row statistics --------------------------------------
     // x += A W^T + bias in the stream (fp16 rows in place, the CLS rows' fp32 stream through the finalize step); rstd of the new rows
@@ -397,7 +400,7 @@ struct VitChunk {
         void* Qc = (char*)b.Cls + (size_t)b.Mcp * D * 2;
         if (st == VS_FOLD || st == VS_STREAM) {
             // K / V of every token from the stream (LN1 in the epilogue); the CLS rows' LN1 image from their fp32 stream
-            IISAN_TRY(launch_layernorm768(dt, b.Xc, L.ln1_w, L.ln1_b, eps, Hc, nullptr, mc, s));
+            IISAN_TRY(launch_layernorm768(dt, b.Xc, L.ln1_w, L.ln1_b, eps, Hc, nullptr, mc, D, s));
             IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l) + (size_t)D * D * 2, bf_qkv(l) + D, b.RS, b.QKV, 2 * D, tok, s, T, heads, 1, xblk));
             IISAN_TRY(gemm(dt, EPI_OUT16, Hc, D, L.qkv_w, L.qkv_b, Qc, D, nullptr, mc, s));
         } else {
@@ -408,10 +411,10 @@ struct VitChunk {
         float* Xc = (float*)b.QKV;      // free once the CLS attention has run (stream order)
         IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, mc, s));
         if (mixed()) IISAN_TRY(launch_gather_cls(b.Xc, Xc, mc, 1, D, 1, 0, s)); else IISAN_TRY(launch_gather_cls(b.X, Xc, mc, T, D, 1, 0, s));
-        IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, eps, Xc, b.H, nullptr, mc, s));
+        IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, eps, Xc, b.H, nullptr, mc, D, s));
         IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, mc, s));
         IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, nullptr, mc, s));
-        IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, nullptr, nullptr, eps, Xc, nullptr, nullptr, mc, s));
+        IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, nullptr, nullptr, eps, Xc, nullptr, nullptr, mc, D, s));
         return launch_gather_cls(Xc, tp, mc, 1, D, n_taps, k, s);     // hidden state `live` (before any final LayerNorm)
     }
 };
@@ -528,6 +531,9 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
     const bool dropping = drop && (drop->hidden_p > 0.f || drop->attn_p > 0.f);
     // never a silent fall-back to eval mode: the variants exist for the mixed stream only
     IISAN_CHECK_SHAPE(!(dropping && g_resid32), "bert dropout: not built for the fp32 residual stream of the dev switch resid32 = 1");
+    // ... and for 768-wide rows only (bert_drop.hip): tap caches of the wide towers are built in eval mode
+    IISAN_CHECK_SHAPE(!(dropping && w->hidden != 768), "bert dropout: the train-mode kernels are 768 wide, hidden size %d runs in eval mode only "
+                      "(drop == NULL or both probabilities 0)", w->hidden);
     const float hp = dropping ? drop->hidden_p : 0.f, ap = dropping ? drop->attn_p : 0.f;
     const uint64_t seed = dropping ? drop->seed : 0;
     IISAN_CHECK_SHAPE(M > 0, "bert_forward_taps: M must be positive");
@@ -558,15 +564,15 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
                                                           w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b, w->eps, IMG, b.KB, mc, T, w->vocab,
                                                           b.X16, b.Xc, make_drop(seed, 0, hp), m0, s));
         else if (index) IISAN_TRY(launch_bert_embed_ln_indexed(dt, text, rows, index + m0, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w,
-                                                          w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, s, b.X16, b.Xc));
+                                                          w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc));
         else IISAN_TRY(launch_bert_embed_ln(dt, text + m0 * 2 * words, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w,
-                                            w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, s, b.X16, b.Xc));
+                                            w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc));
         auto tap = [&](int k) { return mixed ? launch_gather_cls(b.Xc, tp, mc, 1, D, n_taps, k, s) : launch_gather_cls(b.X, tp, mc, T, D, n_taps, k, s); };
         // x = LN(x + delta): stream and 16-bit image out
         auto add_ln = [&](const float* g, const float* be, int site) {
             if (dropping) return launch_add_ln_drop_mixed(dt, alias, b.X16, b.Xc, b.D16, g, be, w->eps, IMG, mc, T, make_drop(seed, site, hp), m0 * T, s);
-            return mixed ? launch_layernorm768_mixed(dt, MX_D1 | MX_LN | MX_RESY | (alias ? MX_ALIAS : 0), nullptr, b.X16, b.Xc, b.D16, nullptr, g, be, w->eps, IMG, mc, T, s)
-                         : launch_add_layernorm768(dt, b.X, b.D16, g, be, w->eps, nullptr, b.H, b.X, tok, s);
+            return mixed ? launch_layernorm768_mixed(dt, MX_D1 | MX_LN | MX_RESY | (alias ? MX_ALIAS : 0), nullptr, b.X16, b.Xc, b.D16, nullptr, g, be, w->eps, IMG, mc, T, D, s)
+                         : launch_add_layernorm768(dt, b.X, b.D16, g, be, w->eps, nullptr, b.H, b.X, tok, D, s);
         };
         int k = tap_index(tap_layers, n_taps, 0);
         if (k >= 0) IISAN_TRY(tap(k));
@@ -600,11 +606,11 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
                 if (mixed) IISAN_TRY(launch_gather_cls(b.Xc, Xc, mc, 1, D, 1, 0, s)); else IISAN_TRY(launch_gather_cls(b.X, Xc, mc, T, D, 1, 0, s));
                 // (dropping: the masks of token row t = 0 of the all-token execution)
                 if (dropping) IISAN_TRY(launch_add_ln_drop_rows(dt, Xc, b.D16, L.ln1_w, L.ln1_b, w->eps, b.H, mc, make_drop(seed, 2 + 3 * l, hp), m0, T, s));
-                else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln1_w, L.ln1_b, w->eps, nullptr, b.H, Xc, mc, s));
+                else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln1_w, L.ln1_b, w->eps, nullptr, b.H, Xc, mc, D, s));
                 IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, mc, s));
                 IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, nullptr, mc, s));
                 if (dropping) IISAN_TRY(launch_add_ln_drop_rows(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, mc, make_drop(seed, 3 + 3 * l, hp), m0, T, s));
-                else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, nullptr, Xc, mc, s));
+                else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, nullptr, Xc, mc, D, s));
                 k = tap_index(tap_layers, n_taps, live);
                 IISAN_TRY(launch_gather_cls(Xc, tp, mc, 1, D, n_taps, k, s));
             }

@@ -1,11 +1,14 @@
 // Row-wise HBM-bound kernels of the frozen encoders: LayerNorm, patch extraction, embedding gather, CLS taps.
-// Roofline: HBM (one read + one write of each row); one wave64 per 768-wide row, 16-byte lane accesses,
+// Roofline: HBM (one read + one write of each row); one wave64 per row, 16-byte lane accesses,
 // wavefront-shuffle reductions, fp32 statistics (two-pass mean / centred variance in registers).
+// The row width D is a template parameter of the LayerNorm / embedding kernels (D / 256 pieces per lane: 3 at 768 — ViT-B, BERT-base —
+// 4 at 1024 — ViT-L, BERT-large); their names keep the 768 they were written for.  The kernels of the ViT's product route
+// (fold_ln_weights, stream_stats_finalize, the MX_STAT / MX_BLK32 operand sets) are 768 wide only.
 #include "common.h"
 
 namespace {
 
-// ---- (residual add +) LayerNorm over rows of 768 fp32 (HF nn.LayerNorm, eps inside the sqrt) ----------------------
+// ---- (residual add +) LayerNorm over rows of D fp32 (HF nn.LayerNorm, eps inside the sqrt) ----------------------
 // v = x + delta16 (delta optional: the 16-bit output of the preceding O / FC2 GEMM, so the fp32 read-modify-write of
 // the residual stream happens HERE, in an HBM-bound kernel, instead of stalling the MFMA pipeline in a GEMM epilogue);
 // sum32 <- v (optional, may alias x); out32 / out16 <- LN(v) (optional, out32 may alias x).  g == nullptr: add only.
@@ -13,35 +16,37 @@ namespace {
 // null tests every load sat behind its own branch and hipcc waited for each one before issuing the next — one load in flight
 // per wave, six HBM round trips per row (ISA: load, s_waitcnt vmcnt(0), load, s_waitcnt vmcnt(0), ...).  Now all loads of a
 // row are requested first.
-template <typename T, int V>
+template <typename T, int V, int D = 768>
 __global__ __launch_bounds__(256) void layernorm768_kernel(const float* x, const typename T::elem* __restrict__ delta,
                                                            const typename T::elem* __restrict__ delta2,
                                                            const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                            float* sum32, typename T::elem* __restrict__ out16,
                                                            float* out32, int64_t rows) {
     constexpr bool D1 = V & 1, D2 = (V & 2) != 0, SUM = (V & 4) != 0, LN = (V & 8) != 0;
+    constexpr int NP = D / 256;        // 4-element pieces per lane of the wave: 3 (768) or 4 (1024)
+    static_assert(D % 256 == 0 && NP >= 1 && NP <= 4, "row width: a multiple of 256, at most 1024 (the row lives in registers)");
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     // The fp32 residual stream and the 16-bit deltas are read once and not touched again for gigabytes: non-temporal
     // accesses (measured: 220.7 -> 201.8 us average per launch over a step's 49 launches)
-    const float* xr = x + row * 768;
-    f4 v[3];
-    typename T::v4 d1[3], d2[3];
+    const float* xr = x + row * D;
+    f4 v[NP];
+    typename T::v4 d1[NP], d2[NP];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < NP; ++i) {
         v[i] = __builtin_nontemporal_load((const f4*)(xr + i * 256 + lane * 4));
-        if (D1) d1[i] = __builtin_nontemporal_load((const typename T::v4*)(delta + row * 768 + i * 256 + lane * 4));
-        if (D2) d2[i] = __builtin_nontemporal_load((const typename T::v4*)(delta2 + row * 768 + i * 256 + lane * 4));
+        if (D1) d1[i] = __builtin_nontemporal_load((const typename T::v4*)(delta + row * D + i * 256 + lane * 4));
+        if (D2) d2[i] = __builtin_nontemporal_load((const typename T::v4*)(delta2 + row * D + i * 256 + lane * 4));
     }
-    f4 gg[3], bb[3];
+    f4 gg[NP], bb[NP];
     if (LN) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { gg[i] = *(const f4*)(g + i * 256 + lane * 4); bb[i] = *(const f4*)(b + i * 256 + lane * 4); }
+        for (int i = 0; i < NP; ++i) { gg[i] = *(const f4*)(g + i * 256 + lane * 4); bb[i] = *(const f4*)(b + i * 256 + lane * 4); }
     }
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < NP; ++i) {
         if (D1) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[i][e] += T::to_f32(d1[i][e]);
@@ -50,32 +55,32 @@ __global__ __launch_bounds__(256) void layernorm768_kernel(const float* x, const
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[i][e] += T::to_f32(d2[i][e]);
         }
-        if (SUM) __builtin_nontemporal_store(v[i], (f4*)(sum32 + row * 768 + i * 256 + lane * 4));
+        if (SUM) __builtin_nontemporal_store(v[i], (f4*)(sum32 + row * D + i * 256 + lane * 4));
         s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
     }
     if (!LN) return;
-    const float mean = wave_sum(s) * (1.0f / 768.0f);
+    const float mean = wave_sum(s) * (1.0f / (float)D);
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NP; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float d = v[i][e] - mean;
             q += d * d;
         }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / 768.0f) + eps);
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / (float)D) + eps);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < NP; ++i) {
         const int c = i * 256 + lane * 4;
         f4 y;
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] = (v[i][e] - mean) * rstd * gg[i][e] + bb[i][e];
-        if (out32) *(f4*)(out32 + row * 768 + c) = y;
+        if (out32) *(f4*)(out32 + row * D + c) = y;
         if (out16) {
             typename T::v4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = T::from_f32(y[e]);
-            *(typename T::v4*)(out16 + row * 768 + c) = o;
+            *(typename T::v4*)(out16 + row * D + c) = o;
         }
     }
 }
@@ -84,17 +89,17 @@ __global__ __launch_bounds__(256) void layernorm768_kernel(const float* x, const
 // ---- the same with a MIXED-PRECISION residual stream (round 4) ------------------------------------------------------
 // The path consumes only the CLS row of every hidden state (Code_Uncached/model/model.py:210-213), and every token row already
 // reaches the next GEMM through a 16-bit LayerNorm image.  So the residual stream is kept in fp32 for the CLS rows only
-// (`xc` [items, 768], compact: the taps are copies of it) and in fp16 for the patch / word rows (`x16` [rows, 768]; always
+// (`xc` [items, D], compact: the taps are copies of it) and in fp16 for the patch / word rows (`x16` [rows, D]; always
 // IEEE half, whatever the MFMA operand type — bf16 would keep 8 bits).  A non-CLS row's rounding (2^-11, once per block)
 // reaches the CLS row only through the attention average over the item's tokens: measured on the golden ViT-B inputs with
 // fp32 arithmetic everywhere else, +9e-5 relative on every tap (all rows in fp16: 6.8e-4) against the 8.8e-4 the 16-bit operands
 // cost and the 1.5e-3 budget.  Bytes per token row and ViT block: LN1 10 + LN2 6 = 16 instead of 14 + 8 = 22 (BERT: 8
 // instead of 12 per LayerNorm) in kernels that run at the HBM rate.
-// HALF a wave per token row (32 lanes x three 8-element pieces), a workgroup = 8 consecutive tokens of ONE item (the CLS test costs no
+// HALF a wave per token row (32 lanes x D / 256 = three or four 8-element pieces), a workgroup = 8 consecutive tokens of ONE item (the CLS test costs no
 // division per lane): every access of the fp16 stream, the 16-bit deltas and the 16-bit image is a full 16-byte lane access.  (The
 // first version gave a row to a whole wave — 12 elements per lane as three 8-byte pieces: 4.3 TB/s on LN1 where the fp32 kernel's
 // 16-byte accesses reach 6.7; MI355X_MICROARCH.md: 8-byte accesses run at 0.54-0.70 x the 16-byte rate.)  V: which operands exist.
-template <typename T, int V>
+template <typename T, int V, int D = 768>
 __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __restrict__ x32, _Float16* x16, float* xc,
                                                                  const typename T::elem* __restrict__ delta,
                                                                  const typename T::elem* __restrict__ delta2,
@@ -105,6 +110,9 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
                    RESY = (V & MX_RESY) != 0, SRC32 = (V & MX_SRC32) != 0, CLSONLY = (V & MX_CLSONLY) != 0, POSROW = (V & MX_POSROW) != 0,
                    STAT = (V & MX_STAT) != 0, ALIAS = (V & MX_ALIAS) != 0, BLK32 = (V & MX_BLK32) != 0;
     static_assert(!BLK32 || (STAT && SRC32), "block-major stream: written by the ViT's first add only (the products do the rest)");
+    constexpr int NP = D / 256;        // 8-element pieces per lane of the half-wave: 3 (768) or 4 (1024)
+    static_assert(D % 256 == 0 && NP >= 1 && NP <= 4, "row width: a multiple of 256, at most 1024 (the row lives in registers)");
+    static_assert(D == 768 || !(STAT || BLK32), "the product route's stream (row statistics, block-major rows) is 768 wide");
     typedef typename T::v8 V8;
     const int lane = threadIdx.x & 31, half = threadIdx.x >> 5;          // 8 half-waves per workgroup
     int64_t item;
@@ -120,35 +128,35 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
     }
     const int64_t row = item * Ttok + tok;
     const bool cls = tok == 0;                                            // uniform within the half-wave
-    V8 d1[3], d2[3];
+    V8 d1[NP], d2[NP];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        if (D1) d1[i] = __builtin_nontemporal_load((const V8*)(delta + row * 768 + i * 256 + lane * 8));
-        if (D2) d2[i] = __builtin_nontemporal_load((const V8*)(delta2 + row * 768 + i * 256 + lane * 8));
+    for (int i = 0; i < NP; ++i) {
+        if (D1) d1[i] = __builtin_nontemporal_load((const V8*)(delta + row * D + i * 256 + lane * 8));
+        if (D2) d2[i] = __builtin_nontemporal_load((const V8*)(delta2 + row * D + i * 256 + lane * 8));
     }
-    float v[3][8];
+    float v[NP][8];
     if (cls) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const f4 a = *(const f4*)(xc + item * 768 + i * 256 + lane * 8), c = *(const f4*)(xc + item * 768 + i * 256 + lane * 8 + 4);
+        for (int i = 0; i < NP; ++i) {
+            const f4 a = *(const f4*)(xc + item * D + i * 256 + lane * 8), c = *(const f4*)(xc + item * D + i * 256 + lane * 8 + 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[i][e] = a[e]; v[i][4 + e] = c[e]; }
         }
     } else if (SRC32) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
+        for (int i = 0; i < NP; ++i) {
             const int64_t srow = POSROW ? (int64_t)tok : row;            // POSROW: the position-embedding table (L2-resident), by token
-            const f4 a = POSROW ? *(const f4*)(x32 + srow * 768 + i * 256 + lane * 8) : __builtin_nontemporal_load((const f4*)(x32 + srow * 768 + i * 256 + lane * 8));
-            const f4 c = POSROW ? *(const f4*)(x32 + srow * 768 + i * 256 + lane * 8 + 4) : __builtin_nontemporal_load((const f4*)(x32 + srow * 768 + i * 256 + lane * 8 + 4));
+            const f4 a = POSROW ? *(const f4*)(x32 + srow * D + i * 256 + lane * 8) : __builtin_nontemporal_load((const f4*)(x32 + srow * D + i * 256 + lane * 8));
+            const f4 c = POSROW ? *(const f4*)(x32 + srow * D + i * 256 + lane * 8 + 4) : __builtin_nontemporal_load((const f4*)(x32 + srow * D + i * 256 + lane * 8 + 4));
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[i][e] = a[e]; v[i][4 + e] = c[e]; }
         }
     } else {
-        h8 xh[3];
+        h8 xh[NP];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) xh[i] = __builtin_nontemporal_load((const h8*)(x16 + row * 768 + i * 256 + lane * 8));
+        for (int i = 0; i < NP; ++i) xh[i] = __builtin_nontemporal_load((const h8*)(x16 + row * D + i * 256 + lane * 8));
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+        for (int i = 0; i < NP; ++i)
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[i][e] = (float)xh[i][e];
     }
@@ -156,16 +164,16 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
     // ROUNDED row (what the product multiplies); val is rounded in place
     auto put_resid = [&](int i, float (&val)[8]) {
         if (cls) {
-            *(f4*)(xc + item * 768 + i * 256 + lane * 8) = (f4){val[0], val[1], val[2], val[3]};
-            *(f4*)(xc + item * 768 + i * 256 + lane * 8 + 4) = (f4){val[4], val[5], val[6], val[7]};
+            *(f4*)(xc + item * D + i * 256 + lane * 8) = (f4){val[0], val[1], val[2], val[3]};
+            *(f4*)(xc + item * D + i * 256 + lane * 8 + 4) = (f4){val[4], val[5], val[6], val[7]};
         }
         if ((!cls || STAT) && !ALIAS) {
             h8 o;
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (_Float16)val[e];
             // read again by the GEMM that follows (MX_BLK32: block-major, common.h — the lane's 8 columns are one 16-byte granule of it)
-            if (STAT) *(h8*)(x16 + (BLK32 ? blk32_byte(row, i * 256 + lane * 8, 768) >> 1 : row * 768 + i * 256 + lane * 8)) = o;
-            else __builtin_nontemporal_store(o, (h8*)(x16 + row * 768 + i * 256 + lane * 8));
+            if (STAT) *(h8*)(x16 + (BLK32 ? blk32_byte(row, i * 256 + lane * 8, D) >> 1 : row * D + i * 256 + lane * 8)) = o;
+            else __builtin_nontemporal_store(o, (h8*)(x16 + row * D + i * 256 + lane * 8));
             if (STAT) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) val[e] = (float)o[e];
@@ -175,7 +183,7 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
     float s = 0.f;
     const bool use_d = !(POSROW && cls);          // POSROW: the CLS slot of the patch-embedding buffer was never written
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < NP; ++i) {
         if (D1 && use_d) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[i][e] += T::to_f32(d1[i][e]);
@@ -194,22 +202,22 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
         for (int o = 16; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
         return t;
     };
-    const float mean = sum32(s) * (1.0f / 768.0f);
+    const float mean = sum32(s) * (1.0f / (float)D);
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NP; ++i)
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float d = v[i][e] - mean;
             q += d * d;
         }
-    const float rstd = rsqrtf(sum32(q) * (1.0f / 768.0f) + eps);
+    const float rstd = rsqrtf(sum32(q) * (1.0f / (float)D) + eps);
     if (STAT) {
         if (lane == 0) stat[row] = rstd;
         return;
     }
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < NP; ++i) {
         const int c = i * 256 + lane * 8;
         const f4 g0 = *(const f4*)(g + c), g1 = *(const f4*)(g + c + 4), b0 = *(const f4*)(b + c), b1 = *(const f4*)(b + c + 4);
         float y[8];
@@ -222,7 +230,7 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
         V8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = T::from_f32(y[e]);
-        *(V8*)(out16 + row * 768 + c) = o;
+        *(V8*)(out16 + row * D + c) = o;
     }
 }
 
@@ -295,7 +303,7 @@ __global__ void vit_cls_rows_kernel(float* __restrict__ X, const float* __restri
 // ---- BERT embeddings: LN(word[id] + pos[t] + type[0]) -> X fp32 + H 16-bit; key bias from the attention mask ------
 // IDX: `text` is a resident table [rows, 2W] and item m reads row index[m]; a value outside [0, rows) is a padding slot — never
 // dereferenced, all-zero ids and mask (what `dataset.py:79-84` ships for pad slots).
-template <typename T, bool IDX = false>
+template <typename T, bool IDX = false, int D = 768>
 __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __restrict__ text, const float* __restrict__ word,
                                                             const float* __restrict__ pos, const float* __restrict__ type0,
                                                             const float* __restrict__ g, const float* __restrict__ b, float eps,
@@ -303,6 +311,8 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __res
                                                             float* __restrict__ key_bias, int64_t M, int W, int vocab,
                                                             _Float16* __restrict__ X16, float* __restrict__ Xc,
                                                             const int64_t* __restrict__ index = nullptr, int64_t rows = 0) {
+    constexpr int NP = D / 256;
+    static_assert(D % 256 == 0 && NP >= 1 && NP <= 4, "row width: a multiple of 256, at most 1024");
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M * W) return;
@@ -320,30 +330,30 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __res
     }
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     if (lane == 0) key_bias[row] = msk != 0 ? 0.0f : -1.0f;
-    const float* wr = word + id * 768;
-    const float* pr = pos + (int64_t)t * 768;
-    f4 v[3];
+    const float* wr = word + id * D;
+    const float* pr = pos + (int64_t)t * D;
+    f4 v[NP];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < NP; ++i) {
         const int c = i * 256 + lane * 4;
         const f4 a = *(const f4*)(wr + c), p2 = *(const f4*)(pr + c), ty = *(const f4*)(type0 + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[i][e] = a[e] + p2[e] + ty[e];
         s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
     }
-    const float mean = wave_sum(s) * (1.0f / 768.0f);
+    const float mean = wave_sum(s) * (1.0f / (float)D);
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NP; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float d = v[i][e] - mean;
             q += d * d;
         }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / 768.0f) + eps);
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / (float)D) + eps);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < NP; ++i) {
         const int c = i * 256 + lane * 4;
         const f4 gg = *(const f4*)(g + c), bb = *(const f4*)(b + c);
         f4 y;
@@ -354,17 +364,17 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __res
             o[e] = T::from_f32(y[e]);
         }
         if (X) {
-            *(f4*)(X + row * 768 + c) = y;
+            *(f4*)(X + row * D + c) = y;
         } else if (t == 0) {                 // mixed-precision residual stream: CLS rows fp32 (compact), the others fp16
-            *(f4*)(Xc + m * 768 + c) = y;
+            *(f4*)(Xc + m * D + c) = y;
         } else if ((const void*)H != (const void*)X16) {     // (H == X16: the fp16 image is the stream — one store below covers every row)
             typedef _Float16 hv4 __attribute__((ext_vector_type(4)));
             hv4 xh;
 #pragma unroll
             for (int e = 0; e < 4; ++e) xh[e] = (_Float16)y[e];
-            *(hv4*)(X16 + row * 768 + c) = xh;
+            *(hv4*)(X16 + row * D + c) = xh;
         }
-        *(typename T::v4*)(H + row * 768 + c) = o;
+        *(typename T::v4*)(H + row * D + c) = o;
     }
 }
 
@@ -396,72 +406,92 @@ __global__ void cast16_kernel(const float* __restrict__ src, typename T::elem* _
 
 }  // namespace
 
+// width: 768 or 1024 (the two instantiated row widths; anything else is IISAN_EBADSHAPE)
 int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, const void* delta16b, const float* g,
-                             const float* b, float eps, float* sum32, void* out16, float* out32, int64_t rows, hipStream_t s) {
+                             const float* b, float eps, float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s) {
+    IISAN_CHECK_SHAPE(width == 768 || width == 1024, "layernorm: row width %d not instantiated (768 and 1024 are)", width);
     if (rows <= 0) return IISAN_OK;
     dim3 grid((unsigned)ceil_div(rows, 4)), block(256);
     const int v = (delta16 ? 1 : 0) | (delta16b ? 2 : 0) | (sum32 ? 4 : 0) | (g ? 8 : 0);
+#define LN768_LAUNCH(TT, EL, V, W)                                                                                             \
+    hipLaunchKernelGGL((layernorm768_kernel<TT, V, W>), grid, block, 0, s, x, (const EL*)delta16, (const EL*)delta16b, g, b, eps, sum32, (EL*)out16, out32, rows)
 #define LN768_CASE(V)                                                                                                          \
     case V:                                                                                                                    \
-        if (dtype16 == IISAN_BF16)                                                                                             \
-            hipLaunchKernelGGL((layernorm768_kernel<BF16, V>), grid, block, 0, s, x, (const __bf16*)delta16, (const __bf16*)delta16b, g, b, eps, sum32, (__bf16*)out16, out32, rows); \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((layernorm768_kernel<F16, V>), grid, block, 0, s, x, (const _Float16*)delta16, (const _Float16*)delta16b, g, b, eps, sum32, (_Float16*)out16, out32, rows); \
+        if (width == 768) {                                                                                                    \
+            if (dtype16 == IISAN_BF16) LN768_LAUNCH(BF16, __bf16, V, 768); else LN768_LAUNCH(F16, _Float16, V, 768);           \
+        } else {                                                                                                               \
+            if (dtype16 == IISAN_BF16) LN768_LAUNCH(BF16, __bf16, V, 1024); else LN768_LAUNCH(F16, _Float16, V, 1024);         \
+        }                                                                                                                      \
         break
     switch (v) {
         LN768_CASE(0); LN768_CASE(1); LN768_CASE(2); LN768_CASE(3); LN768_CASE(4); LN768_CASE(5); LN768_CASE(6); LN768_CASE(7);
         LN768_CASE(8); LN768_CASE(9); LN768_CASE(10); LN768_CASE(11); LN768_CASE(12); LN768_CASE(13); LN768_CASE(14); LN768_CASE(15);
     }
 #undef LN768_CASE
+#undef LN768_LAUNCH
     IISAN_LAUNCH_OK();
     return IISAN_OK;
 }
 
 
-// mixed-precision residual stream (layernorm768_mixed_kernel): V = MX_* flags of the operands that exist
+// mixed-precision residual stream (layernorm768_mixed_kernel): V = MX_* flags of the operands that exist; width 768 or 1024 — the
+// operand sets of the LayerNorm-image routes exist at both, those of the product route (MX_STAT, MX_BLK32) at 768 only
 int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, float* xc, const void* delta16, const void* delta16b,
-                              const float* g, const float* b, float eps, void* out16, int64_t items, int Ttok, hipStream_t s,
+                              const float* g, const float* b, float eps, void* out16, int64_t items, int Ttok, int width, hipStream_t s,
                               float* stat) {
+    IISAN_CHECK_SHAPE(width == 768 || width == 1024, "layernorm768_mixed: row width %d not instantiated (768 and 1024 are)", width);
     if (items <= 0) return IISAN_OK;
     IISAN_CHECK_SHAPE(!(V & MX_STAT) || stat, "layernorm768_mixed: MX_STAT needs the statistics buffer");
     const int64_t blocks = (V & MX_CLSONLY) ? ceil_div(items, 8) : items * ((Ttok + 7) / 8);
     IISAN_CHECK_SHAPE(blocks < (1ll << 31), "layernorm768_mixed: grid too large");
     dim3 grid((unsigned)blocks), block(256);
+#define MX_LAUNCH(TT, EL, VV, W)                                                                                               \
+    hipLaunchKernelGGL((layernorm768_mixed_kernel<TT, VV, W>), grid, block, 0, s, x32, (_Float16*)x16, xc, (const EL*)delta16, (const EL*)delta16b, g, b, eps, (EL*)out16, items, Ttok, stat)
+#define MX_CASE768(VV)                                                                                                         \
+    case VV:                                                                                                                   \
+        if (width != 768) break;                                                                                               \
+        if (dtype16 == IISAN_BF16) MX_LAUNCH(BF16, __bf16, VV, 768); else MX_LAUNCH(F16, _Float16, VV, 768);                   \
+        IISAN_LAUNCH_OK();                                                                                                     \
+        return IISAN_OK
 #define MX_CASE(VV)                                                                                                            \
     case VV:                                                                                                                   \
-        if (dtype16 == IISAN_BF16)                                                                                             \
-            hipLaunchKernelGGL((layernorm768_mixed_kernel<BF16, VV>), grid, block, 0, s, x32, (_Float16*)x16, xc, (const __bf16*)delta16, (const __bf16*)delta16b, g, b, eps, (__bf16*)out16, items, Ttok, stat); \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((layernorm768_mixed_kernel<F16, VV>), grid, block, 0, s, x32, (_Float16*)x16, xc, (const _Float16*)delta16, (const _Float16*)delta16b, g, b, eps, (_Float16*)out16, items, Ttok, stat); \
-        break
+        if (width == 768) {                                                                                                    \
+            if (dtype16 == IISAN_BF16) MX_LAUNCH(BF16, __bf16, VV, 768); else MX_LAUNCH(F16, _Float16, VV, 768);               \
+        } else {                                                                                                               \
+            if (dtype16 == IISAN_BF16) MX_LAUNCH(BF16, __bf16, VV, 1024); else MX_LAUNCH(F16, _Float16, VV, 1024);             \
+        }                                                                                                                      \
+        IISAN_LAUNCH_OK();                                                                                                     \
+        return IISAN_OK
     switch (V) {
         MX_CASE(MX_SRC32 | MX_RESV | MX_LN);               // ViT block 0, LN1: fp32 embeddings -> fp16 stream + LN image
         MX_CASE(MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_LN);   // ViT block 0, LN1: position table + 16-bit patch embedding -> stream + image
         MX_CASE(MX_D1 | MX_LN);                            // ViT LN2: LN(x + dO), x not written
         MX_CASE(MX_D1 | MX_D2 | MX_RESV | MX_LN);          // ViT LN1: x += dO + dF; LN
-        MX_CASE(MX_D1 | MX_D2 | MX_RESV | MX_CLSONLY);     // ViT closing add of the CLS rows (hidden state 12)
+        MX_CASE(MX_D1 | MX_D2 | MX_RESV | MX_CLSONLY);     // ViT closing add of the CLS rows (the last hidden state)
         MX_CASE(MX_D1 | MX_LN | MX_RESY);                  // BERT: x = LN(x + d)
         MX_CASE(MX_D1 | MX_LN | MX_RESY | MX_ALIAS);       // BERT, fp16 operands: ... and the image IS the stream
-        // LayerNorm applied by the consuming product (Gemm16Args::rowstat): the stream and the row statistics only
-        MX_CASE(MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_STAT);   // ViT block 0
-        MX_CASE(MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_STAT | MX_BLK32);   // ... into a block-major stream
-        MX_CASE(MX_D1 | MX_RESV | MX_STAT);                // ViT LN1 (x += dF) and LN2 (x += dO)
-        MX_CASE(MX_D1 | MX_RESV | MX_CLSONLY);             // ViT closing add of the CLS rows when x + dO is in the stream already
-        default: iisan_set_error("layernorm768_mixed: operand set %d not instantiated", V); return IISAN_EBADSHAPE;
+        // LayerNorm applied by the consuming product (Gemm16Args::rowstat): the stream and the row statistics only — 768 wide
+        MX_CASE768(MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_STAT);   // ViT block 0
+        MX_CASE768(MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_STAT | MX_BLK32);   // ... into a block-major stream
+        MX_CASE768(MX_D1 | MX_RESV | MX_STAT);             // ViT LN1 (x += dF) and LN2 (x += dO)
+        MX_CASE768(MX_D1 | MX_RESV | MX_CLSONLY);          // ViT closing add of the CLS rows when x + dO is in the stream already
+        default: break;
     }
 #undef MX_CASE
-    IISAN_LAUNCH_OK();
-    return IISAN_OK;
+#undef MX_CASE768
+#undef MX_LAUNCH
+    iisan_set_error("layernorm768_mixed: operand set %d not instantiated at row width %d", V, width);
+    return IISAN_EBADSHAPE;
 }
 
 int launch_add_layernorm768(int dtype16, const float* x, const void* delta16, const float* g, const float* b, float eps,
-                            float* sum32, void* out16, float* out32, int64_t rows, hipStream_t s) {
-    return launch_add2_layernorm768(dtype16, x, delta16, nullptr, g, b, eps, sum32, out16, out32, rows, s);
+                            float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s) {
+    return launch_add2_layernorm768(dtype16, x, delta16, nullptr, g, b, eps, sum32, out16, out32, rows, width, s);
 }
 
 int launch_layernorm768(int dtype16, const float* x, const float* g, const float* b, float eps, void* out16,
-                        float* out32, int64_t rows, hipStream_t s) {
-    return launch_add_layernorm768(dtype16, x, nullptr, g, b, eps, nullptr, out16, out32, rows, s);
+                        float* out32, int64_t rows, int width, hipStream_t s) {
+    return launch_add_layernorm768(dtype16, x, nullptr, g, b, eps, nullptr, out16, out32, rows, width, s);
 }
 
 int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64_t M, int C, int R, int p, hipStream_t s) {
@@ -500,28 +530,35 @@ int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M,
     return IISAN_OK;
 }
 
-int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, const float* pos, const float* type0,
-                         const float* g, const float* b, float eps, float* X, void* H, float* key_bias, int64_t M,
-                         int W, int vocab, hipStream_t s, void* X16, float* Xc) {       // X == null: mixed stream (X16 + Xc)
+// one launcher for the direct (index == null) and the indexed form; width 768 or 1024
+template <bool IDX>
+static int bert_embed_ln_any(int dtype16, const int64_t* text, int64_t rows, const int64_t* index, const float* word, const float* pos,
+                             const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
+                             int64_t M, int W, int vocab, int width, hipStream_t s, void* X16, float* Xc) {
+    IISAN_CHECK_SHAPE(width == 768 || width == 1024, "bert_embed_ln: row width %d not instantiated (768 and 1024 are)", width);
     dim3 grid((unsigned)ceil_div(M * W, 4)), block(256);
-    if (dtype16 == IISAN_BF16)
-        hipLaunchKernelGGL(bert_embed_ln_kernel<BF16>, grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (__bf16*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc);
-    else
-        hipLaunchKernelGGL(bert_embed_ln_kernel<F16>, grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (_Float16*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc);
+#define EMBED_LAUNCH(TT, EL, WD)                                                                                               \
+    hipLaunchKernelGGL((bert_embed_ln_kernel<TT, IDX, WD>), grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (EL*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows)
+    if (width == 768) {
+        if (dtype16 == IISAN_BF16) EMBED_LAUNCH(BF16, __bf16, 768); else EMBED_LAUNCH(F16, _Float16, 768);
+    } else {
+        if (dtype16 == IISAN_BF16) EMBED_LAUNCH(BF16, __bf16, 1024); else EMBED_LAUNCH(F16, _Float16, 1024);
+    }
+#undef EMBED_LAUNCH
     IISAN_LAUNCH_OK();
     return IISAN_OK;
 }
 
+int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, const float* pos, const float* type0,
+                         const float* g, const float* b, float eps, float* X, void* H, float* key_bias, int64_t M,
+                         int W, int vocab, int width, hipStream_t s, void* X16, float* Xc) {       // X == null: mixed stream (X16 + Xc)
+    return bert_embed_ln_any<false>(dtype16, text, 0, nullptr, word, pos, type0, g, b, eps, X, H, key_bias, M, W, vocab, width, s, X16, Xc);
+}
+
 int launch_bert_embed_ln_indexed(int dtype16, const int64_t* table, int64_t rows, const int64_t* index, const float* word, const float* pos,
                                  const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
-                                 int64_t M, int W, int vocab, hipStream_t s, void* X16, float* Xc) {
-    dim3 grid((unsigned)ceil_div(M * W, 4)), block(256);
-    if (dtype16 == IISAN_BF16)
-        hipLaunchKernelGGL((bert_embed_ln_kernel<BF16, true>), grid, block, 0, s, table, word, pos, type0, g, b, eps, X, (__bf16*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows);
-    else
-        hipLaunchKernelGGL((bert_embed_ln_kernel<F16, true>), grid, block, 0, s, table, word, pos, type0, g, b, eps, X, (_Float16*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows);
-    IISAN_LAUNCH_OK();
-    return IISAN_OK;
+                                 int64_t M, int W, int vocab, int width, hipStream_t s, void* X16, float* Xc) {
+    return bert_embed_ln_any<true>(dtype16, table, rows, index, word, pos, type0, g, b, eps, X, H, key_bias, M, W, vocab, width, s, X16, Xc);
 }
 
 int launch_gather_rows16(const void* H, void* out, int64_t M, int T, int D, hipStream_t s) {
@@ -539,7 +576,12 @@ int launch_gather_cls(const float* X, float* taps, int64_t M, int T, int D, int 
 
 extern "C" int iisan_layernorm768(int32_t dtype16, const float* x, const float* g, const float* b, float eps,
                                   void* out16, float* out32, int64_t rows, void* stream) {
-    return launch_layernorm768(dtype16, x, g, b, eps, out16, out32, rows, (hipStream_t)stream);
+    return launch_layernorm768(dtype16, x, g, b, eps, out16, out32, rows, 768, (hipStream_t)stream);
+}
+
+extern "C" int iisan_layernorm(int32_t dtype16, const float* x, const float* g, const float* b, float eps,
+                               void* out16, float* out32, int64_t rows, int32_t width, void* stream) {
+    return launch_layernorm768(dtype16, x, g, b, eps, out16, out32, rows, width, (hipStream_t)stream);
 }
 
 // ---- packed tap store gather: out[m, :] = fp32(table[ids[m], :]), rows of `row_elems` (multiple of 8) ----

@@ -95,12 +95,13 @@ class PackedVit(_PackedEncoder):
         s.image, s.patch, s.channels, s.dtype16, s.eps = cfg.image, cfg.patch, cfg.channels, dtype16, cfg.eps
         s.patch_w, s.patch_b = self._m16("patch_w"), self._v32("patch_b")
         s.cls_token, s.pos_emb = self._v32("cls_token"), self._v32("pos_emb")
-        self._layers(s, cfg.layers, masters=dtype16 == _lib.IISAN_F16)
-        self.struct = s
-        self._w = None
-        # LayerNorm 1 / 2 folded into the QKV / FC1 weights once, here, instead of at the start of every forward call
+        # LayerNorm 1 / 2 folded into the QKV / FC1 weights once, here, instead of at the start of every forward call — where the
+        # executor has that route (fp16 operands, hidden 768; 0 bytes otherwise: a 1024-wide tower keeps no fp32 masters)
         lib = _lib.load()
         nbytes = lib.iisan_vit_fold_bytes(C.byref(s))
+        self._layers(s, cfg.layers, masters=nbytes > 0)
+        self.struct = s
+        self._w = None
         if nbytes and self.device.type == "cuda":
             self._folded = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
             with torch.cuda.device(self.device):

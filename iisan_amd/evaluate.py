@@ -10,7 +10,8 @@
 * `item_table`  replaces `get_MM_item_embeddings` (`metrics.py:69-107`): items are sharded across ranks instead of being
   encoded redundantly by every rank.
 * `build_tap_cache`  is what `Code_Cached/preprocess_vectors.py:68-112` does with HuggingFace models: the per-layer CLS
-  taps `[N, L+1, 768]` of a catalogue, from the same encoder kernels as the Uncached path.
+  taps `[N, L+1, D]` of a catalogue, from the same encoder kernels as the Uncached path; D is each tower's OWN hidden size
+  (768: ViT-B / BERT-base; 1024: ViT-L / BERT-large — the widths `Code_Cached_Asym/preprocess_*.py` caches for Versa).
 * `item_table_from_store` / `build_tap_cache_from_store`  the same two over an item store (`iisan_amd.itemstore`): id ranges
   through the indexed encoder entries, no image batch on the host or the device.
 """
@@ -26,7 +27,9 @@ from . import dp, ops
 
 @torch.no_grad()
 def build_tap_cache(model, images: torch.Tensor, text: torch.Tensor, batch: int = 256) -> Tuple[torch.Tensor, torch.Tensor]:
-    """CLS taps of every hidden state for a catalogue: ([N, Lc+1, 768], [N, Lt+1, 768]) fp32 on the inputs' device."""
+    """CLS taps of every hidden state for a catalogue: ([N, Lc+1, Dc], [N, Lt+1, Dt]) fp32 on the inputs' device.  The widths are
+    the towers' own hidden sizes (768 or 1024; the two towers may differ), not the side network's: a 24-layer ViT-L/16 gives the
+    [N, 25, 1024] image taps of the Versa variant.  Always eval mode (no tower dropout)."""
     enc = model.mm_encoder
     cvs, txs = [], []
     for i in range(0, images.shape[0], batch):
@@ -77,7 +80,8 @@ def _store_batches(model, store, lo: int, hi: int, batch: int):
 @torch.no_grad()
 def build_tap_cache_from_store(model, store, batch: int = 256) -> Tuple[torch.Tensor, torch.Tensor]:
     """`build_tap_cache` over the catalogue of an item store (`iisan_amd.itemstore`): the encoders read the store's rows by index,
-    no image batch is materialised.  Row 0 = the padding item (zero image, zero title)."""
+    no image batch is materialised.  Row 0 = the padding item (zero image, zero title).  Widths as in `build_tap_cache`: each
+    tower's own hidden size."""
     enc = model.mm_encoder
     cvs, txs = [], []
     for cat, txt, index in _store_batches(model, store, 0, store.rows, batch):

@@ -90,7 +90,7 @@ class Vit_Encoder(nn.Module):                      # encoders.py:23-31
         return _vit_canonical(self.image_net)[1].layers if self._packed is None else self._packed.cfg.layers
 
     def forward_taps(self, item_content, tap_layers):
-        """CLS rows of the requested hidden states, [M, len(tap_layers), 768] fp32 (no grad)."""
+        """CLS rows of the requested hidden states, [M, len(tap_layers), D] fp32 (no grad); D = the tower's hidden size (768 or 1024)."""
         with torch.no_grad():
             pk = self.packed(item_content.device)
             pk.full_blocks = getattr(self, "full_blocks", False)      # True: every block on every token, like HF (bench.py)

@@ -71,6 +71,10 @@ class BertConfig:
 
 VIT_BASE = VitConfig()
 BERT_BASE = BertConfig()
+# the 1024-wide pair (HF `vit-large-patch16-224` / `bert-large-uncased`: 24 layers, 16 heads x 64, mlp 4096; 30522 words, eps 1e-12):
+# the towers whose taps the Versa variant consumes (`Code_Cached_Asym/parameters.py`: text_embedding_dim 1024, text_layers 24)
+VIT_LARGE = VitConfig(hidden=1024, layers=24, heads=16, mlp=4096)
+BERT_LARGE = BertConfig(hidden=1024, layers=24, heads=16, mlp=4096)
 
 
 def _normal(rs: np.random.RandomState, shape, std: float) -> torch.Tensor:

@@ -47,6 +47,11 @@ const char* iisan_last_error(void);
 /* ------------------------------------------------------------------------------------------------------------
  * Frozen encoders (no-grad).  Weights are packed once by the host (iisan_amd/encoders.py): matrices in the 16-bit
  * operand type, [out,in] row-major exactly like torch.nn.Linear.weight; vectors in fp32.
+ * Hidden size D = 64 * heads with D = 768 (ViT-B/16, BERT-base: 12 heads) or D = 1024 (ViT-L/16, BERT-large: 16 heads); any other
+ * width is IISAN_EBADSHAPE before any launch.  The taps are D wide — the tower's own width, not the side network's.
+ * D = 1024 runs on the LayerNorm-image route of both executors (mixed fp16 / fp32-CLS residual stream; dev switch resid32 works
+ * too).  The LayerNorm-folded route of the ViT executor (folded weights, stream epilogues, block-major stream) is 768 wide only:
+ * at D = 1024 iisan_vit_fold_bytes is 0, `folded` is ignored, and the dev switch ln_fold selects nothing.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct {
     const void* qkv_w;  const float* qkv_b;   /* [3D,D] 16-bit, [3D]  (q;k;v stacked)                          */
@@ -97,7 +102,7 @@ typedef struct {
  * array.  `chunk_items` (0 = whole batch) bounds the activation working set. */
 /* The folded weights of `w` (LayerNorm 1 / 2 of every layer folded into qkv_w / fc1_w: gamma-scaled, centred, fp16, rounded
  * sum-preservingly from the fp32 masters when the layer has them, + the folded biases): [layers][(3D + F) x D] fp16, then
- * [layers][3D + F] fp32.  0 bytes when the executor would not use them (bf16 operands). */
+ * [layers][3D + F] fp32.  0 bytes when the executor would not use them (bf16 operands; hidden size 1024). */
 size_t iisan_vit_fold_bytes(const iisan_vit_weights* w);
 int iisan_vit_fold_layernorm(const iisan_vit_weights* w, void* folded, size_t bytes, void* stream);
 /* fp16 operands (dtype16 = IISAN_F16), production sizes: the executor folds LayerNorm 1 / 2 of every block into the QKV / FC1
@@ -160,7 +165,8 @@ typedef struct { float hidden_p; float attn_p; uint64_t seed; } iisan_bert_dropo
  * (index != NULL) with dropout.  drop == NULL or both probabilities 0: exactly the launches and the bits of those two.  Otherwise
  * the variants of csrc/bert_drop.hip run, for both operand types; dead-work pruning is unchanged.  Workspace:
  * iisan_bert_forward_taps_ws_bytes is sufficient.  IISAN_EBADSHAPE before any launch: a probability outside [0, 1); dropout asked for
- * under the development switch resid32 = 1 (never a silent fall-back to eval mode). */
+ * under the development switch resid32 = 1, or at a hidden size other than 768 — the train-mode kernels are 768 wide, and tap caches
+ * of the wide towers are built in eval mode (never a silent fall-back to eval mode). */
 int iisan_bert_forward_taps_dropout(const iisan_bert_weights* w, const int64_t* text_or_table, int64_t rows,
                                     const int64_t* index, int64_t M, int32_t words,
                                     const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
@@ -327,6 +333,10 @@ int iisan_gemm16(int32_t dtype16, int32_t mode, const void* A, const void* W, co
 /* LayerNorm over rows of width 768: out16 (nullable) / out32 (nullable) */
 int iisan_layernorm768(int32_t dtype16, const float* x, const float* g, const float* b, float eps,
                        void* out16, float* out32, int64_t rows, void* stream);
+/* The same over rows of `width` elements, width 768 or 1024 — the two row widths the encoders' row kernels are built for
+ * (ViT-B / BERT-base, ViT-L / BERT-large).  Any other width: IISAN_EBADSHAPE, nothing launched.  At width 768 it is the call above. */
+int iisan_layernorm(int32_t dtype16, const float* x, const float* g, const float* b, float eps,
+                    void* out16, float* out32, int64_t rows, int32_t width, void* stream);
 /* softmax(QK^T/sqrt(64) + key_bias)V per (item, head); qkv 16-bit HEAD-MAJOR [items, H, 3 (q|k|v), S, 64] (what the QKV
  * GEMM epilogue of the encoders writes); ctx 16-bit token-major [items*S, H*64];
  * key_bias fp32 [items,S] or NULL (values < 0 mark masked keys) */
