@@ -5,13 +5,18 @@
 //   site 0 = embeddings, 1 + 3l = attention probabilities of block l, 2 + 3l = attention-output dense, 3 + 3l = FFN-output dense,
 //   hidden sites:    index = (m T + t) 768 + c          attention sites: index = ((m H + h) T + q) T + k
 // where m is the slot's position in the WHOLE call — so chunked and unchunked, indexed and direct calls, and the CLS-only last block
-// and the all-token execution draw the same masks.  The eval-mode kernels (attn16.hip, rowops.hip) are not touched: every kernel here is
-// a variant of its own, launched only when a dropout description with a non-zero probability is given.
+// and the all-token execution draw the same masks.
+// This file holds the attention kernel, built from the per-block core it shares with the eval-mode kernels (attn16_block.h).  The three
+// hidden sites are instantiations of the eval-mode row kernels with a keep functor (RowKeep, common.h; rowops.hip).  Either way a
+// train-mode kernel is launched only when a dropout description with a non-zero probability is given, and the eval-mode instantiations
+// compile to the code they had before the functor existed (profiles/rowops_shared_body.md).
 #include "attn16_block.h"
 
-// launches of this file's kernels: with the switch off a step leaves it at 0 — it runs the eval-mode launch sequence (tests, tools/bert_dropout_time.py)
+// train-mode launches, this file's and those of rowops.hip: with the switch off a step leaves it at 0 — it runs the eval-mode launch
+// sequence (tests, tools/bert_dropout_time.py)
 static int64_t g_cnt_bert_drop = 0;
 IISAN_DEV_COUNTER(bert_drop, g_cnt_bert_drop);
+void iisan_count_bert_drop() { ++g_cnt_bert_drop; }
 
 namespace {
 
@@ -151,223 +156,6 @@ int launch_attn_t(const void* qkv, const float* key_bias, void* ctx, const void*
     return IISAN_OK;
 }
 
-// ---- x = LN(x + drop(delta)) on the mixed residual stream ---------------------------------------------------------------------------
-// The add + LayerNorm step behind the O / FC2 products (layernorm768_mixed_kernel with MX_D1 | MX_LN | MX_RESY [| MX_ALIAS], rowops.hip)
-// with the keep factor applied to the 16-bit delta as it is read: no extra pass over HBM, no extra rounding of the delta.  CLS rows fp32
-// in `xc` [items, 768], every other row fp16 in `x16`; ALIAS: out16 IS x16 (fp16 operands).  Half a wave per token row, a workgroup = 8
-// consecutive tokens of one item.  row0 = index of the chunk's first token row in the whole call.
-template <typename T, bool ALIAS>
-__global__ __launch_bounds__(256) void add_ln_drop_mixed_kernel(_Float16* x16, float* xc, const typename T::elem* __restrict__ delta,
-                                                                const float* __restrict__ g, const float* __restrict__ b, float eps,
-                                                                typename T::elem* out16, int64_t items, int Ttok, DropCfg drop,
-                                                                int64_t row0) {
-    typedef typename T::v8 V8;
-    const int lane = threadIdx.x & 31, half = threadIdx.x >> 5;
-    const int bpi = (Ttok + 7) >> 3;
-    const int64_t item = blockIdx.x / bpi;
-    const int tok = (int)(blockIdx.x - item * bpi) * 8 + half;
-    if (tok >= Ttok) return;
-    const int64_t row = item * Ttok + tok;
-    const bool cls = tok == 0;                                            // uniform within the half-wave
-    V8 d1[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) d1[i] = __builtin_nontemporal_load((const V8*)(delta + row * 768 + i * 256 + lane * 8));
-    float v[3][8];
-    if (cls) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const f4 a = *(const f4*)(xc + item * 768 + i * 256 + lane * 8), c = *(const f4*)(xc + item * 768 + i * 256 + lane * 8 + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { v[i][e] = a[e]; v[i][4 + e] = c[e]; }
-        }
-    } else {
-        h8 xh[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) xh[i] = __builtin_nontemporal_load((const h8*)(x16 + row * 768 + i * 256 + lane * 8));
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[i][e] = (float)xh[i][e];
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const uint64_t idx = (uint64_t)(row0 + row) * 768u + (uint64_t)(i * 256 + lane * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            v[i][e] += drop_scale(drop.seed, drop.site, idx + e, drop.thr24, drop.inv_keep) * T::to_f32(d1[i][e]);
-            s += v[i][e];
-        }
-    }
-    auto sum32 = [](float t) {          // over the 32 lanes of the half-wave
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-        return t;
-    };
-    const float mean = sum32(s) * (1.0f / 768.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float d = v[i][e] - mean;
-            q += d * d;
-        }
-    const float rstd = rsqrtf(sum32(q) * (1.0f / 768.0f) + eps);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int c = i * 256 + lane * 8;
-        const f4 g0 = *(const f4*)(g + c), g1 = *(const f4*)(g + c + 4), b0 = *(const f4*)(b + c), b1 = *(const f4*)(b + c + 4);
-        float y[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            y[e] = (v[i][e] - mean) * rstd * g0[e] + b0[e];
-            y[4 + e] = (v[i][4 + e] - mean) * rstd * g1[e] + b1[e];
-        }
-        if (cls) {
-            *(f4*)(xc + item * 768 + c) = (f4){y[0], y[1], y[2], y[3]};
-            *(f4*)(xc + item * 768 + c + 4) = (f4){y[4], y[5], y[6], y[7]};
-        } else if (!ALIAS) {
-            h8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (_Float16)y[e];
-            __builtin_nontemporal_store(o, (h8*)(x16 + row * 768 + c));
-        }
-        V8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = T::from_f32(y[e]);
-        *(V8*)(out16 + row * 768 + c) = o;
-    }
-}
-
-// ---- the same on compact fp32 rows: the CLS rows of the last live block -------------------------------------------------------------
-// x [rows, 768] fp32 in place, row r = the CLS token of item item0 + r: the mask index is that of TOKEN row (item0 + r) Ttok of the
-// all-token execution.  out16 (optional): the 16-bit image of the result.  One wave per row (layernorm768_kernel, rowops.hip).
-template <typename T>
-__global__ __launch_bounds__(256) void add_ln_drop_rows_kernel(float* x, const typename T::elem* __restrict__ delta,
-                                                               const float* __restrict__ g, const float* __restrict__ b, float eps,
-                                                               typename T::elem* __restrict__ out16, int64_t rows, DropCfg drop,
-                                                               int64_t item0, int Ttok) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    f4 v[3];
-    typename T::v4 d1[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        v[i] = *(const f4*)(x + row * 768 + i * 256 + lane * 4);
-        d1[i] = *(const typename T::v4*)(delta + row * 768 + i * 256 + lane * 4);
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const uint64_t idx = (uint64_t)(item0 + row) * (uint64_t)Ttok * 768u + (uint64_t)(i * 256 + lane * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[i][e] += drop_scale(drop.seed, drop.site, idx + e, drop.thr24, drop.inv_keep) * T::to_f32(d1[i][e]);
-        s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-    }
-    const float mean = wave_sum(s) * (1.0f / 768.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d = v[i][e] - mean;
-            q += d * d;
-        }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / 768.0f) + eps);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int c = i * 256 + lane * 4;
-        const f4 gg = *(const f4*)(g + c), bb = *(const f4*)(b + c);
-        f4 y;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
-        *(f4*)(x + row * 768 + c) = y;
-        if (out16) {
-            typename T::v4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = T::from_f32(y[e]);
-            *(typename T::v4*)(out16 + row * 768 + c) = o;
-        }
-    }
-}
-
-// ---- embeddings: drop(LN(word[id] + pos[t] + type[0])) = hidden state 0 --------------------------------------------------------------
-// bert_embed_ln_kernel (rowops.hip) for the mixed stream, with the keep factor applied to the fp32 LayerNorm output BEFORE it is rounded:
-// every copy the executor keeps of the row — the 16-bit image H, the fp16 stream X16 (when it is not the image) and the fp32 CLS rows Xc
-// that become tap 0 — holds the dropped value.  m0 = position of the chunk's first slot in the whole call.
-template <typename T, bool IDX>
-__global__ __launch_bounds__(256) void bert_embed_ln_drop_kernel(const int64_t* __restrict__ text, const float* __restrict__ word,
-                                                                 const float* __restrict__ pos, const float* __restrict__ type0,
-                                                                 const float* __restrict__ g, const float* __restrict__ b, float eps,
-                                                                 typename T::elem* __restrict__ H, float* __restrict__ key_bias,
-                                                                 int64_t M, int W, int vocab, _Float16* __restrict__ X16,
-                                                                 float* __restrict__ Xc, const int64_t* __restrict__ index, int64_t rows,
-                                                                 DropCfg drop, int64_t m0) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M * W) return;
-    const int64_t m = row / W;
-    const int t = (int)(row % W);
-    int64_t id, msk;
-    if constexpr (IDX) {
-        const int64_t sm = index[m];
-        const bool pad = (uint64_t)sm >= (uint64_t)rows;      // a padding slot: never dereferenced, all-zero ids and mask
-        id = pad ? 0 : text[sm * 2 * W + t];
-        msk = pad ? 0 : text[sm * 2 * W + W + t];
-    } else {
-        id = text[m * 2 * W + t];
-        msk = text[m * 2 * W + W + t];
-    }
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    if (lane == 0) key_bias[row] = msk != 0 ? 0.0f : -1.0f;
-    const float* wr = word + id * 768;
-    const float* pr = pos + (int64_t)t * 768;
-    f4 v[3];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int c = i * 256 + lane * 4;
-        const f4 a = *(const f4*)(wr + c), p2 = *(const f4*)(pr + c), ty = *(const f4*)(type0 + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[i][e] = a[e] + p2[e] + ty[e];
-        s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-    }
-    const float mean = wave_sum(s) * (1.0f / 768.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d = v[i][e] - mean;
-            q += d * d;
-        }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / 768.0f) + eps);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int c = i * 256 + lane * 4;
-        const f4 gg = *(const f4*)(g + c), bb = *(const f4*)(b + c);
-        const uint64_t idx = (uint64_t)(m0 * W + row) * 768u + (uint64_t)c;
-        f4 y;
-        typename T::v4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            y[e] = ((v[i][e] - mean) * rstd * gg[e] + bb[e]) * drop_scale(drop.seed, drop.site, idx + e, drop.thr24, drop.inv_keep);
-            o[e] = T::from_f32(y[e]);
-        }
-        if (t == 0) {                        // CLS rows fp32 (compact), the others fp16
-            *(f4*)(Xc + m * 768 + c) = y;
-        } else if ((const void*)H != (const void*)X16) {     // (H == X16: the fp16 image is the stream — one store below covers every row)
-            h4 xh;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xh[e] = (_Float16)y[e];
-            *(h4*)(X16 + row * 768 + c) = xh;
-        }
-        *(typename T::v4*)(H + row * 768 + c) = o;
-    }
-}
-
 }  // namespace
 
 int launch_attention16_drop(int dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int S, int heads,
@@ -382,51 +170,6 @@ int launch_attention16_drop(int dtype16, const void* qkv, const float* key_bias,
                         : launch_attn_t<BF16, false>(qkv, key_bias, ctx, nullptr, items, S, heads, drop, slot0, s);
     return cls_only ? launch_attn_t<F16, true>(qkv, key_bias, ctx, q_cls, items, S, heads, drop, slot0, s)
                     : launch_attn_t<F16, false>(qkv, key_bias, ctx, nullptr, items, S, heads, drop, slot0, s);
-}
-
-int launch_add_ln_drop_mixed(int dtype16, bool alias, void* x16, float* xc, const void* delta16, const float* g, const float* b, float eps,
-                             void* out16, int64_t items, int Ttok, const DropCfg& drop, int64_t row0, hipStream_t s) {
-    if (items <= 0) return IISAN_OK;
-    IISAN_CHECK_SHAPE(!alias || (dtype16 == IISAN_F16 && out16 == x16), "add_ln_drop_mixed: the aliased image needs fp16 operands and out16 == x16");
-    const int64_t blocks = items * ((Ttok + 7) / 8);
-    IISAN_CHECK_SHAPE(blocks < (1ll << 31), "add_ln_drop_mixed: grid too large");
-    dim3 grid((unsigned)blocks), block(256);
-    if (dtype16 == IISAN_BF16)
-        hipLaunchKernelGGL((add_ln_drop_mixed_kernel<BF16, false>), grid, block, 0, s, (_Float16*)x16, xc, (const __bf16*)delta16, g, b, eps, (__bf16*)out16, items, Ttok, drop, row0);
-    else if (alias)
-        hipLaunchKernelGGL((add_ln_drop_mixed_kernel<F16, true>), grid, block, 0, s, (_Float16*)x16, xc, (const _Float16*)delta16, g, b, eps, (_Float16*)out16, items, Ttok, drop, row0);
-    else
-        hipLaunchKernelGGL((add_ln_drop_mixed_kernel<F16, false>), grid, block, 0, s, (_Float16*)x16, xc, (const _Float16*)delta16, g, b, eps, (_Float16*)out16, items, Ttok, drop, row0);
-    ++g_cnt_bert_drop;
-    IISAN_LAUNCH_OK();
-    return IISAN_OK;
-}
-
-int launch_add_ln_drop_rows(int dtype16, float* x, const void* delta16, const float* g, const float* b, float eps, void* out16,
-                            int64_t rows, const DropCfg& drop, int64_t item0, int Ttok, hipStream_t s) {
-    if (rows <= 0) return IISAN_OK;
-    dim3 grid((unsigned)ceil_div(rows, 4)), block(256);
-    if (dtype16 == IISAN_BF16)
-        hipLaunchKernelGGL(add_ln_drop_rows_kernel<BF16>, grid, block, 0, s, x, (const __bf16*)delta16, g, b, eps, (__bf16*)out16, rows, drop, item0, Ttok);
-    else
-        hipLaunchKernelGGL(add_ln_drop_rows_kernel<F16>, grid, block, 0, s, x, (const _Float16*)delta16, g, b, eps, (_Float16*)out16, rows, drop, item0, Ttok);
-    ++g_cnt_bert_drop;
-    IISAN_LAUNCH_OK();
-    return IISAN_OK;
-}
-
-int launch_bert_embed_ln_drop(int dtype16, const int64_t* text, int64_t rows, const int64_t* index, const float* word, const float* pos,
-                              const float* type0, const float* g, const float* b, float eps, void* H, float* key_bias, int64_t M, int W,
-                              int vocab, void* X16, float* Xc, const DropCfg& drop, int64_t m0, hipStream_t s) {
-    dim3 grid((unsigned)ceil_div(M * W, 4)), block(256);
-#define IISAN_EMBED_DROP(T, E, IDX) \
-    hipLaunchKernelGGL((bert_embed_ln_drop_kernel<T, IDX>), grid, block, 0, s, text, word, pos, type0, g, b, eps, (E*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows, drop, m0)
-    if (dtype16 == IISAN_BF16) { if (index) IISAN_EMBED_DROP(BF16, __bf16, true); else IISAN_EMBED_DROP(BF16, __bf16, false); }
-    else { if (index) IISAN_EMBED_DROP(F16, _Float16, true); else IISAN_EMBED_DROP(F16, _Float16, false); }
-#undef IISAN_EMBED_DROP
-    ++g_cnt_bert_drop;
-    IISAN_LAUNCH_OK();
-    return IISAN_OK;
 }
 
 extern "C" int iisan_attention16_dropout(int32_t dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int32_t S,

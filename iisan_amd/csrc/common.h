@@ -234,6 +234,20 @@ static inline DropCfg make_drop(uint64_t seed, uint32_t site, float p) {
     d.inv_keep = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
     return d;
 }
+// Keep functor of the row kernels (rowops.hip: trailing template parameter KEEP, trailing kernel argument).  Off — the default, eval
+// mode — is an empty type and every use sits under `if constexpr (KEEP::on)`: the eval instantiations compile as if it did not exist.
+// On: the dropout site plus the two integers that turn the kernel's LOCAL row number into the row of the whole call, so that the masks
+// do not depend on the chunking: index = (r0 + row * rs) * D + column (include/iisan_hip.h, iisan_bert_dropout).  A launcher takes a
+// `const RowKeep*`, null = eval.
+struct RowKeepNone { static constexpr bool on = false; };
+struct RowKeep {
+    static constexpr bool on = true;
+    DropCfg d;
+    int64_t r0;            // mixed stream: m0 * T     CLS rows: item0 * T     embeddings: m0 * W
+    int32_t rs;            //               1                    T                         1
+    __device__ __forceinline__ uint64_t index(int64_t row, int D, int col) const { return (uint64_t)(r0 + row * rs) * (uint64_t)D + (uint64_t)col; }
+    __device__ __forceinline__ float operator()(uint64_t idx) const { return drop_scale(d.seed, d.site, idx, d.thr24, d.inv_keep); }
+};
 
 // async global -> LDS, 16 bytes per lane; LDS destination = wave-uniform base + lane*16 (guide §5)
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
@@ -339,10 +353,12 @@ int launch_layernorm768(int dtype16, const float* x, const float* g, const float
                         float* out32, int64_t rows, int width, hipStream_t s);
 // x (+ delta16) -> [sum32 = x + delta] -> LayerNorm -> out16 / out32 (any output may be null; g == null: no LayerNorm)
 int launch_add_layernorm768(int dtype16, const float* x, const void* delta16, const float* g, const float* b, float eps,
-                            float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s);
+                            float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s, const RowKeep* keep = nullptr);
 // ... with a second 16-bit delta: v = (x + delta16) + delta16b (either may be null)
+// keep (train mode): v = x + keep * delta16 — instantiated for delta16 + LayerNorm alone (no delta16b, no sum32), width 768
 int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, const void* delta16b, const float* g,
-                             const float* b, float eps, float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s);
+                             const float* b, float eps, float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s,
+                             const RowKeep* keep = nullptr);
 // mixed-precision residual stream (rowops.hip: layernorm768_mixed_kernel): CLS rows fp32 in `xc` [items, width], every other token
 // row fp16 in `x16` [items * Ttok, width]; V = which operands exist (MX_STAT / MX_BLK32 sets: width 768 only)
 enum { MX_D1 = 1, MX_D2 = 2, MX_LN = 4, MX_RESV = 8, MX_RESY = 16, MX_SRC32 = 32, MX_CLSONLY = 64, MX_POSROW = 128, MX_STAT = 256, MX_ALIAS = 512, MX_BLK32 = 1024 };
@@ -353,9 +369,10 @@ enum { MX_D1 = 1, MX_D2 = 2, MX_LN = 4, MX_RESV = 8, MX_RESY = 16, MX_SRC32 = 32
 // is the next GEMM's A operand) and `stat` [rows] receives rstd of the ROUNDED row — Gemm16Args::rowstat
 // MX_POSROW (with MX_SRC32 | MX_D1): the fp32 source is a [Ttok, width] table indexed by the TOKEN (the position embedding) and the delta is
 // the patch embedding of that token; CLS rows take neither (their stream holds cls + pos[0] already)
+// keep (train mode): the delta is added as keep * delta16 — instantiated for MX_D1 | MX_LN | MX_RESY [| MX_ALIAS] at width 768
 int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, float* xc, const void* delta16, const void* delta16b,
                               const float* g, const float* b, float eps, void* out16, int64_t items, int Ttok, int width, hipStream_t s,
-                              float* stat = nullptr);
+                              float* stat = nullptr, const RowKeep* keep = nullptr);
 // LayerNorm folded into the weights of the product that consumes it (rowops.hip): Wf[n][k] = fp16(gamma[k] W[n][k] - mean_k(gamma W[n]))
 // with sum_k Wf[n][k] = 0 to the last bit that matters, bf[n] = bias[n] + sum_k beta[k] W[n][k]; K = 768, fp16 weights.  Up to 32 jobs in one launch.
 struct LnFoldJob { const void* W; const float* bias; const float* g; const float* b; void* Wf; float* bf; int32_t N;
@@ -381,27 +398,20 @@ int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64
 int launch_vit_im2col_indexed(int dtype16, const uint8_t* catalogue, int64_t rows, const int64_t* index, void* out, int64_t M, int C,
                               int R, int p, hipStream_t s);
 int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M, int T, int D, hipStream_t s);
+// keep (train mode): the keep factor multiplies the fp32 LayerNorm output before it is rounded or stored — width 768
 int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, const float* pos, const float* type0,
                          const float* g, const float* b, float eps, float* X, void* H, float* key_bias, int64_t M,
-                         int W, int vocab, int width, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
+                         int W, int vocab, int width, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr, const RowKeep* keep = nullptr);
 // item m = row index[m] of a resident table [rows, 2W]; values outside [0, rows) = padding (zero ids and mask, no read)
 int launch_bert_embed_ln_indexed(int dtype16, const int64_t* table, int64_t rows, const int64_t* index, const float* word, const float* pos,
                                  const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
-                                 int64_t M, int W, int vocab, int width, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr);
-// train-mode dropout of the BERT tower (bert_drop.hip; DropCfg above): variants of the four steps above that apply a counter-based keep
-// factor — slot0 / row0 / item0 / m0 place the chunk in the whole call, so the masks do not depend on the chunking
+                                 int64_t M, int W, int vocab, int width, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr,
+                                 const RowKeep* keep = nullptr);
+// train-mode dropout of the BERT tower: the attention kernel with dropped probabilities (bert_drop.hip) — slot0 places the chunk in the whole
+// call, so the masks do not depend on the chunking; the embedding and add + LayerNorm steps are the row kernels above with a RowKeep
 int launch_attention16_drop(int dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int S, int heads,
                             const DropCfg& drop, int64_t slot0, bool cls_only, const void* q_cls, hipStream_t s);
-// x = LN(x + drop(delta16)) on the mixed stream (launch_layernorm768_mixed with MX_D1 | MX_LN | MX_RESY [| MX_ALIAS])
-int launch_add_ln_drop_mixed(int dtype16, bool alias, void* x16, float* xc, const void* delta16, const float* g, const float* b, float eps,
-                             void* out16, int64_t items, int Ttok, const DropCfg& drop, int64_t row0, hipStream_t s);
-// ... on compact fp32 CLS rows, in place (row r = token row (item0 + r) * Ttok of the all-token execution); out16 may be null
-int launch_add_ln_drop_rows(int dtype16, float* x, const void* delta16, const float* g, const float* b, float eps, void* out16,
-                            int64_t rows, const DropCfg& drop, int64_t item0, int Ttok, hipStream_t s);
-// drop(LN(embeddings)) for the mixed stream; index != null: the indexed form
-int launch_bert_embed_ln_drop(int dtype16, const int64_t* text, int64_t rows, const int64_t* index, const float* word, const float* pos,
-                              const float* type0, const float* g, const float* b, float eps, void* H, float* key_bias, int64_t M, int W,
-                              int vocab, void* X16, float* Xc, const DropCfg& drop, int64_t m0, hipStream_t s);
+void iisan_count_bert_drop();      // ++count:bert_drop (bert_drop.hip): every train-mode launch, whichever file holds the kernel
 int launch_gather_cls(const float* X, float* taps, int64_t M, int T, int D, int n_taps, int k, hipStream_t s);
 int launch_gather_rows16(const void* H, void* out, int64_t M, int T, int D, hipStream_t s);   // out[m] = H[m*T] (16-bit rows)
 

@@ -517,8 +517,9 @@ extern "C" size_t iisan_bert_forward_taps_ws_bytes(const iisan_bert_weights* w, 
 }
 
 // index != null: `text` is a resident table [rows, 2W] and slot m reads row index[m] (the chunk loop offsets the index, never the table)
-// drop: null or both probabilities 0 = eval mode, the launch sequence below unchanged; otherwise the train-mode variants of bert_drop.hip
-// take the place of the embedding, attention and add + LayerNorm steps (sites and indices: include/iisan_hip.h, iisan_bert_dropout)
+// drop: null or both probabilities 0 = eval mode, the launch sequence below unchanged; otherwise the attention kernel of bert_drop.hip takes
+// the place of the eval-mode one, and the embedding and add + LayerNorm steps run their train-mode instantiations (a RowKeep instead of
+// null; rowops.hip) — sites and indices: include/iisan_hip.h, iisan_bert_dropout
 static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* text, int64_t M, int32_t words,
                                   const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
                                   void* ws, size_t ws_bytes, void* stream, const int64_t* index = nullptr, int64_t rows = 0,
@@ -529,10 +530,10 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
         IISAN_CHECK_SHAPE(drop->attn_p >= 0.f && drop->attn_p < 1.f, "bert dropout: attn_p %.3f out of range", drop->attn_p);
     }
     const bool dropping = drop && (drop->hidden_p > 0.f || drop->attn_p > 0.f);
-    // never a silent fall-back to eval mode: the variants exist for the mixed stream only
-    IISAN_CHECK_SHAPE(!(dropping && g_resid32), "bert dropout: not built for the fp32 residual stream of the dev switch resid32 = 1");
-    // ... and for 768-wide rows only (bert_drop.hip): tap caches of the wide towers are built in eval mode
-    IISAN_CHECK_SHAPE(!(dropping && w->hidden != 768), "bert dropout: the train-mode kernels are 768 wide, hidden size %d runs in eval mode only "
+    // never a silent fall-back to eval mode: the row kernels have train-mode instantiations for the mixed stream only
+    IISAN_CHECK_SHAPE(!(dropping && g_resid32), "bert dropout: no train-mode instantiation for the fp32 residual stream of the dev switch resid32 = 1");
+    // ... and for 768-wide rows only (rowops.hip): tap caches of the wide towers are built in eval mode
+    IISAN_CHECK_SHAPE(!(dropping && w->hidden != 768), "bert dropout: no train-mode instantiation at this width, hidden size %d runs in eval mode only "
                       "(drop == NULL or both probabilities 0)", w->hidden);
     const float hp = dropping ? drop->hidden_p : 0.f, ap = dropping ? drop->attn_p : 0.f;
     const uint64_t seed = dropping ? drop->seed : 0;
@@ -560,18 +561,22 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
         // LayerNorm kernels move 6 instead of 8 bytes per element)
         const bool alias = mixed && dt == IISAN_F16 && g_ln_fold;
         void* IMG = alias ? b.X16 : b.H;
-        if (dropping) IISAN_TRY(launch_bert_embed_ln_drop(dt, index ? text : text + m0 * 2 * words, rows, index ? index + m0 : nullptr, w->word_emb,
-                                                          w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b, w->eps, IMG, b.KB, mc, T, w->vocab,
-                                                          b.X16, b.Xc, make_drop(seed, 0, hp), m0, s));
-        else if (index) IISAN_TRY(launch_bert_embed_ln_indexed(dt, text, rows, index + m0, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w,
-                                                          w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc));
-        else IISAN_TRY(launch_bert_embed_ln(dt, text + m0 * 2 * words, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w,
-                                            w->emb_ln_b, w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc));
+        // train mode: the keep functor of a hidden site, local row r of the launch = token row r0 + r * rs of the whole call; eval: null
+        RowKeep rk;
+        auto keep = [&](int site, int64_t r0, int rs) -> const RowKeep* {
+            if (!dropping) return nullptr;
+            rk = RowKeep{make_drop(seed, site, hp), r0, rs};
+            return &rk;
+        };
+        if (index) IISAN_TRY(launch_bert_embed_ln_indexed(dt, text, rows, index + m0, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b,
+                                                          w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc, keep(0, m0 * T, 1)));
+        else IISAN_TRY(launch_bert_embed_ln(dt, text + m0 * 2 * words, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b,
+                                            w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc, keep(0, m0 * T, 1)));
         auto tap = [&](int k) { return mixed ? launch_gather_cls(b.Xc, tp, mc, 1, D, n_taps, k, s) : launch_gather_cls(b.X, tp, mc, T, D, n_taps, k, s); };
         // x = LN(x + delta): stream and 16-bit image out
         auto add_ln = [&](const float* g, const float* be, int site) {
-            if (dropping) return launch_add_ln_drop_mixed(dt, alias, b.X16, b.Xc, b.D16, g, be, w->eps, IMG, mc, T, make_drop(seed, site, hp), m0 * T, s);
-            return mixed ? launch_layernorm768_mixed(dt, MX_D1 | MX_LN | MX_RESY | (alias ? MX_ALIAS : 0), nullptr, b.X16, b.Xc, b.D16, nullptr, g, be, w->eps, IMG, mc, T, D, s)
+            return mixed ? launch_layernorm768_mixed(dt, MX_D1 | MX_LN | MX_RESY | (alias ? MX_ALIAS : 0), nullptr, b.X16, b.Xc, b.D16, nullptr, g, be, w->eps, IMG, mc, T, D, s,
+                                                     nullptr, keep(site, m0 * T, 1))
                          : launch_add_layernorm768(dt, b.X, b.D16, g, be, w->eps, nullptr, b.H, b.X, tok, D, s);
         };
         int k = tap_index(tap_layers, n_taps, 0);
@@ -604,13 +609,11 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
                 else IISAN_TRY(launch_attention_cls16(dt, b.QKV, b.KB, b.H, mc, T, w->heads, s, Qc));
                 IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, mc, s));
                 if (mixed) IISAN_TRY(launch_gather_cls(b.Xc, Xc, mc, 1, D, 1, 0, s)); else IISAN_TRY(launch_gather_cls(b.X, Xc, mc, T, D, 1, 0, s));
-                // (dropping: the masks of token row t = 0 of the all-token execution)
-                if (dropping) IISAN_TRY(launch_add_ln_drop_rows(dt, Xc, b.D16, L.ln1_w, L.ln1_b, w->eps, b.H, mc, make_drop(seed, 2 + 3 * l, hp), m0, T, s));
-                else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln1_w, L.ln1_b, w->eps, nullptr, b.H, Xc, mc, D, s));
+                // (train mode: the masks of token row t = 0 of the all-token execution — compact row r is token row (m0 + r) T)
+                IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln1_w, L.ln1_b, w->eps, nullptr, b.H, Xc, mc, D, s, keep(2 + 3 * l, m0 * T, T)));
                 IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, mc, s));
                 IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, nullptr, mc, s));
-                if (dropping) IISAN_TRY(launch_add_ln_drop_rows(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, mc, make_drop(seed, 3 + 3 * l, hp), m0, T, s));
-                else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, nullptr, Xc, mc, D, s));
+                IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, nullptr, Xc, mc, D, s, keep(3 + 3 * l, m0 * T, T)));
                 k = tap_index(tap_layers, n_taps, live);
                 IISAN_TRY(launch_gather_cls(Xc, tp, mc, 1, D, n_taps, k, s));
             }

@@ -4,6 +4,12 @@
 // The row width D is a template parameter of the LayerNorm / embedding kernels (D / 256 pieces per lane: 3 at 768 — ViT-B, BERT-base —
 // 4 at 1024 — ViT-L, BERT-large); their names keep the 768 they were written for.  The kernels of the ViT's product route
 // (fold_ln_weights, stream_stats_finalize, the MX_STAT / MX_BLK32 operand sets) are 768 wide only.
+// Train-mode dropout of the BERT tower (opt-in, bert_drop.hip) runs the SAME three kernels — layernorm768_mixed_kernel,
+// layernorm768_kernel, bert_embed_ln_kernel — with a keep functor as trailing template parameter and kernel argument (RowKeep,
+// common.h): the keep factor multiplies the 16-bit delta as it is added, or the embedding's LayerNorm output before it is rounded.  The
+// default RowKeepNone is empty and every use sits under `if constexpr (KEEP::on)`: the eval-mode instantiations compile to the
+// instruction stream they had without it (tools/isa_compare.py --ignore-arg RowKeepNone; profiles/rowops_shared_body.md).  RowKeep is
+// instantiated only where the BERT executor launches it, 768 wide: a launcher given a RowKeep for anything else refuses.
 #include "common.h"
 
 namespace {
@@ -16,13 +22,15 @@ namespace {
 // null tests every load sat behind its own branch and hipcc waited for each one before issuing the next — one load in flight
 // per wave, six HBM round trips per row (ISA: load, s_waitcnt vmcnt(0), load, s_waitcnt vmcnt(0), ...).  Now all loads of a
 // row are requested first.
-template <typename T, int V, int D = 768>
+// KEEP on (the CLS rows of BERT's last live block in train mode, V = 9): v = x + keep * delta, local row r = token row r0 + r * rs.
+template <typename T, int V, int D = 768, typename KEEP = RowKeepNone>
 __global__ __launch_bounds__(256) void layernorm768_kernel(const float* x, const typename T::elem* __restrict__ delta,
                                                            const typename T::elem* __restrict__ delta2,
                                                            const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                            float* sum32, typename T::elem* __restrict__ out16,
-                                                           float* out32, int64_t rows) {
+                                                           float* out32, int64_t rows, KEEP keep = KEEP()) {
     constexpr bool D1 = V & 1, D2 = (V & 2) != 0, SUM = (V & 4) != 0, LN = (V & 8) != 0;
+    static_assert(!KEEP::on || (D1 && !D2 && !SUM && LN), "train mode: x = LN(x + keep * delta) alone (delta2 is never dropped)");
     constexpr int NP = D / 256;        // 4-element pieces per lane of the wave: 3 (768) or 4 (1024)
     static_assert(D % 256 == 0 && NP >= 1 && NP <= 4, "row width: a multiple of 256, at most 1024 (the row lives in registers)");
     const int lane = threadIdx.x & 63;
@@ -47,7 +55,11 @@ __global__ __launch_bounds__(256) void layernorm768_kernel(const float* x, const
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        if (D1) {
+        if constexpr (KEEP::on) {
+            const uint64_t idx = keep.index(row, D, i * 256 + lane * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[i][e] += keep(idx + e) * T::to_f32(d1[i][e]);
+        } else if (D1) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[i][e] += T::to_f32(d1[i][e]);
         }
@@ -99,13 +111,15 @@ __global__ __launch_bounds__(256) void layernorm768_kernel(const float* x, const
 // division per lane): every access of the fp16 stream, the 16-bit deltas and the 16-bit image is a full 16-byte lane access.  (The
 // first version gave a row to a whole wave — 12 elements per lane as three 8-byte pieces: 4.3 TB/s on LN1 where the fp32 kernel's
 // 16-byte accesses reach 6.7; MI355X_MICROARCH.md: 8-byte accesses run at 0.54-0.70 x the 16-byte rate.)  V: which operands exist.
-template <typename T, int V, int D = 768>
+// KEEP on (BERT's x = LN(x + d) in train mode): the keep factor multiplies the 16-bit delta as it is added — no extra pass over HBM, no
+// extra rounding of the delta; the CLS rows take it like every other row.
+template <typename T, int V, int D = 768, typename KEEP = RowKeepNone>
 __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __restrict__ x32, _Float16* x16, float* xc,
                                                                  const typename T::elem* __restrict__ delta,
                                                                  const typename T::elem* __restrict__ delta2,
                                                                  const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                                  typename T::elem* __restrict__ out16, int64_t items, int Ttok,
-                                                                 float* __restrict__ stat) {
+                                                                 float* __restrict__ stat, KEEP keep = KEEP()) {
     constexpr bool D1 = (V & MX_D1) != 0, D2 = (V & MX_D2) != 0, LN = (V & MX_LN) != 0, RESV = (V & MX_RESV) != 0,
                    RESY = (V & MX_RESY) != 0, SRC32 = (V & MX_SRC32) != 0, CLSONLY = (V & MX_CLSONLY) != 0, POSROW = (V & MX_POSROW) != 0,
                    STAT = (V & MX_STAT) != 0, ALIAS = (V & MX_ALIAS) != 0, BLK32 = (V & MX_BLK32) != 0;
@@ -113,6 +127,7 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
     constexpr int NP = D / 256;        // 8-element pieces per lane of the half-wave: 3 (768) or 4 (1024)
     static_assert(D % 256 == 0 && NP >= 1 && NP <= 4, "row width: a multiple of 256, at most 1024 (the row lives in registers)");
     static_assert(D == 768 || !(STAT || BLK32), "the product route's stream (row statistics, block-major rows) is 768 wide");
+    static_assert(!KEEP::on || (V & ~MX_ALIAS) == (MX_D1 | MX_LN | MX_RESY), "train mode: x = LN(x + keep * delta) alone (delta2 is never dropped)");
     typedef typename T::v8 V8;
     const int lane = threadIdx.x & 31, half = threadIdx.x >> 5;          // 8 half-waves per workgroup
     int64_t item;
@@ -184,7 +199,11 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
     const bool use_d = !(POSROW && cls);          // POSROW: the CLS slot of the patch-embedding buffer was never written
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        if (D1 && use_d) {
+        if constexpr (KEEP::on) {
+            const uint64_t idx = keep.index(row, D, i * 256 + lane * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[i][e] += keep(idx + e) * T::to_f32(d1[i][e]);
+        } else if (D1 && use_d) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[i][e] += T::to_f32(d1[i][e]);
         }
@@ -303,14 +322,17 @@ __global__ void vit_cls_rows_kernel(float* __restrict__ X, const float* __restri
 // ---- BERT embeddings: LN(word[id] + pos[t] + type[0]) -> X fp32 + H 16-bit; key bias from the attention mask ------
 // IDX: `text` is a resident table [rows, 2W] and item m reads row index[m]; a value outside [0, rows) is a padding slot — never
 // dereferenced, all-zero ids and mask (what `dataset.py:79-84` ships for pad slots).
-template <typename T, bool IDX = false, int D = 768>
+// KEEP on (train mode): drop(LN(...)) — the keep factor multiplies the fp32 LayerNorm output BEFORE it is rounded, so every copy the
+// executor keeps of the row (the 16-bit image H, the fp16 stream X16, the fp32 CLS rows Xc that become tap 0) holds the dropped value.
+template <typename T, bool IDX = false, int D = 768, typename KEEP = RowKeepNone>
 __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __restrict__ text, const float* __restrict__ word,
                                                             const float* __restrict__ pos, const float* __restrict__ type0,
                                                             const float* __restrict__ g, const float* __restrict__ b, float eps,
                                                             float* __restrict__ X, typename T::elem* __restrict__ H,
                                                             float* __restrict__ key_bias, int64_t M, int W, int vocab,
                                                             _Float16* __restrict__ X16, float* __restrict__ Xc,
-                                                            const int64_t* __restrict__ index = nullptr, int64_t rows = 0) {
+                                                            const int64_t* __restrict__ index = nullptr, int64_t rows = 0,
+                                                            KEEP keep = KEEP()) {
     constexpr int NP = D / 256;
     static_assert(D % 256 == 0 && NP >= 1 && NP <= 4, "row width: a multiple of 256, at most 1024");
     const int lane = threadIdx.x & 63;
@@ -361,6 +383,7 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __res
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             y[e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
+            if constexpr (KEEP::on) y[e] *= keep(keep.index(row, D, c) + e);
             o[e] = T::from_f32(y[e]);
         }
         if (X) {
@@ -408,13 +431,23 @@ __global__ void cast16_kernel(const float* __restrict__ src, typename T::elem* _
 
 // width: 768 or 1024 (the two instantiated row widths; anything else is IISAN_EBADSHAPE)
 int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, const void* delta16b, const float* g,
-                             const float* b, float eps, float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s) {
+                             const float* b, float eps, float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s,
+                             const RowKeep* keep) {
     IISAN_CHECK_SHAPE(width == 768 || width == 1024, "layernorm: row width %d not instantiated (768 and 1024 are)", width);
     if (rows <= 0) return IISAN_OK;
     dim3 grid((unsigned)ceil_div(rows, 4)), block(256);
     const int v = (delta16 ? 1 : 0) | (delta16b ? 2 : 0) | (sum32 ? 4 : 0) | (g ? 8 : 0);
 #define LN768_LAUNCH(TT, EL, V, W)                                                                                             \
     hipLaunchKernelGGL((layernorm768_kernel<TT, V, W>), grid, block, 0, s, x, (const EL*)delta16, (const EL*)delta16b, g, b, eps, sum32, (EL*)out16, out32, rows)
+#define LN768_KEEP(TT, EL)                                                                                                     \
+    hipLaunchKernelGGL((layernorm768_kernel<TT, 9, 768, RowKeep>), grid, block, 0, s, x, (const EL*)delta16, (const EL*)delta16b, g, b, eps, sum32, (EL*)out16, out32, rows, *keep)
+    if (keep) {         // train mode: x = LN(x + keep * delta16) at 768 or a refusal, never a silent eval launch
+        IISAN_CHECK_SHAPE(v == 9 && width == 768, "layernorm: no train-mode instantiation of operand set %d at row width %d", v, width);
+        if (dtype16 == IISAN_BF16) LN768_KEEP(BF16, __bf16); else LN768_KEEP(F16, _Float16);
+        iisan_count_bert_drop();
+        IISAN_LAUNCH_OK();
+        return IISAN_OK;
+    }
 #define LN768_CASE(V)                                                                                                          \
     case V:                                                                                                                    \
         if (width == 768) {                                                                                                    \
@@ -428,6 +461,7 @@ int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, c
         LN768_CASE(8); LN768_CASE(9); LN768_CASE(10); LN768_CASE(11); LN768_CASE(12); LN768_CASE(13); LN768_CASE(14); LN768_CASE(15);
     }
 #undef LN768_CASE
+#undef LN768_KEEP
 #undef LN768_LAUNCH
     IISAN_LAUNCH_OK();
     return IISAN_OK;
@@ -438,7 +472,7 @@ int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, c
 // operand sets of the LayerNorm-image routes exist at both, those of the product route (MX_STAT, MX_BLK32) at 768 only
 int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, float* xc, const void* delta16, const void* delta16b,
                               const float* g, const float* b, float eps, void* out16, int64_t items, int Ttok, int width, hipStream_t s,
-                              float* stat) {
+                              float* stat, const RowKeep* keep) {
     IISAN_CHECK_SHAPE(width == 768 || width == 1024, "layernorm768_mixed: row width %d not instantiated (768 and 1024 are)", width);
     if (items <= 0) return IISAN_OK;
     IISAN_CHECK_SHAPE(!(V & MX_STAT) || stat, "layernorm768_mixed: MX_STAT needs the statistics buffer");
@@ -447,6 +481,20 @@ int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, f
     dim3 grid((unsigned)blocks), block(256);
 #define MX_LAUNCH(TT, EL, VV, W)                                                                                               \
     hipLaunchKernelGGL((layernorm768_mixed_kernel<TT, VV, W>), grid, block, 0, s, x32, (_Float16*)x16, xc, (const EL*)delta16, (const EL*)delta16b, g, b, eps, (EL*)out16, items, Ttok, stat)
+#define MX_KEEP(TT, EL, VV)                                                                                                    \
+    hipLaunchKernelGGL((layernorm768_mixed_kernel<TT, VV, 768, RowKeep>), grid, block, 0, s, x32, (_Float16*)x16, xc, (const EL*)delta16, (const EL*)delta16b, g, b, eps, (EL*)out16, items, Ttok, stat, *keep)
+    if (keep) {         // train mode: BERT's x = LN(x + keep * d) at 768 or a refusal, never a silent eval launch
+        const bool alias = (V & MX_ALIAS) != 0;
+        IISAN_CHECK_SHAPE((V & ~MX_ALIAS) == (MX_D1 | MX_LN | MX_RESY) && width == 768,
+                          "layernorm768_mixed: no train-mode instantiation of operand set %d at row width %d", V, width);
+        IISAN_CHECK_SHAPE(!alias || (dtype16 == IISAN_F16 && out16 == x16), "layernorm768_mixed, train mode: the aliased image needs fp16 operands and out16 == x16");
+        if (dtype16 == IISAN_BF16) MX_KEEP(BF16, __bf16, MX_D1 | MX_LN | MX_RESY);
+        else if (alias) MX_KEEP(F16, _Float16, MX_D1 | MX_LN | MX_RESY | MX_ALIAS);
+        else MX_KEEP(F16, _Float16, MX_D1 | MX_LN | MX_RESY);
+        iisan_count_bert_drop();
+        IISAN_LAUNCH_OK();
+        return IISAN_OK;
+    }
 #define MX_CASE768(VV)                                                                                                         \
     case VV:                                                                                                                   \
         if (width != 768) break;                                                                                               \
@@ -479,14 +527,15 @@ int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, f
     }
 #undef MX_CASE
 #undef MX_CASE768
+#undef MX_KEEP
 #undef MX_LAUNCH
     iisan_set_error("layernorm768_mixed: operand set %d not instantiated at row width %d", V, width);
     return IISAN_EBADSHAPE;
 }
 
 int launch_add_layernorm768(int dtype16, const float* x, const void* delta16, const float* g, const float* b, float eps,
-                            float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s) {
-    return launch_add2_layernorm768(dtype16, x, delta16, nullptr, g, b, eps, sum32, out16, out32, rows, width, s);
+                            float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s, const RowKeep* keep) {
+    return launch_add2_layernorm768(dtype16, x, delta16, nullptr, g, b, eps, sum32, out16, out32, rows, width, s, keep);
 }
 
 int launch_layernorm768(int dtype16, const float* x, const float* g, const float* b, float eps, void* out16,
@@ -534,16 +583,23 @@ int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M,
 template <bool IDX>
 static int bert_embed_ln_any(int dtype16, const int64_t* text, int64_t rows, const int64_t* index, const float* word, const float* pos,
                              const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
-                             int64_t M, int W, int vocab, int width, hipStream_t s, void* X16, float* Xc) {
+                             int64_t M, int W, int vocab, int width, hipStream_t s, void* X16, float* Xc, const RowKeep* keep) {
     IISAN_CHECK_SHAPE(width == 768 || width == 1024, "bert_embed_ln: row width %d not instantiated (768 and 1024 are)", width);
     dim3 grid((unsigned)ceil_div(M * W, 4)), block(256);
 #define EMBED_LAUNCH(TT, EL, WD)                                                                                               \
     hipLaunchKernelGGL((bert_embed_ln_kernel<TT, IDX, WD>), grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (EL*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows)
-    if (width == 768) {
+#define EMBED_KEEP(TT, EL)                                                                                                     \
+    hipLaunchKernelGGL((bert_embed_ln_kernel<TT, IDX, 768, RowKeep>), grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (EL*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows, *keep)
+    if (keep) {         // train mode: 768 or a refusal, never a silent eval launch
+        IISAN_CHECK_SHAPE(width == 768, "bert_embed_ln: no train-mode instantiation at row width %d", width);
+        if (dtype16 == IISAN_BF16) EMBED_KEEP(BF16, __bf16); else EMBED_KEEP(F16, _Float16);
+        iisan_count_bert_drop();
+    } else if (width == 768) {
         if (dtype16 == IISAN_BF16) EMBED_LAUNCH(BF16, __bf16, 768); else EMBED_LAUNCH(F16, _Float16, 768);
     } else {
         if (dtype16 == IISAN_BF16) EMBED_LAUNCH(BF16, __bf16, 1024); else EMBED_LAUNCH(F16, _Float16, 1024);
     }
+#undef EMBED_KEEP
 #undef EMBED_LAUNCH
     IISAN_LAUNCH_OK();
     return IISAN_OK;
@@ -551,14 +607,14 @@ static int bert_embed_ln_any(int dtype16, const int64_t* text, int64_t rows, con
 
 int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, const float* pos, const float* type0,
                          const float* g, const float* b, float eps, float* X, void* H, float* key_bias, int64_t M,
-                         int W, int vocab, int width, hipStream_t s, void* X16, float* Xc) {       // X == null: mixed stream (X16 + Xc)
-    return bert_embed_ln_any<false>(dtype16, text, 0, nullptr, word, pos, type0, g, b, eps, X, H, key_bias, M, W, vocab, width, s, X16, Xc);
+                         int W, int vocab, int width, hipStream_t s, void* X16, float* Xc, const RowKeep* keep) {       // X == null: mixed stream (X16 + Xc)
+    return bert_embed_ln_any<false>(dtype16, text, 0, nullptr, word, pos, type0, g, b, eps, X, H, key_bias, M, W, vocab, width, s, X16, Xc, keep);
 }
 
 int launch_bert_embed_ln_indexed(int dtype16, const int64_t* table, int64_t rows, const int64_t* index, const float* word, const float* pos,
                                  const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
-                                 int64_t M, int W, int vocab, int width, hipStream_t s, void* X16, float* Xc) {
-    return bert_embed_ln_any<true>(dtype16, table, rows, index, word, pos, type0, g, b, eps, X, H, key_bias, M, W, vocab, width, s, X16, Xc);
+                                 int64_t M, int W, int vocab, int width, hipStream_t s, void* X16, float* Xc, const RowKeep* keep) {
+    return bert_embed_ln_any<true>(dtype16, table, rows, index, word, pos, type0, g, b, eps, X, H, key_bias, M, W, vocab, width, s, X16, Xc, keep);
 }
 
 int launch_gather_rows16(const void* H, void* out, int64_t M, int T, int D, hipStream_t s) {

@@ -163,10 +163,11 @@ int iisan_bert_forward_taps_indexed(const iisan_bert_weights* w, const int64_t* 
 typedef struct { float hidden_p; float attn_p; uint64_t seed; } iisan_bert_dropout;
 /* iisan_bert_forward_taps (index == NULL: text_or_table is the text [M, 2W], `rows` is ignored) or iisan_bert_forward_taps_indexed
  * (index != NULL) with dropout.  drop == NULL or both probabilities 0: exactly the launches and the bits of those two.  Otherwise
- * the variants of csrc/bert_drop.hip run, for both operand types; dead-work pruning is unchanged.  Workspace:
+ * the train-mode kernels run, for both operand types — the attention kernel of csrc/bert_drop.hip, and at the hidden sites the
+ * embedding and add + LayerNorm kernels of csrc/rowops.hip instantiated with a keep functor; dead-work pruning is unchanged.  Workspace:
  * iisan_bert_forward_taps_ws_bytes is sufficient.  IISAN_EBADSHAPE before any launch: a probability outside [0, 1); dropout asked for
- * under the development switch resid32 = 1, or at a hidden size other than 768 — the train-mode kernels are 768 wide, and tap caches
- * of the wide towers are built in eval mode (never a silent fall-back to eval mode). */
+ * under the development switch resid32 = 1, or at a hidden size other than 768 — the row kernels have no train-mode instantiation at
+ * another width, and tap caches of the wide towers are built in eval mode (never a silent fall-back to eval mode). */
 int iisan_bert_forward_taps_dropout(const iisan_bert_weights* w, const int64_t* text_or_table, int64_t rows,
                                     const int64_t* index, int64_t M, int32_t words,
                                     const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,

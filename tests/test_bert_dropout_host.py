@@ -1,6 +1,7 @@
-"""CPU side of the opt-in train-mode dropout of the frozen BERT tower (`iisan_bert_forward_taps_dropout`, csrc/bert_drop.hip):
-where HF's `BertModel` applies dropout under `train()` and with which masks — pinned against HF itself —, the struct layout of the
-new ABI argument, the Python switch, and the code-object metadata of the new kernel file.
+"""CPU side of the opt-in train-mode dropout of the frozen BERT tower (`iisan_bert_forward_taps_dropout`: the attention kernel of
+csrc/bert_drop.hip, the keep-functor instantiations of the row kernels of csrc/rowops.hip): where HF's `BertModel` applies dropout
+under `train()` and with which masks — pinned against HF itself —, the struct layout of the ABI argument, the Python switch, and the
+code-object metadata of the train-mode kernels.
 
 `bert_hidden_states_dropped` is `oracle.bert_hidden_states` with the four keep-factor multiplications inserted; the GPU tests
 (tests/test_gpu_bert_dropout.py) feed it the masks the kernels draw."""
@@ -191,13 +192,19 @@ def test_the_python_switch_reads_a_real_hf_config():
 def test_dropout_kernels_have_no_scratch_and_no_spilled_vgpr(tmp_path):
     import test_isa_screen as isa
     meta, txt = isa._kernel_meta(os.path.join(isa.CSRC, "bert_drop.hip"), tmp_path)
-    for family, n in (("attention16_drop_kernel", 20), ("add_ln_drop_mixed_kernel", 3), ("add_ln_drop_rows_kernel", 2),
-                      ("bert_embed_ln_drop_kernel", 4)):
-        assert sum(family in k for k in meta) == n, (family, sorted(meta))
+    assert sum("attention16_drop_kernel" in k for k in meta) == len(meta) == 20, sorted(meta)
+    # the three hidden sites: the instantiations of the eval-mode row kernels that carry the keep functor (`7RowKeep` in the mangled
+    # name; the eval-mode ones carry `11RowKeepNone`), 768 wide
+    rows_meta, rows_txt = isa._kernel_meta(os.path.join(isa.CSRC, "rowops.hip"), tmp_path)
+    train = {k: m for k, m in rows_meta.items() if "Li768E7RowKeepE" in k}
+    for family, n in (("25layernorm768_mixed_kernelI", 3), ("19layernorm768_kernelI", 2), ("20bert_embed_ln_kernelI", 4)):
+        assert sum(family in k for k in train) == n, (family, sorted(train))
+    assert len(train) == 9 and not any("7RowKeepE" in k for k in set(rows_meta) - set(train)), sorted(train)
+    meta.update(train)
     for name, m in meta.items():
         assert m["scratch"] == 0 and m["vgpr_spill"] == 0, (name, m)
     # the text tower's instantiations (S <= 32) leave room for several waves per SIMD
     for name, m in meta.items():
         if "attention16_drop_kernel" in name and "Li2E" in name:
             assert m["vgpr"] <= 128, (name, m)
-    assert not isa._opsel_sites(txt)
+    assert not isa._opsel_sites(txt) and not isa._opsel_sites(rows_txt)

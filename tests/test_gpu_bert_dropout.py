@@ -1,6 +1,7 @@
-"""GPU tests of the opt-in train-mode dropout of the frozen BERT tower (csrc/bert_drop.hip, `iisan_bert_forward_taps_dropout`):
-the attention kernel with dropped probabilities against fp64, the taps against the HF-pinned restatement of
-tests/test_bert_dropout_host.py fed the masks the kernels draw, the bit-level properties of the mask convention, and the model switch.
+"""GPU tests of the opt-in train-mode dropout of the frozen BERT tower (`iisan_bert_forward_taps_dropout`: the attention kernel of
+csrc/bert_drop.hip, the keep-functor instantiations of the row kernels of csrc/rowops.hip): the attention kernel with dropped
+probabilities against fp64, the taps against the HF-pinned restatement of tests/test_bert_dropout_host.py fed the masks the kernels
+draw, the bit-level properties of the mask convention, every train-mode kernel against its eval-mode twin, and the model switch.
 
 Measured (MI355X): profiles/r8_bert_dropout.md."""
 import ctypes as C
@@ -219,6 +220,56 @@ def test_cls_only_last_block_draws_the_masks_of_row_zero(lib):
     # a tapped prefix: block 1 is not run at all, block 0 is the CLS-only one
     pre = pk.forward_taps(text.cuda(), [0, 1], dropout=d).cpu()
     assert torch.equal(pre[:, 0], full[:, 0]) and _rel(pre[:, 1], full[:, 1]) < 5e-4
+
+
+# ---- 8b. every train-mode instantiation against its eval twin ---------------------------------------------------------------------------
+
+# make_drop (csrc/common.h) turns p = 1e-9 into thr24 = 0 and inv_keep = 1.0f: every keep factor is exactly 1 — yet the call is a
+# train-mode one (p > 0), so the executor launches the train-mode kernel at every site
+IDENTITY = (1e-9, 1e-9, SEED)
+
+
+def _counted(fn):
+    """(taps on the CPU, train-mode launches of the call)"""
+    _lib.dev_set("count:bert_drop", 0)
+    out = fn().cpu()
+    return out, _lib.dev_get("count:bert_drop")
+
+
+@pytest.mark.parametrize("dt", [_lib.IISAN_F16, _lib.IISAN_BF16])
+def test_identity_mask_ties_every_train_mode_kernel_to_its_eval_twin(lib, dt):
+    """The train-mode kernels of the three hidden sites are instantiations of the eval-mode row kernels (csrc/rowops.hip) and the
+    attention one shares its block core with the eval-mode kernel (csrc/attn16_block.h): with the identity mask every tap is
+    bit-equal to the eval-mode tap, direct and indexed, chunked and not, all-token and pruned.  The pruned last block included, though
+    its train-mode attention is `attention16_drop_kernel<.., CLS>` where eval mode runs `attention_cls_kernel`, another kernel: on
+    this fixture the two agree bit for bit, and did so at the commit before the row kernels were unified — which makes equality the
+    contract there too (profiles/rowops_shared_body.md)."""
+    bw, text, ref = _fixture()
+    pk = _packed(dt)
+    td = text.cuda()
+    table, index = text[[3, 1, 5, 2, 4, 6]].contiguous().cuda(), torch.tensor([3, 1, 6, 0, 4, 2, 5]).cuda()     # slot 2: a padding slot
+    taps_l, per_chunk = [0, 1, 2], 1 + 3 * pk.cfg.layers         # embeddings + (attention, two add + LayerNorm steps) per block
+    routes = {"direct": (lambda d: pk.forward_taps(td, taps_l, dropout=d), 1),
+              "direct, chunks of 3": (lambda d: pk.forward_taps(td, taps_l, chunk_items=3, dropout=d), 3),
+              "indexed": (lambda d: pk.forward_taps_indexed(table, index, taps_l, dropout=d), 1),
+              "indexed, chunks of 2": (lambda d: pk.forward_taps_indexed(table, index, taps_l, chunk_items=2, dropout=d), 4)}
+    for full_blocks in (True, False):
+        pk.full_blocks = full_blocks
+        try:
+            for name, (run, chunks) in routes.items():
+                plain, n_eval = _counted(lambda: run(None))
+                train, n_train = _counted(lambda: run(IDENTITY))
+                assert n_eval == 0 and n_train == chunks * per_chunk, (name, n_eval, n_train)
+                print(f"identity mask dt={dt} full_blocks={full_blocks} {name}: taps 0, 1 equal {torch.equal(train[:, :2], plain[:, :2])}, "
+                      f"tap 2 equal {torch.equal(train[:, 2], plain[:, 2])} (rel {_rel(train[:, 2], plain[:, 2]):.2e})")
+                assert torch.equal(train, plain), (full_blocks, name)
+        finally:
+            pk.full_blocks = False
+    # negative control: a real mask at the hidden sites alone moves every tap
+    plain = pk.forward_taps(td, taps_l).cpu()
+    dropped = pk.forward_taps(td, taps_l, dropout=(P_DROP, 0.0, SEED)).cpu()
+    for l in range(3):
+        assert not torch.equal(dropped[:, l], plain[:, l]), l
 
 
 # ---- 9. model level ------------------------------------------------------------------------------------------------------------------------

@@ -9,8 +9,9 @@ both sides alike; the eval-mode route is the yardstick on the same box, in the s
   tower       `PackedBert.forward_taps` without and with `dropout=(0.1, 0.1, seed)`
   step        one `FlatTrainer.step` (fwd + bwd + Adam from the same state) with `Text_Encoder.train_dropout` off and on
 
-and one check: with the switch off the step launches no kernel of csrc/bert_drop.hip (`count:bert_drop` stays 0) and the same number
-of encoder GEMMs as before the switch existed in the process.  Prints one JSON line per comparison."""
+and one check: with the switch off the step launches no train-mode kernel — neither the attention kernel of csrc/bert_drop.hip nor a
+keep-functor instantiation of the row kernels of csrc/rowops.hip: `count:bert_drop` counts both and stays 0 (37 per step with the
+switch on) — and the same number of encoder GEMMs as before the switch existed in the process.  Prints one JSON line per comparison."""
 import argparse
 import json
 import os
