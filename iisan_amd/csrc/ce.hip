@@ -7,11 +7,19 @@
 //     z[row,c]  = -1e4   if id_c occurs in the row's own sequence and c is not the row's positive  (model.py:92-100)
 //     loss      = mean over rows with log_mask != 0 of  logsumexp(z[row,:]) - z[row, label]       (model.py:102-104)
 //
-// One workgroup owns 16 rows of X (prec rows for fwd / d_prec, score rows for d_score) and streams the other
-// matrix in 16-row tiles, four waves taking tiles round-robin.  Logit tiles are computed TRANSPOSED on the f32
-// matrix cores (v_mfma_f32_16x16x4_f32, K = E = 64) so a lane owns one X row and 4 Y columns per tile: the online
-// log-sum-exp is per-lane + two xor-shuffles, and the dZ registers are already the B operand of the second product
-// dX^T = Y^T·dZ^T.  The Y tile is staged once per wave in LDS (272-byte rows: conflict-free ds_read_b128).
+// Three families of kernels compute it (ce_route below says which one a call takes):
+//     ce_pass_kernel                          the plain statement of the loss, any shape
+//     ce_rowpass_kernel / ce_colpass_kernel   the same walk with the per-logit work done once per wave and tile (5 <= S <= 15)
+//     ce16_*                                  split fp16 operands on the 16-bit matrix cores (large batches)
+//
+// THE LAYOUT OF THE f32 PASSES (the first two families; stated here once).  A pass fixes 16 rows of X per workgroup (prec rows for
+// the forward and d_prec, score rows for d_score) and streams the other matrix Y in 16-row tiles, its four waves taking tiles
+// round-robin.  Logit tiles are computed TRANSPOSED on the f32 matrix cores (v_mfma_f32_16x16x4_f32, K = E = 64): lane (j, g) =
+// (lane & 15, lane >> 4) owns X row x0 + j and the Y rows y0 + 4g .. 4g + 3 of the tile.  So the online log-sum-exp is per lane plus
+// two xor-shuffles (16, 32), and the four dZ registers of a lane are already the B operand of the second product dX^T += Y^T·dZ^T,
+// whose accumulators dacc[et][r] hold dX[x0 + j][16 et + 4g + r].  A wave stages its Y tile in LDS once, rows of YLD = 68 floats
+// (272 bytes: conflict-free ds_read_b128); both products read their A operand from it, the second one transposed.  The four waves'
+// results meet in sRed after the walk.
 #include <type_traits>
 
 #include "common.h"
@@ -19,7 +27,7 @@
 namespace {
 
 constexpr int E = 64;
-constexpr int MAXS1 = 16;         // sequences of up to 16 slots keep their ids in registers / LDS (longer ones take the slow loop)
+constexpr int MAXS1 = 16;         // sequences of up to 16 slots keep their ids in registers / LDS (longer ones take the plain kernel)
 constexpr int YLD = 68;           // padded LDS row (floats)
 constexpr float MASKV = -1e4f;
 
@@ -57,9 +65,20 @@ __global__ void ce_prep_kernel(const int64_t* __restrict__ ids, const float* __r
     }
 }
 
+// sum of one value per thread of a 256-thread workgroup, in a fixed order (a tree over the thread index); the result is thread 0's
+__device__ __forceinline__ float block_sum256(float s) {
+    __shared__ float red[256];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 // n_valid = #{log_mask != 0}; single block, fixed order
 __global__ __launch_bounds__(256) void ce_count_kernel(const float* __restrict__ log_mask, int64_t T, float* out) {
-    __shared__ float red[256];
     float s = 0.f;
     // (16-byte loads, all of a thread's requests in flight: one dependent 4-byte load per iteration made this single-workgroup pass 10.7 us at T = 10,240;
     //  the counts are small integers: any summation order is exact)
@@ -69,18 +88,13 @@ __global__ __launch_bounds__(256) void ce_count_kernel(const float* __restrict__
         s += (v[0] != 0.f ? 1.f : 0.f) + (v[1] != 0.f ? 1.f : 0.f) + (v[2] != 0.f ? 1.f : 0.f) + (v[3] != 0.f ? 1.f : 0.f);
     }
     for (int64_t i = 4 * T4 + threadIdx.x; i < T; i += 256) s += log_mask[i] != 0.f ? 1.f : 0.f;
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0];
+    s = block_sum256(s);
+    if (threadIdx.x == 0) out[0] = s;
 }
 
+// loss = sum of the row losses / n_valid; single block
 __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict__ rowloss, int64_t T, const float* nvalid,
                                                         float* loss) {
-    __shared__ float red[256];
     float s = 0.f;
     // 16-byte loads (as ce_count_kernel); the order is fixed — thread t adds the groups t, t + 256, ... of four rows, each as (r0 + r1) + (r2 + r3)
     const int64_t T4 = (T % 4 == 0 && ((uintptr_t)rowloss & 15) == 0) ? T / 4 : 0;
@@ -89,13 +103,26 @@ __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict_
         s += (v[0] + v[1]) + (v[2] + v[3]);
     }
     for (int64_t i = 4 * T4 + threadIdx.x; i < T; i += 256) s += rowloss[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = red[0] / nvalid[0];
+    s = block_sum256(s);
+    if (threadIdx.x == 0) loss[0] = s / nvalid[0];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The pieces the three f32 passes are written over (layout: top of the file).  Index types are the caller's: `int` in the row-fixed
+// kernels (M < 2^31 is their launch condition), int64_t in the plain one; an address is widened where E multiplies it.  Every
+// floating-point expression below is evaluated in this order by every pass: the routes agree to the bit wherever they share one.
+enum { CE_FWD = 0, CE_DPREC = 1, CE_DSCORE = 2, CE_FUSED = 3 };
+typedef float CeRed[4][16][E + 4];      // per wave and X row: 64 features (+ m, l, z_label of the fused finish)
+
+// exp(x) = v_exp_f32(x * log2 e): 2 instructions, relative error < 3e-6 for the |x| <= 40 that matter (the loss tolerance is 2e-5, the
+// gradients' 2e-4; masked logits underflow to 0 exactly as with expf)
+__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
+
+// the label column of prec row x: the next slot of its sequence (S rows, S + 1 columns per sequence)
+template <class I>
+__device__ __forceinline__ I ce_label(I x, int S) {
+    const I seq = x / S;
+    return seq * (S + 1) + (x - seq * S) + 1;
 }
 
 __device__ __forceinline__ bool id_in_seq(const int* __restrict__ ids32, int64_t seq, int S1, int idc) {
@@ -104,317 +131,254 @@ __device__ __forceinline__ bool id_in_seq(const int* __restrict__ ids32, int64_t
     return hit;
 }
 
-enum { CE_FWD = 0, CE_DPREC = 1, CE_DSCORE = 2, CE_FUSED = 3 };
-
-// X rows: prec (FWD, DPREC) or score (DSCORE).  Y rows: the other matrix.
-// RS1: slots per sequence held in registers by the row-fixed passes (11 = the reference's max_seq_len 10 + 1: five fewer
-// id compares per logit than the generic 16)
-template <int MODE, int RS1 = MAXS1>
-__global__ __launch_bounds__(256) void ce_pass_kernel(const float* __restrict__ prec, const float* __restrict__ score,
-                                                      const float* __restrict__ log_mask, CeBufs b, int64_t bs, int S,
-                                                      float d_loss, float* __restrict__ dX) {
-    __shared__ __attribute__((aligned(16))) float sY[4][16 * YLD];
-    __shared__ float sRed[4][16][E + 4];
-    // per-wave, per-tile metadata (the first version fetched it from global memory per logit: 3 + S1 loads — and in the
-    // d_score pass 3 more plus two 64-bit divisions — for each of a lane's 4 logits, ~56 load instructions per 16 MFMAs:
-    // the passes ran at 15 TF of the 157 TF f32 MFMA rate at bs=1024).
-    //   FWD / DPREC (row fixed per lane): sMeta = ids | pad flags | debias of the tile's 16 columns.
-    //   DSCORE (column fixed per lane):   sMeta = ids of the <=4 sequences the tile's 16 rows belong to,
-    //                                     sRow  = per row: sequence index in that table | label column | lse | scale.
-    __shared__ __attribute__((aligned(16))) int sMeta[4][64];
-    __shared__ __attribute__((aligned(16))) int sRow[4][64];
-    const int S1 = S + 1;
-    const int64_t T = bs * S, M = bs * S1;
-    const float* X = MODE == CE_DSCORE ? score : prec;
-    const float* Y = MODE == CE_DSCORE ? prec : score;
-    const int64_t NX = MODE == CE_DSCORE ? M : T, NY = MODE == CE_DSCORE ? T : M;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 15, g = lane >> 4;
-    const int64_t x0 = (int64_t)blockIdx.x * 16;
-    const int64_t x = x0 + j;
-    const bool xok = x < NX;
-    const int64_t xc = xok ? x : NX - 1;
-
-    // X fragments (B operand): e(ks, kq) = 16*kq + ks  -> 16 consecutive floats per lane
-    float xb[16];
+// X fragments of row xc (B operand of the logits product): e(ks, kq) = 16*kq + ks -> 16 consecutive floats per lane
+__device__ __forceinline__ void ce_load_x(float (&xb)[16], const float* __restrict__ X, int64_t xc, int g) {
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
         const f4 t = *(const f4*)(X + xc * E + 16 * g + 4 * v);
 #pragma unroll
         for (int e = 0; e < 4; ++e) xb[4 * v + e] = t[e];
     }
+}
 
-    // per-X-row constants
-    int64_t row_seq = 0, row_label = 0;
-    float row_lse = 0.f, row_scale = 0.f;
-    bool row_valid = false;
-    int col_id = 0, col_pad = 0;
-    float col_debias = 0.f;
-    if (MODE != CE_DSCORE) {
-        row_seq = xc / S;
-        row_label = row_seq * S1 + (xc - row_seq * S) + 1;
-        row_valid = xok && log_mask[xc] != 0.f;
-        if (MODE == CE_DPREC) {
-            row_lse = b.lse[xc];
-            row_scale = row_valid ? d_loss / b.nvalid[0] : 0.f;
+// the wave's Y tile from registers into LDS: 16 rows x 64 floats, lane -> row lane >> 2, 16-float chunk lane & 3
+__device__ __forceinline__ void ce_stage_y(float* myY, const f4 (&yreg)[4], int lane) {
+    const int r = lane >> 2, ch = lane & 3;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) *(f4*)(myY + r * YLD + ch * 16 + v * 4) = yreg[v];
+}
+
+// Z^T tile: A = Y rows (i = lane & 15), B = X rows; the lane receives z(x0 + j, y0 + 4g + r).  Two independent accumulator chains
+// (a single one is 16 MFMAs each waiting for the previous result)
+__device__ __forceinline__ f4 ce_logits(const float* myY, const float (&xb)[16], int j, int g) {
+    f4 z = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int v = 0; v < 4; v += 2) {
+        const f4 ya = *(const f4*)(myY + j * YLD + 16 * g + 4 * v);
+        const f4 yb = *(const f4*)(myY + j * YLD + 16 * g + 4 * v + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            z = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[e], xb[4 * v + e], z, 0, 0, 0);
+            z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(yb[e], xb[4 * v + 4 + e], z1, 0, 0, 0);
         }
-    } else {
-        col_id = b.ids32[xc];
-        col_pad = b.colpad[xc];
-        col_debias = b.debias[xc];
     }
+    z += z1;
+    return z;
+}
 
-    // FWD / DPREC: this lane's row belongs to one sequence for the whole pass: its ids live in registers
-    const bool fast = S1 <= RS1 && S >= 5 && M < (1ll << 31);
-    int rid[RS1];
+// dX^T[e][x] += sum_y Y[y][e] dZ(x, y):  A = Y^T (i = e within feature block et, k = y0 + 4kq + r), B = dz[r].  The 16 transposed
+// fragments are read by ce_read_yt — right in front of the product, or ahead of it (ce_rowpass_kernel)
+__device__ __forceinline__ void ce_read_yt(float (&yt16)[4][4], const float* myY, int j, int g) {
 #pragma unroll
-    for (int p = 0; p < RS1; ++p) rid[p] = -1;
-    if (MODE != CE_DSCORE && fast) {
+    for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int p = 0; p < RS1; ++p)
-            if (p < S1) rid[p] = b.ids32[row_seq * S1 + p];
+        for (int et = 0; et < 4; ++et) yt16[r][et] = myY[(4 * g + r) * YLD + 16 * et + j];
+}
+__device__ __forceinline__ void ce_second(f4 (&dacc)[4], const float (&yt16)[4][4], const float (&dz)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int et = 0; et < 4; ++et) dacc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(yt16[r][et], dz[r], dacc[et], 0, 0, 0);
+}
+
+// the wave's accumulators into its plane of sRed, and (behind a barrier) the four planes summed into dX
+__device__ __forceinline__ void ce_dacc_to_red(CeRed& sRed, const f4 (&dacc)[4], int wave, int j, int g) {
+#pragma unroll
+    for (int et = 0; et < 4; ++et)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sRed[wave][j][16 * et + 4 * g + r] = dacc[et][r];
+}
+template <class I>
+__device__ __forceinline__ void ce_sum_store(const CeRed& sRed, float* __restrict__ dX, I x0, I NX, int tid) {
+    for (int i = tid; i < 16 * E; i += 256) {
+        const int rj = i / E, e = i - rj * E;
+        if (x0 + rj < NX) dX[(int64_t)(x0 + rj) * E + e] = sRed[0][rj][e] + sRed[1][rj][e] + sRed[2][rj][e] + sRed[3][rj][e];
     }
-    int* myMeta = sMeta[wave];
-    int* myRow = sRow[wave];
-    const float dscale = MODE == CE_DSCORE ? d_loss / b.nvalid[0] : 0.f;
+}
 
-    // CE_FUSED: forward and d_prec in ONE pass, flash-attention style: the accumulators hold sum_y exp(z - run_m) * score[y]
-    // against a running ROW maximum (common to the four lanes of a row, because the MFMA sums over their columns) and are
-    // rescaled when it moves — after the first tiles it almost never does, and the test is one ballot per tile.
-    float run_m = MODE == CE_FUSED ? -3.0e38f : -INFINITY, run_l = 0.f, zlab = 0.f;
+// FWD, per tile: the lane's four logits folded into its running (max, sum).  One rescale per tile instead of a data-dependent branch
+// with an exp on both sides per logit (5 exps per 4 logits instead of 8, no divergence); masked logits are finite (MASKV), structural
+// padding is -inf -> 0.  EXP: expf in the plain kernel, fexp in the row pass
+template <class EXP>
+__device__ __forceinline__ void ce_online(float& run_m, float& run_l, const float (&fv)[4], EXP ex) {
+    const float m4 = fmaxf(fmaxf(fv[0], fv[1]), fmaxf(fv[2], fv[3]));
+    const float mn = fmaxf(run_m, m4);
+    if (mn > -INFINITY) {
+        float add = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) add += ex(fv[r] - mn);
+        run_l = run_l * ex(run_m - mn) + add;
+        run_m = mn;
+    }
+}
+
+// FWD, after the walk: (m, l) and the label logit combined across the 4 lane groups and the 4 waves; lse and the row loss of X row x
+template <class I>
+__device__ __forceinline__ void ce_fwd_finish(CeRed& sRed, float run_m, float run_l, float zlab, int wave, int j, int g, bool xok, I x,
+                                              bool row_valid, const CeBufs& b) {
+    auto comb = [](float& m, float& l, float m2, float l2) {
+        const float mn = fmaxf(m, m2);
+        const float a = m == -INFINITY ? 0.f : l * expf(m - mn);
+        const float c = m2 == -INFINITY ? 0.f : l2 * expf(m2 - mn);
+        m = mn;
+        l = a + c;
+    };
+#pragma unroll
+    for (int o = 16; o <= 32; o <<= 1) {
+        const float m2 = __shfl_xor(run_m, o, 64), l2 = __shfl_xor(run_l, o, 64);
+        comb(run_m, run_l, m2, l2);
+        zlab += __shfl_xor(zlab, o, 64);
+    }
+    if (g == 0) {
+        sRed[wave][j][0] = run_m;
+        sRed[wave][j][1] = run_l;
+        sRed[wave][j][2] = zlab;
+    }
+    __syncthreads();
+    if (wave == 0 && g == 0 && xok) {
+        float m = sRed[0][j][0], l = sRed[0][j][1], zl = sRed[0][j][2];
+        for (int w = 1; w < 4; ++w) {
+            comb(m, l, sRed[w][j][0], sRed[w][j][1]);
+            zl += sRed[w][j][2];
+        }
+        const float lse = m + logf(l);
+        b.lse[x] = lse;
+        b.rowloss[x] = row_valid ? lse - zl : 0.f;
+    }
+}
+
+// The finish of the fused forward + d_prec passes (ce_rowpass_kernel<CE_FUSED>: its four waves, from LDS; ce16_row_combine_kernel: the
+// Y ranges of the split route, from the workspace), for feature e of prec row xr.  part(w, k) is partial result w = 0 .. n - 1 of the
+// row: k < E the accumulator sum_y exp(z - m_w) score[y][k], k = E its maximum m_w, E + 1 its sum l_w, E + 2 its label logit.  The
+// partials are brought to the common maximum in the order w = 0, 1, ...;  d_prec = (sum_y p_y score_y - score_label) / n for d_loss = 1
+template <class PART>
+__device__ __forceinline__ void ce_fused_finish(int n, PART part, int xr, int e, const float* __restrict__ score,
+                                                const float* __restrict__ log_mask, const CeBufs& b, int S) {
+    float m = part(0, E);
+    for (int w = 1; w < n; ++w) m = fmaxf(m, part(w, E));
+    float l = 0.f, acc = 0.f, zl = 0.f;
+    for (int w = 0; w < n; ++w) {
+        const float f = fexp(part(w, E) - m);
+        l += part(w, E + 1) * f;
+        acc += part(w, e) * f;
+        zl += part(w, E + 2);
+    }
+    const bool valid = log_mask[xr] != 0.f;
+    const int lab = ce_label(xr, S);
+    b.dprec[(int64_t)xr * E + e] = valid ? (acc / l - score[(int64_t)lab * E + e]) / b.nvalid[0] : 0.f;
+    if (e == 0) {
+        const float lse = m + logf(l);
+        b.lse[xr] = lse;
+        b.rowloss[xr] = valid ? lse - zl : 0.f;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The plain kernel: the loss as it is defined, one logit at a time.  X rows: prec (FWD, DPREC) or score (DSCORE); Y rows: the other
+// matrix.  Every logit (row, col) fetches its own column id / padding flag / debias, its row's lse and mask, and scans the row's
+// sequence for the id (id_in_seq) — 3 + S1 loads per logit, 64-bit indices, libm expf: 2.9 ms forward + backward at bs = 1024, S = 10
+// against 0.85 ms of the row-fixed passes (profiles/ce_shared_core.md).  It serves the shapes the row-fixed kernels do not take
+// (S < 5, S > 15, M >= 2^31) and is the text they are read against.
+template <int MODE>
+__global__ __launch_bounds__(256) void ce_pass_kernel(const float* __restrict__ prec, const float* __restrict__ score,
+                                                      const float* __restrict__ log_mask, CeBufs b, int64_t bs, int S,
+                                                      float d_loss, float* __restrict__ dX) {
+    static_assert(MODE == CE_FWD || MODE == CE_DPREC || MODE == CE_DSCORE, "the fused forward exists in the row-fixed kernels only");
+    __shared__ __attribute__((aligned(16))) float sY[4][16 * YLD];
+    __shared__ CeRed sRed;
+    const int S1 = S + 1;
+    const int64_t T = bs * S, M = bs * S1;
+    const float* X = MODE == CE_DSCORE ? score : prec;
+    const float* Y = MODE == CE_DSCORE ? prec : score;
+    const int64_t NX = MODE == CE_DSCORE ? M : T, NY = MODE == CE_DSCORE ? T : M;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 15, g = lane >> 4;
+    const int64_t x0 = (int64_t)blockIdx.x * 16;
+    const int64_t x = x0 + j;
+    const bool xok = x < NX;
+    const int64_t xc = xok ? x : NX - 1;
+    float xb[16];
+    ce_load_x(xb, X, xc, g);
+
+    float run_m = -INFINITY, run_l = 0.f, zlab = 0.f;
     f4 dacc[4];
 #pragma unroll
     for (int et = 0; et < 4; ++et) dacc[et] = (f4){0.f, 0.f, 0.f, 0.f};
-
     float* myY = sY[wave];
     const int64_t ntiles = (NY + 15) / 16;
     for (int64_t yt = wave; yt < ntiles; yt += 4) {
         const int64_t y0 = yt * 16;
-        // stage the Y tile: 16 rows x 64 floats, lane -> row lane>>2, 16-float chunk lane&3
-        {
-            const int r = lane >> 2, ch = lane & 3;
-            const int64_t yr = y0 + r;
+        f4 yreg[4];
+        const int64_t yr = y0 + (lane >> 2);
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                f4 t = {0.f, 0.f, 0.f, 0.f};
-                if (yr < NY) t = *(const f4*)(Y + yr * E + ch * 16 + v * 4);
-                *(f4*)(myY + r * YLD + ch * 16 + v * 4) = t;
-            }
+        for (int v = 0; v < 4; ++v) {
+            yreg[v] = (f4){0.f, 0.f, 0.f, 0.f};
+            if (yr < NY) yreg[v] = *(const f4*)(Y + yr * E + (lane & 3) * 16 + v * 4);
         }
-        unsigned hitmask = 0;                        // DSCORE: bit s = this lane's column id occurs in sequence seq0 + s
-        if (fast) {
-            if (MODE != CE_DSCORE) {                 // columns y0 .. y0+15
-                if (lane < 16) {
-                    const int64_t cc = y0 + lane < NY ? y0 + lane : NY - 1;
-                    myMeta[lane] = b.ids32[cc];
-                    myMeta[16 + lane] = b.colpad[cc];
-                    myMeta[32 + lane] = __float_as_int(b.debias[cc]);
-                }
-            } else {                                 // rows y0 .. y0+15 span at most 4 sequences (S >= 5)
-                const unsigned seq0 = (unsigned)y0 / (unsigned)S;
-                for (int i = lane; i < 4 * S1; i += 64) {
-                    const int64_t sq_ = (int64_t)seq0 + i / S1;
-                    myMeta[i] = sq_ < bs ? b.ids32[sq_ * S1 + (i % S1)] : -1;
-                }
-                if (lane < 16) {
-                    const unsigned rw = (unsigned)(y0 + lane < NY ? y0 + lane : NY - 1);
-                    const unsigned rs = rw / (unsigned)S;
-                    myRow[lane] = (int)(rs - seq0);
-                    myRow[16 + lane] = (int)(rs * (unsigned)S1 + (rw - rs * (unsigned)S) + 1u);
-                    myRow[32 + lane] = __float_as_int(b.lse[rw]);
-                    myRow[48 + lane] = __float_as_int(log_mask[rw] != 0.f ? dscale : 0.f);
-                }
-            }
-        }
+        ce_stage_y(myY, yreg, lane);
         __builtin_amdgcn_wave_barrier();
-        if (fast && MODE == CE_DSCORE) {
-            if (RS1 == 11 && S1 == 11) {             // the reference's shape: 44 ids = 11 x ds_read_b128, indices known at compile time
-#pragma unroll
-                for (int i = 0; i < 11; ++i) {
-                    typedef int i4 __attribute__((ext_vector_type(4)));
-                    const i4 v = *(const i4*)(myMeta + 4 * i);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) hitmask |= v[k] == col_id ? (1u << ((4 * i + k) / 11)) : 0u;
-                }
-            } else {
-                for (int sidx = 0; sidx < 4; ++sidx) {
-                    bool h = false;
-                    for (int p = 0; p < S1; ++p) h |= myMeta[sidx * S1 + p] == col_id;       // wave-uniform addresses: LDS broadcast
-                    hitmask |= h ? (1u << sidx) : 0u;
-                }
-            }
-        }
-        // Z^T tile: A = Y rows (i = lane&15), B = X rows
-        // two independent accumulator chains (a single one is 16 MFMAs each waiting for the previous result)
-        f4 z = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int v = 0; v < 4; v += 2) {
-            const f4 ya = *(const f4*)(myY + j * YLD + 16 * g + 4 * v);
-            const f4 yb = *(const f4*)(myY + j * YLD + 16 * g + 4 * v + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                z = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[e], xb[4 * v + e], z, 0, 0, 0);
-                z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(yb[e], xb[4 * v + 4 + e], z1, 0, 0, 0);
-            }
-        }
-        z += z1;
-        // lane holds z(x, y = y0 + 4g + r)
+        const f4 z = ce_logits(myY, xb, j, g);
         float dz[4], fv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int64_t y = y0 + 4 * g + r;
             const bool yok = y < NY;
             const int64_t yc = yok ? y : NY - 1;
-            int64_t row, col, seq, label;
-            int idc, pad;
-            float deb;
-            bool hit = false;
-            float r_lse = 0.f, r_scale = 0.f;        // DSCORE fast path: per-row values from the tile table
-            if (MODE != CE_DSCORE) {
-                row = xc; col = yc; seq = row_seq; label = row_label;
-                if (fast) {
-                    const int cl = (int)(yc - y0);
-                    idc = myMeta[cl]; pad = myMeta[16 + cl]; deb = __int_as_float(myMeta[32 + cl]);
-                } else {
-                    idc = b.ids32[col]; pad = b.colpad[col]; deb = b.debias[col];
-                }
-            } else {
-                row = yc; col = xc;
-                idc = col_id; pad = col_pad; deb = col_debias;
-                if (fast) {
-                    const int rr = (int)(yc - y0);
-                    seq = 0;
-                    label = myRow[16 + rr];
-                    hit = (hitmask >> myRow[rr]) & 1u;
-                    r_lse = __int_as_float(myRow[32 + rr]);
-                    r_scale = __int_as_float(myRow[48 + rr]);
-                } else {
-                    seq = row / S; label = seq * S1 + (row - seq * S) + 1;
-                }
-            }
-            float val = z[r] - deb;
-            if (pad) val = MASKV;
-            else if (col != label) {
-                if (MODE != CE_DSCORE && fast) {
-#pragma unroll
-                    for (int p = 0; p < RS1; ++p) hit |= rid[p] == idc;
-                } else if (!fast) {
-                    hit = id_in_seq(b.ids32, seq, S1, idc);
-                }
-                if (hit) val = MASKV;
-            }
+            const int64_t row = MODE == CE_DSCORE ? yc : xc, col = MODE == CE_DSCORE ? xc : yc;
+            const int64_t label = ce_label(row, S);
+            float val = z[r] - b.debias[col];
+            if (b.colpad[col]) val = MASKV;
+            else if (col != label && id_in_seq(b.ids32, row / S, S1, b.ids32[col])) val = MASKV;
             if (MODE == CE_FWD) {
-                fv[r] = yok ? val : -INFINITY;        // folded into the running (max, sum) after the tile, four at a time
+                fv[r] = yok ? val : -INFINITY;
                 if (yok && col == label) zlab = val;
             } else {
-                float lse, scale;
-                if (MODE == CE_DPREC) {
-                    lse = row_lse; scale = row_scale;
-                } else if (fast) {
-                    lse = r_lse; scale = r_scale;
-                } else {
-                    lse = b.lse[row];
-                    scale = log_mask[row] != 0.f ? d_loss / b.nvalid[0] : 0.f;
-                }
-                const float p = expf(val - lse);
+                const float scale = log_mask[row] != 0.f ? d_loss / b.nvalid[0] : 0.f;
+                const float p = expf(val - b.lse[row]);
                 dz[r] = (yok && xok) ? (p - (col == label ? 1.f : 0.f)) * scale : 0.f;
             }
         }
         if (MODE == CE_FWD) {
-            // one rescale per tile instead of a data-dependent branch with an exp on both sides per logit (5 exps per 4
-            // logits instead of 8, no divergence); masked logits are finite (MASKV), structural padding is -inf -> 0
-            const float m4 = fmaxf(fmaxf(fv[0], fv[1]), fmaxf(fv[2], fv[3]));
-            const float mn = fmaxf(run_m, m4);
-            if (mn > -INFINITY) {
-                float add = 0.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) add += expf(fv[r] - mn);
-                run_l = run_l * expf(run_m - mn) + add;
-                run_m = mn;
-            }
-        }
-        if (MODE != CE_FWD) {
-            // dX^T[e][x] += sum_y Y[y][e] dZ(x,y):  A = Y^T (i = e within tile et, k = y0 + 4kq + r), B = dz[r]
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int et = 0; et < 4; ++et) {
-                    const float ya = myY[(4 * g + r) * YLD + 16 * et + j];
-                    dacc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(ya, dz[r], dacc[et], 0, 0, 0);
-                }
+            ce_online(run_m, run_l, fv, [](float v) { return expf(v); });
+        } else {
+            float yt16[4][4];
+            ce_read_yt(yt16, myY, j, g);
+            ce_second(dacc, yt16, dz);
         }
         __builtin_amdgcn_wave_barrier();
     }
-
     if (MODE == CE_FWD) {
-        // combine (m, l) and the label logit across the 4 lane groups and the 4 waves
-        auto comb = [](float& m, float& l, float m2, float l2) {
-            const float mn = fmaxf(m, m2);
-            const float a = m == -INFINITY ? 0.f : l * expf(m - mn);
-            const float c = m2 == -INFINITY ? 0.f : l2 * expf(m2 - mn);
-            m = mn;
-            l = a + c;
-        };
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-            const float m2 = __shfl_xor(run_m, o, 64), l2 = __shfl_xor(run_l, o, 64);
-            comb(run_m, run_l, m2, l2);
-            zlab += __shfl_xor(zlab, o, 64);
-        }
-        if (g == 0) {
-            sRed[wave][j][0] = run_m;
-            sRed[wave][j][1] = run_l;
-            sRed[wave][j][2] = zlab;
-        }
-        __syncthreads();
-        if (wave == 0 && g == 0 && xok) {
-            float m = sRed[0][j][0], l = sRed[0][j][1], zl = sRed[0][j][2];
-            for (int w = 1; w < 4; ++w) {
-                comb(m, l, sRed[w][j][0], sRed[w][j][1]);
-                zl += sRed[w][j][2];
-            }
-            const float lse = m + logf(l);
-            b.lse[x] = lse;
-            b.rowloss[x] = row_valid ? lse - zl : 0.f;
-        }
+        ce_fwd_finish(sRed, run_m, run_l, zlab, wave, j, g, xok, x, xok && log_mask[xc] != 0.f, b);
     } else {
-        // lane (j, g) holds dX[x0+j][16et + 4g + r]; sum over the 4 waves
-#pragma unroll
-        for (int et = 0; et < 4; ++et)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sRed[wave][j][16 * et + 4 * g + r] = dacc[et][r];
+        ce_dacc_to_red(sRed, dacc, wave, j, g);
         __syncthreads();
-        for (int i = tid; i < 16 * E; i += 256) {
-            const int rj = i / E, e = i - rj * E;
-            if (x0 + rj < NX) dX[(x0 + rj) * E + e] = sRed[0][rj][e] + sRed[1][rj][e] + sRed[2][rj][e] + sRed[3][rj][e];
-        }
+        ce_sum_store(sRed, dX, x0, NX, tid);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Row-fixed passes (FWD, DPREC) with the per-logit work cut down (round 2).  rocprofv3 of the Cached step at bs = 1024 had
-// the three passes at 476 / 586 / 634 us against 110 / 220 / 220 us of f32 MFMA time: they were VALU-bound — per logit
-// eleven id compares for the false-negative mask, 64-bit index arithmetic, three LDS reads and a libm expf (~100 VALU
-// instructions, four logits per lane and tile).  Here
+// The row-fixed passes (X = prec, Y = score; FWD, DPREC, and FUSED = both in one walk) with the per-logit work cut down.  rocprofv3 of
+// the Cached step at bs = 1024 had the plain passes at 476 / 586 / 634 us against 110 / 220 / 220 us of f32 MFMA time: they were
+// VALU-bound (~100 VALU instructions per logit).  What is particular here:
 //   * the false-negative test is done ONCE PER WAVE AND TILE: the 16 rows of a workgroup belong to at most four sequences
-//     (S >= 5), lane l tests column l&15 against the ids of sequence slot l>>4 (held in its registers for the whole pass)
-//     and a ballot turns the 64 answers into a mask every lane indexes with (its row's slot, the logit's column);
+//     (S >= 5), lane l tests column l&15 against the ids of sequence slot l>>4 (held in its registers for the whole pass, RS1 of
+//     them: 11 = the reference's max_seq_len 10 + 1, or MAXS1) and a ballot turns the 64 answers into a mask every lane indexes
+//     with (its row's slot, the logit's column);
 //   * column padding is a second ballot, the debias of a lane's four columns one 16-byte LDS read;
-//   * exp(x) = v_exp_f32(x * log2 e): 2 instructions, relative error < 3e-6 for the |x| <= 40 that matter (the loss
-//     tolerance is 2e-5, the gradients' 2e-4; masked logits underflow to 0 exactly as before);
-//   * all indices are 32-bit (M < 2^31 is a launch condition).
-// Same tile walk, same MFMA layout and the same reduction as ce_pass_kernel, which remains the generic path.
-__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-
+//   * fexp instead of expf, 32-bit indices;
+//   * the next tile's rows and column metadata travel in registers while the current tile is multiplied, and the second product's
+//     fragments are read ahead of the mask / exp arithmetic.
+// CE_FUSED: forward and d_prec in ONE pass, flash-attention style: the accumulators hold sum_y exp(z - run_m) * score[y] against a
+// running ROW maximum (common to the four lanes of a row, because the MFMA sums over their columns) and are rescaled when it moves —
+// after the first tiles it almost never does, and the test is one ballot per tile.  d_prec for d_loss = 1 stays in the workspace.
 template <int MODE, int RS1>
 __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict__ prec, const float* __restrict__ score,
                                                          const float* __restrict__ log_mask, CeBufs b, int bs, int S,
-                                                         float d_loss, float* __restrict__ dX, int dbg = 0) {
+                                                         float d_loss, float* __restrict__ dX) {
     static_assert(MODE == CE_FWD || MODE == CE_DPREC || MODE == CE_FUSED, "row-fixed passes only");
     __shared__ __attribute__((aligned(16))) float sY[4][16 * YLD];
-    __shared__ float sRed[4][16][E + 4];
-    __shared__ __attribute__((aligned(16))) int sMeta[4][64];
+    __shared__ CeRed sRed;
+    __shared__ __attribute__((aligned(16))) int sMeta[4][64];    // per wave: ids | pad flags | debias of the tile's 16 columns
     const int S1 = S + 1;
     const int T = bs * S, M = bs * S1;
     const float* X = prec;
@@ -428,14 +392,9 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
     const int xc = xok ? x : NX - 1;
 
     float xb[16];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const f4 t = *(const f4*)(X + (int64_t)xc * E + 16 * g + 4 * v);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) xb[4 * v + e] = t[e];
-    }
+    ce_load_x(xb, X, xc, g);
     const int row_seq = xc / S;
-    const int row_label = row_seq * S1 + (xc - row_seq * S) + 1;
+    const int row_label = ce_label(xc, S);
     const bool row_valid = xok && log_mask[xc] != 0.f;
     const float row_lse = MODE == CE_DPREC ? b.lse[xc] : 0.f;
     const float row_scale = (MODE == CE_DPREC && row_valid) ? d_loss / b.nvalid[0] : 0.f;
@@ -449,9 +408,6 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
         for (int p = 0; p < RS1; ++p) sid[p] = (p < S1 && sq < bs) ? b.ids32[sq * S1 + p] : -2;
     }
 
-    // CE_FUSED: forward and d_prec in ONE pass, flash-attention style: the accumulators hold sum_y exp(z - run_m) * score[y]
-    // against a running ROW maximum (common to the four lanes of a row, because the MFMA sums over their columns) and are
-    // rescaled when it moves — after the first tiles it almost never does, and the test is one ballot per tile.
     float run_m = MODE == CE_FUSED ? -3.0e38f : -INFINITY, run_l = 0.f, zlab = 0.f;
     f4 dacc[4];
 #pragma unroll
@@ -460,8 +416,8 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
     float* myY = sY[wave];
     int* myMeta = sMeta[wave];
     const int ntiles = (NY + 15) / 16;
-    // the next tile's rows and column metadata travel in registers while the current tile is multiplied: with the loads at
-    // the top of the iteration every tile waited for an L2 round trip (FWD 303 us against 110 us of MFMA time)
+    // the prefetch registers: with the loads at the top of the iteration every tile waited for an L2 round trip (FWD 303 us against
+    // 110 us of MFMA time)
     f4 yreg[4];
     int mreg[3] = {0, 0, 0};
     // Branch-free: a tile index past the end re-reads the last tile, a row past NY re-reads row NY-1 (finite values that
@@ -481,11 +437,7 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
     prefetch(wave);
     for (int yt = wave; yt < ntiles; yt += 4) {
         const int y0 = yt * 16;
-        {
-            const int r = lane >> 2, ch = lane & 3;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) *(f4*)(myY + r * YLD + ch * 16 + v * 4) = yreg[v];
-        }
+        ce_stage_y(myY, yreg, lane);
         if (lane < 16) {
             myMeta[lane] = mreg[0];
             myMeta[16 + lane] = mreg[1];
@@ -504,30 +456,13 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
         const unsigned pad4 = (pm >> (4 * g)) & 0xfu;
         const f4 deb4 = *(const f4*)(myMeta + 32 + 4 * g);      // bit patterns of four floats
 
-        f4 z = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int v = 0; v < 4; v += 2) {
-            const f4 ya = *(const f4*)(myY + j * YLD + 16 * g + 4 * v);
-            const f4 yb = *(const f4*)(myY + j * YLD + 16 * g + 4 * v + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#ifdef CE_ABLATE      // build with -DCE_ABLATE for tools/ce_ablate.py: even the untaken branch costs the row pass 130 us (450 -> 585)
-                if (dbg & 1) { z[0] += ya[e] * xb[4 * v + e]; continue; }       // ablation (timing only): no logits product
-#endif
-                z = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[e], xb[4 * v + e], z, 0, 0, 0);
-                z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(yb[e], xb[4 * v + 4 + e], z1, 0, 0, 0);
-            }
-        }
-        z += z1;
+        const f4 z = ce_logits(myY, xb, j, g);
         // the second product's 16 transposed tile reads are requested NOW, fenced, and land behind the mask / exp arithmetic:
         // left to the compiler each pair sat right in front of its two MFMAs behind an lgkmcnt(0) (eight exposed LDS
         // round trips per tile)
         float yt16[4][4];
         if (MODE != CE_FWD) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int et = 0; et < 4; ++et) yt16[r][et] = myY[(4 * g + r) * YLD + 16 * et + j];
+            ce_read_yt(yt16, myY, j, g);
             __builtin_amdgcn_sched_barrier(0);
         }
         const bool whole = y0 + 16 <= NY;            // wave-uniform
@@ -548,15 +483,7 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
             }
         }
         if (MODE == CE_FWD) {
-            const float m4 = fmaxf(fmaxf(fv[0], fv[1]), fmaxf(fv[2], fv[3]));
-            const float mn = fmaxf(run_m, m4);
-            if (mn > -INFINITY) {
-                float add = 0.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) add += fexp(fv[r] - mn);
-                run_l = run_l * fexp(run_m - mn) + add;
-                run_m = mn;
-            }
+            ce_online(run_m, run_l, fv, fexp);
         } else {
             if (MODE == CE_FUSED) {
                 const float m4 = fmaxf(fmaxf(fv[0], fv[1]), fmaxf(fv[2], fv[3]));
@@ -576,100 +503,37 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
                     run_l += dz[r];
                 }
             }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int et = 0; et < 4; ++et) {
-#ifdef CE_ABLATE
-                    if (dbg & 2) { dacc[et][0] += yt16[r][et] * dz[r]; continue; }         // ablation (timing only)
-#endif
-                    dacc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(yt16[r][et], dz[r], dacc[et], 0, 0, 0);
-                }
+            ce_second(dacc, yt16, dz);
         }
         __builtin_amdgcn_wave_barrier();
     }
 
     if (MODE == CE_FWD) {
-        auto comb = [](float& m, float& l, float m2, float l2) {
-            const float mn = fmaxf(m, m2);
-            const float a = m == -INFINITY ? 0.f : l * expf(m - mn);
-            const float c = m2 == -INFINITY ? 0.f : l2 * expf(m2 - mn);
-            m = mn;
-            l = a + c;
-        };
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-            const float m2 = __shfl_xor(run_m, o, 64), l2 = __shfl_xor(run_l, o, 64);
-            comb(run_m, run_l, m2, l2);
-            zlab += __shfl_xor(zlab, o, 64);
-        }
-        if (g == 0) {
-            sRed[wave][j][0] = run_m;
-            sRed[wave][j][1] = run_l;
-            sRed[wave][j][2] = zlab;
-        }
-        __syncthreads();
-        if (wave == 0 && g == 0 && xok) {
-            float m = sRed[0][j][0], l = sRed[0][j][1], zl = sRed[0][j][2];
-            for (int w = 1; w < 4; ++w) {
-                comb(m, l, sRed[w][j][0], sRed[w][j][1]);
-                zl += sRed[w][j][2];
-            }
-            const float lse = m + logf(l);
-            b.lse[x] = lse;
-            b.rowloss[x] = row_valid ? lse - zl : 0.f;
-        }
+        ce_fwd_finish(sRed, run_m, run_l, zlab, wave, j, g, xok, x, row_valid, b);
     } else if (MODE == CE_FUSED) {
+        // the four lanes of a row share run_m; their sums add up
 #pragma unroll
         for (int o = 16; o <= 32; o <<= 1) {
             run_l += __shfl_xor(run_l, o, 64);
             zlab += __shfl_xor(zlab, o, 64);
         }
-#pragma unroll
-        for (int et = 0; et < 4; ++et)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sRed[wave][j][16 * et + 4 * g + r] = dacc[et][r];
+        ce_dacc_to_red(sRed, dacc, wave, j, g);
         if (g == 0) {
             sRed[wave][j][E] = run_m;
             sRed[wave][j][E + 1] = run_l;
             sRed[wave][j][E + 2] = zlab;
         }
         __syncthreads();
-        // per row: the four waves' partial sums brought to the common maximum; d_prec = (sum_y p_y score_y - score_label) / n
         for (int i = tid; i < 16 * E; i += 256) {
             const int rj = i / E, e = i - rj * E;
             const int xr = x0 + rj;
             if (xr >= NX) continue;
-            float m = sRed[0][rj][E];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) m = fmaxf(m, sRed[w][rj][E]);
-            float l = 0.f, acc = 0.f, zl = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const float f = fexp(sRed[w][rj][E] - m);
-                l += sRed[w][rj][E + 1] * f;
-                acc += sRed[w][rj][e] * f;
-                zl += sRed[w][rj][E + 2];
-            }
-            const bool valid = log_mask[xr] != 0.f;
-            const int sq = xr / S, lab = sq * S1 + (xr - sq * S) + 1;
-            b.dprec[(int64_t)xr * E + e] = valid ? (acc / l - Y[(int64_t)lab * E + e]) / b.nvalid[0] : 0.f;
-            if (e == 0) {
-                const float lse = m + logf(l);
-                b.lse[xr] = lse;
-                b.rowloss[xr] = valid ? lse - zl : 0.f;
-            }
+            ce_fused_finish(4, [&](int w, int k) { return sRed[w][rj][k]; }, xr, e, Y, log_mask, b, S);
         }
     } else {
-#pragma unroll
-        for (int et = 0; et < 4; ++et)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sRed[wave][j][16 * et + 4 * g + r] = dacc[et][r];
+        ce_dacc_to_red(sRed, dacc, wave, j, g);
         __syncthreads();
-        for (int i = tid; i < 16 * E; i += 256) {
-            const int rj = i / E, e = i - rj * E;
-            if (x0 + rj < NX) dX[(int64_t)(x0 + rj) * E + e] = sRed[0][rj][e] + sRed[1][rj][e] + sRed[2][rj][e] + sRed[3][rj][e];
-        }
+        ce_sum_store(sRed, dX, x0, NX, tid);
     }
 }
 
@@ -681,16 +545,16 @@ __global__ void ce_scale_kernel(const float* __restrict__ in, float scale, float
     }
 }
 
-// The column-fixed pass (d_score = dZ^T · prec) in the same style: lane (g, j) owns column x0 + j for the whole pass and, per
-// tile of 16 prec rows (at most four sequences), tests ITS column against the ids of the tile's sequence slot g — the four
-// lanes of a column cover the four slots — and a ballot publishes the 64 answers; per-row label / lse / scale / slot come
-// from a small LDS table, one 16-byte read each.
+// The column-fixed pass (d_score = dZ^T · prec: X = score, Y = prec) in the same style: lane (j, g) owns column x0 + j for the whole
+// pass and, per tile of 16 prec rows (at most four sequences), tests ITS column against the ids of the tile's sequence slot g — the
+// four lanes of a column cover the four slots — and a ballot publishes the 64 answers; per-row label / lse / scale / slot come from
+// a small LDS table, one 16-byte read each.  The tile's ids and per-row values are prefetched with its rows.
 template <int RS1>
 __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict__ prec, const float* __restrict__ score,
                                                          const float* __restrict__ log_mask, CeBufs b, int bs, int S,
                                                          float d_loss, float* __restrict__ dX) {
     __shared__ __attribute__((aligned(16))) float sY[4][16 * YLD];
-    __shared__ float sRed[4][16][E + 4];
+    __shared__ CeRed sRed;
     __shared__ __attribute__((aligned(16))) int sMeta[4][64];     // ids of the tile's four sequences, 16 per slot
     __shared__ __attribute__((aligned(16))) int sRow[4][64];      // per row: slot | label column | lse | scale
     const int S1 = S + 1;
@@ -706,12 +570,7 @@ __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict
     const int xc = xok ? x : NX - 1;
 
     float xb[16];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const f4 t = *(const f4*)(X + (int64_t)xc * E + 16 * g + 4 * v);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) xb[4 * v + e] = t[e];
-    }
+    ce_load_x(xb, X, xc, g);
     const int col_id = b.ids32[xc];
     const bool col_pad = b.colpad[xc] != 0;
     const float col_debias = b.debias[xc];
@@ -749,53 +608,34 @@ __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict
     prefetch(wave);
     for (int yt = wave; yt < ntiles; yt += 4) {
         const int y0 = yt * 16;
-        {
-            const int r = lane >> 2, ch = lane & 3;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) *(f4*)(myY + r * YLD + ch * 16 + v * 4) = yreg[v];
-        }
+        ce_stage_y(myY, yreg, lane);
         myMeta[lane] = idreg;
         if (lane < 16) {
             const int seq0 = y0 / S;
             const int rw = y0 + lane < NY ? y0 + lane : NY - 1;
-            const int rs = rw / S;
-            myRow[lane] = rs - seq0;
-            myRow[16 + lane] = rs * S1 + (rw - rs * S) + 1;
+            myRow[lane] = rw / S - seq0;
+            myRow[16 + lane] = ce_label(rw, S);
             myRow[32 + lane] = __float_as_int(lsereg);
             myRow[48 + lane] = __float_as_int(lmreg != 0.f ? dscale : 0.f);
         }
         prefetch(yt + 4);
         __builtin_amdgcn_wave_barrier();
+        typedef int i4 __attribute__((ext_vector_type(4)));
         bool h = false;
-        {
-            typedef int i4 __attribute__((ext_vector_type(4)));
 #pragma unroll
-            for (int q = 0; q < (RS1 + 3) / 4; ++q) {
-                const i4 v = *(const i4*)(myMeta + 16 * g + 4 * q);
+        for (int q = 0; q < (RS1 + 3) / 4; ++q) {
+            const i4 v = *(const i4*)(myMeta + 16 * g + 4 * q);
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (4 * q + k < RS1) h |= v[k] == col_id;
-            }
+            for (int k = 0; k < 4; ++k)
+                if (4 * q + k < RS1) h |= v[k] == col_id;
         }
         const unsigned long long hm = __ballot(h);      // bit 16*slot + j
-        typedef int i4 __attribute__((ext_vector_type(4)));
         const i4 slot4 = *(const i4*)(myRow + 4 * g);
         const i4 lab4 = *(const i4*)(myRow + 16 + 4 * g);
         const f4 lse4 = *(const f4*)(myRow + 32 + 4 * g);
         const f4 sc4 = *(const f4*)(myRow + 48 + 4 * g);
 
-        f4 z = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int v = 0; v < 4; v += 2) {
-            const f4 ya = *(const f4*)(myY + j * YLD + 16 * g + 4 * v);
-            const f4 yb = *(const f4*)(myY + j * YLD + 16 * g + 4 * v + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                z = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[e], xb[4 * v + e], z, 0, 0, 0);
-                z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(yb[e], xb[4 * v + 4 + e], z1, 0, 0, 0);
-            }
-        }
-        z += z1;
+        const f4 z = ce_logits(myY, xb, j, g);
         const bool whole = y0 + 16 <= NY;
         float dz[4];
 #pragma unroll
@@ -808,26 +648,15 @@ __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict
             const float pr = fexp(val - lse4[r]);
             dz[r] = (yok && xok) ? (pr - (is_lab ? 1.f : 0.f)) * sc4[r] : 0.f;
         }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int et = 0; et < 4; ++et) {
-                const float ya = myY[(4 * g + r) * YLD + 16 * et + j];
-                dacc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(ya, dz[r], dacc[et], 0, 0, 0);
-            }
+        float yt16[4][4];
+        ce_read_yt(yt16, myY, j, g);
+        ce_second(dacc, yt16, dz);
         __builtin_amdgcn_wave_barrier();
     }
-#pragma unroll
-    for (int et = 0; et < 4; ++et)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sRed[wave][j][16 * et + 4 * g + r] = dacc[et][r];
+    ce_dacc_to_red(sRed, dacc, wave, j, g);
     __syncthreads();
-    for (int i = tid; i < 16 * E; i += 256) {
-        const int rj = i / E, e = i - rj * E;
-        if (x0 + rj < NX) dX[(int64_t)(x0 + rj) * E + e] = sRed[0][rj][e] + sRed[1][rj][e] + sRed[2][rj][e] + sRed[3][rj][e];
-    }
+    ce_sum_store(sRed, dX, x0, NX, tid);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Round 6: the same two passes on the 16-bit matrix cores with SPLIT operands (the idea of split.hip, inside the loss).
@@ -1153,28 +982,11 @@ __global__ __launch_bounds__(256, NSUB == 1 ? 4 : 2) void ce16_rowpass_kernel(co
 // lse, row loss and d_prec (for d_loss = 1) from the per-range partial results: the ranges brought to the common maximum, fixed order
 __global__ __launch_bounds__(256) void ce16_row_combine_kernel(const float* __restrict__ score, const float* __restrict__ log_mask, CeBufs b, Ce16Bufs c,
                                                                int bs, int S, int ysplits) {
-    const int S1 = S + 1, T = bs * S;
+    const int T = bs * S;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int xr = i >> 6, e = i & 63;
     if (xr >= T) return;
-    float m = -3.0e38f;
-    for (int y = 0; y < ysplits; ++y) m = fmaxf(m, c.part_row[((int64_t)y * T + xr) * 68 + E]);
-    float l = 0.f, acc = 0.f, zl = 0.f;
-    for (int y = 0; y < ysplits; ++y) {
-        const float* p = c.part_row + ((int64_t)y * T + xr) * 68;
-        const float f = fexp(p[E] - m);
-        l += p[E + 1] * f;
-        acc += p[e] * f;
-        zl += p[E + 2];
-    }
-    const bool valid = log_mask[xr] != 0.f;
-    const int sq = xr / S, lab = sq * S1 + (xr - sq * S) + 1;
-    b.dprec[(int64_t)xr * E + e] = valid ? (acc / l - score[(int64_t)lab * E + e]) / b.nvalid[0] : 0.f;
-    if (e == 0) {
-        const float lse = m + logf(l);
-        b.lse[xr] = lse;
-        b.rowloss[xr] = valid ? lse - zl : 0.f;
-    }
+    ce_fused_finish(ysplits, [&](int y, int k) { return c.part_row[((int64_t)y * T + xr) * 68 + k]; }, xr, e, score, log_mask, b, S);
 }
 
 // The column-fixed pass (d_score = dZ^T · prec): X = score (a lane owns one column), Y = prec.  grid (x blocks, ysplits)
@@ -1313,7 +1125,7 @@ __global__ __launch_bounds__(256) void ce16_col_combine_kernel(CeBufs b, Ce16Buf
 // from the forward's token.  ce_fast:
 //   1 (default): one fused FWD + DPREC row pass (online softmax) and the cooperative column pass — on the 16-bit matrix cores with split
 //      operands (ce16_*) from C16_MIN_LOGITS logits on, on the f32 cores below; 2: separate FWD and DPREC row passes (round-2a form); 0: the
-//      generic kernel everywhere; 3: ce16_* at every size; 4: the f32 fused passes at every size (test knobs)
+//      plain kernel everywhere (per-logit work: slow); 3: ce16_* at every size; 4: the f32 fused passes at every size (test knobs)
 enum { CE_ROUTE_GENERIC = 0,      // ce_pass_kernel for all three passes (any S <= 63)
        CE_ROUTE_ROWPASS = 1,      // ce_rowpass_kernel<CE_FWD>, <CE_DPREC>, ce_colpass_kernel
        CE_ROUTE_FUSED = 2,        // ce_rowpass_kernel<CE_FUSED> leaves d_prec for d_loss = 1 in the workspace; backward scales it + ce_colpass_kernel
@@ -1328,7 +1140,7 @@ int ce_route(int64_t bs, int S) {
     return (g_ce_fast == 1 || g_ce_fast == 4) ? CE_ROUTE_FUSED : CE_ROUTE_ROWPASS;
 }
 // The run-time S + 1 as the RS1 template argument (slots per sequence compared per logit): f(integral_constant<int, 11 or MAXS1>).  11 is the
-// reference's max_seq_len 10 + 1; every kernel's RS1 = 11 instantiation also handles shorter sequences, except the generic CE_DSCORE pass (below).
+// reference's max_seq_len 10 + 1; every kernel's RS1 = 11 instantiation also handles shorter sequences.  The plain kernel has no such argument.
 template <class F>
 void with_rs1(int S, F&& f) {
     if (S + 1 <= 11) f(std::integral_constant<int, 11>{});
@@ -1443,7 +1255,7 @@ extern "C" int iisan_inbatch_ce_fwd(const int64_t* ids, const float* score, cons
             with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_FWD, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, 0.f, none); });
             break;
         default:
-            with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_pass_kernel<CE_FWD, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, bs, S, 0.f, none); });
+            hipLaunchKernelGGL((ce_pass_kernel<CE_FWD>), rows, dim3(256), 0, s, prec, score, log_mask, b, bs, S, 0.f, none);
     }
     IISAN_LAUNCH_OK();
     hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, b.rowloss, T, b.nvalid, loss);
@@ -1480,7 +1292,7 @@ extern "C" int iisan_inbatch_ce_bwd(const int64_t* ids, const float* score, cons
     else if (route == CE_ROUTE_ROWPASS)
         with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_DPREC, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, d_loss, d_prec); });
     else
-        with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_pass_kernel<CE_DPREC, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_prec); });
+        hipLaunchKernelGGL((ce_pass_kernel<CE_DPREC>), rows, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_prec);
     IISAN_LAUNCH_OK();
     // d_score: the column pass
     if (route == CE_ROUTE_SPLIT16) {
@@ -1489,13 +1301,8 @@ extern "C" int iisan_inbatch_ce_bwd(const int64_t* ids, const float* score, cons
         hipLaunchKernelGGL(ce16_col_combine_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(M * E / 4, 256), 2048)), dim3(256), 0, s, b, b16, M * E / 4, ys, d_loss, d_score);
     } else if (route != CE_ROUTE_GENERIC) {
         with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_colpass_kernel<CE_RS1>), cols, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, d_loss, d_score); });
-    } else if (S + 1 == 11) {
-        // == 11, not <= 11: in its CE_DSCORE mode ce_pass_kernel holds no ids in registers (RS1 sizes only the unused `rid`) and RS1 = 11 selects
-        // the id scan with compile-time indices, which that kernel takes for S + 1 == 11 alone — for a shorter sequence the instantiation would
-        // run the very loop of the MAXS1 one, so those stay there
-        hipLaunchKernelGGL((ce_pass_kernel<CE_DSCORE, 11>), cols, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_score);
     } else {
-        hipLaunchKernelGGL((ce_pass_kernel<CE_DSCORE, MAXS1>), cols, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_score);
+        hipLaunchKernelGGL((ce_pass_kernel<CE_DSCORE>), cols, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_score);
     }
     IISAN_LAUNCH_OK();
     return IISAN_OK;

@@ -651,9 +651,9 @@ def test_d_loss_is_a_plain_multiplier_on_every_loss_route(lib, ce_fast, bs, S):
       * the last call BIT-equal to the first: the backward does not modify what the forward left in the workspace (the fused and the
         split-operand routes keep d_prec for d_loss = 1 there and only scale it);
       * -0.3: against -0.3 x the fp64 gradient of `O.inbatch_ce`, the bound of the ragged-shape loss test (2e-4 of the scale + 1e-9).
-    Shapes: ragged 16-row tiles, RS1 = 16 (S = 15), S = 5, S = 4 (generic under every switch: the MAXS1 column pass), and for the generic
-    route S = 10 (the `CE_DSCORE, 11` instantiation).  Workspace of exactly `iisan_inbatch_ce_ws_bytes`, guard zones around it, the loss
-    and both gradients."""
+    Shapes: ragged 16-row tiles, RS1 = 16 (S = 15), S = 5, S = 4 (the plain kernel under every switch), and for the generic route
+    S = 10 once more at a batch of 5 (T = 50, M = 55: the plain kernel's column pass over four X blocks, the last one partial).  Workspace
+    of exactly `iisan_inbatch_ce_ws_bytes`, guard zones around it, the loss and both gradients."""
     b, _, _, loss_ref, ds_ref, dp_ref = _ce_problem(bs, S)
     want_route = 0 if (ce_fast == 0 or S < 5) else CE_ROUTE_OF[ce_fast]
     res = {}

@@ -11,7 +11,9 @@ leaves the instantiations that do not name it on the key they had.  The paramete
 argument renumbers the substitutions (`S9_` -> `SA_`) in it, which no textual rewrite of the name can follow.
 --strip OLD=NEW rewrites mangled names of the NEW listing before matching (enough when the added argument is the last thing that can
 be substituted: the 768-wide instantiations of rowops.hip gained a trailing `Li768E`).
-Kernels only in the new listing are listed with their own figures."""
+Kernels only in the new listing are listed with their own figures.
+--classes (anywhere on the line) adds a second table: per kernel and listing, the number of v_mfma*, v_exp_f32, ds_* and global_* /
+buffer_* instructions — what has to stay put when a refactor moves only integer address arithmetic."""
 import re
 import sys
 
@@ -106,8 +108,14 @@ def template_key(sym, ignore=()):
     return name + ("<" + ", ".join(args) + ">" if args else "")
 
 
+# --classes: the instructions whose number decides a kernel's speed, counted per kernel in both listings
+CLASSES = {"v_mfma": r"v_mfma", "v_exp_f32": r"v_exp_f32", "ds": r"ds_", "global/buffer": r"(global|buffer)_"}
+
+
 def main():
     args = sys.argv[1:]
+    classes = "--classes" in args
+    args = [a for a in args if a != "--classes"]
     strip, only, ignore = [], None, []
     while len(args) > 2:
         flag, val = args[-2], args[-1]
@@ -155,6 +163,12 @@ def main():
             n = newk[k]
             print(f"| `{k if ignore else n}` | - -> {len(new[n])} | - -> {nm[n]} | new |")
     print(f"\n{n_cmp} kernels compared, {n_diff} differ")
+    if classes:
+        count = lambda ins: " / ".join(str(sum(bool(re.match(c, x)) for x in ins)) for c in CLASSES.values())
+        print("\n| kernel | " + " / ".join(CLASSES) + " parent | new |\n|---|---|---|")
+        for k in sorted(set(oldk) | set(newk)):
+            if not only or only in k:
+                print(f"| `{k}` | {count(old[oldk[k]]) if k in oldk else '-'} | {count(new[newk[k]]) if k in newk else '-'} |")
     return 1 if n_diff else 0
 
 
