@@ -6,6 +6,8 @@
 //     z[:,c]    = -1e4   if slot c is history padding (position < S and log_mask == 0)            (model.py:88-89)
 //     z[row,c]  = -1e4   if id_c occurs in the row's own sequence and c is not the row's positive  (model.py:92-100)
 //     loss      = mean over rows with log_mask != 0 of  logsumexp(z[row,:]) - z[row, label]       (model.py:102-104)
+// The -1e4 are ASSIGNED: a filled logit is a constant.  The false-negative fill spares the label, the padding fill does not — a label
+// column with log_mask == 0 (a hole in the mask; never with left padding) is -1e4 in the loss and carries no gradient.
 //
 // Three families of kernels compute it (ce_route below says which one a call takes):
 //     ce_pass_kernel                          the plain statement of the loss, any shape
@@ -114,8 +116,11 @@ __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict_
 enum { CE_FWD = 0, CE_DPREC = 1, CE_DSCORE = 2, CE_FUSED = 3 };
 typedef float CeRed[4][16][E + 4];      // per wave and X row: 64 features (+ m, l, z_label of the fused finish)
 
-// exp(x) = v_exp_f32(x * log2 e): 2 instructions, relative error < 3e-6 for the |x| <= 40 that matter (the loss tolerance is 2e-5, the
-// gradients' 2e-4; masked logits underflow to 0 exactly as with expf)
+// exp(x) = v_exp_f32(x * log2 e): 2 instructions.  The product is rounded once, so the relative error is |x| 2^-24 plus the ulp of
+// v_exp_f32 — and every argument here is a logit minus a maximum or an lse, <= 0 up to rounding: a term that far below the top weighs
+// e^-|x|, its share of the error of a sum is |x| e^-|x| 2^-24 <= 2.2e-8 at ANY |x|.  tests/test_gpu_ce_regimes.py runs arguments from 0
+// down to -300 (logits of +-150) next to the -1e4 fills, which underflow to 0 exactly as with expf: loss within 2.1e-6 and gradients
+// within 4.7e-6 of the float64 oracle on every route (profiles/ce_regimes.md; the bounds are 2e-5 and 2e-4)
 __device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
 // the label column of prec row x: the next slot of its sequence (S rows, S + 1 columns per sequence)
@@ -250,22 +255,25 @@ __device__ __forceinline__ void ce_fwd_finish(CeRed& sRed, float run_m, float ru
 // The finish of the fused forward + d_prec passes (ce_rowpass_kernel<CE_FUSED>: its four waves, from LDS; ce16_row_combine_kernel: the
 // Y ranges of the split route, from the workspace), for feature e of prec row xr.  part(w, k) is partial result w = 0 .. n - 1 of the
 // row: k < E the accumulator sum_y exp(z - m_w) score[y][k], k = E its maximum m_w, E + 1 its sum l_w, E + 2 its label logit.  The
-// partials are brought to the common maximum in the order w = 0, 1, ...;  d_prec = (sum_y p_y score_y - score_label) / n for d_loss = 1
-template <class PART>
-__device__ __forceinline__ void ce_fused_finish(int n, PART part, int xr, int e, const float* __restrict__ score,
+// partials are brought to the common maximum in the order w = 0, 1, ...;  d_prec = (sum_y p_y score_y - score_label) / n for d_loss = 1.
+// labv(lab) is score[lab][e] AS THE PASS'S PRODUCTS SAW IT (the f32 value, or hi + lo of the split planes): where p_label = 1 the two
+// terms then cancel to the bit.  A label column that is history padding keeps its fill value (model.py:88-89 assigns it): no gradient
+template <class PART, class LABV>
+__device__ __forceinline__ void ce_fused_finish(int n, PART part, LABV labv, int xr, int e,
                                                 const float* __restrict__ log_mask, const CeBufs& b, int S) {
+#pragma clang fp contract(off)      // the two sums below as written (l fused, acc not), whatever else the caller inlines around them
     float m = part(0, E);
     for (int w = 1; w < n; ++w) m = fmaxf(m, part(w, E));
     float l = 0.f, acc = 0.f, zl = 0.f;
     for (int w = 0; w < n; ++w) {
         const float f = fexp(part(w, E) - m);
-        l += part(w, E + 1) * f;
+        l = fmaf(part(w, E + 1), f, l);
         acc += part(w, e) * f;
         zl += part(w, E + 2);
     }
     const bool valid = log_mask[xr] != 0.f;
     const int lab = ce_label(xr, S);
-    b.dprec[(int64_t)xr * E + e] = valid ? (acc / l - score[(int64_t)lab * E + e]) / b.nvalid[0] : 0.f;
+    b.dprec[(int64_t)xr * E + e] = valid ? (acc / l - (b.colpad[lab] ? 0.f : labv(lab))) / b.nvalid[0] : 0.f;
     if (e == 0) {
         const float lse = m + logf(l);
         b.lse[xr] = lse;
@@ -335,7 +343,7 @@ __global__ __launch_bounds__(256) void ce_pass_kernel(const float* __restrict__ 
             } else {
                 const float scale = log_mask[row] != 0.f ? d_loss / b.nvalid[0] : 0.f;
                 const float p = expf(val - b.lse[row]);
-                dz[r] = (yok && xok) ? (p - (col == label ? 1.f : 0.f)) * scale : 0.f;
+                dz[r] = (yok && xok) ? (p - ((col == label && !b.colpad[col]) ? 1.f : 0.f)) * scale : 0.f;
             }
         }
         if (MODE == CE_FWD) {
@@ -479,7 +487,7 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
                 if (yok && is_lab) zlab = val;
             } else {
                 const float pr = fexp(val - row_lse);
-                dz[r] = (yok && xok) ? (pr - (is_lab ? 1.f : 0.f)) * row_scale : 0.f;
+                dz[r] = (yok && xok) ? (pr - ((is_lab && !((pad4 >> r) & 1u)) ? 1.f : 0.f)) * row_scale : 0.f;
             }
         }
         if (MODE == CE_FWD) {
@@ -528,7 +536,7 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
             const int rj = i / E, e = i - rj * E;
             const int xr = x0 + rj;
             if (xr >= NX) continue;
-            ce_fused_finish(4, [&](int w, int k) { return sRed[w][rj][k]; }, xr, e, Y, log_mask, b, S);
+            ce_fused_finish(4, [&](int w, int k) { return sRed[w][rj][k]; }, [&](int lab) { return Y[(int64_t)lab * E + e]; }, xr, e, log_mask, b, S);
         }
     } else {
         ce_dacc_to_red(sRed, dacc, wave, j, g);
@@ -646,7 +654,7 @@ __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict
             const float val = masked ? MASKV : z[r] - col_debias;
             const bool yok = whole || (y0 + 4 * g + r < NY);
             const float pr = fexp(val - lse4[r]);
-            dz[r] = (yok && xok) ? (pr - (is_lab ? 1.f : 0.f)) * sc4[r] : 0.f;
+            dz[r] = (yok && xok) ? (pr - ((is_lab && !col_pad) ? 1.f : 0.f)) * sc4[r] : 0.f;
         }
         float yt16[4][4];
         ce_read_yt(yt16, myY, j, g);
@@ -787,7 +795,10 @@ __device__ __forceinline__ void c16_store(C16Tiles& t, const C16Stage& st, int t
     *(h8*)(t.th + to) = st.th;
     *(h8*)(t.tl + to) = st.tl;
 }
-// logits^T of one half (16 Y rows) of the step against the 16 X rows whose fragments the lane holds: lane (j, g) -> X row j, Y rows 4g..4g+3
+// logits^T of one half (16 Y rows) of the step against the 16 X rows whose fragments the lane holds: lane (j, g) -> X row j, Y rows 4g..4g+3.
+// The three terms are added in the order score_hi prec_hi, score_hi prec_lo, score_lo prec_hi in BOTH passes (COL: Y = prec), so the column
+// pass sees the logits of the row pass's lse to the bit: where a row's probability is all on its label, p - 1 is exactly 0
+template <bool COL>
 __device__ __forceinline__ f4 c16_logits(const C16Tiles& t, int half, int j, int g, const h8 (&xh)[2], const h8 (&xl)[2]) {
     f4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -795,8 +806,8 @@ __device__ __forceinline__ f4 c16_logits(const C16Tiles& t, int half, int j, int
         const int o = (16 * half + j) * C16_YLD + 32 * cc + 8 * g;
         const h8 ah = *(const h8*)(t.yh + o), al = *(const h8*)(t.yl + o);
         z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xh[cc], z, 0, 0, 0);
-        z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xl[cc], z, 0, 0, 0);
-        z = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, xh[cc], z, 0, 0, 0);
+        z = __builtin_amdgcn_mfma_f32_16x16x32_f16(COL ? al : ah, COL ? xh[cc] : xl[cc], z, 0, 0, 0);
+        z = __builtin_amdgcn_mfma_f32_16x16x32_f16(COL ? ah : al, COL ? xl[cc] : xh[cc], z, 0, 0, 0);
     }
     return z;
 }
@@ -908,7 +919,7 @@ __global__ __launch_bounds__(256, NSUB == 1 ? 4 : 2) void ce16_rowpass_kernel(co
             bool lab[8];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const f4 z = c16_logits(tl, h, j, g, xh[u], xl[u]);
+                const f4 z = c16_logits<false>(tl, h, j, g, xh[u], xl[u]);
                 // once per wave and half: (sequence slot g, column j) hit bits and the 16 column-padding bits
                 const int idc = meta[16 * h + j];
                 bool hit = false;
@@ -980,13 +991,16 @@ __global__ __launch_bounds__(256, NSUB == 1 ? 4 : 2) void ce16_rowpass_kernel(co
 }
 
 // lse, row loss and d_prec (for d_loss = 1) from the per-range partial results: the ranges brought to the common maximum, fixed order
-__global__ __launch_bounds__(256) void ce16_row_combine_kernel(const float* __restrict__ score, const float* __restrict__ log_mask, CeBufs b, Ce16Bufs c,
+__global__ __launch_bounds__(256) void ce16_row_combine_kernel(const float* __restrict__ log_mask, CeBufs b, Ce16Bufs c,
                                                                int bs, int S, int ysplits) {
     const int T = bs * S;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int xr = i >> 6, e = i & 63;
     if (xr >= T) return;
-    ce_fused_finish(ysplits, [&](int y, int k) { return c.part_row[((int64_t)y * T + xr) * 68 + k]; }, xr, e, score, log_mask, b, S);
+    const float inv_s = 1.0f / c16_scale_of(c.amax[1]);
+    ce_fused_finish(ysplits, [&](int y, int k) { return c.part_row[((int64_t)y * T + xr) * 68 + k]; },
+                    [&](int lab) { return ((float)c.img[1][0][(int64_t)lab * E + e] + (float)c.img[1][1][(int64_t)lab * E + e]) * inv_s; },
+                    xr, e, log_mask, b, S);
 }
 
 // The column-fixed pass (d_score = dZ^T · prec): X = score (a lane owns one column), Y = prec.  grid (x blocks, ysplits)
@@ -1072,7 +1086,7 @@ __global__ __launch_bounds__(256, NSUB == 1 ? 4 : 2) void ce16_colpass_kernel(co
             float q[8];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const f4 z = c16_logits(tl, h, j, g, xh[u], xl[u]);
+                const f4 z = c16_logits<true>(tl, h, j, g, xh[u], xl[u]);
                 bool hit = false;
 #pragma unroll
                 for (int qq = 0; qq < (RS1 + 3) / 4; ++qq) {
@@ -1094,7 +1108,7 @@ __global__ __launch_bounds__(256, NSUB == 1 ? 4 : 2) void ce16_colpass_kernel(co
                     const float val = masked ? MASKV : z[r] * inv_z - col_debias[u];
                     const bool yok = whole || (y0 + 16 * h + 4 * g + r < T);
                     const float pr = fexp(val - lse4[r]);
-                    q[4 * h + r] = (yok && xok[u]) ? (pr - (is_lab ? 1.f : 0.f)) * ok4[r] : 0.f;
+                    q[4 * h + r] = (yok && xok[u]) ? (pr - ((is_lab && !col_pad[u]) ? 1.f : 0.f)) * ok4[r] : 0.f;
                 }
             }
             c16_second(tl, j, g, q, dacc[u]);
@@ -1245,7 +1259,7 @@ extern "C" int iisan_inbatch_ce_fwd(const int64_t* ids, const float* score, cons
             IISAN_LAUNCH_OK();
             int ys = 1;
             IISAN_TRY(launch_ce16_pass<false>(log_mask, b, b16, bs, S, s, &ys));
-            hipLaunchKernelGGL(ce16_row_combine_kernel, dim3((unsigned)ceil_div(T * E, 256)), dim3(256), 0, s, score, log_mask, b, b16, (int)bs, S, ys);
+            hipLaunchKernelGGL(ce16_row_combine_kernel, dim3((unsigned)ceil_div(T * E, 256)), dim3(256), 0, s, log_mask, b, b16, (int)bs, S, ys);
             break;
         }
         case CE_ROUTE_FUSED:         // the forward pass leaves d_prec (for d_loss = 1) in the workspace, the backward call only scales it

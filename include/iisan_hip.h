@@ -272,6 +272,9 @@ int iisan_sasrec_bwd(const iisan_sasrec_cfg* cfg, const float* x, const float* l
  * log_mask fp32 [bs,S], pop_prob fp32 [n_pop = item_num+1].  loss: 1 float.  row_lse: [bs*S] scratch kept for bwd.
  * The library never syncs, so a bad INPUT VALUE cannot come back as a return code: an id outside [0, n_pop) is
  * not dereferenced and makes the loss NaN (the reference would raise an IndexError at model.py:63).
+ * Ids repeated inside a sequence and log_mask values other than 0 / 1 follow the reference: a position counts where log_mask != 0, a
+ * column whose id occurs anywhere in the row's own sequence is filled with -1e4 and only the label column is spared — unless the label
+ * column is itself history padding (log_mask == 0 there), which keeps the fill and carries no gradient (tests/test_gpu_ce_regimes.py).
  * From 2^24 logits on (bs = 1024: 10,240 x 11,264) the two passes run on the 16-bit matrix cores with score / prec split
  * into fp16 hi + lo planes (csrc/ce.hip ce16_*: the accuracy of an fp32 product to ~2^-22; the workspace also holds the
  * operand images and the per-range partial results: ~95 MB at bs = 1024); below, on the f32-input matrix cores.
