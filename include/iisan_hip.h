@@ -252,6 +252,13 @@ int iisan_linear_bwd(const float* x, const float* w, const float* dy, float* dx,
  * other shapes (seq <= 32, emb a multiple of 64 up to 256, emb / heads <= 64, 1 .. 8 blocks; anything else is IISAN_EBADSHAPE)
  * take one launch per operator.  Either way the forward keeps every intermediate the backward needs in `ws`
  * (same slots), and gradients ACCUMULATE (+=) into the caller's tensors.
+ * Mask: key k is allowed for query q where k <= q and log_mask[b, k] != 0 (ANY non-zero value, not only 1); every other
+ * key gets -1e9 added to score / sqrt(emb / heads), as the reference does.  A query row WITHOUT an allowed key (left padding
+ * in front of the first real position, a sequence whose log_mask is all 0: the eval user without history) therefore carries
+ * -1e9 on every key: while |score / sqrt(emb / heads)| < 32 the float32 sum is -1e9 exactly (the spacing at 1e9 is 64) and the
+ * row attends UNIFORMLY OVER ALL `seq` POSITIONS, later ones included; beyond that it is the softmax of the float32
+ * roundings of -1e9 + score, as in the reference.  Such a row's position is itself padding, a masked key for every query:
+ * it never reaches a row that has an allowed key (tests/test_gpu_sasrec_regimes.py).
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t seq, emb, heads, blocks;       /* 10, 64, 2, 2                                                     */

@@ -226,22 +226,25 @@ def versa_side_network(taps_cv: Tensor, taps_text: Tensor, P: Dict[str, Tensor],
 # U5  SASRec user encoder                          reference: Code_Uncached/model/encoders.py:60-65, modules.py:6-96
 # ---------------------------------------------------------------------------------------------------------------
 
-def sasrec_mask(log_mask: Tensor) -> Tensor:
-    """[B,1,S,S] additive mask: 0 where key<=query and key is a real position, else -1e9 (`encoders.py:60-64`)."""
+def sasrec_mask(log_mask: Tensor, fill: float = -1e9) -> Tensor:
+    """[B,1,S,S] additive mask: 0 where key<=query and key is a real position, else `fill` (-1e9: `encoders.py:60-64`)."""
     S = log_mask.shape[-1]
     m = (log_mask != 0)[:, None, None, :].expand(-1, -1, S, -1)
-    return torch.where(torch.tril(m), 0.0, -1e9)
+    return torch.where(torch.tril(m), 0.0, fill)
 
 
 def sasrec(x: Tensor, log_mask: Tensor, P: Dict[str, Tensor], heads: int, n_layers: int,
-           pre: str = "user_encoder.transformer_encoder.", drop: Dict[int, Tensor] | None = None) -> Tensor:
+           pre: str = "user_encoder.transformer_encoder.", drop: Dict[int, Tensor] | None = None, fill: float = -1e9) -> Tensor:
     """x [B,S,E] -> [B,S,E].  `drop` (optional) maps a dropout site to its keep-factor tensor (0 or 1/(1-p)) so a test
     can inject the exact masks the HIP path generates; sites follow the reference's four nn.Dropout calls
     (modules.py:17,31,62,94): 0 = after the embedding LayerNorm [B,S,E]; 1+3l = attention probabilities of block l
-    [B,H,S,S]; 2+3l = fc output [B,S,E]; 3+3l = FFN output [B,S,E].  None = identity (eval)."""
+    [B,H,S,S]; 2+3l = fc output [B,S,E]; 3+3l = FFN output [B,S,E].  None = identity (eval).
+    `fill` is the additive mask value.  A query without any allowed key carries it on every key: in float32 `score / sqrt(d) - 1e9`
+    is -1e9 exactly while |score / sqrt(d)| < 32 (the spacing at 1e9 is 64) and the row is uniform over all S keys, which float64
+    states only with a fill that swallows the scores there too (-1e30)."""
     B, S, E = x.shape
     d = E // heads
-    mask = sasrec_mask(log_mask)
+    mask = sasrec_mask(log_mask, fill)
     dr = (lambda site, t: t * drop[site]) if drop is not None else (lambda site, t: t)
     x = F.layer_norm(x + P[pre + "position_embedding.weight"][:S][None], (E,),
                      P[pre + "layer_norm.weight"], P[pre + "layer_norm.bias"], 1e-6)       # modules.py:89-93

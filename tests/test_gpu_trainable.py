@@ -578,6 +578,59 @@ def test_batched_eval_pipeline_matches_reference_metrics():
     assert abs(hit - float(z["hit10"])) < 1e-6 and abs(ndcg - float(z["ndcg10"])) < 1e-6
 
 
+def test_eval_users_without_history_are_ranked_like_the_reference(lib):
+    """An eval user whose sequence is only its target reaches the user encoder with an empty window: every token the padding item,
+    `log_mask` all 0 (`evaluate._pack_users`), so every query row is without an allowed key and attends uniformly over all `seq`
+    positions (-1e9 swallows the scores in float32; include/iisan_hip.h).  A quarter of 48 users on a 301-row item table:
+    `evaluate_ranks` / `recommend_topk` bit-equal to `O.eval_ranks` / `O.eval_topk` on the user vectors the device returns, and those
+    vectors within 2e-5 (relative Frobenius, the forward bound of the SASRec tests) of `O.sasrec` in float64 with the fill -1e30, which
+    states that function - for all users and for the users without history alone.  Guard: the float32 oracle with the reference's own
+    -1e9 is within 5e-6 of it; control: the float64 oracle with -1e9 (no uniform rows) is rejected."""
+    S, H, L, n, U = 10, 2, 2, 300, 48
+    model = helpers.build_model(helpers.make_args(drop_rate=0.0), n, synth.make_pop_prob(n), cached=True)
+    shapes = {k: tuple(p.shape) for k, p in model.named_parameters() if p.requires_grad}
+    P = weights.fill_params_seeded(shapes, seed=560)
+    helpers.load_trainables(model, P)
+    ids = torch.arange(n + 1)
+    with torch.no_grad():
+        item_emb = evaluate.item_table(model, synth.cached_taps(ids, 12, 768, seed=37).cuda(), synth.cached_taps(ids, 12, 768, seed=38).cuda())
+    rs = np.random.RandomState(8)
+    seqs = [[int(c) for c in rs.choice(np.arange(1, n + 1), size=1 if u % 4 == 1 else 2 + u % 13, replace=False)] for u in range(U)]
+    none = torch.tensor([len(s) == 1 for s in seqs])
+    assert int(none.sum()) == U // 4 and max(len(s) for s in seqs) > S + 1
+    hists = [s[:-1] for s in seqs]
+    tgt = torch.tensor([s[-1] for s in seqs])
+    ranks = evaluate.evaluate_ranks(model, item_emb, seqs, hists, max_seq_len=S).cpu().long()
+    top, _ = evaluate.recommend_topk(model, item_emb, hists, hists, max_seq_len=S, k=10)
+    tok, lm = torch.zeros(U, S, dtype=torch.int64), torch.zeros(U, S)
+    for u, h in enumerate(hists):
+        t = h[-S:]
+        tok[u, S - len(t):] = torch.tensor(t, dtype=torch.int64)
+        lm[u, S - len(t):] = 1
+    assert bool((lm[none] == 0).all()) and bool((tok[none] == 0).all())
+    model.eval()
+    with torch.no_grad():
+        prec = model.user_encoder(item_emb[tok.cuda()], lm.cuda(), None)[:, -1].contiguous().cpu()
+    emb = item_emb.cpu()
+    ht = [torch.tensor(h, dtype=torch.int64) for h in hists]
+    assert torch.equal(ranks, O.eval_ranks(prec, emb, ht, tgt))
+    assert torch.equal(top.cpu().long(), O.eval_topk(prec, emb, ht, 10))
+    Pu = {k: v for k, v in P.items() if k.startswith("user_encoder.")}
+    with torch.no_grad():
+        want = O.sasrec(emb.double()[tok], lm.double(), {k: v.double() for k, v in Pu.items()}, H, L, fill=-1e30)[:, -1]
+        f32 = O.sasrec(emb[tok], lm, Pu, H, L)[:, -1]
+        keeps_scores = O.sasrec(emb.double()[tok], lm.double(), {k: v.double() for k, v in Pu.items()}, H, L)[:, -1]
+
+    def err(a, rows):
+        return ((a.double()[rows] - want[rows]).norm() / want[rows].norm()).item()
+    every = torch.ones(U, dtype=torch.bool)
+    assert err(f32, every) < 5e-6 and err(f32, none) < 5e-6, (err(f32, every), err(f32, none))
+    assert not err(keeps_scores, none) < 2e-5 and err(keeps_scores, ~none) < 1e-12
+    print(f"eval without history: prec {err(prec, every):.2e}, the {int(none.sum())} users without history {err(prec, none):.2e} (bound 2e-5; "
+          f"float32 oracle {err(f32, every):.1e} / {err(f32, none):.1e}; float64 oracle with -1e9 on them {err(keeps_scores, none):.1e})")
+    assert err(prec, every) < 2e-5 and err(prec, none) < 2e-5, (err(prec, every), err(prec, none))
+
+
 def test_overlapped_towers_give_identical_embeddings():
     """`mm_encoder.overlap_towers` (the product default since round 6: image tower on a high-priority HIP stream, text tower on a
     normal-priority one beside it) is a scheduling choice only: bit-identical to both towers back to back on one stream."""
