@@ -95,11 +95,15 @@ __global__ __launch_bounds__(256) void amax_batch_kernel(AmaxBatch b) {
     amax_body(b.x[z], b.rows[z], b.cols[z], b.ld[z], b.out[z], blockIdx.x, gridDim.x);
 }
 
-// s = 2^(13 - floor(log2 amax)): the largest element lands in [2^13, 2^14) (fp16 max 65504); amax == 0 or denormal -> s = 1
+// s = 2^(13 - floor(log2 amax)): the largest element lands in [2^13, 2^14) (fp16 max 65504); amax == 0 or denormal -> s = 1.
+// The exponent field stops at 253 (s = 2^126, 1 / s = 2^-126 still normal): for an amax in [2^-126, 2^-113) the field 267 - e is
+// 254 (1 / s denormal), 255 (s = inf: hi = inf, lo = NaN) or runs into the sign bit (s = -0.0 and 1 / s = -inf, or a negative
+// scale).  Clamped, such an operand lands below 2^13 - it only has fewer bits above the 2^-38 floor, and it is about 0 anyway.
 __device__ __forceinline__ float scale_of(uint32_t amax_bits) {
     const int e = (int)(amax_bits >> 23) & 0xff;
     if (e == 0 || e == 0xff) return 1.0f;
-    return __uint_as_float((uint32_t)(267 - e) << 23);
+    const int f = 267 - e;
+    return __uint_as_float((uint32_t)(f < 253 ? f : 253) << 23);
 }
 
 __device__ __forceinline__ void split1(float xs, _Float16& hi, _Float16& lo) {

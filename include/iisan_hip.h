@@ -190,6 +190,13 @@ int iisan_bert_forward_taps_dropout(const iisan_bert_weights* w, const int64_t* 
  *   fc_mm_down.w, fc_mm_down.b
  * Gradients are written to a parallel host array of device pointers (same order), ACCUMULATING (+=) into them;
  * the caller zeroes them.
+ * Gate saturation: g = sigmoid(theta / 0.1) and 1 - g are float32, as in the reference.  From theta >= 1.7 g is exactly 1 and
+ * 1 - g exactly 0: the gate's own gradient (factor g (1 - g) / 0.1) is exactly 0, and in the cv / text towers
+ * (F = g tap + (1 - g) state) so is every gradient that would flow back through the state, i.e. of all earlier SANBs and gates
+ * of that tower.  From theta <= -1.8 1 - g is exactly 1 and g = e^(theta / 0.1) a tiny non-zero number (2e-9 at -2.0) that
+ * still multiplies the tap; it becomes exactly 0, and the gate gradient with it, only from theta <= -10.4 (where the kernels'
+ * exp overflows to inf and 1 / inf gives that 0).  The float32 reference behaves the same way in every one of these cases.
+ * ReLU's derivative at a pre-activation of exactly 0 is 0 (torch's convention), GELU's is 0.5.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t n_side;           /* SANBs of the image tower (7; 6 with remove_first); also of the text tower unless versa */

@@ -381,6 +381,10 @@ X3_CASES = [
     (1024, 8192, 1408, 1, 1, 1, 1e-3, 0.25),       # Versa dPd += dDP^T · tap
     (130, 72, 100, 0, 0, 0, 1.0, 1.0),             # ragged everything
     (8, 8, 4, 0, 0, 0, 300.0, 1e-8),               # tiny, extreme magnitudes
+    # operands as trained tower states carry them (ONE power-of-two scale per operand, from the whole tensor's amax: split.hip scale_of)
+    (407, 768, 768, 0, 0, 0, 1.0, 0.03, "massive_col"),    # one column of A x 1,000 (B's matching column x 1e-3: it does not own the result)
+    (407, 768, 768, 0, 0, 0, 1.0, 0.03, "row_scales"),     # rows of A alternate between scale 1 and 1e-4: each row against ITS OWN scale
+    (130, 72, 100, 0, 0, 0, 2.5e-37, 1.0, "tiny_amax"),    # amax(A) ~ 1e-36: the scale's exponent field must stay representable
 ]
 
 
@@ -389,11 +393,18 @@ def test_gemm_x3_matches_fp64(lib, case):
     """Split-operand GEMM (fp32 operands as hi+lo fp16 planes, three MFMA terms, csrc/split.hip) against the product in
     fp64: within a few fp32 ulps of the result scale — the same class of error as an fp32 FMA chain — for every operand
     layout the side network uses (`nn.Linear` forward, dX, dW) and for operand magnitudes far from 1."""
-    M, N, K, ta, tb, acc, sa, sb = case
+    M, N, K, ta, tb, acc, sa, sb = case[:8]
+    kind = case[8] if len(case) > 8 else None
     g = torch.Generator().manual_seed(M * 7 + N)
-    A = (torch.randn((K, M) if ta else (M, K), generator=g) * sa).cuda()
-    B = (torch.randn((K, N) if tb else (N, K), generator=g) * sb).cuda()
-    bias = None if acc else (torch.randn(N, generator=g) * sa * sb).cuda()
+    A = torch.randn((K, M) if ta else (M, K), generator=g) * sa
+    B = torch.randn((K, N) if tb else (N, K), generator=g) * sb
+    if kind == "massive_col":
+        A[:, 5] *= 1000.0
+        B[:, 5] *= 1e-3
+    if kind == "row_scales":
+        A[1::2] *= 1e-4
+    A, B = A.cuda(), B.cuda()
+    bias = None if (acc or kind == "row_scales") else (torch.randn(N, generator=g) * sa * sb).cuda()     # (a bias would own the small rows)
     C0 = (torch.randn(M, N, generator=g) * sa * sb * K ** 0.5).cuda() if acc else None
     C = C0.clone() if acc else torch.full((M, N), float("nan"), device="cuda")
     ws = torch.empty(lib.iisan_gemm_x3_ws_bytes(M, N, K), dtype=torch.uint8, device="cuda")
@@ -416,7 +427,19 @@ def test_gemm_x3_matches_fp64(lib, case):
     if acc:
         f32 = f32 + C0
     err32 = (f32.double() - ref).abs().max().item() / scale
-    assert err < max(4e-6, 8 * err32), (case, err, err32)
+    # (tiny_amax: products below the smallest normal may flush - K of them per output, 2^-126 each)
+    slack = K * 2.0 ** -126 / scale if kind == "tiny_amax" else 0.0
+    assert err < max(4e-6, 8 * err32) + slack, (case, err, err32)
+    if kind == "massive_col":
+        big = (A[:, 5].double()[:, None] * B[:, 5].double()[None]).abs().max().item()
+        assert big < 0.5 * scale and A[:, 5].abs().min().item() > 0, "the massive column owns the result"
+    if kind == "row_scales":       # the whole-tensor figure is blind to the small rows: each row against that row's reference scale
+        rs = ref.abs().max(1).values
+        e_row = (C.double() - ref).abs().max(1).values / rs
+        e32_row = (f32.double() - ref).abs().max(1).values / rs
+        assert rs[1::2].max().item() < 1e-3 * scale
+        bad = e_row >= torch.clamp(8 * e32_row, min=4e-6)
+        assert not bool(bad.any()), (case, int(bad.sum()), e_row.max().item(), e32_row.max().item())
 
 
 @pytest.mark.parametrize("which", ["A", "B"])
