@@ -77,6 +77,7 @@ SIGNATURES = {
     "iisan_sasrec_fwd": (i32, [C.POINTER(SasrecCfg), vp, vp, i64, C.POINTER(vp), vp, vp, sz, vp]),
     "iisan_sasrec_bwd": (i32, [C.POINTER(SasrecCfg), vp, vp, i64, C.POINTER(vp), vp, vp, C.POINTER(vp), vp, sz, vp]),
     "iisan_inbatch_ce_ws_bytes": (sz, [i64, i32]),
+    "iisan_inbatch_ce_ws_bytes_e": (sz, [i64, i32, i32]),
     "iisan_inbatch_ce_fwd": (i32, [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, vp, sz, C.POINTER(u64), vp]),
     "iisan_inbatch_ce_bwd": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, sz, u64, vp]),
     "iisan_score_rank": (i32, [vp, vp, i64, i64, i32, vp, i32, vp, vp, vp]),
@@ -105,6 +106,7 @@ SIGNATURES = {
     "iisan_gemm16_route": (i32, [i32, i32, i64, i32, i32, i32, i32, i32, i32]),
     "iisan_gemm32_plan": (i32, [C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), i32, i32, i64, i32, C.POINTER(i32)]),
     "iisan_inbatch_ce_route": (i32, [i64, i32]),
+    "iisan_inbatch_ce_route_e": (i32, [i64, i32, i32]),
     # DEV section: the library's only process-global state (development switches + measurement hooks)
     "iisan_dev_set": (i32, [C.c_char_p, i64]),
     "iisan_dev_get": (i64, [C.c_char_p]),

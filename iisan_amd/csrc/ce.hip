@@ -19,18 +19,19 @@
 // round-robin.  Logit tiles are computed TRANSPOSED on the f32 matrix cores (v_mfma_f32_16x16x4_f32, K = E = 64): lane (j, g) =
 // (lane & 15, lane >> 4) owns X row x0 + j and the Y rows y0 + 4g .. 4g + 3 of the tile.  So the online log-sum-exp is per lane plus
 // two xor-shuffles (16, 32), and the four dZ registers of a lane are already the B operand of the second product dX^T += Y^T·dZ^T,
-// whose accumulators dacc[et][r] hold dX[x0 + j][16 et + 4g + r].  A wave stages its Y tile in LDS once, rows of YLD = 68 floats
+// whose accumulators dacc[et][r] hold dX[x0 + j][16 et + 4g + r].  A wave stages its Y tile in LDS once, rows of E + 4 = 68 floats
 // (272 bytes: conflict-free ds_read_b128); both products read their A operand from it, the second one transposed.  The four waves'
-// results meet in sRed after the walk.
+// results meet in sRed after the walk.  The passes are templates over the width EW = 64 NE (NE = 1 .. 4 feature blocks of 64): K = EW,
+// rows of EW + 4 floats (4 mod 64 at every width: the same bank walk), 4 NE accumulators; what is said of E = 64 here is the NE = 1 case.
 #include <type_traits>
 
 #include "common.h"
 
 namespace {
 
-constexpr int E = 64;
+constexpr int E = 64;             // the width of the split-operand route (ce16_*) and of the calls without a width argument
+constexpr int EMAX = 256;         // the f32 passes are instantiated at EW = 64, 128, 192, 256: NE = EW / 64 feature blocks of 64
 constexpr int MAXS1 = 16;         // sequences of up to 16 slots keep their ids in registers / LDS (longer ones take the plain kernel)
-constexpr int YLD = 68;           // padded LDS row (floats)
 constexpr float MASKV = -1e4f;
 
 struct CeBufs {
@@ -43,7 +44,7 @@ struct CeBufs {
     float* dprec;    // [T, E] d loss / d prec for d_loss = 1, left by the fused forward pass (ce_rowpass_kernel<CE_FUSED>)
 };
 
-void carve(WsCarver& c, CeBufs& b, int64_t bs, int S) {
+void carve(WsCarver& c, CeBufs& b, int64_t bs, int S, int EW) {
     const size_t M = (size_t)bs * (S + 1), T = (size_t)bs * S;
     b.ids32 = c.take<int>(M);
     b.debias = c.take<float>(M);
@@ -51,7 +52,7 @@ void carve(WsCarver& c, CeBufs& b, int64_t bs, int S) {
     b.lse = c.take<float>(T);
     b.rowloss = c.take<float>(T);
     b.nvalid = c.take<float>(4);
-    b.dprec = c.take<float>(T * E);
+    b.dprec = c.take<float>(T * EW);
 }
 
 __global__ void ce_prep_kernel(const int64_t* __restrict__ ids, const float* __restrict__ log_mask,
@@ -111,10 +112,24 @@ __global__ __launch_bounds__(256) void ce_reduce_kernel(const float* __restrict_
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The pieces the three f32 passes are written over (layout: top of the file).  Index types are the caller's: `int` in the row-fixed
-// kernels (M < 2^31 is their launch condition), int64_t in the plain one; an address is widened where E multiplies it.  Every
+// kernels (M < 2^31 is their launch condition), int64_t in the plain one; an address is widened where EW multiplies it.  Every
 // floating-point expression below is evaluated in this order by every pass: the routes agree to the bit wherever they share one.
+// EW is the embedding width, NE = EW / 64: feature 64 nb + 16 g + 4 v + e is K-step (nb, v, e) of lane group g in the logits product,
+// and feature block et = 4 nb + .. of the second one — at EW = 64 the pieces are the code they were before they took a width.
 enum { CE_FWD = 0, CE_DPREC = 1, CE_DSCORE = 2, CE_FUSED = 3 };
-typedef float CeRed[4][16][E + 4];      // per wave and X row: 64 features (+ m, l, z_label of the fused finish)
+template <int EW>
+using CeRed = float[4][16][EW + 4];     // per wave and X row: EW features (+ m, l, z_label of the fused finish)
+// The planes the four waves' results meet in.  A wave's plane is as large as its Y tile (16 rows of EW + 4 floats), and a wave is done
+// with its tile when it writes its plane: at EW > 64 the planes ARE the tiles (66.6 KB of LDS instead of 133 KB at EW = 256: two
+// workgroups per CU, as many as its registers allow; profiles/wide_embedding.md).  EW = 64 keeps planes of its own (34.8 KB with the
+// tiles, four workgroups per CU either way).
+template <int EW>
+using CeRedOwn = std::conditional_t<(EW > 64), float[4], CeRed<EW>>;
+template <int EW>
+__device__ __forceinline__ CeRed<EW>& ce_red(float (&sY)[4][16 * (EW + 4)], CeRedOwn<EW>& own) {
+    if constexpr (EW > 64) return *reinterpret_cast<CeRed<EW>*>(&sY[0][0]);
+    else return own;
+}
 
 // exp(x) = v_exp_f32(x * log2 e): 2 instructions.  The product is rounded once, so the relative error is |x| 2^-24 plus the ulp of
 // v_exp_f32 — and every argument here is a logit minus a maximum or an lse, <= 0 up to rounding: a term that far below the top weighs
@@ -137,67 +152,98 @@ __device__ __forceinline__ bool id_in_seq(const int* __restrict__ ids32, int64_t
 }
 
 // X fragments of row xc (B operand of the logits product): e(ks, kq) = 16*kq + ks -> 16 consecutive floats per lane
-__device__ __forceinline__ void ce_load_x(float (&xb)[16], const float* __restrict__ X, int64_t xc, int g) {
+template <int EW>
+__device__ __forceinline__ void ce_load_x(float (&xb)[EW / 4], const float* __restrict__ X, int64_t xc, int g) {
 #pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const f4 t = *(const f4*)(X + xc * E + 16 * g + 4 * v);
+    for (int nb = 0; nb < EW / 64; ++nb)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) xb[4 * v + e] = t[e];
-    }
+        for (int v = 0; v < 4; ++v) {
+            const f4 t = *(const f4*)(X + xc * EW + 64 * nb + 16 * g + 4 * v);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xb[16 * nb + 4 * v + e] = t[e];
+        }
 }
 
-// the wave's Y tile from registers into LDS: 16 rows x 64 floats, lane -> row lane >> 2, 16-float chunk lane & 3
-__device__ __forceinline__ void ce_stage_y(float* myY, const f4 (&yreg)[4], int lane) {
+// the wave's Y tile from registers into LDS: 16 rows x EW floats, lane -> row lane >> 2, 16-float chunk lane & 3 of every feature block
+// (ce_ypart: where lane's piece (nb, v) of row yr sits in global memory)
+template <int EW>
+__device__ __forceinline__ const float* ce_ypart(const float* __restrict__ Y, int64_t yr, int lane, int nb, int v) {
+    return Y + yr * EW + 64 * nb + (lane & 3) * 16 + v * 4;
+}
+template <int EW>
+__device__ __forceinline__ void ce_stage_y(float* myY, const f4 (&yreg)[EW / 16], int lane) {
     const int r = lane >> 2, ch = lane & 3;
 #pragma unroll
-    for (int v = 0; v < 4; ++v) *(f4*)(myY + r * YLD + ch * 16 + v * 4) = yreg[v];
+    for (int nb = 0; nb < EW / 64; ++nb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) *(f4*)(myY + r * (EW + 4) + 64 * nb + ch * 16 + v * 4) = yreg[4 * nb + v];
 }
 
 // Z^T tile: A = Y rows (i = lane & 15), B = X rows; the lane receives z(x0 + j, y0 + 4g + r).  Two independent accumulator chains
 // (a single one is 16 MFMAs each waiting for the previous result)
-__device__ __forceinline__ f4 ce_logits(const float* myY, const float (&xb)[16], int j, int g) {
+template <int EW>
+__device__ __forceinline__ f4 ce_logits(const float* myY, const float (&xb)[EW / 4], int j, int g) {
     f4 z = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int v = 0; v < 4; v += 2) {
-        const f4 ya = *(const f4*)(myY + j * YLD + 16 * g + 4 * v);
-        const f4 yb = *(const f4*)(myY + j * YLD + 16 * g + 4 * v + 4);
+    for (int nb = 0; nb < EW / 64; ++nb)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            z = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[e], xb[4 * v + e], z, 0, 0, 0);
-            z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(yb[e], xb[4 * v + 4 + e], z1, 0, 0, 0);
+        for (int v = 0; v < 4; v += 2) {
+            const f4 ya = *(const f4*)(myY + j * (EW + 4) + 64 * nb + 16 * g + 4 * v);
+            const f4 yb = *(const f4*)(myY + j * (EW + 4) + 64 * nb + 16 * g + 4 * v + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                z = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[e], xb[16 * nb + 4 * v + e], z, 0, 0, 0);
+                z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(yb[e], xb[16 * nb + 4 * v + 4 + e], z1, 0, 0, 0);
+            }
         }
-    }
     z += z1;
     return z;
 }
 
 // dX^T[e][x] += sum_y Y[y][e] dZ(x, y):  A = Y^T (i = e within feature block et, k = y0 + 4kq + r), B = dz[r].  The 16 transposed
-// fragments are read by ce_read_yt — right in front of the product, or ahead of it (ce_rowpass_kernel)
-__device__ __forceinline__ void ce_read_yt(float (&yt16)[4][4], const float* myY, int j, int g) {
+// fragments of the 64 features nb are read by ce_read_yt — those of nb = 0 right in front of the product, or ahead of it
+// (ce_rowpass_kernel) — and the product walks the blocks of 64, the next one's fragments requested in front of this one's MFMAs: 32
+// fragment registers at any width, and every accumulator still adds its four rows in the order r = 0 .. 3
+template <int EW>
+__device__ __forceinline__ void ce_read_yt(float (&yt16)[4][4], const float* myY, int j, int g, int nb = 0) {
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int et = 0; et < 4; ++et) yt16[r][et] = myY[(4 * g + r) * YLD + 16 * et + j];
+        for (int et = 0; et < 4; ++et) yt16[r][et] = myY[(4 * g + r) * (EW + 4) + 64 * nb + 16 * et + j];
 }
-__device__ __forceinline__ void ce_second(f4 (&dacc)[4], const float (&yt16)[4][4], const float (&dz)[4]) {
+template <int EW>
+__device__ __forceinline__ void ce_second(f4 (&dacc)[EW / 16], float (&yt16)[4][4], const float (&dz)[4], const float* myY, int j, int g) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+    for (int nb = 0; nb < EW / 64; ++nb) {
+        float nx[4][4];
+        if (nb + 1 < EW / 64) ce_read_yt<EW>(nx, myY, j, g, nb + 1);
 #pragma unroll
-        for (int et = 0; et < 4; ++et) dacc[et] = __builtin_amdgcn_mfma_f32_16x16x4f32(yt16[r][et], dz[r], dacc[et], 0, 0, 0);
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int et = 0; et < 4; ++et)
+                dacc[4 * nb + et] = __builtin_amdgcn_mfma_f32_16x16x4f32(yt16[r][et], dz[r], dacc[4 * nb + et], 0, 0, 0);
+        if (nb + 1 < EW / 64) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int et = 0; et < 4; ++et) yt16[r][et] = nx[r][et];
+        }
+    }
 }
 
 // the wave's accumulators into its plane of sRed, and (behind a barrier) the four planes summed into dX
-__device__ __forceinline__ void ce_dacc_to_red(CeRed& sRed, const f4 (&dacc)[4], int wave, int j, int g) {
+template <int EW>
+__device__ __forceinline__ void ce_dacc_to_red(CeRed<EW>& sRed, const f4 (&dacc)[EW / 16], int wave, int j, int g) {
 #pragma unroll
-    for (int et = 0; et < 4; ++et)
+    for (int et = 0; et < EW / 16; ++et)
 #pragma unroll
         for (int r = 0; r < 4; ++r) sRed[wave][j][16 * et + 4 * g + r] = dacc[et][r];
 }
-template <class I>
-__device__ __forceinline__ void ce_sum_store(const CeRed& sRed, float* __restrict__ dX, I x0, I NX, int tid) {
-    for (int i = tid; i < 16 * E; i += 256) {
-        const int rj = i / E, e = i - rj * E;
-        if (x0 + rj < NX) dX[(int64_t)(x0 + rj) * E + e] = sRed[0][rj][e] + sRed[1][rj][e] + sRed[2][rj][e] + sRed[3][rj][e];
+template <int EW, class I>
+__device__ __forceinline__ void ce_sum_store(const CeRed<EW>& sRed, float* __restrict__ dX, I x0, I NX, int tid) {
+    for (int i = tid; i < 16 * EW; i += 256) {
+        const int rj = i / EW, e = i - rj * EW;
+        if (x0 + rj < NX) dX[(int64_t)(x0 + rj) * EW + e] = sRed[0][rj][e] + sRed[1][rj][e] + sRed[2][rj][e] + sRed[3][rj][e];
     }
 }
 
@@ -218,8 +264,8 @@ __device__ __forceinline__ void ce_online(float& run_m, float& run_l, const floa
 }
 
 // FWD, after the walk: (m, l) and the label logit combined across the 4 lane groups and the 4 waves; lse and the row loss of X row x
-template <class I>
-__device__ __forceinline__ void ce_fwd_finish(CeRed& sRed, float run_m, float run_l, float zlab, int wave, int j, int g, bool xok, I x,
+template <int EW, class I>
+__device__ __forceinline__ void ce_fwd_finish(CeRed<EW>& sRed, float run_m, float run_l, float zlab, int wave, int j, int g, bool xok, I x,
                                               bool row_valid, const CeBufs& b) {
     auto comb = [](float& m, float& l, float m2, float l2) {
         const float mn = fmaxf(m, m2);
@@ -254,26 +300,26 @@ __device__ __forceinline__ void ce_fwd_finish(CeRed& sRed, float run_m, float ru
 
 // The finish of the fused forward + d_prec passes (ce_rowpass_kernel<CE_FUSED>: its four waves, from LDS; ce16_row_combine_kernel: the
 // Y ranges of the split route, from the workspace), for feature e of prec row xr.  part(w, k) is partial result w = 0 .. n - 1 of the
-// row: k < E the accumulator sum_y exp(z - m_w) score[y][k], k = E its maximum m_w, E + 1 its sum l_w, E + 2 its label logit.  The
+// row: k < EW the accumulator sum_y exp(z - m_w) score[y][k], k = EW its maximum m_w, EW + 1 its sum l_w, EW + 2 its label logit.  The
 // partials are brought to the common maximum in the order w = 0, 1, ...;  d_prec = (sum_y p_y score_y - score_label) / n for d_loss = 1.
 // labv(lab) is score[lab][e] AS THE PASS'S PRODUCTS SAW IT (the f32 value, or hi + lo of the split planes): where p_label = 1 the two
 // terms then cancel to the bit.  A label column that is history padding keeps its fill value (model.py:88-89 assigns it): no gradient
-template <class PART, class LABV>
+template <int EW, class PART, class LABV>
 __device__ __forceinline__ void ce_fused_finish(int n, PART part, LABV labv, int xr, int e,
                                                 const float* __restrict__ log_mask, const CeBufs& b, int S) {
 #pragma clang fp contract(off)      // the two sums below as written (l fused, acc not), whatever else the caller inlines around them
-    float m = part(0, E);
-    for (int w = 1; w < n; ++w) m = fmaxf(m, part(w, E));
+    float m = part(0, EW);
+    for (int w = 1; w < n; ++w) m = fmaxf(m, part(w, EW));
     float l = 0.f, acc = 0.f, zl = 0.f;
     for (int w = 0; w < n; ++w) {
-        const float f = fexp(part(w, E) - m);
-        l = fmaf(part(w, E + 1), f, l);
+        const float f = fexp(part(w, EW) - m);
+        l = fmaf(part(w, EW + 1), f, l);
         acc += part(w, e) * f;
-        zl += part(w, E + 2);
+        zl += part(w, EW + 2);
     }
     const bool valid = log_mask[xr] != 0.f;
     const int lab = ce_label(xr, S);
-    b.dprec[(int64_t)xr * E + e] = valid ? (acc / l - (b.colpad[lab] ? 0.f : labv(lab))) / b.nvalid[0] : 0.f;
+    b.dprec[(int64_t)xr * EW + e] = valid ? (acc / l - (b.colpad[lab] ? 0.f : labv(lab))) / b.nvalid[0] : 0.f;
     if (e == 0) {
         const float lse = m + logf(l);
         b.lse[xr] = lse;
@@ -287,13 +333,14 @@ __device__ __forceinline__ void ce_fused_finish(int n, PART part, LABV labv, int
 // sequence for the id (id_in_seq) — 3 + S1 loads per logit, 64-bit indices, libm expf: 2.9 ms forward + backward at bs = 1024, S = 10
 // against 0.85 ms of the row-fixed passes (profiles/ce_shared_core.md).  It serves the shapes the row-fixed kernels do not take
 // (S < 5, S > 15, M >= 2^31) and is the text they are read against.
-template <int MODE>
+template <int MODE, int EW>
 __global__ __launch_bounds__(256) void ce_pass_kernel(const float* __restrict__ prec, const float* __restrict__ score,
                                                       const float* __restrict__ log_mask, CeBufs b, int64_t bs, int S,
                                                       float d_loss, float* __restrict__ dX) {
     static_assert(MODE == CE_FWD || MODE == CE_DPREC || MODE == CE_DSCORE, "the fused forward exists in the row-fixed kernels only");
-    __shared__ __attribute__((aligned(16))) float sY[4][16 * YLD];
-    __shared__ CeRed sRed;
+    __shared__ __attribute__((aligned(16))) float sY[4][16 * (EW + 4)];
+    __shared__ CeRedOwn<EW> sRedOwn;
+    CeRed<EW>& sRed = ce_red<EW>(sY, sRedOwn);
     const int S1 = S + 1;
     const int64_t T = bs * S, M = bs * S1;
     const float* X = MODE == CE_DSCORE ? score : prec;
@@ -305,27 +352,29 @@ __global__ __launch_bounds__(256) void ce_pass_kernel(const float* __restrict__ 
     const int64_t x = x0 + j;
     const bool xok = x < NX;
     const int64_t xc = xok ? x : NX - 1;
-    float xb[16];
-    ce_load_x(xb, X, xc, g);
+    float xb[EW / 4];
+    ce_load_x<EW>(xb, X, xc, g);
 
     float run_m = -INFINITY, run_l = 0.f, zlab = 0.f;
-    f4 dacc[4];
+    f4 dacc[EW / 16];
 #pragma unroll
-    for (int et = 0; et < 4; ++et) dacc[et] = (f4){0.f, 0.f, 0.f, 0.f};
+    for (int et = 0; et < EW / 16; ++et) dacc[et] = (f4){0.f, 0.f, 0.f, 0.f};
     float* myY = sY[wave];
     const int64_t ntiles = (NY + 15) / 16;
     for (int64_t yt = wave; yt < ntiles; yt += 4) {
         const int64_t y0 = yt * 16;
-        f4 yreg[4];
+        f4 yreg[EW / 16];
         const int64_t yr = y0 + (lane >> 2);
 #pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            yreg[v] = (f4){0.f, 0.f, 0.f, 0.f};
-            if (yr < NY) yreg[v] = *(const f4*)(Y + yr * E + (lane & 3) * 16 + v * 4);
-        }
-        ce_stage_y(myY, yreg, lane);
+        for (int nb = 0; nb < EW / 64; ++nb)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                yreg[4 * nb + v] = (f4){0.f, 0.f, 0.f, 0.f};
+                if (yr < NY) yreg[4 * nb + v] = *(const f4*)ce_ypart<EW>(Y, yr, lane, nb, v);
+            }
+        ce_stage_y<EW>(myY, yreg, lane);
         __builtin_amdgcn_wave_barrier();
-        const f4 z = ce_logits(myY, xb, j, g);
+        const f4 z = ce_logits<EW>(myY, xb, j, g);
         float dz[4], fv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -350,17 +399,17 @@ __global__ __launch_bounds__(256) void ce_pass_kernel(const float* __restrict__ 
             ce_online(run_m, run_l, fv, [](float v) { return expf(v); });
         } else {
             float yt16[4][4];
-            ce_read_yt(yt16, myY, j, g);
-            ce_second(dacc, yt16, dz);
+            ce_read_yt<EW>(yt16, myY, j, g);
+            ce_second<EW>(dacc, yt16, dz, myY, j, g);
         }
         __builtin_amdgcn_wave_barrier();
     }
     if (MODE == CE_FWD) {
-        ce_fwd_finish(sRed, run_m, run_l, zlab, wave, j, g, xok, x, xok && log_mask[xc] != 0.f, b);
+        ce_fwd_finish<EW>(sRed, run_m, run_l, zlab, wave, j, g, xok, x, xok && log_mask[xc] != 0.f, b);
     } else {
-        ce_dacc_to_red(sRed, dacc, wave, j, g);
+        ce_dacc_to_red<EW>(sRed, dacc, wave, j, g);
         __syncthreads();
-        ce_sum_store(sRed, dX, x0, NX, tid);
+        ce_sum_store<EW>(sRed, dX, x0, NX, tid);
     }
 }
 
@@ -379,13 +428,14 @@ __global__ __launch_bounds__(256) void ce_pass_kernel(const float* __restrict__ 
 // CE_FUSED: forward and d_prec in ONE pass, flash-attention style: the accumulators hold sum_y exp(z - run_m) * score[y] against a
 // running ROW maximum (common to the four lanes of a row, because the MFMA sums over their columns) and are rescaled when it moves —
 // after the first tiles it almost never does, and the test is one ballot per tile.  d_prec for d_loss = 1 stays in the workspace.
-template <int MODE, int RS1>
+template <int MODE, int RS1, int EW>
 __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict__ prec, const float* __restrict__ score,
                                                          const float* __restrict__ log_mask, CeBufs b, int bs, int S,
                                                          float d_loss, float* __restrict__ dX) {
     static_assert(MODE == CE_FWD || MODE == CE_DPREC || MODE == CE_FUSED, "row-fixed passes only");
-    __shared__ __attribute__((aligned(16))) float sY[4][16 * YLD];
-    __shared__ CeRed sRed;
+    __shared__ __attribute__((aligned(16))) float sY[4][16 * (EW + 4)];
+    __shared__ CeRedOwn<EW> sRedOwn;
+    CeRed<EW>& sRed = ce_red<EW>(sY, sRedOwn);
     __shared__ __attribute__((aligned(16))) int sMeta[4][64];    // per wave: ids | pad flags | debias of the tile's 16 columns
     const int S1 = S + 1;
     const int T = bs * S, M = bs * S1;
@@ -399,8 +449,8 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
     const bool xok = x < NX;
     const int xc = xok ? x : NX - 1;
 
-    float xb[16];
-    ce_load_x(xb, X, xc, g);
+    float xb[EW / 4];
+    ce_load_x<EW>(xb, X, xc, g);
     const int row_seq = xc / S;
     const int row_label = ce_label(xc, S);
     const bool row_valid = xok && log_mask[xc] != 0.f;
@@ -417,16 +467,16 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
     }
 
     float run_m = MODE == CE_FUSED ? -3.0e38f : -INFINITY, run_l = 0.f, zlab = 0.f;
-    f4 dacc[4];
+    f4 dacc[EW / 16];
 #pragma unroll
-    for (int et = 0; et < 4; ++et) dacc[et] = (f4){0.f, 0.f, 0.f, 0.f};
+    for (int et = 0; et < EW / 16; ++et) dacc[et] = (f4){0.f, 0.f, 0.f, 0.f};
 
     float* myY = sY[wave];
     int* myMeta = sMeta[wave];
     const int ntiles = (NY + 15) / 16;
     // the prefetch registers: with the loads at the top of the iteration every tile waited for an L2 round trip (FWD 303 us against
     // 110 us of MFMA time)
-    f4 yreg[4];
+    f4 yreg[EW / 16];
     int mreg[3] = {0, 0, 0};
     // Branch-free: a tile index past the end re-reads the last tile, a row past NY re-reads row NY-1 (finite values that
     // meet dz = 0) — every conditional load was a saveexec / branch pair in the loop, and a join makes the waitcnt pass drain.
@@ -434,9 +484,11 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
         const int y0_ = (yt_ < ntiles ? yt_ : ntiles - 1) * 16;
         const int r = lane >> 2, ch = lane & 3;
         const int yr = y0_ + r < NY ? y0_ + r : NY - 1;
-        const float* yp = Y + (int64_t)yr * E + ch * 16;
+        const float* yp = Y + (int64_t)yr * EW + ch * 16;
 #pragma unroll
-        for (int v = 0; v < 4; ++v) yreg[v] = *(const f4*)(yp + v * 4);
+        for (int nb = 0; nb < EW / 64; ++nb)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) yreg[4 * nb + v] = *(const f4*)(yp + 64 * nb + v * 4);
         const int cc = y0_ + (lane & 15) < NY ? y0_ + (lane & 15) : NY - 1;
         mreg[0] = b.ids32[cc];
         mreg[1] = b.colpad[cc];
@@ -445,7 +497,7 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
     prefetch(wave);
     for (int yt = wave; yt < ntiles; yt += 4) {
         const int y0 = yt * 16;
-        ce_stage_y(myY, yreg, lane);
+        ce_stage_y<EW>(myY, yreg, lane);
         if (lane < 16) {
             myMeta[lane] = mreg[0];
             myMeta[16 + lane] = mreg[1];
@@ -464,13 +516,13 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
         const unsigned pad4 = (pm >> (4 * g)) & 0xfu;
         const f4 deb4 = *(const f4*)(myMeta + 32 + 4 * g);      // bit patterns of four floats
 
-        const f4 z = ce_logits(myY, xb, j, g);
-        // the second product's 16 transposed tile reads are requested NOW, fenced, and land behind the mask / exp arithmetic:
+        const f4 z = ce_logits<EW>(myY, xb, j, g);
+        // the second product's 16 transposed tile reads (of its first 64 features) are requested NOW, fenced, and land behind the mask / exp arithmetic:
         // left to the compiler each pair sat right in front of its two MFMAs behind an lgkmcnt(0) (eight exposed LDS
         // round trips per tile)
         float yt16[4][4];
         if (MODE != CE_FWD) {
-            ce_read_yt(yt16, myY, j, g);
+            ce_read_yt<EW>(yt16, myY, j, g);
             __builtin_amdgcn_sched_barrier(0);
         }
         const bool whole = y0 + 16 <= NY;            // wave-uniform
@@ -502,7 +554,7 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
                     const float f = fexp(run_m - mn);    // run_m starts at -3e38: f = 0 on the first tile
                     run_l *= f;
 #pragma unroll
-                    for (int et = 0; et < 4; ++et) dacc[et] *= f;
+                    for (int et = 0; et < EW / 16; ++et) dacc[et] *= f;
                     run_m = mn;
                 }
 #pragma unroll
@@ -511,13 +563,13 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
                     run_l += dz[r];
                 }
             }
-            ce_second(dacc, yt16, dz);
+            ce_second<EW>(dacc, yt16, dz, myY, j, g);
         }
         __builtin_amdgcn_wave_barrier();
     }
 
     if (MODE == CE_FWD) {
-        ce_fwd_finish(sRed, run_m, run_l, zlab, wave, j, g, xok, x, row_valid, b);
+        ce_fwd_finish<EW>(sRed, run_m, run_l, zlab, wave, j, g, xok, x, row_valid, b);
     } else if (MODE == CE_FUSED) {
         // the four lanes of a row share run_m; their sums add up
 #pragma unroll
@@ -525,23 +577,23 @@ __global__ __launch_bounds__(256) void ce_rowpass_kernel(const float* __restrict
             run_l += __shfl_xor(run_l, o, 64);
             zlab += __shfl_xor(zlab, o, 64);
         }
-        ce_dacc_to_red(sRed, dacc, wave, j, g);
+        ce_dacc_to_red<EW>(sRed, dacc, wave, j, g);
         if (g == 0) {
-            sRed[wave][j][E] = run_m;
-            sRed[wave][j][E + 1] = run_l;
-            sRed[wave][j][E + 2] = zlab;
+            sRed[wave][j][EW] = run_m;
+            sRed[wave][j][EW + 1] = run_l;
+            sRed[wave][j][EW + 2] = zlab;
         }
         __syncthreads();
-        for (int i = tid; i < 16 * E; i += 256) {
-            const int rj = i / E, e = i - rj * E;
+        for (int i = tid; i < 16 * EW; i += 256) {
+            const int rj = i / EW, e = i - rj * EW;
             const int xr = x0 + rj;
             if (xr >= NX) continue;
-            ce_fused_finish(4, [&](int w, int k) { return sRed[w][rj][k]; }, [&](int lab) { return Y[(int64_t)lab * E + e]; }, xr, e, log_mask, b, S);
+            ce_fused_finish<EW>(4, [&](int w, int k) { return sRed[w][rj][k]; }, [&](int lab) { return Y[(int64_t)lab * EW + e]; }, xr, e, log_mask, b, S);
         }
     } else {
-        ce_dacc_to_red(sRed, dacc, wave, j, g);
+        ce_dacc_to_red<EW>(sRed, dacc, wave, j, g);
         __syncthreads();
-        ce_sum_store(sRed, dX, x0, NX, tid);
+        ce_sum_store<EW>(sRed, dX, x0, NX, tid);
     }
 }
 
@@ -557,12 +609,13 @@ __global__ void ce_scale_kernel(const float* __restrict__ in, float scale, float
 // pass and, per tile of 16 prec rows (at most four sequences), tests ITS column against the ids of the tile's sequence slot g — the
 // four lanes of a column cover the four slots — and a ballot publishes the 64 answers; per-row label / lse / scale / slot come from
 // a small LDS table, one 16-byte read each.  The tile's ids and per-row values are prefetched with its rows.
-template <int RS1>
+template <int RS1, int EW>
 __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict__ prec, const float* __restrict__ score,
                                                          const float* __restrict__ log_mask, CeBufs b, int bs, int S,
                                                          float d_loss, float* __restrict__ dX) {
-    __shared__ __attribute__((aligned(16))) float sY[4][16 * YLD];
-    __shared__ CeRed sRed;
+    __shared__ __attribute__((aligned(16))) float sY[4][16 * (EW + 4)];
+    __shared__ CeRedOwn<EW> sRedOwn;
+    CeRed<EW>& sRed = ce_red<EW>(sY, sRedOwn);
     __shared__ __attribute__((aligned(16))) int sMeta[4][64];     // ids of the tile's four sequences, 16 per slot
     __shared__ __attribute__((aligned(16))) int sRow[4][64];      // per row: slot | label column | lse | scale
     const int S1 = S + 1;
@@ -577,21 +630,21 @@ __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict
     const bool xok = x < NX;
     const int xc = xok ? x : NX - 1;
 
-    float xb[16];
-    ce_load_x(xb, X, xc, g);
+    float xb[EW / 4];
+    ce_load_x<EW>(xb, X, xc, g);
     const int col_id = b.ids32[xc];
     const bool col_pad = b.colpad[xc] != 0;
     const float col_debias = b.debias[xc];
     const float dscale = d_loss / b.nvalid[0];
 
-    f4 dacc[4];
+    f4 dacc[EW / 16];
 #pragma unroll
-    for (int et = 0; et < 4; ++et) dacc[et] = (f4){0.f, 0.f, 0.f, 0.f};
+    for (int et = 0; et < EW / 16; ++et) dacc[et] = (f4){0.f, 0.f, 0.f, 0.f};
     float* myY = sY[wave];
     int* myMeta = sMeta[wave];
     int* myRow = sRow[wave];
     const int ntiles = (NY + 15) / 16;
-    f4 yreg[4];
+    f4 yreg[EW / 16];
     int idreg = -2;
     float lsereg = 0.f, lmreg = 0.f;
     auto prefetch = [&](int yt_) {
@@ -599,10 +652,12 @@ __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict
         const int r = lane >> 2, ch = lane & 3;
         const int yr = y0_ + r;
 #pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            yreg[v] = (f4){0.f, 0.f, 0.f, 0.f};
-            if (yt_ < ntiles && yr < NY) yreg[v] = *(const f4*)(Y + (int64_t)yr * E + ch * 16 + v * 4);
-        }
+        for (int nb = 0; nb < EW / 64; ++nb)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                yreg[4 * nb + v] = (f4){0.f, 0.f, 0.f, 0.f};
+                if (yt_ < ntiles && yr < NY) yreg[4 * nb + v] = *(const f4*)(Y + (int64_t)yr * EW + 64 * nb + ch * 16 + v * 4);
+            }
         if (yt_ < ntiles) {
             const int sq = y0_ / S + g;                 // lane (g, j): id j of the tile's sequence slot g
             idreg = (j < S1 && sq < bs) ? b.ids32[sq * S1 + j] : -2;
@@ -616,7 +671,7 @@ __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict
     prefetch(wave);
     for (int yt = wave; yt < ntiles; yt += 4) {
         const int y0 = yt * 16;
-        ce_stage_y(myY, yreg, lane);
+        ce_stage_y<EW>(myY, yreg, lane);
         myMeta[lane] = idreg;
         if (lane < 16) {
             const int seq0 = y0 / S;
@@ -643,7 +698,7 @@ __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict
         const f4 lse4 = *(const f4*)(myRow + 32 + 4 * g);
         const f4 sc4 = *(const f4*)(myRow + 48 + 4 * g);
 
-        const f4 z = ce_logits(myY, xb, j, g);
+        const f4 z = ce_logits<EW>(myY, xb, j, g);
         const bool whole = y0 + 16 <= NY;
         float dz[4];
 #pragma unroll
@@ -657,13 +712,13 @@ __global__ __launch_bounds__(256) void ce_colpass_kernel(const float* __restrict
             dz[r] = (yok && xok) ? (pr - ((is_lab && !col_pad) ? 1.f : 0.f)) * sc4[r] : 0.f;
         }
         float yt16[4][4];
-        ce_read_yt(yt16, myY, j, g);
-        ce_second(dacc, yt16, dz);
+        ce_read_yt<EW>(yt16, myY, j, g);
+        ce_second<EW>(dacc, yt16, dz, myY, j, g);
         __builtin_amdgcn_wave_barrier();
     }
-    ce_dacc_to_red(sRed, dacc, wave, j, g);
+    ce_dacc_to_red<EW>(sRed, dacc, wave, j, g);
     __syncthreads();
-    ce_sum_store(sRed, dX, x0, NX, tid);
+    ce_sum_store<EW>(sRed, dX, x0, NX, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -998,7 +1053,7 @@ __global__ __launch_bounds__(256) void ce16_row_combine_kernel(const float* __re
     const int xr = i >> 6, e = i & 63;
     if (xr >= T) return;
     const float inv_s = 1.0f / c16_scale_of(c.amax[1]);
-    ce_fused_finish(ysplits, [&](int y, int k) { return c.part_row[((int64_t)y * T + xr) * 68 + k]; },
+    ce_fused_finish<E>(ysplits, [&](int y, int k) { return c.part_row[((int64_t)y * T + xr) * 68 + k]; },
                     [&](int lab) { return ((float)c.img[1][0][(int64_t)lab * E + e] + (float)c.img[1][1][(int64_t)lab * E + e]) * inv_s; },
                     xr, e, log_mask, b, S);
 }
@@ -1147,12 +1202,24 @@ enum { CE_ROUTE_GENERIC = 0,      // ce_pass_kernel for all three passes (any S 
 int g_ce_fast = 1;
 // bs = 128 (1,280 x 1,408 logits): 29 us per f32 pass, launch-sized — the split route's four extra small launches would cost more than it gains
 constexpr int64_t C16_MIN_LOGITS = (int64_t)1 << 24;
-int ce_route(int64_t bs, int S) {
+// EW: the embedding width.  The split-operand route is 64 wide: at EW > 64 its two cases take the f32 fused passes.
+int ce_route(int64_t bs, int S, int EW) {
     // the row-fixed kernels keep a sequence's ids in registers / LDS, span at most four sequences per 16-row tile and index with 32 bits
     if (!g_ce_fast || S < 5 || S + 1 > MAXS1 || bs * (int64_t)(S + 1) >= (1ll << 31)) return CE_ROUTE_GENERIC;
-    if (g_ce_fast == 3 || (g_ce_fast == 1 && bs * S * bs * (int64_t)(S + 1) >= C16_MIN_LOGITS)) return CE_ROUTE_SPLIT16;
+    if (g_ce_fast == 3 || (g_ce_fast == 1 && bs * S * bs * (int64_t)(S + 1) >= C16_MIN_LOGITS)) return EW == E ? CE_ROUTE_SPLIT16 : CE_ROUTE_FUSED;
     return (g_ce_fast == 1 || g_ce_fast == 4) ? CE_ROUTE_FUSED : CE_ROUTE_ROWPASS;
 }
+// The run-time width as the EW template argument: f(integral_constant<int, 64 | 128 | 192 | 256>) — the widths `check` lets through
+template <class F>
+void with_ew(int EW, F&& f) {
+    switch (EW) {
+        case 64: f(std::integral_constant<int, 64>{}); break;
+        case 128: f(std::integral_constant<int, 128>{}); break;
+        case 192: f(std::integral_constant<int, 192>{}); break;
+        default: f(std::integral_constant<int, 256>{});
+    }
+}
+#define CE_EW decltype(ew)::value
 // The run-time S + 1 as the RS1 template argument (slots per sequence compared per logit): f(integral_constant<int, 11 or MAXS1>).  11 is the
 // reference's max_seq_len 10 + 1; every kernel's RS1 = 11 instantiation also handles shorter sequences.  The plain kernel has no such argument.
 template <class F>
@@ -1196,25 +1263,38 @@ int launch_ce16_pass(const float* log_mask, const CeBufs& b, const Ce16Bufs& c, 
 
 int check(int64_t bs, int S, int Ein) {
     IISAN_CHECK_SHAPE(bs > 0 && S >= 1 && S <= 63, "inbatch_ce: bs %lld / S %d unsupported", (long long)bs, S);
-    IISAN_CHECK_SHAPE(Ein == E, "inbatch_ce: embedding_dim must be %d (got %d)", E, Ein);
+    IISAN_CHECK_SHAPE(Ein > 0 && Ein <= EMAX && Ein % 64 == 0, "inbatch_ce: embedding_dim must be 64, 128, 192 or 256 (got %d)", Ein);
     return IISAN_OK;
+}
+
+// the workspace of one call: the f32 passes' buffers, and at the width of the split-operand route (alone) that route's images and partials
+void carve_all(WsCarver& c, CeBufs& b, Ce16Bufs& b16, int64_t bs, int S, int EW) {
+    carve(c, b, bs, S, EW);
+    if (EW == E) carve16(c, b16, bs, S);
 }
 
 }  // namespace
 
+extern "C" size_t iisan_inbatch_ce_ws_bytes_e(int64_t bs, int32_t S, int32_t Ein) {
+    if (bs <= 0 || S < 1 || S > 63 || Ein <= 0 || Ein > EMAX || Ein % 64) return 0;
+    WsCarver c(nullptr, 0);
+    CeBufs b;
+    Ce16Bufs b16;
+    carve_all(c, b, b16, bs, S, Ein);
+    return c.off;
+}
 extern "C" size_t iisan_inbatch_ce_ws_bytes(int64_t bs, int32_t S) {
     WsCarver c(nullptr, 0);
     CeBufs b;
     Ce16Bufs b16;
-    carve(c, b, bs, S);
-    carve16(c, b16, bs, S);
+    carve_all(c, b, b16, bs, S, E);
     return c.off;
 }
 
-// the forward call's token: a tag, the call shape and the route it took (CE_ROUTE_*) — so that the backward call follows what THAT call
-// did, not the dev switch's later value, and the library keeps no per-call state
-static uint64_t ce_token(int64_t bs, int32_t S, int route) {
-    return 0xCE00000000000000ull | ((uint64_t)(bs & 0xFFFFFFFFll) << 16) | ((uint64_t)(S & 0xFF) << 8) | (uint64_t)(route + 1);
+// the forward call's token: a tag, the call shape (the width as EW / 64 - 1 in bits 48..55: 0 at 64) and the route it took (CE_ROUTE_*) —
+// so that the backward call follows what THAT call did, not the dev switch's later value, and the library keeps no per-call state
+static uint64_t ce_token(int64_t bs, int32_t S, int EW, int route) {
+    return 0xCE00000000000000ull | ((uint64_t)(EW / 64 - 1) << 48) | ((uint64_t)(bs & 0xFFFFFFFFll) << 16) | ((uint64_t)(S & 0xFF) << 8) | (uint64_t)(route + 1);
 }
 IISAN_DEV_KNOB(ce_fast, g_ce_fast);
 IISAN_DEV_KNOB(ce16_nsub, g_ce16_nsub);
@@ -1222,7 +1302,11 @@ IISAN_DEV_KNOB(ce16_ys, g_ce16_ys);
 static int64_t g_cnt_ce16 = 0;            // forward calls on the split-operand route (route counter, common.h)
 IISAN_DEV_COUNTER(ce16, g_cnt_ce16);
 
-extern "C" int32_t iisan_inbatch_ce_route(int64_t bs, int32_t S) { return check(bs, S, E) == IISAN_OK ? ce_route(bs, S) : -1; }
+extern "C" int32_t iisan_inbatch_ce_route(int64_t bs, int32_t S) { return check(bs, S, E) == IISAN_OK ? ce_route(bs, S, E) : -1; }
+extern "C" int32_t iisan_inbatch_ce_route_e(int64_t bs, int32_t S, int32_t Ein) {
+    if (bs <= 0 || S < 1 || S > 63 || Ein <= 0 || Ein > EMAX || Ein % 64) return -1;      // (check() would leave an error message behind)
+    return ce_route(bs, S, Ein);
+}
 
 extern "C" int iisan_inbatch_ce_fwd(const int64_t* ids, const float* score, const float* prec, const float* log_mask,
                                     const float* pop_prob, int64_t n_pop, int64_t bs, int32_t S, int32_t Ein, float* loss,
@@ -1233,8 +1317,7 @@ extern "C" int iisan_inbatch_ce_fwd(const int64_t* ids, const float* score, cons
     WsCarver c(ws, ws_bytes);
     CeBufs b;
     Ce16Bufs b16;
-    carve(c, b, bs, S);
-    carve16(c, b16, bs, S);
+    carve_all(c, b, b16, bs, S, Ein);
     if (c.overflow || !ws) {
         iisan_set_error("inbatch_ce_fwd: workspace too small (%zu < %zu)", ws_bytes, c.off);
         return IISAN_EWORKSPACE;
@@ -1246,8 +1329,8 @@ extern "C" int iisan_inbatch_ce_fwd(const int64_t* ids, const float* score, cons
     hipLaunchKernelGGL(ce_count_kernel, dim3(1), dim3(256), 0, s, log_mask, T, b.nvalid);
     IISAN_LAUNCH_OK();
     IISAN_CHECK_SHAPE(fwd_token != nullptr, "inbatch_ce_fwd: fwd_token must not be null");
-    const int route = ce_route(bs, S);
-    *fwd_token = ce_token(bs, S, route);
+    const int route = ce_route(bs, S, Ein);
+    *fwd_token = ce_token(bs, S, Ein, route);
     float* const none = nullptr;
     switch (route) {
         case CE_ROUTE_SPLIT16: {     // amax -> images -> fused row pass per Y range -> combine (lse, row loss, d_prec for d_loss = 1 in the workspace)
@@ -1263,13 +1346,13 @@ extern "C" int iisan_inbatch_ce_fwd(const int64_t* ids, const float* score, cons
             break;
         }
         case CE_ROUTE_FUSED:         // the forward pass leaves d_prec (for d_loss = 1) in the workspace, the backward call only scales it
-            with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_FUSED, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, 0.f, none); });
+            with_ew(Ein, [&](auto ew) { with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_FUSED, CE_RS1, CE_EW>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, 0.f, none); }); });
             break;
         case CE_ROUTE_ROWPASS:
-            with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_FWD, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, 0.f, none); });
+            with_ew(Ein, [&](auto ew) { with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_FWD, CE_RS1, CE_EW>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, 0.f, none); }); });
             break;
         default:
-            hipLaunchKernelGGL((ce_pass_kernel<CE_FWD>), rows, dim3(256), 0, s, prec, score, log_mask, b, bs, S, 0.f, none);
+            with_ew(Ein, [&](auto ew) { hipLaunchKernelGGL((ce_pass_kernel<CE_FWD, CE_EW>), rows, dim3(256), 0, s, prec, score, log_mask, b, bs, S, 0.f, none); });
     }
     IISAN_LAUNCH_OK();
     hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, b.rowloss, T, b.nvalid, loss);
@@ -1285,8 +1368,8 @@ extern "C" int iisan_inbatch_ce_bwd(const int64_t* ids, const float* score, cons
     WsCarver c(ws, ws_bytes);
     CeBufs b;
     Ce16Bufs b16;
-    carve(c, b, bs, S);       // ids32/debias/colpad/lse/nvalid were filled by the forward call on the same workspace
-    carve16(c, b16, bs, S);   // ... and, on the split-operand route, the operand images and their amax
+    carve_all(c, b, b16, bs, S, Ein);      // ids32/debias/colpad/lse/nvalid were filled by the forward call on the same workspace, and, on
+                                           // the split-operand route, the operand images and their amax
     if (c.overflow || !ws) {
         iisan_set_error("inbatch_ce_bwd: workspace too small (%zu < %zu)", ws_bytes, c.off);
         return IISAN_EWORKSPACE;
@@ -1295,18 +1378,19 @@ extern "C" int iisan_inbatch_ce_bwd(const int64_t* ids, const float* score, cons
     const dim3 rows((unsigned)ceil_div(T, 16)), cols((unsigned)ceil_div(M, 16));
     int route = -1;           // the forward's, whatever the dev switch says by now: what this route needs is in the workspace
     for (int r = CE_ROUTE_GENERIC; r <= CE_ROUTE_SPLIT16; ++r)
-        if (fwd_token == ce_token(bs, S, r)) route = r;
+        if (fwd_token == ce_token(bs, S, Ein, r)) route = r;
+    if (route == CE_ROUTE_SPLIT16 && Ein != E) route = -1;      // (no forward call returns it)
     if (route < 0) {
-        iisan_set_error("inbatch_ce_bwd: fwd_token %llx is not what inbatch_ce_fwd returns for bs = %lld, S = %d", (unsigned long long)fwd_token, (long long)bs, S);
+        iisan_set_error("inbatch_ce_bwd: fwd_token %llx is not what inbatch_ce_fwd returns for bs = %lld, S = %d, embedding_dim = %d", (unsigned long long)fwd_token, (long long)bs, S, Ein);
         return IISAN_EBADSHAPE;
     }
     // d_prec: scaled from the forward's d_prec for d_loss = 1, or its own row pass
     if (route == CE_ROUTE_FUSED || route == CE_ROUTE_SPLIT16)
-        hipLaunchKernelGGL(ce_scale_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(T * E / 4, 256), 1024)), dim3(256), 0, s, b.dprec, d_loss, d_prec, T * E / 4);
+        hipLaunchKernelGGL(ce_scale_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(T * Ein / 4, 256), 1024)), dim3(256), 0, s, b.dprec, d_loss, d_prec, T * Ein / 4);
     else if (route == CE_ROUTE_ROWPASS)
-        with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_DPREC, CE_RS1>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, d_loss, d_prec); });
+        with_ew(Ein, [&](auto ew) { with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_rowpass_kernel<CE_DPREC, CE_RS1, CE_EW>), rows, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, d_loss, d_prec); }); });
     else
-        hipLaunchKernelGGL((ce_pass_kernel<CE_DPREC>), rows, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_prec);
+        with_ew(Ein, [&](auto ew) { hipLaunchKernelGGL((ce_pass_kernel<CE_DPREC, CE_EW>), rows, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_prec); });
     IISAN_LAUNCH_OK();
     // d_score: the column pass
     if (route == CE_ROUTE_SPLIT16) {
@@ -1314,9 +1398,9 @@ extern "C" int iisan_inbatch_ce_bwd(const int64_t* ids, const float* score, cons
         IISAN_TRY(launch_ce16_pass<true>(log_mask, b, b16, bs, S, s, &ys));
         hipLaunchKernelGGL(ce16_col_combine_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(M * E / 4, 256), 2048)), dim3(256), 0, s, b, b16, M * E / 4, ys, d_loss, d_score);
     } else if (route != CE_ROUTE_GENERIC) {
-        with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_colpass_kernel<CE_RS1>), cols, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, d_loss, d_score); });
+        with_ew(Ein, [&](auto ew) { with_rs1(S, [&](auto rs1) { hipLaunchKernelGGL((ce_colpass_kernel<CE_RS1, CE_EW>), cols, dim3(256), 0, s, prec, score, log_mask, b, (int)bs, S, d_loss, d_score); }); });
     } else {
-        hipLaunchKernelGGL((ce_pass_kernel<CE_DSCORE>), cols, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_score);
+        with_ew(Ein, [&](auto ew) { hipLaunchKernelGGL((ce_pass_kernel<CE_DSCORE, CE_EW>), cols, dim3(256), 0, s, prec, score, log_mask, b, bs, S, d_loss, d_score); });
     }
     IISAN_LAUNCH_OK();
     return IISAN_OK;

@@ -18,6 +18,8 @@
 // item sits in a tile.  The target's and the history items' scores are taken from the diagonal of extra tiles whose row i
 // is "the h-th item of user i".  History: a history item contributes with score -inf instead of its raw score; if the
 // target itself is in the history its score is -inf as well (metrics.py:204-205: reproduced, not fixed).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -27,12 +29,19 @@ constexpr int MAXH = 256;       // history entries per user (33 KB of LDS for th
 
 __device__ __forceinline__ bool ahead(float s, int c, float st, int t) { return s > st || (s == st && c < t); }
 
+// Widths: EW = 64 NE, NE = 1 .. 4 feature blocks of 64.  A row's fragment is f4[4 NE]: lane group g holds features 64 nb + 16 g ..
+// + 15 of every block nb, and a score is ONE chain of 16 NE MFMAs in the order (nb, v, e) — in the rank kernel's gathered tiles, in its
+// table tiles and in the top-k kernel alike, so the exactness argument above holds at every width.  32 users per workgroup at every
+// width too: 32 NE registers of user fragments and 8 NE of item rows, one wave per SIMD at EW = 256 — 16 users per workgroup there (two
+// waves) measured 12 % slower, 22 % at 192: one item-row load then feeds one MFMA instead of two (profiles/wide_embedding.md).
+//
 // one 16-item tile against both user sets: acc[u][r] = score(item 4*(lane/16) + r of the tile, user 16u + lane%16)
-__device__ __forceinline__ void tile_scores(const f4 (&a)[4], const f4 (&b)[2][4], f4 (&acc)[2]) {
+template <int NE>
+__device__ __forceinline__ void tile_scores(const f4 (&a)[4 * NE], const f4 (&b)[2][4 * NE], f4 (&acc)[2]) {
     acc[0] = (f4){0.f, 0.f, 0.f, 0.f};
     acc[1] = (f4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int v = 0; v < 4; ++v)
+    for (int v = 0; v < 4 * NE; ++v)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[v][e], b[0][v][e], acc[0], 0, 0, 0);
@@ -40,11 +49,15 @@ __device__ __forceinline__ void tile_scores(const f4 (&a)[4], const f4 (&b)[2][4
         }
 }
 
-__device__ __forceinline__ void load_row16(const float* __restrict__ row, int g, f4 (&a)[4]) {
+template <int NE>
+__device__ __forceinline__ void load_row16(const float* __restrict__ row, int g, f4 (&a)[4 * NE]) {
 #pragma unroll
-    for (int v = 0; v < 4; ++v) a[v] = *(const f4*)(row + 16 * g + 4 * v);
+    for (int nb = 0; nb < NE; ++nb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) a[4 * nb + v] = *(const f4*)(row + 64 * nb + 16 * g + 4 * v);
 }
 
+template <int NE>
 __global__ __launch_bounds__(256) void score_rank_mfma_kernel(const float* __restrict__ prec, const float* __restrict__ item_emb,
                                                               int n_items, const int32_t* __restrict__ history, int hist_stride,
                                                               const int32_t* __restrict__ target, int32_t* __restrict__ ranks,
@@ -58,14 +71,14 @@ __global__ __launch_bounds__(256) void score_rank_mfma_kernel(const float* __res
     const int u0 = blockIdx.x * UB;
 
     // the users' vectors as B fragments: lane (j, g) holds prec[u0 + 16u + j][16g .. 16g+15]
-    f4 b[2][4];
+    f4 b[2][4 * NE];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int uu = u0 + 16 * u + j;
-        if (uu < U) load_row16(prec + (int64_t)uu * 64, g, b[u]);
+        if (uu < U) load_row16<NE>(prec + (int64_t)uu * (64 * NE), g, b[u]);
         else
 #pragma unroll
-            for (int v = 0; v < 4; ++v) b[u][v] = (f4){0.f, 0.f, 0.f, 0.f};
+            for (int v = 0; v < 4 * NE; ++v) b[u][v] = (f4){0.f, 0.f, 0.f, 0.f};
     }
     if (threadIdx.x < UB) {
         const int uu = u0 + (int)threadIdx.x;
@@ -85,9 +98,9 @@ __global__ __launch_bounds__(256) void score_rank_mfma_kernel(const float* __res
         int c = 0;
         if (uu < U) c = h < hist_stride ? history[(int64_t)uu * hist_stride + h] : s_t[16 * half + j];
         if (c < 0 || c >= n_items) c = 0;
-        f4 a[4], acc[2];
-        load_row16(item_emb + (int64_t)c * 64, g, a);
-        tile_scores(a, b, acc);
+        f4 a[4 * NE], acc[2];
+        load_row16<NE>(item_emb + (int64_t)c * (64 * NE), g, a);
+        tile_scores<NE>(a, b, acc);
         // D[i][jj] sits in lane (jj, i / 4), element i % 4: the diagonal i == jj
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -112,15 +125,15 @@ __global__ __launch_bounds__(256) void score_rank_mfma_kernel(const float* __res
     int tile_hi = tile_lo + tiles_per_split;
     if (tile_hi > n_tiles) tile_hi = n_tiles;
     int cnt[2] = {0, 0};
-    f4 a[4], an[4];
+    f4 a[4 * NE], an[4 * NE];
     int tile = tile_lo + wave;
-    auto row_of = [&](int tl) { int c = tl * 16 + j; return item_emb + (int64_t)(c < n_items ? c : 0) * 64; };
-    if (tile < tile_hi) load_row16(row_of(tile), g, a);
+    auto row_of = [&](int tl) { int c = tl * 16 + j; return item_emb + (int64_t)(c < n_items ? c : 0) * (64 * NE); };
+    if (tile < tile_hi) load_row16<NE>(row_of(tile), g, a);
     for (; tile < tile_hi; tile += 4) {
         const bool more = tile + 4 < tile_hi;
-        if (more) load_row16(row_of(tile + 4), g, an);          // next tile's rows in flight during this tile's MFMAs
+        if (more) load_row16<NE>(row_of(tile + 4), g, an);      // next tile's rows in flight during this tile's MFMAs
         f4 acc[2];
-        tile_scores(a, b, acc);
+        tile_scores<NE>(a, b, acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int c = tile * 16 + 4 * g + r;
@@ -130,7 +143,7 @@ __global__ __launch_bounds__(256) void score_rank_mfma_kernel(const float* __res
         }
         if (more)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) a[v] = an[v];
+            for (int v = 0; v < 4 * NE; ++v) a[v] = an[v];
     }
     // lanes (j, g = 0..3) hold partial counts of the same user
 #pragma unroll
@@ -269,7 +282,7 @@ __device__ __forceinline__ int topk_compact(tkey (*cand)[UB], tkey (*tmp)[UB], i
     return m;
 }
 
-template <bool DIRECT>
+template <bool DIRECT, int NE>
 __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict__ prec, const float* __restrict__ item_emb, int n_items,
                                                          const int32_t* __restrict__ history, int hist_stride, int U, int tiles_per_split,
                                                          int k, tkey* __restrict__ part, int32_t* __restrict__ ids, float* __restrict__ scores) {
@@ -281,14 +294,14 @@ __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict
     const int j = lane & 15, g = lane >> 4;
     const int u0 = blockIdx.x * UB;
 
-    f4 b[2][4];
+    f4 b[2][4 * NE];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int uu = u0 + 16 * u + j;
-        if (uu < U) load_row16(prec + (int64_t)uu * 64, g, b[u]);
+        if (uu < U) load_row16<NE>(prec + (int64_t)uu * (64 * NE), g, b[u]);
         else
 #pragma unroll
-            for (int v = 0; v < 4; ++v) b[u][v] = (f4){0.f, 0.f, 0.f, 0.f};
+            for (int v = 0; v < 4 * NE; ++v) b[u][v] = (f4){0.f, 0.f, 0.f, 0.f};
     }
     if (hist_stride <= TK_HS)
         for (int i = threadIdx.x; i < UB * hist_stride; i += 256) {
@@ -318,15 +331,15 @@ __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict
     const int tile_lo = blockIdx.y * tiles_per_split;
     int tile_hi = tile_lo + tiles_per_split;
     if (tile_hi > n_tiles) tile_hi = n_tiles;
-    f4 a[4], an[4];
+    f4 a[4 * NE], an[4 * NE];
     int tile = tile_lo + wave;
-    auto row_of = [&](int tl) { int c = tl * 16 + j; return item_emb + (int64_t)(c < n_items ? c : 0) * 64; };
-    if (tile < tile_hi) load_row16(row_of(tile), g, a);
+    auto row_of = [&](int tl) { int c = tl * 16 + j; return item_emb + (int64_t)(c < n_items ? c : 0) * (64 * NE); };
+    if (tile < tile_hi) load_row16<NE>(row_of(tile), g, a);
     for (; tile < tile_hi; tile += 4) {
         const bool more = tile + 4 < tile_hi;
-        if (more) load_row16(row_of(tile + 4), g, an);
+        if (more) load_row16<NE>(row_of(tile + 4), g, an);
         f4 acc[2];
-        tile_scores(a, b, acc);
+        tile_scores<NE>(a, b, acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int c = tile * 16 + 4 * g + r;
@@ -344,7 +357,7 @@ __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict
         if (__any(cnt[0] > TK_CAP - 16 || cnt[1] > TK_CAP - 16)) { wave_sync(); compact(); }
         if (more)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) a[v] = an[v];
+            for (int v = 0; v < 4 * NE; ++v) a[v] = an[v];
     }
     wave_sync();
     compact();
@@ -432,13 +445,26 @@ static int topk_splits(int64_t U, int64_t n_items_plus1) {
     return (int)ceil_div(n_tiles, per);
 }
 
+// The run-time width as the NE template argument: f(integral_constant<int, 1 .. 4>), after score_width let it through
+template <class F>
+void with_ne(int E, F&& f) {
+    switch (E / 64) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{});
+    }
+}
+#define SC_NE decltype(ne)::value
+bool score_width(int E) { return E > 0 && E <= 256 && E % 64 == 0; }
+
 }  // namespace
 
 extern "C" int iisan_score_rank(const float* prec, const float* item_emb, int64_t U, int64_t n_items_plus1, int32_t E,
                                 const int32_t* history, int32_t hist_stride, const int32_t* target, int32_t* ranks,
                                 void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    IISAN_CHECK_SHAPE(E == 64, "score_rank: embedding_dim must be 64 (got %d)", E);
+    IISAN_CHECK_SHAPE(score_width(E), "score_rank: embedding_dim must be 64, 128, 192 or 256 (got %d)", E);
     IISAN_CHECK_SHAPE(U > 0 && n_items_plus1 > 1 && hist_stride >= 0, "score_rank: empty problem");
     IISAN_CHECK_SHAPE(hist_stride <= MAXH, "score_rank: at most %d history entries per user (got %d)", MAXH, hist_stride);
     IISAN_CHECK_SHAPE(U < (1ll << 31) - UB && n_items_plus1 < (1ll << 31) - 16, "score_rank: problem too large for 32-bit indices");
@@ -453,8 +479,10 @@ extern "C" int iisan_score_rank(const float* prec, const float* item_emb, int64_
     splits = (int)ceil_div(n_tiles, per);
     hipLaunchKernelGGL(zero_ranks_kernel, dim3((unsigned)ceil_div(U, 256)), dim3(256), 0, s, ranks, U);
     IISAN_LAUNCH_OK();
-    hipLaunchKernelGGL(score_rank_mfma_kernel, dim3((unsigned)ublocks, (unsigned)splits), dim3(256), 0, s, prec, item_emb,
-                       (int)n_items_plus1, history, hist_stride, target, ranks, (int)U, per);
+    with_ne(E, [&](auto ne) {
+        hipLaunchKernelGGL(score_rank_mfma_kernel<SC_NE>, dim3((unsigned)ublocks, (unsigned)splits), dim3(256), 0, s, prec, item_emb,
+                           (int)n_items_plus1, history, hist_stride, target, ranks, (int)U, per);
+    });
     IISAN_LAUNCH_OK();
     return IISAN_OK;
 }
@@ -469,7 +497,7 @@ extern "C" int iisan_score_topk(const float* prec, const float* item_emb, int64_
                                 const int32_t* history, int32_t hist_stride, int32_t k, int32_t* topk_ids, float* topk_scores,
                                 void* ws, size_t ws_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    IISAN_CHECK_SHAPE(E == 64, "score_topk: embedding_dim must be 64 (got %d)", E);
+    IISAN_CHECK_SHAPE(score_width(E), "score_topk: embedding_dim must be 64, 128, 192 or 256 (got %d)", E);
     IISAN_CHECK_SHAPE(U > 0 && n_items_plus1 > 1 && hist_stride >= 0, "score_topk: empty problem");
     IISAN_CHECK_SHAPE(k >= 1 && k <= TK_MAX, "score_topk: k must be in 1..%d (got %d)", TK_MAX, k);
     IISAN_CHECK_SHAPE(hist_stride == 0 || history, "score_topk: hist_stride %d without a history array", hist_stride);
@@ -485,13 +513,17 @@ extern "C" int iisan_score_topk(const float* prec, const float* item_emb, int64_
         return IISAN_EWORKSPACE;
     }
     if (splits == 1) {
-        hipLaunchKernelGGL(score_topk_kernel<true>, dim3((unsigned)ublocks, 1), dim3(256), 0, s, prec, item_emb, (int)n_items_plus1, history,
-                           hist_stride, (int)U, per, k, (tkey*)nullptr, topk_ids, topk_scores);
+        with_ne(E, [&](auto ne) {
+            hipLaunchKernelGGL((score_topk_kernel<true, SC_NE>), dim3((unsigned)ublocks, 1), dim3(256), 0, s, prec, item_emb, (int)n_items_plus1, history,
+                               hist_stride, (int)U, per, k, (tkey*)nullptr, topk_ids, topk_scores);
+        });
         IISAN_LAUNCH_OK();
         return IISAN_OK;
     }
-    hipLaunchKernelGGL(score_topk_kernel<false>, dim3((unsigned)ublocks, (unsigned)splits), dim3(256), 0, s, prec, item_emb, (int)n_items_plus1,
-                       history, hist_stride, (int)U, per, k, (tkey*)ws, topk_ids, topk_scores);
+    with_ne(E, [&](auto ne) {
+        hipLaunchKernelGGL((score_topk_kernel<false, SC_NE>), dim3((unsigned)ublocks, (unsigned)splits), dim3(256), 0, s, prec, item_emb, (int)n_items_plus1,
+                           history, hist_stride, (int)U, per, k, (tkey*)ws, topk_ids, topk_scores);
+    });
     IISAN_LAUNCH_OK();
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)U), dim3(64), 0, s, (const tkey*)ws, splits, (int)U, k, topk_ids, topk_scores);
     IISAN_LAUNCH_OK();

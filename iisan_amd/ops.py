@@ -375,7 +375,8 @@ class InbatchCeFn(torch.autograd.Function):
         E = score.shape[1]
         assert ids.numel() == bs * (S + 1) and score.shape[0] == bs * (S + 1) and prec.shape == (bs * S, E)
         loss = torch.empty((), dtype=torch.float32, device=score.device)
-        ws = torch.empty(lib.iisan_inbatch_ce_ws_bytes(bs, S), dtype=torch.uint8, device=score.device)
+        # (0 bytes = a shape or width outside the limits: the forward call below says which)
+        ws = torch.empty(max(lib.iisan_inbatch_ce_ws_bytes_e(bs, S, E), 16), dtype=torch.uint8, device=score.device)
         token = C.c_uint64(0)
         _lib.check(lib.iisan_inbatch_ce_fwd(ids.data_ptr(), score.data_ptr(), prec.data_ptr(), log_mask.data_ptr(),
                                             pop_prob.data_ptr(), pop_prob.numel(), bs, S, E, loss.data_ptr(), ws.data_ptr(), ws.numel(),

@@ -292,14 +292,19 @@ int iisan_sasrec_bwd(const iisan_sasrec_cfg* cfg, const float* x, const float* l
  * From 2^24 logits on (bs = 1024: 10,240 x 11,264) the two passes run on the 16-bit matrix cores with score / prec split
  * into fp16 hi + lo planes (csrc/ce.hip ce16_*: the accuracy of an fp32 product to ~2^-22; the workspace also holds the
  * operand images and the per-range partial results: ~95 MB at bs = 1024); below, on the f32-input matrix cores.
+ * Limits (IISAN_EBADSHAPE otherwise, before any launch): bs > 0, 1 <= S <= 63, E in {64, 128, 192, 256} (the multiples of 64 up to 256, as
+ * iisan_sasrec_*).  E > 64 runs on the f32-input matrix cores at every size (the split-operand passes are 64 wide), and its workspace
+ * holds no operand images: iisan_inbatch_ce_ws_bytes_e(bs, S, E), 10.7 MB at bs = 1024, S = 10, E = 256.
+ * iisan_inbatch_ce_ws_bytes(bs, S) is iisan_inbatch_ce_ws_bytes_e(bs, S, 64); _ws_bytes_e returns 0 for a shape outside the limits.
  * ---------------------------------------------------------------------------------------------------------- */
 size_t iisan_inbatch_ce_ws_bytes(int64_t bs, int32_t S);
+size_t iisan_inbatch_ce_ws_bytes_e(int64_t bs, int32_t S, int32_t E);
 int iisan_inbatch_ce_fwd(const int64_t* ids, const float* score, const float* prec, const float* log_mask,
                          const float* pop_prob, int64_t n_pop, int64_t bs, int32_t S, int32_t E, float* loss,
                          void* ws, size_t ws_bytes, uint64_t* fwd_token, void* stream);
 /* d_loss: host scalar multiplier (upstream gradient).  d_score [M,E] and d_prec [T,E] are overwritten.  `fwd_token`: the value
  * the forward call on this workspace returned (it says whether that call left d_prec for d_loss = 1 in the workspace, which
- * this call then only scales); 0 or a token of another call shape is IISAN_EBADSHAPE. */
+ * this call then only scales); 0 or a token of another call shape (bs, S or E) is IISAN_EBADSHAPE. */
 int iisan_inbatch_ce_bwd(const int64_t* ids, const float* score, const float* prec, const float* log_mask,
                          const float* pop_prob, int64_t bs, int32_t S, int32_t E, float d_loss,
                          float* d_score, float* d_prec, void* ws, size_t ws_bytes, uint64_t fwd_token, void* stream);
@@ -309,8 +314,8 @@ int iisan_inbatch_ce_bwd(const int64_t* ids, const float* score, const float* pr
  * the 1-based rank of `target` among items 1..item_num by score = prec . item_emb, history scored -inf, ties
  * towards the lower item id.  history: int32 [U, hist_stride] padded with 0.  ranks: int32 [U]; a target outside
  * 1..item_num is not dereferenced and yields rank -1, history ids outside that range are ignored.
- * Limits (IISAN_EBADSHAPE otherwise): E == 64, hist_stride <= 256 (the history correction of a user lives in LDS), prec and
- * item_emb 16-byte aligned.
+ * Limits (IISAN_EBADSHAPE otherwise): E in {64, 128, 192, 256}, hist_stride <= 256 (the history correction of a user lives in LDS),
+ * prec and item_emb 16-byte aligned.
  * ---------------------------------------------------------------------------------------------------------- */
 int iisan_score_rank(const float* prec, const float* item_emb, int64_t U, int64_t n_items_plus1, int32_t E,
                      const int32_t* history, int32_t hist_stride, const int32_t* target, int32_t* ranks,
@@ -323,8 +328,8 @@ int iisan_score_rank(const float* prec, const float* item_emb, int64_t U, int64_
  * iisan_score_rank's: a target that call ranks r <= k sits at topk_ids[u, r-1].  topk_scores fp32 [U, k] (nullable): the scores of
  * those items.  history ids outside 1..item_num are ignored, any hist_stride >= 0 is accepted.  When fewer than k items remain outside
  * a user's history the trailing slots hold id 0 / score -inf (the reference's argsort lists the -inf items there).
- * Limits (IISAN_EBADSHAPE otherwise): E == 64, 1 <= k <= 16, prec and item_emb 16-byte aligned; workspace from
- * iisan_score_topk_ws_bytes (0 bytes when one workgroup per 32 users covers the whole catalogue). */
+ * Limits (IISAN_EBADSHAPE otherwise): E in {64, 128, 192, 256}, 1 <= k <= 16, prec and item_emb 16-byte aligned; workspace from
+ * iisan_score_topk_ws_bytes (the same at every width; 0 bytes when one workgroup per 32 users covers the whole catalogue). */
 size_t iisan_score_topk_ws_bytes(int64_t U, int64_t n_items_plus1, int32_t k);
 int iisan_score_topk(const float* prec, const float* item_emb, int64_t U, int64_t n_items_plus1, int32_t E,
                      const int32_t* history, int32_t hist_stride, int32_t k, int32_t* topk_ids, float* topk_scores,
@@ -433,6 +438,8 @@ int32_t iisan_gemm32_plan(const int64_t* M, const int32_t* N, const int64_t* K, 
 /* host-side query: the route iisan_inbatch_ce_fwd takes for this shape under the current ce_fast — 0 generic kernel, 1 separate row passes,
  * 2 fused f32 row pass, 3 split-operand passes; negative = the shape is rejected (iisan_last_error) */
 int32_t iisan_inbatch_ce_route(int64_t bs, int32_t S);
+/* the same at embedding width E (iisan_inbatch_ce_route is the E = 64 call): never 3 at E > 64; -1 for a shape or width outside the limits */
+int32_t iisan_inbatch_ce_route_e(int64_t bs, int32_t S, int32_t E);
 
 /* ------------------------------------------------------------------------------------------------------------
  * DEV section — process-wide development switches and measurement hooks.  NOT part of the product contract: a

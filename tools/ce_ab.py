@@ -23,6 +23,10 @@ from iisan_amd import _lib, ops, synth
 
 if os.environ.get("IISAN_LIB"):
     _lib.LIB_PATH = os.path.abspath(os.environ["IISAN_LIB"])
+    # a build from before an entry point was added: `digest` calls the 64-wide ABI alone and still runs (`time` goes through `ops`, which
+    # asks iisan_inbatch_ce_ws_bytes_e; tools/wide_emb_time.py times either build through the ABI)
+    for name in [n for n in _lib.SIGNATURES if not hasattr(C.CDLL(_lib.LIB_PATH), n)]:
+        del _lib.SIGNATURES[name]
 lib = _lib.load()
 E = 64
 
