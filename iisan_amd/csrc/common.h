@@ -255,6 +255,10 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
+// W-row permutation of the 128-wide 16x16x32 kernels (gemm16.hip, gemm16_x3.hip): LDS row q of the W tile holds W row
+// n0 + nperm(q); accumulator register r of fragment a (0/1) in a 32-column block then lands on column 8*(lane>>4) + 4*a + r.
+__device__ __forceinline__ int nperm(int q) { return (q & ~31) + 8 * ((q & 15) >> 2) + 4 * ((q >> 4) & 1) + (q & 3); }
+
 // XCD-aware bijective remap of a linear workgroup id: the dispatcher places id b on XCD b%8; give every XCD a
 // contiguous range of logical tiles so neighbouring tiles (sharing operand panels) hit the same L2 (guide T1).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

@@ -21,10 +21,6 @@ constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_BYTES = BM * BK * 2;       // 16 KiB per operand tile
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;   // A + W
 
-// LDS row q of the W tile holds W row n0 + nperm(q): accumulator register r of fragment a (0/1) in a 32-column
-// block then lands on column 8*(lane>>4) + 4*a + r.
-__device__ __forceinline__ int nperm(int q) { return (q & ~31) + 8 * ((q & 15) >> 2) + 4 * ((q >> 4) & 1) + (q & 3); }
-
 template <typename T, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
     typedef typename T::v8 V8;
@@ -236,11 +232,20 @@ int launch_gemm16_f32(const Gemm16Args& a, int ksplit, hipStream_t s) {
     return IISAN_OK;
 }
 
+// The shape of the extern "C" entries below — A [M, K], W [N, K] and out [M, N] with their natural leading dimensions — and the
+// two layout flags of the block-major intermediates (DEV section; in the product only the encoder executors set them)
+static Gemm16Args natural_args(int64_t M, int32_t N, int32_t K, int32_t a_blk32, int32_t out_blk32) {
+    Gemm16Args a{};
+    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N;
+    a.a_blk32 = a_blk32 != 0; a.out_blk32 = out_blk32 != 0;
+    return a;
+}
+
 // bench / test entry: fp16 operands [M,K] x [N,K]^T -> fp32 out (plain or split-K with atomics into a caller-zeroed out)
 extern "C" int iisan_gemm16_f32(const void* A, const void* W, float* out, int64_t M, int32_t N, int32_t K, int32_t ksplit,
                                 void* stream) {
-    Gemm16Args a{};
-    a.A = A; a.W = W; a.out = out; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N;
+    Gemm16Args a = natural_args(M, N, K, 0, 0);
+    a.A = A; a.W = W; a.out = out;
     a.atomic = ksplit > 1 ? 1 : 0;
     return launch_gemm16_f32(a, ksplit, (hipStream_t)stream);
 }
@@ -335,82 +340,66 @@ int launch_gemm16(int dtype16, int mode, const Gemm16Args& a, hipStream_t s) {
     }
 }
 
+// The entries that come in pairs: NAME_blk32 carries the two layout flags of the block-major ("blk32") intermediates (DEV section;
+// tests/test_gpu_blk32.py, tools/gemm_blk32_ab.py), NAME is the same call with both flags off.
+
 // the routing query for host-side tests (tests/test_host_logic.py): operands with natural leading dimensions, qkv_S doubles as the
 // patch count of EPI_PATCH16, non-null placeholders for the buffers the checks ask for; no device is touched
-extern "C" int32_t iisan_gemm16_route(int32_t dtype16, int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t qkv_heads,
-                                      int32_t qkv_which0, int32_t with_rowstat) {
+extern "C" int32_t iisan_gemm16_route_blk32(int32_t dtype16, int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t qkv_heads,
+                                            int32_t qkv_which0, int32_t with_rowstat, int32_t a_blk32, int32_t out_blk32) {
     static float dummy = 0.f;
-    Gemm16Args a{};
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N; a.qkv_S = qkv_S; a.qkv_heads = qkv_heads; a.qkv_which0 = qkv_which0;
+    Gemm16Args a = natural_args(M, N, K, a_blk32, out_blk32);
+    a.qkv_S = qkv_S; a.qkv_heads = qkv_heads; a.qkv_which0 = qkv_which0;
     a.patch_P = mode == EPI_PATCH16 || mode == EPI_PATCH32 ? qkv_S : 0;
     a.rowstat = with_rowstat ? &dummy : nullptr;
     a.rowpart = &dummy; a.resid = &dummy; a.pos = &dummy;
     return gemm16_route(dtype16, mode, a);
 }
-
-// bench / test entry: x += A W^T + bias in the fp16 stream x [Mpad, N] (in place), per-slice row sums into rowpart [N / 64][Mpad][2]
-extern "C" int iisan_gemm16_stream(const void* A, const void* W, const float* bias, void* x16, float* rowpart, int64_t M, int32_t N,
-                                   int32_t K, int32_t S, void* stream) {
-    Gemm16Args a{};
-    a.A = A; a.W = W; a.bias = bias; a.out = x16; a.rowpart = rowpart; a.qkv_S = S;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N;
-    return launch_gemm16(IISAN_F16, EPI_STREAM16, a, (hipStream_t)stream);
+extern "C" int32_t iisan_gemm16_route(int32_t dtype16, int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t qkv_heads,
+                                      int32_t qkv_which0, int32_t with_rowstat) {
+    return iisan_gemm16_route_blk32(dtype16, mode, M, N, K, qkv_S, qkv_heads, qkv_which0, with_rowstat, 0, 0);
 }
 
+// bench / test entry: x += A W^T + bias in the fp16 stream x [Mpad, N] (in place), per-slice row sums into rowpart [N / 64][Mpad][2]
+extern "C" int iisan_gemm16_stream_blk32(const void* A, const void* W, const float* bias, void* x16, float* rowpart, int64_t M, int32_t N,
+                                         int32_t K, int32_t S, int32_t a_blk32, int32_t x_blk32, void* stream) {
+    Gemm16Args a = natural_args(M, N, K, a_blk32, x_blk32);
+    a.A = A; a.W = W; a.bias = bias; a.out = x16; a.rowpart = rowpart; a.qkv_S = S;
+    return launch_gemm16(IISAN_F16, EPI_STREAM16, a, (hipStream_t)stream);
+}
+extern "C" int iisan_gemm16_stream(const void* A, const void* W, const float* bias, void* x16, float* rowpart, int64_t M, int32_t N,
+                                   int32_t K, int32_t S, void* stream) {
+    return iisan_gemm16_stream_blk32(A, W, bias, x16, rowpart, M, N, K, S, 0, 0, stream);
+}
+
+// ... and the finalize step behind it
+extern "C" int iisan_stream_stats_finalize_blk32(const float* rowpart, int32_t nslots, int64_t Mpad, void* x16, float* xc, float* rstat, float eps,
+                                                 int64_t items, int32_t Ttok, int32_t x_blk32, void* stream) {
+    return launch_stream_stats_finalize(rowpart, nslots, Mpad, x16, xc, rstat, eps, items, Ttok, (hipStream_t)stream, x_blk32 != 0);
+}
 extern "C" int iisan_stream_stats_finalize(const float* rowpart, int32_t nslots, int64_t Mpad, void* x16, float* xc, float* rstat, float eps,
                                            int64_t items, int32_t Ttok, void* stream) {
-    return launch_stream_stats_finalize(rowpart, nslots, Mpad, x16, xc, rstat, eps, items, Ttok, (hipStream_t)stream);
+    return iisan_stream_stats_finalize_blk32(rowpart, nslots, Mpad, x16, xc, rstat, eps, items, Ttok, 0, stream);
 }
 
 // bench / test entry (not in the product ABI): LN(x) W^T + b with the LayerNorm applied in the epilogue — A = x [M, K] fp16,
 // W = the folded weights, rowstat [Mpad] (null: plain product); mode 1 (GELU) or 4 (head-major QKV: S tokens per item, N / 192 heads)
 extern "C" int iisan_gemm16_lna(int32_t mode, const void* A, const void* W, const float* bias, void* out, const float* rowstat,
                                 int64_t M, int32_t N, int32_t K, int32_t S, void* stream) {
-    Gemm16Args a{};
+    Gemm16Args a = natural_args(M, N, K, 0, 0);
     a.A = A; a.W = W; a.bias = bias; a.out = out; a.rowstat = rowstat;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N;
     if (mode == EPI_QKVH16) { a.qkv_S = S; a.qkv_heads = N / 192; }
     return launch_gemm16(IISAN_F16, mode, a, (hipStream_t)stream);
 }
 
-// DEV-section entries of the block-major ("blk32") intermediates (tests/test_gpu_blk32.py, tools/gemm_blk32_ab.py): the product of
-// iisan_gemm16 (modes 0 / 1; rowstat != null: LayerNorm in the epilogue, fp16), of iisan_gemm16_stream and the finalize step behind it
-// with the two layout flags of Gemm16Args — in the product only the encoder executors set them (encoders.hip, dev switch blk32)
+// DEV-section entry of the block-major intermediates: the product of iisan_gemm16 (modes 0 / 1; rowstat != null: LayerNorm in the
+// epilogue, fp16) with the two layout flags
 extern "C" int iisan_gemm16_blk32(int32_t dtype16, int32_t mode, const void* A, const void* W, const float* bias, void* out,
                                   const float* rowstat, int64_t M, int32_t N, int32_t K, int32_t a_blk32, int32_t out_blk32, void* stream) {
     IISAN_CHECK_SHAPE(mode == EPI_OUT16 || mode == EPI_GELU16, "iisan_gemm16_blk32: mode must be 0 or 1");
-    Gemm16Args a{};
+    Gemm16Args a = natural_args(M, N, K, a_blk32, out_blk32);
     a.A = A; a.W = W; a.bias = bias; a.out = out; a.rowstat = rowstat;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N;
-    a.a_blk32 = a_blk32 != 0; a.out_blk32 = out_blk32 != 0;
     return launch_gemm16(dtype16, mode, a, (hipStream_t)stream);
-}
-
-extern "C" int iisan_gemm16_stream_blk32(const void* A, const void* W, const float* bias, void* x16, float* rowpart, int64_t M, int32_t N,
-                                         int32_t K, int32_t S, int32_t a_blk32, int32_t x_blk32, void* stream) {
-    Gemm16Args a{};
-    a.A = A; a.W = W; a.bias = bias; a.out = x16; a.rowpart = rowpart; a.qkv_S = S;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N;
-    a.a_blk32 = a_blk32 != 0; a.out_blk32 = x_blk32 != 0;
-    return launch_gemm16(IISAN_F16, EPI_STREAM16, a, (hipStream_t)stream);
-}
-
-extern "C" int iisan_stream_stats_finalize_blk32(const float* rowpart, int32_t nslots, int64_t Mpad, void* x16, float* xc, float* rstat, float eps,
-                                                 int64_t items, int32_t Ttok, int32_t x_blk32, void* stream) {
-    return launch_stream_stats_finalize(rowpart, nslots, Mpad, x16, xc, rstat, eps, items, Ttok, (hipStream_t)stream, x_blk32 != 0);
-}
-
-// iisan_gemm16_route with the two layout flags (host side, no device touched)
-extern "C" int32_t iisan_gemm16_route_blk32(int32_t dtype16, int32_t mode, int64_t M, int32_t N, int32_t K, int32_t qkv_S, int32_t qkv_heads,
-                                            int32_t qkv_which0, int32_t with_rowstat, int32_t a_blk32, int32_t out_blk32) {
-    static float dummy = 0.f;
-    Gemm16Args a{};
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N; a.qkv_S = qkv_S; a.qkv_heads = qkv_heads; a.qkv_which0 = qkv_which0;
-    a.patch_P = mode == EPI_PATCH16 || mode == EPI_PATCH32 ? qkv_S : 0;
-    a.rowstat = with_rowstat ? &dummy : nullptr;
-    a.rowpart = &dummy; a.resid = &dummy; a.pos = &dummy;
-    a.a_blk32 = a_blk32 != 0; a.out_blk32 = out_blk32 != 0;
-    return gemm16_route(dtype16, mode, a);
 }
 
 // bench / test entry: the weight fold of one LayerNorm + product pair (rowops.hip)
@@ -423,9 +412,8 @@ extern "C" int iisan_fold_ln_weights(const void* W, int32_t w32, const float* bi
 extern "C" int iisan_gemm16(int32_t dtype16, int32_t mode, const void* A, const void* W, const float* bias, void* out,
                             const float* resid, int64_t M, int32_t N, int32_t K, void* stream) {
     IISAN_CHECK_SHAPE(mode >= 0 && mode <= 2, "iisan_gemm16: mode must be 0, 1 or 2");
-    Gemm16Args a{};
-    a.A = A; a.W = W; a.bias = bias; a.out = out; a.resid = resid; a.pos = nullptr;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N; a.patch_P = 0;
+    Gemm16Args a = natural_args(M, N, K, 0, 0);
+    a.A = A; a.W = W; a.bias = bias; a.out = out; a.resid = resid;
     return launch_gemm16(dtype16, mode, a, (hipStream_t)stream);
 }
 

@@ -35,7 +35,14 @@
 //                  W 0..127 of 2'  -> read in [11],[12];    W buffer last read in [5],[6]
 //   B Mhi(0') [9]: W 128..255 of 2'-> read in [11],[12];                                       waited at the end of [10]
 // (the whole W fragment set of a step is read in Rlo, the A-operand rows 0..63 in Rlo and 64..127 in Rhi).
-// Tile walk, LDS swizzle, operand swap / W-row permutation, fences and the 16-bit epilogues are those of gemm16_s256.hip.
+//
+// What this kernel shares with gemm16_s256.hip, its race screen (dev switch gemm16_variant = 3), lives ONCE in gemm16_t256.h: tile constants,
+// the MFMA with swapped operands, the W-row permutation, the fences, the fragment reads (t256_read: whole steps and the half-steps here), the DMA
+// plan of an MFMA slot and its inline-asm piece (used by the full step and by mfma_half here), the full MFMA step of the middle K-steps, the
+// host's grid rule.
+// This file's own: the slot program above, the tile walk with step_at / make_plan, mfma_half and its MODE table, stream_load, the three epilogue
+// families, the timeline hooks, the builtin wait macros — and its copy of the lane staging offsets with vj, the prologue pieces and the
+// accumulator / fragment-offset set-up, which gemm16_s256.hip repeats for the row-major case (gemm16_t256.h says why).
 //
 // Round 4, second half — two epilogue families that remove every kernel between the products of a pre-LN block:
 //   LNA (template flag; EPI_QKVH16 / EPI_GELU16, fp16): A is the un-normalised residual stream, W the gamma-folded, centred weights
@@ -49,39 +56,16 @@
 // kernel alone — F1 between FC1 and FC2, the ViT stream of EPI_STREAM16 — it is stored as 32 x 32 blocks of 2 KiB in the order the epilogue's lanes
 // hold them: every store (and stream_load) instruction covers one contiguous KiB instead of 32 cache lines, and the consumer's LDS-DMA pieces copy
 // a wave's 4-KiB run per K-step into LDS as it is.  Same arithmetic, same summation order: bit-equal to the row-major instantiations.
-#include "common.h"
-#include <type_traits>
+#include "gemm16_t256.h"
 
 namespace {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
-
-constexpr int SBM = 256, SBN = 256, SBK = 64;
-constexpr int S_OP_BYTES = SBM * SBK * 2;        // 32 KiB per operand tile
-constexpr int S_STAGE_BYTES = 2 * S_OP_BYTES;    // 64 KiB per K-step
 constexpr int STG_BIAS_BYTES = 8192 * 4;           // LDS after the ring: the layer's bias vector (N <= 8192 floats; 160 KiB in all)
 // LNA (LayerNorm applied in the epilogue, Gemm16Args::rowstat): two 1-KiB buffers of row statistics (rstd of the tile's 256 rows, one
 // buffer per tile, alternating) sit at 24 KiB of the bias area
 constexpr int LNA_STAT_OFF = 24576, LNA_MAX_N = 6144;
 constexpr int STG_TILE_BYTES = 0;
 
-template <typename T> struct Mfma32s;
-template <> struct Mfma32s<F16> {
-    static __device__ __forceinline__ f16v run(h8 a, h8 b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mfma32s<BF16> {
-    static __device__ __forceinline__ f16v run(b8 a, b8 b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-
-__device__ __forceinline__ int nperm32s(int q) { return (q & ~31) + 16 * ((q >> 2) & 1) + 4 * ((q & 31) >> 3) + (q & 3); }
-
-#define S256_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define S256_BARRIER()                                   \
-    do {                                                 \
-        S256_FENCE();                                    \
-        asm volatile("s_barrier" ::: "memory");          \
-        S256_FENCE();                                    \
-    } while (0)
 // vmcnt(n) / lgkmcnt(0) as the BUILTIN (gfx9 encoding: vmcnt[3:0] | expcnt << 4 | lgkmcnt << 8 | vmcnt[5:4] << 14), not inline asm:
 // hipcc's own wait insertion then knows what has retired.  With the asm form it re-waited `vmcnt(0)` at the first touch of a
 // register it had reloaded from scratch slots earlier — in the middle of the epilogue arithmetic, behind the LDS-DMA issued since.
@@ -188,7 +172,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
     const int rowA = r8 * p.lda * 2;                                             // A-operand: LDS row == global row
     // Block-major A operand: the 32 rows x 64 K-elements a wave stages per K-step are ONE 4-KiB run of the matrix (two blocks), and
     // they go into the wave's 4 KiB of the LDS tile AS THEY ARE — piece j = KiB j of the run, lane l its 16 bytes l: the LDS image of
-    // those rows is block-major too, and the fragment reads address it (read_step: granule 2 ks + fh of row frow sits at
+    // those rows is block-major too, and the fragment reads address it (t256_read / t256_aslot: granule 2 ks + fh of row frow sits at
     // (ks / 2) * 2048 + fh * 1024 + (ks & 1) * 512 + frow * 16: each half-wave reads 512 contiguous bytes, no swizzle needed).
     // (First built with the row-major LDS image kept and the GATHER on the global side — lane (r8, slot) fetching its granule from
     //  wherever the block holds it: 8 complete lines per piece as in the row-major matrix, but adjacent lanes in 8 different lines;
@@ -232,56 +216,18 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)      // group g reads only its A-half (block-major LDS image: see a_lane_blk)
         xoff[mi] = A_BLK ? (grp * 128 + mi * 32) * 128 + fh * 1024 + frow * 16 : (grp * 128 + mi * 32 + frow) * 128;
-    // byte offset of K-slice ks inside a 32-row run of the A tile, added to xoff: the swizzled slot, or a constant (block-major)
-#define S256_ASLOT(ks, slot) (A_BLK ? ((ks) >> 1) * 2048 + ((ks) & 1) * 512 : (slot))
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) woff2[ni] = (wq * 64 + ni * 32 + frow) * 128;
 
     V8 wf[2][4], xf[4][4];
-    auto read_step = [&](int s) {
-        const char* sA = smem + (s & 1) * S_STAGE_BYTES;
-        const char* sW = sA + S_OP_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const int slot = ((2 * ks + fh) ^ fsw) << 4;
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) wf[ni][ks] = *(const V8*)(sW + woff2[ni] + slot);
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi) xf[mi][ks] = *(const V8*)(sA + xoff[mi] + S256_ASLOT(ks, slot));
-        }
-    };
-    // half-steps of a tile's last / first K-step: Rlo = every W fragment of the step + the A-operand rows 0..63 of the
-    // group's half (16 reads), Rhi = rows 64..127 (8 reads)
-    auto read_lo = [&](int s) {
-        const char* sA = smem + (s & 1) * S_STAGE_BYTES;
-        const char* sW = sA + S_OP_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const int slot = ((2 * ks + fh) ^ fsw) << 4;
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) wf[ni][ks] = *(const V8*)(sW + woff2[ni] + slot);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) xf[mi][ks] = *(const V8*)(sA + xoff[mi] + S256_ASLOT(ks, slot));
-        }
-    };
-    auto read_hi = [&](int s) {
-        const char* sA = smem + (s & 1) * S_STAGE_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const int slot = ((2 * ks + fh) ^ fsw) << 4;
-#pragma unroll
-            for (int mi = 2; mi < 4; ++mi) xf[mi][ks] = *(const V8*)(sA + xoff[mi] + S256_ASLOT(ks, slot));
-        }
-    };
-    // ---- DMA plan of one MFMA slot: 8 wave-uniform (global address, LDS offset) pairs, computed in the preceding READ
-    // slot (which idles ~1000 cycles at its barrier).  Nothing but the MFMAs, one 64-bit add, `s_mov m0` and the
-    // `global_load_lds` itself may sit in the MFMA slot: slot timelines showed every scalar instruction or branch between
-    // MFMAs to cost matrix-pipe time (an MFMA slot took 1440 cycles with 8 skipped `if`s, 1540 with 32, 1046 bare).
-    // The plan is therefore unconditional: past the end of the workgroup's steps it re-loads the last step into
-    // buffers that nobody reads any more.
-    struct Plan {
-        uint32_t g1lo, g1hi, g2lo, g2hi;      // global byte address of pieces 0..3 / 4..7 (SGPRs)
-        uint32_t l1, l2;                      // LDS byte offset of piece 0 / piece 4
+    // Fragment reads of flat step s.  R_FULL: a middle step's read slot (24 reads, as gemm16_s256.hip); the half-steps of a tile's
+    // last / first K-step: R_LO = every W fragment of the step + the A-operand rows 0..63 of the group's half (16 reads),
+    // R_HI = rows 64..127 (8 reads)
+    enum { R_FULL = 0, R_LO = 1, R_HI = 2 };
+    auto read_frags = [&](auto PART_T, int s) {
+        constexpr int PART = decltype(PART_T)::value;
+        constexpr int MI0 = PART == R_HI ? 2 : 0, MI1 = PART == R_LO ? 2 : 4;
+        t256_read<V8, MI0, MI1, PART != R_HI, A_BLK>(smem, s, wf, xf, xoff, woff2, fh, fsw);
     };
     // per-lane source offset of piece j (j = pc & 3): row-in-chunk and swizzled 16-B slot, plus j chunks of 8 (A operand)
     // or 4 (permuted W) rows
@@ -290,11 +236,9 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
     for (int j = 0; j < 4; ++j)
         if (A_BLK && grp == 0) vj[j] = (uint32_t)a_lane_blk(j);
         else vj[j] = (uint32_t)((grp == 0 ? rowA : rowW) + ((j & 1) ? slotx1 : slotx0)) + (uint32_t)j * (grp == 0 ? 8u * p.lda * 2u : 4u * p.ldw * 2u);
-    auto sgpr = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
-    // Group A: pieces 0..3 = B's A-operand half of step s+1, 4..7 = A's own half of step s+2;
-    // group B: the W tile of step s+2 (pieces 0..3 rows 0..127, 4..7 rows 128..255).
+    // DMA plan (T256Plan) of the MFMA slot(s) of flat step s
     auto make_plan = [&](int s, int kt) {          // kt = K-step of flat step s inside the current tile (-1: before step 0)
-        Plan q;
+        T256Plan q;
         uint64_t g1, g2;
         int tm2, tn2, kt2;
         step_at(kt, 2, tm2, tn2, kt2);
@@ -312,49 +256,10 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
             q.l1 = (s & 1) * S_STAGE_BYTES + S_OP_BYTES + (wq * 32) * 128;
             q.l2 = q.l1 + 128 * 128;
         }
-        q.g1lo = sgpr((uint32_t)g1); q.g1hi = sgpr((uint32_t)(g1 >> 32));
-        q.g2lo = sgpr((uint32_t)g2); q.g2hi = sgpr((uint32_t)(g2 >> 32));
-        q.l1 = sgpr(q.l1); q.l2 = sgpr(q.l2);
+        q.g1lo = t256_sgpr((uint32_t)g1); q.g1hi = t256_sgpr((uint32_t)(g1 >> 32));
+        q.g2lo = t256_sgpr((uint32_t)g2); q.g2hi = t256_sgpr((uint32_t)(g2 >> 32));
+        q.l1 = t256_sgpr(q.l1); q.l2 = t256_sgpr(q.l2);
         return q;
-    };
-    // 32 MFMAs with this wave's 8 DMA pieces interleaved: piece pc after MFMA 4*pc + 3.  Only the 8 MFMAs of K-slice 0
-    // exist in two versions (a tile's first K-step starts from C = 0, an inline-constant operand, instead of zeroing
-    // 128 VGPRs): with two full bodies the compiler hoisted the 8 piece addresses above the branch -> 16 VGPRs, spills,
-    // and a `s_waitcnt vmcnt(0)` for the reload at the top of every MFMA slot.
-    auto mfma_step = [&](const Plan& q, bool first) {
-        auto piece = [&](int pc) {
-            const int j = pc & 3;
-            const uint64_t gb = ((uint64_t)(pc < 4 ? q.g1hi : q.g2hi) << 32) | (pc < 4 ? q.g1lo : q.g2lo);
-            S256_FENCE();
-            // SGPR base + 32-bit lane offset, written as inline asm: the builtin is selected with a 64-bit VGPR address
-            // (a v_lshl_add_u64 per piece between the MFMAs and two address registers read per lane).  Same-box A/B
-            // over 6 rounds: QKV 915 -> 921, O 940 -> 942, FC1 921 -> 931, FC2 1146 -> 1162 TFLOP/s.  (M0 is only
-            // written here and, in the prologue, by the builtin right before its own use.)
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                         :: "s"(smem_lds + (pc < 4 ? q.l1 : q.l2) + j * 1024), "v"(vj[j]), "s"(gb) : "memory");
-            S256_FENCE();
-        };
-        auto slice = [&](auto FIRST, int ks) {
-            f16v zero;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) zero[r] = 0.f;
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    acc[mi][ni] = Mfma32s<T>::run(wf[ni][ks], xf[mi][ks], decltype(FIRST)::value ? zero : acc[mi][ni]);
-                    if (((mi * 2 + ni) & 3) == 3) piece(ks * 2 + (mi >> 1));
-                }
-        };
-        // The sibling wave of this SIMD is in its read slot (ds_reads, address VALU, plan SALU): with equal priority the
-        // arbiter prefers the OLDER wave, and the slot timeline showed group B's MFMA slots at 1,680 cycles against
-        // group A's 1,252.  Priority 1 for whoever is on the matrix pipe removes that.
-        __builtin_amdgcn_s_setprio(1);
-        if (first) slice(std::true_type{}, 0); else slice(std::false_type{}, 0);
-        S256_FENCE();
-#pragma unroll
-        for (int ks = 1; ks < 4; ++ks) slice(std::false_type{}, ks);
-        __builtin_amdgcn_s_setprio(0);
     };
     // One half-step: the 16 MFMAs of output rows lo (HI = 0: acc[0..1]) or hi (HI = 1: acc[2..3]) of a K-step, with the DMA
     // pieces the schedule in the file header assigns to it (MODE, compile time — nothing but MFMAs and pieces in the slot):
@@ -362,17 +267,11 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
     //   H_FIRST_LO: pieces 4..7 of qp (the previous tile's last plan) and 0..3 of q, one after every 2 MFMAs; C = 0 at ks 0
     //   H_FIRST_HI: pieces 4..7 of q;                                                                      C = 0 at ks 0
     enum { H_LAST_LO = 0, H_LAST_HI = 1, H_FIRST_LO = 2, H_FIRST_HI = 3 };
-    auto mfma_half = [&](auto MODE_T, const Plan& q, const Plan& qp) {
+    auto mfma_half = [&](auto MODE_T, const T256Plan& q, const T256Plan& qp) {
         constexpr int MODE = decltype(MODE_T)::value;
         constexpr int HI = MODE & 1;
         constexpr bool FIRST = MODE >= 2;
-        auto piece = [&](uint32_t lo32, uint32_t hi32, uint32_t lds, int j) {
-            const uint64_t gb = ((uint64_t)hi32 << 32) | lo32;
-            S256_FENCE();
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                         :: "s"(smem_lds + lds + j * 1024), "v"(vj[j]), "s"(gb) : "memory");
-            S256_FENCE();
-        };
+        auto piece = [&](uint32_t lo32, uint32_t hi32, uint32_t lds, int j) { t256_dma_piece(smem_lds, lds, j, vj[j], lo32, hi32); };
         f16v zero;
 #pragma unroll
         for (int r = 0; r < 16; ++r) zero[r] = 0.f;
@@ -731,15 +630,15 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
     // half-epilogue of this slot issued exactly 8 store instructions (full row tile, stores enabled), all YOUNGER than the
     // loads the wait is for: `vmcnt(8)` lets them fly on.
     using std::integral_constant;
-    Plan qprev = make_plan(-1, -1);    // pieces 4..7: what the prologue loaded for step 1 (re-issued identically at s = 0)
+    T256Plan qprev = make_plan(-1, -1);    // pieces 4..7: what the prologue loaded for step 1 (re-issued identically at s = 0)
     int ti = 0;                        // index of the tile being computed in this workgroup's walk
     if (grp == 1) S256_BARRIER();      // B: slot 0 (A is in Rlo(0))
     for (int s = 0; s < nsteps;) {
         {
             // ======== first K-step of a tile: Rlo | Mlo | Rhi + E(hi, previous tile) | Mhi ========
             if (s > 0) stream_load(prev_tm, prev_tn, 1);
-            read_lo(s);
-            const Plan q = make_plan(s, 0);
+            read_frags(integral_constant<int, R_LO>{}, s);
+            const T256Plan q = make_plan(s, 0);
             S256_LGKM0();
             S256_FENCE();              // nothing to wait for: the only vector-memory operations in flight are stores
             stamp();
@@ -751,7 +650,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
             stamp();
             stat_dma(cur_tm, ti & 1);
             if (s > 0) epilogue(prev_tm, prev_tn, 1, (ti - 1) & 1);
-            read_hi(s);
+            read_frags(integral_constant<int, R_HI>{}, s);
             S256_LGKM0();
             // the 8 pieces of Mlo (and, older, the 8 stores of the lo half); the 8 stores just issued stay in flight
             if (s > 0 && stores8) S256_VMCNT_EPI(); else S256_VMCNT(0);
@@ -765,22 +664,22 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
         }
         for (int kt = 1; kt < nk - 1; ++kt, ++s) {
             // ======== middle K-steps: R | M (as gemm16_s256.hip) ========
-            read_step(s);
-            const Plan q = make_plan(s, kt);
+            read_frags(integral_constant<int, R_FULL>{}, s);
+            const T256Plan q = make_plan(s, kt);
             S256_LGKM0();
             S256_VMCNT(0);             // the pieces of the previous MFMA slot (after a first step: the hi half's stores too, two slots old)
             stamp();
             S256_BARRIER();
             stamp();
-            mfma_step(q, false);
+            t256_mfma_step<T>(acc, wf, xf, q, false, smem_lds, vj);
             stamp();
             S256_BARRIER();
         }
         {
             // ======== last K-step of a tile: Rlo | Mlo | Rhi + E(lo) | Mhi ========
             stream_load(cur_tm, cur_tn, 0);
-            read_lo(s);
-            const Plan q = make_plan(s, nk - 1);
+            read_frags(integral_constant<int, R_LO>{}, s);
+            const T256Plan q = make_plan(s, nk - 1);
             S256_LGKM0();
             if constexpr (EPI == EPI_STREAM16) S256_VMCNT(8); else S256_VMCNT(0);      // (the 8 stream loads just issued fly on)
             stamp();
@@ -791,7 +690,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
             S256_BARRIER();
             stamp();
             epilogue(cur_tm, cur_tn, 0, ti & 1);
-            read_hi(s);
+            read_frags(integral_constant<int, R_HI>{}, s);
             S256_LGKM0();
             if (stores8) S256_VMCNT_EPI(); else S256_VMCNT(0);      // the 4 pieces of Mlo; the 8 stores just issued stay in flight
             stamp();
@@ -829,13 +728,9 @@ int launch_epi(const Gemm16Args& a, hipStream_t s) {
     static OncePerDevice attr;
     auto kern = gemm16_h256_kernel<T, EPI, LNA, BLK>;
     constexpr int LDS = 2 * S_STAGE_BYTES + STG_BIAS_BYTES + STG_TILE_BYTES;       // 160 KiB: the whole LDS of a CU
-    if (attr.first())
-        IISAN_HIP_OK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
     const int tiles_m = (int)ceil_div(a.M, SBM), tiles_n = a.N / SBN;
-    const int64_t ntiles = (int64_t)tiles_m * tiles_n;
-    const int cus = iisan_cu_count();
-    int grid = (int)(ntiles < cus ? ntiles : cus);
-    grid = (grid + 7) / 8 * 8;
+    int grid;
+    IISAN_TRY(t256_prepare_launch(attr, (const void*)kern, LDS, tiles_m, tiles_n, grid));
     // EPI_QKVH16: item = row / S as one v_mul_hi_u32 by floor(2^32 / S) + 1 — exact while row * S < 2^32 (gemm16_h256_applicable)
     const int div = EPI == EPI_PATCH16 ? a.patch_P : a.qkv_S;       // (EPI_STREAM16: S, for the CLS-row test)
     const uint32_t magic = div > 0 ? (uint32_t)((1ull << 32) / (uint64_t)div) + 1u : 0u;

@@ -1,6 +1,6 @@
 // Third-generation 16-bit MFMA GEMM: persistent 256x256x64 tiles with two STAGGERED wave groups.
 //
-// Ablation of the second generation (gemm16_p256.hip): with DMA and epilogue removed its K loop still reached only
+// Ablation of the second generation (lock-step 256x256 tiles): with DMA and epilogue removed its K loop still reached only
 // 55 % of the MFMA peak — all 8 waves read their fragments from LDS at the same time and then all issue MFMAs at the
 // same time, so the two waves sharing a SIMD never overlap (LDS-read phase: matrix pipe idle; MFMA phase: LDS idle).
 //
@@ -25,38 +25,19 @@
 //        B in M(s)   (slot 2s+2) : the whole W tile of step s+2   (read in slots 2s+4, 2s+5)
 //        A and B: `s_waitcnt vmcnt(0)` at the END of each read slot (so the stores of an epilogue get a slot as well)
 // Each ring buffer was last read at least one slot before it is overwritten (2 stages of 64 KiB).
-// The compiler must be fenced (`sched_barrier`) around every barrier / wait: MFMAs are pure register ops, and without
-// the fences 28 of group B's 32 MFMAs were hoisted above the `s_barrier` into its read slot and the `s_waitcnt vmcnt`
-// to the top of the MFMA slot — turning the stagger back into lock-step (seen in the ISA, cost ~10 %).
-// Tile walk, LDS swizzle, operand swap / W-row permutation and the 16-bit epilogues are those of gemm16_p256.hip.
-#include "common.h"
-#include <type_traits>
+//
+// This kernel is also the race screen of gemm16_h256.hip (dev switch gemm16_variant = 3) and serves the shapes
+// gemm16_h256_applicable() turns down.  What the two share lives ONCE, in gemm16_t256.h: tile constants, the MFMA with swapped
+// operands, the W-row permutation, the fences (and why the compiler needs them), the fragment reads, the DMA plan of an MFMA slot
+// with its inline-asm piece, the full MFMA step, the host's grid rule.
+// This file's own: the slot program above (groups A and B), the row-major tile walk (make_plan divides the flat step by nk), the
+// plain 16-bit epilogue with slots of its own, the timeline hooks, the inline-asm wait macros — and its copy of the lane staging
+// offsets with vj, the prologue pieces and the accumulator / fragment-offset set-up, which gemm16_h256.hip repeats (gemm16_t256.h
+// says why).
+#include "gemm16_t256.h"
 
 namespace {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
-
-constexpr int SBM = 256, SBN = 256, SBK = 64;
-constexpr int S_OP_BYTES = SBM * SBK * 2;        // 32 KiB per operand tile
-constexpr int S_STAGE_BYTES = 2 * S_OP_BYTES;    // 64 KiB per K-step
-
-template <typename T> struct Mfma32s;
-template <> struct Mfma32s<F16> {
-    static __device__ __forceinline__ f16v run(h8 a, h8 b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mfma32s<BF16> {
-    static __device__ __forceinline__ f16v run(b8 a, b8 b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-
-__device__ __forceinline__ int nperm32s(int q) { return (q & ~31) + 16 * ((q >> 2) & 1) + 4 * ((q & 31) >> 3) + (q & 3); }
-
-#define S256_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define S256_BARRIER()                                   \
-    do {                                                 \
-        S256_FENCE();                                    \
-        asm volatile("s_barrier" ::: "memory");          \
-        S256_FENCE();                                    \
-    } while (0)
 #define S256_VMCNT(n)                                        \
     do {                                                     \
         S256_FENCE();                                        \
@@ -136,39 +117,16 @@ __global__ __launch_bounds__(512, 2) void gemm16_s256_kernel(Gemm16Args p, int t
     for (int ni = 0; ni < 2; ++ni) woff2[ni] = (wq * 64 + ni * 32 + frow) * 128;
 
     V8 wf[2][4], xf[4][4];
-    auto read_step = [&](int s) {
-        const char* sA = smem + (s & 1) * S_STAGE_BYTES;
-        const char* sW = sA + S_OP_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const int slot = ((2 * ks + fh) ^ fsw) << 4;
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) wf[ni][ks] = *(const V8*)(sW + woff2[ni] + slot);
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi) xf[mi][ks] = *(const V8*)(sA + xoff[mi] + slot);
-        }
-    };
-    // ---- DMA plan of one MFMA slot: 8 wave-uniform (global address, LDS offset) pairs, computed in the preceding READ
-    // slot (which idles ~1000 cycles at its barrier).  Nothing but the MFMAs, one 64-bit add, `s_mov m0` and the
-    // `global_load_lds` itself may sit in the MFMA slot: slot timelines showed every scalar instruction or branch between
-    // MFMAs to cost matrix-pipe time (an MFMA slot took 1440 cycles with 8 skipped `if`s, 1540 with 32, 1046 bare).
-    // The plan is therefore unconditional: past the end of the workgroup's steps it re-loads the last step into
-    // buffers that nobody reads any more.
-    struct Plan {
-        uint32_t g1lo, g1hi, g2lo, g2hi;      // global byte address of pieces 0..3 / 4..7 (SGPRs)
-        uint32_t l1, l2;                      // LDS byte offset of piece 0 / piece 4
-    };
+    auto read_step = [&](int s) { t256_read<V8, 0, 4, true, false>(smem, s, wf, xf, xoff, woff2, fh, fsw); };
     // per-lane source offset of piece j (j = pc & 3): row-in-chunk and swizzled 16-B slot, plus j chunks of 8 (A operand)
     // or 4 (permuted W) rows
     uint32_t vj[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         vj[j] = (uint32_t)((grp == 0 ? rowA : rowW) + ((j & 1) ? slotx1 : slotx0)) + (uint32_t)j * (grp == 0 ? 8u * p.lda * 2u : 4u * p.ldw * 2u);
-    auto sgpr = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
-    // Group A: pieces 0..3 = B's A-operand half of step s+1, 4..7 = A's own half of step s+2;
-    // group B: the W tile of step s+2 (pieces 0..3 rows 0..127, 4..7 rows 128..255).
+    // DMA plan (T256Plan) of the MFMA slot of flat step s; past the workgroup's last step it re-loads the last step
     auto make_plan = [&](int s) {
-        Plan q;
+        T256Plan q;
         const int last = nsteps - 1;
         uint64_t g1, g2;
         if (grp == 0) {
@@ -189,49 +147,10 @@ __global__ __launch_bounds__(512, 2) void gemm16_s256_kernel(Gemm16Args p, int t
             q.l1 = (s & 1) * S_STAGE_BYTES + S_OP_BYTES + (wq * 32) * 128;
             q.l2 = q.l1 + 128 * 128;
         }
-        q.g1lo = sgpr((uint32_t)g1); q.g1hi = sgpr((uint32_t)(g1 >> 32));
-        q.g2lo = sgpr((uint32_t)g2); q.g2hi = sgpr((uint32_t)(g2 >> 32));
-        q.l1 = sgpr(q.l1); q.l2 = sgpr(q.l2);
+        q.g1lo = t256_sgpr((uint32_t)g1); q.g1hi = t256_sgpr((uint32_t)(g1 >> 32));
+        q.g2lo = t256_sgpr((uint32_t)g2); q.g2hi = t256_sgpr((uint32_t)(g2 >> 32));
+        q.l1 = t256_sgpr(q.l1); q.l2 = t256_sgpr(q.l2);
         return q;
-    };
-    // 32 MFMAs with this wave's 8 DMA pieces interleaved: piece pc after MFMA 4*pc + 3.  Only the 8 MFMAs of K-slice 0
-    // exist in two versions (a tile's first K-step starts from C = 0, an inline-constant operand, instead of zeroing
-    // 128 VGPRs): with two full bodies the compiler hoisted the 8 piece addresses above the branch -> 16 VGPRs, spills,
-    // and a `s_waitcnt vmcnt(0)` for the reload at the top of every MFMA slot.
-    auto mfma_step = [&](const Plan& q, bool first) {
-        auto piece = [&](int pc) {
-            const int j = pc & 3;
-            const uint64_t gb = ((uint64_t)(pc < 4 ? q.g1hi : q.g2hi) << 32) | (pc < 4 ? q.g1lo : q.g2lo);
-            S256_FENCE();
-            // SGPR base + 32-bit lane offset, written as inline asm: the builtin is selected with a 64-bit VGPR address
-            // (a v_lshl_add_u64 per piece between the MFMAs and two address registers read per lane).  Same-box A/B
-            // over 6 rounds: QKV 915 -> 921, O 940 -> 942, FC1 921 -> 931, FC2 1146 -> 1162 TFLOP/s.  (M0 is only
-            // written here and, in the prologue, by the builtin right before its own use.)
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-                         :: "s"(smem_lds + (pc < 4 ? q.l1 : q.l2) + j * 1024), "v"(vj[j]), "s"(gb) : "memory");
-            S256_FENCE();
-        };
-        auto slice = [&](auto FIRST, int ks) {
-            f16v zero;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) zero[r] = 0.f;
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) {
-                    acc[mi][ni] = Mfma32s<T>::run(wf[ni][ks], xf[mi][ks], decltype(FIRST)::value ? zero : acc[mi][ni]);
-                    if (((mi * 2 + ni) & 3) == 3) piece(ks * 2 + (mi >> 1));
-                }
-        };
-        // The sibling wave of this SIMD is in its read slot (ds_reads, address VALU, plan SALU): with equal priority the
-        // arbiter prefers the OLDER wave, and the slot timeline showed group B's MFMA slots at 1,680 cycles against
-        // group A's 1,252.  Priority 1 for whoever is on the matrix pipe removes that.
-        __builtin_amdgcn_s_setprio(1);
-        if (first) slice(std::true_type{}, 0); else slice(std::false_type{}, 0);
-        S256_FENCE();
-#pragma unroll
-        for (int ks = 1; ks < 4; ++ks) slice(std::false_type{}, ks);
-        __builtin_amdgcn_s_setprio(0);
     };
     bool stores16 = false;     // the last epilogue issued exactly 16 store instructions per wave (full row tile, stores enabled)
     auto epilogue = [&](int s, int half) {
@@ -363,7 +282,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_s256_kernel(Gemm16Args p, int t
             const int kt = s % nk;
             if (kt == 0 && s > 0) epilogue(s - 1, 1);
             read_step(s);
-            const Plan q = make_plan(s);
+            const T256Plan q = make_plan(s);
             S256_LGKM0();
             // B's half of step s and A's half of step s+1 (issued in M(s-1)) must have landed.  Right after an
             // epilogue the 16 stores of a full tile are younger than those loads and vmcnt retires in order on gfx9, so
@@ -373,7 +292,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_s256_kernel(Gemm16Args p, int t
             S256_BARRIER();
             stamp();
             // ---- slot 2s+1 : M(s) ----
-            mfma_step(q, kt == 0);
+            t256_mfma_step<T>(acc, wf, xf, q, kt == 0, smem_lds, vj);
             stamp();
             // Tile end.  The epilogue gets slots of its own so that it overlaps the sibling group's MFMAs instead of
             // serialising with them:   A: M(last) | E1 | E2+R(0') | M(0')      (E1 = rows 0..63 of the group's half,
@@ -391,14 +310,14 @@ __global__ __launch_bounds__(512, 2) void gemm16_s256_kernel(Gemm16Args p, int t
             const int kt = s % nk;
             if (kt == 0 && s > 0) epilogue(s - 1, 1);
             read_step(s);
-            const Plan q = make_plan(s);
+            const T256Plan q = make_plan(s);
             S256_LGKM0();
             if (kt == 0 && s > 0 && stores16) S256_VMCNT(16); else S256_VMCNT(0);      // the W tile of step s+1 (issued in M(s-1))
             stamp();
             S256_BARRIER();
             stamp();
             // ---- slot 2s+2 : M(s) ----
-            mfma_step(q, kt == 0);
+            t256_mfma_step<T>(acc, wf, xf, q, kt == 0, smem_lds, vj);
             stamp();
             if (kt == nk - 1) { S256_BARRIER(); epilogue(s, 0); }
             S256_BARRIER();
@@ -422,13 +341,9 @@ template <typename T, int EPI>
 int launch_epi(const Gemm16Args& a, hipStream_t s) {
     static OncePerDevice attr;
     auto kern = gemm16_s256_kernel<T, EPI>;
-    if (attr.first())
-        IISAN_HIP_OK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * S_STAGE_BYTES + 8192 * 4));
     const int tiles_m = (int)ceil_div(a.M, SBM), tiles_n = a.N / SBN;
-    const int64_t ntiles = (int64_t)tiles_m * tiles_n;
-    const int cus = iisan_cu_count();
-    int grid = (int)(ntiles < cus ? ntiles : cus);
-    grid = (grid + 7) / 8 * 8;
+    int grid;
+    IISAN_TRY(t256_prepare_launch(attr, (const void*)kern, 2 * S_STAGE_BYTES + 8192 * 4, tiles_m, tiles_n, grid));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 2 * S_STAGE_BYTES + (size_t)a.N * 4 + ((a.debug & 16) ? 8192 : 0), s, a, tiles_m, tiles_n);
     IISAN_LAUNCH_OK();
     return IISAN_OK;

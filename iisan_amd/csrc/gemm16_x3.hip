@@ -20,8 +20,6 @@ namespace {
 constexpr int XBM = 128, XBK = 32;
 constexpr int XTILE = XBM * XBK * 2;          // 8 KiB: an A-operand tile (128 rows x 64 B)
 
-__device__ __forceinline__ int nperm_x(int q) { return (q & ~31) + 8 * ((q & 15) >> 2) + 4 * ((q >> 4) & 1) + (q & 3); }
-
 // NB: 32-column groups per wave — 2: 128 x 128 tiles; 3: 128 x 192 tiles (round 6, second step: the chip holds 2 x CUs = 512 workgroups of this
 // kernel, and the Cached fc products are 88 x 6 = 528 tiles of 128 x 128 — a full round and one of 16 workgroups; as 88 x 4 = 352 tiles of
 // 128 x 192 they are ONE round)
@@ -49,7 +47,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_x3p_kernel(X3pArgs p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) a_off[j] = (int64_t)((2 * wave + j) * 16 + prow) * ld + slog * 16;
 #pragma unroll
-    for (int j = 0; j < NB; ++j) b_off[j] = (int64_t)nperm_x((NB * wave + j) * 16 + prow) * ld + slog * 16;
+    for (int j = 0; j < NB; ++j) b_off[j] = (int64_t)nperm((NB * wave + j) * 16 + prow) * ld + slog * 16;
     const int64_t plane = (int64_t)p.kp * 2;                             // byte offset of the lo plane inside a row
     auto stage = [&](int kt, int buf) {
         char* sa = smem + buf * XSTAGE + (2 * wave) * 1024;
