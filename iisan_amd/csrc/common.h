@@ -211,6 +211,10 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
     const float pdf = 0.39894228040143267794f * __expf(-0.5f * x * x);
     return cdf + x * pdf;
 }
+// The fusion gate of the side network: g = sigmoid(theta / GATE_TEMP), theta a device scalar; and d theta for a given dL/dg
+constexpr float GATE_TEMP = 0.1f;
+__device__ __forceinline__ float gate_of(const float* theta) { return 1.0f / (1.0f + __expf(-theta[0] / GATE_TEMP)); }
+__device__ __forceinline__ float gate_grad(float dg, float g) { return dg * g * (1.f - g) / GATE_TEMP; }
 
 // Counter-based dropout: the keep/scale factor of element `idx` at dropout site `site` is a pure function of
 // (seed, site, idx), so the backward pass regenerates the forward mask instead of storing it.  24-bit uniform from a
@@ -504,15 +508,17 @@ enum {
     G32_TB = 2,        // B stored [K, N] (default [N, K], torch Linear weight)
     G32_RELU = 4,      // C = relu(.)
     G32_GELU = 8,      // C = gelu_erf(.)
-    G32_ACCUM = 16,    // C += (atomicAdd; enables split-K)
+    G32_ACCUM = 16,    // C += ; enables split-K: partials in the executor's scratch + a fixed-order reducer, atomicAdd without scratch
     G32_MUL_RELU_MASK = 32,  // C = (.) * (act_src > 0)
     G32_MUL_GELU_GRAD = 64,  // C = (.) * gelu'(act_src)
-    G32_PREACT = 128,
+    G32_PREACT = 128,  // also store the pre-activation (acc + bias) into act_src (as float* out) -- fwd of the adapters
+    G32_DROPOUT = 256, // scale by the dropout keep factor before the residual add
     G32_HINT_B_EXACT16 = 1024,   // gemm_x3 only: the B operand is probably exact in fp16 (cached taps): its lo plane goes last
-    G32_DROPOUT = 256, // scale by the dropout keep factor before the residual add  // also store the pre-activation into act_src (as float* out) -- fwd of GELU adapters
 };
+// problems per launch: launch_gemm32 (both weight-gradient products of a SANB step x three towers) / K = 64 kernel / n64f / colsum
+constexpr int G32_MAXP = 6, K64_MAXP = 4, N64F_MAXP = 3, COLSUM_MAXP = 4;
 int launch_gemm32(const Gemm32Prob* probs, int nprob, int flags, hipStream_t s);
-// out[i][n] += sum_m X[i][m][n] for up to 4 problems in one launch (gemm32.hip): the bias gradients
+// out[i][n] += sum_m X[i][m][n] for up to COLSUM_MAXP problems in one launch (gemm32.hip): the bias gradients
 int launch_colsum(const float* const* X, float* const* out, const int64_t* M, const int32_t* N, const int32_t* ld,
                   int nprob, hipStream_t s);
 

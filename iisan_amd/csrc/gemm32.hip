@@ -9,9 +9,11 @@
 // 64x64x64 tile per 256-thread workgroup (4 waves, 32x32 each = 2x2 MFMA fragments); operands go HBM -> registers
 // (16-byte loads) -> LDS (66-float rows: conflict-free fragment reads), and the registers of K-tile t+1 are filled
 // while tile t is multiplied (the first version loaded a 16-wide K slice, synchronised, multiplied, synchronised: 48
-// exposed HBM latencies for K = 768 — 80 us for a 1.1-GFLOP product, rocprofv3); up to 4 independent problems per launch
-// (blockIdx.z) so the cv / text / mm towers of the side network go out together; split-K (blockIdx.y) with fp32
-// atomics for the weight-gradient products whose M,N are tiny and K = number of item slots.
+// exposed HBM latencies for K = 768 — 80 us for a 1.1-GFLOP product, rocprofv3); up to G32_MAXP independent problems per
+// launch (blockIdx.z) so the cv / text / mm towers of the side network go out together; split-K (blockIdx.y) for the
+// weight-gradient products whose M,N are tiny and K = number of item slots, and for skinny long-K forward products: split y
+// (split_ktiles) stores its raw partial in the executor's scratch and gemm32_reduce_kernel sums the partials in a fixed order
+// and applies the epilogue; without scratch, "+=" products fall back to fp32 atomics and the others are not split.
 //
 // Tried and dropped (round 2, MI355X): the same K loop on the 16-bit matrix cores with bf16x3 split operands (each fp32
 // fragment element cut into three bf16 pieces by truncation after the LDS read, six MFMA terms, fp32 accumulate — 6/16 of
@@ -32,11 +34,21 @@ __host__ __device__ constexpr int ldt(int rows) { return rows == 16 ? 48 : rows 
 __host__ __device__ constexpr int smem_floats(int rows) { return rows * LD > TK * ldt(rows) ? rows * LD : TK * ldt(rows); }
 typedef float f2v __attribute__((ext_vector_type(2)));
 
-constexpr int G32_MAXP = 6;          // problems per launch (round 6: the two weight-gradient products of a SANB step x three towers share one)
 struct Gemm32Batch {
     Gemm32Prob p[G32_MAXP];
 };
 
+// THE split-K rule: split y of `splits` owns the K-tiles [kt0, kt1) = [y, y + 1) * ceil(ktiles / splits), cut at ktiles.  A split with an
+// empty range writes nothing and the reducer reads only the others' partials (nonempty_splits): the kernels and the host all ask here.
+template <typename T> struct KtRange { T kt0, kt1; };        // T: the caller's index width (int where K is 32-bit)
+template <typename T> __host__ __device__ __forceinline__ KtRange<T> split_ktiles(T ktiles, T splits, T y) {
+    const T per = (ktiles + splits - 1) / splits, kt0 = y * per, kt1 = kt0 + per;
+    return {kt0, kt1 > ktiles ? ktiles : kt1};
+}
+
+// The run-time element chain of the epilogue (RELU -> GELU -> MUL_RELU_MASK -> MUL_GELU_GRAD -> DROPOUT at index m * ldc + n) stands three
+// times and the copies must agree, or a split-K product differs from the unsplit one: both paths of gemm32_kernel and the generic loop of
+// gemm32_reduce_kernel.  One shared function slowed a FAST instantiation in every call form tried (profiles/gemm32_shared.md).
 // A 64 x 64 operand tile travels as 4 x float4 per thread.  Source stored [rows, K] (default): thread -> row
 // (tid>>4)+16i, k (tid&15)*4; `trans` (source stored [K, rows], row index contiguous): k (tid>>4)+16i, rows (tid&15)*4..
 template <int ROWS>
@@ -113,11 +125,10 @@ __global__ __launch_bounds__(256) void gemm32_kernel(Gemm32Batch batch, int epi)
     const int64_t m0 = tile_m * TM;
     const int n0 = tile_n * TN;
 
-    // K range of this split
-    const int64_t ktiles = (p.K + TK - 1) / TK;
-    const int64_t per = (ktiles + gridDim.y - 1) / gridDim.y;
-    const int64_t kbeg = (int64_t)blockIdx.y * per * TK;
-    int64_t kend = kbeg + per * TK;
+    // K range of this split, in elements: its K-tiles, the last tile of the problem ragged
+    const KtRange<int64_t> kr = split_ktiles<int64_t>((p.K + TK - 1) / TK, gridDim.y, blockIdx.y);
+    const int64_t kbeg = kr.kt0 * TK;
+    int64_t kend = kr.kt1 * TK;
     if (kend > p.K) kend = p.K;
     if (kbeg >= kend && blockIdx.y > 0) return;
 
@@ -152,7 +163,7 @@ __global__ __launch_bounds__(256) void gemm32_kernel(Gemm32Batch batch, int epi)
     const int64_t sia = TA ? (int64_t)(256 / TPRA) * p.lda : (int64_t)16 * p.lda, sib = TB ? (int64_t)(256 / TPRB) * p.ldb : (int64_t)16 * p.ldb;
     const int64_t ska = TA ? (int64_t)TK * p.lda : TK, skb = TB ? (int64_t)TK * p.ldb : TK;
     const int64_t last_t = (kend - kbeg - 1) / TK;
-    auto fetch = [&](int slot, int64_t k) {
+    auto fetch = [&](int slot, int64_t k) {         // a whole K-tile: the ring's first DEPTH tiles, and every tile of the generic path
         if constexpr (FAST) {
             // Unconditional: a K-tile past the end re-reads the last one (never staged).  Behind `if (k < kend)` every load
             // was a conditional one, the waitcnt pass lost count at the joins and drained the whole ring before each
@@ -164,14 +175,9 @@ __global__ __launch_bounds__(256) void gemm32_kernel(Gemm32Batch batch, int epi)
             for (int i = 0; i < TM / 16; ++i) ra[slot][i] = *(const f4*)(pa + t * ska + i * sia);
 #pragma unroll
             for (int i = 0; i < 4; ++i) rb[slot][i] = *(const f4*)(pb + t * skb + i * sib);
-            return;
-        }
-        if (k < kend) {
-            if constexpr (FAST) {
-            } else {
-                load_tile<TM>(ra[slot], p.A, p.lda, TA, m0, p.M, k, kend, tid);
-                load_tile<TN>(rb[slot], p.B, p.ldb, TB, n0, p.N, k, kend, tid);
-            }
+        } else if (k < kend) {
+            load_tile<TM>(ra[slot], p.A, p.lda, TA, m0, p.M, k, kend, tid);
+            load_tile<TN>(rb[slot], p.B, p.ldb, TB, n0, p.N, k, kend, tid);
         }
     };
     // FAST only: one of the NP = TM/16 + 4 loads of a K-tile.  Issued back to back ahead of the MFMAs, eight 16-byte loads per
@@ -207,17 +213,19 @@ __global__ __launch_bounds__(256) void gemm32_kernel(Gemm32Batch batch, int epi)
                 __syncthreads();
                 if constexpr (!FAST) fetch(u, k0 + (int64_t)DEPTH * TK);
                 const int ksteps = (kend - k0 >= TK) ? TK / 4 : (int)((kend - k0 + 3) / 4);      // zero-filled tail
+                auto frag = [&](int ks, float (&a)[FM], float (&b)[FN]) {       // the wave's fragments of k-slice ks (rows beyond a ragged tail are zero-filled)
+#pragma unroll
+                    for (int f = 0; f < FM; ++f)
+                        a[f] = TA ? As_[(ks * 4 + fk) * ldt(TM) + wm * 16 * FM + f * 16 + fi] : As_[(wm * 16 * FM + f * 16 + fi) * LD + ks * 4 + fk];
+#pragma unroll
+                    for (int f = 0; f < FN; ++f)
+                        b[f] = TB ? Bs_[(ks * 4 + fk) * ldt(TN) + wn * 16 * FN + f * 16 + fi] : Bs_[(wn * 16 * FN + f * 16 + fi) * LD + ks * 4 + fk];
+                };
                 auto kstep = [&](int ks0) {
 #pragma unroll
                     for (int q = 0; q < KA; ++q) {
-                        const int ks = ks0 + q;               // rows beyond the tail are zero-filled: harmless
                         float a[FM], b[FN];
-#pragma unroll
-                        for (int f = 0; f < FM; ++f)
-                            a[f] = TA ? As_[(ks * 4 + fk) * ldt(TM) + wm * 16 * FM + f * 16 + fi] : As_[(wm * 16 * FM + f * 16 + fi) * LD + ks * 4 + fk];
-#pragma unroll
-                        for (int f = 0; f < FN; ++f)
-                            b[f] = TB ? Bs_[(ks * 4 + fk) * ldt(TN) + wn * 16 * FN + f * 16 + fi] : Bs_[(wn * 16 * FN + f * 16 + fi) * LD + ks * 4 + fk];
+                        frag(ks0 + q, a, b);
 #pragma unroll
                         for (int mf = 0; mf < FM; ++mf)
 #pragma unroll
@@ -230,14 +238,6 @@ __global__ __launch_bounds__(256) void gemm32_kernel(Gemm32Batch batch, int epi)
                     // puts each slice's reads directly in front of its MFMAs behind an lgkmcnt(0) (the LDS latency exposed
                     // TK/4 times per tile); reading the whole tile's fragments up front costs 60 registers and a wave of occupancy
                     float ac[FM], bc[FN];
-                    auto frag = [&](int ks, float (&a)[FM], float (&b)[FN]) {
-#pragma unroll
-                        for (int f = 0; f < FM; ++f)
-                            a[f] = TA ? As_[(ks * 4 + fk) * ldt(TM) + wm * 16 * FM + f * 16 + fi] : As_[(wm * 16 * FM + f * 16 + fi) * LD + ks * 4 + fk];
-#pragma unroll
-                        for (int f = 0; f < FN; ++f)
-                            b[f] = TB ? Bs_[(ks * 4 + fk) * ldt(TN) + wn * 16 * FN + f * 16 + fi] : Bs_[(wn * 16 * FN + f * 16 + fi) * LD + ks * 4 + fk];
-                    };
                     frag(0, ac, bc);
 #pragma unroll
                     for (int ks = 0; ks < TK / 4; ++ks) {
@@ -370,11 +370,8 @@ __global__ __launch_bounds__(256, 2) void gemm32_dw_kernel(Gemm32Batch batch) {
     const int tile_n = (int)(blockIdx.x - tile_m * tiles_n);
     const int64_t m0 = tile_m * 64;
     const int n0 = tile_n * 64;
-    const int64_t ktiles = p.K / TK;
-    const int64_t per = (ktiles + gridDim.y - 1) / gridDim.y;
-    const int64_t kt0 = (int64_t)blockIdx.y * per;
-    int64_t kt1 = kt0 + per;
-    if (kt1 > ktiles) kt1 = ktiles;
+    const KtRange<int64_t> kr = split_ktiles<int64_t>(p.K / TK, gridDim.y, blockIdx.y);
+    const int64_t kt0 = kr.kt0, kt1 = kr.kt1;
     if (kt0 >= kt1) return;                                         // (the reducer knows which splits own rows)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -489,18 +486,16 @@ struct N64FProb {
     const float* a; const float* b; const float* prev; int64_t lda, ldb, ldp; const float* gate; int32_t type;
     float* F; const float* W; int32_t ldw; const float* bias; float* U; float* A; float* P; int64_t pstride; int64_t M; int32_t K;
 };
-struct N64FBatch { N64FProb p[3]; int32_t gelu; int32_t rpw; };      // rpw: rows per workgroup (<= 64; waves whose 16 rows start past it only stage)
+struct N64FBatch { N64FProb p[N64F_MAXP]; int32_t gelu; int32_t rpw; };      // rpw: rows per workgroup (<= 64; waves whose 16 rows start past it only stage)
 
 __global__ __launch_bounds__(256, 2) void gemm32_n64f_kernel(N64FBatch batch) {
     __shared__ __attribute__((aligned(16))) float wl[2][64 * 68];
     const N64FProb& p = batch.p[blockIdx.z];
     const int64_t m0 = (int64_t)blockIdx.x * batch.rpw;
     if (m0 >= p.M) return;
-    const int ktiles = p.K >> 6;
-    const int per = (ktiles + (int)gridDim.y - 1) / (int)gridDim.y;
-    const int kt0 = (int)blockIdx.y * per;
-    int kt1 = kt0 + per;
-    if (kt1 > ktiles) kt1 = ktiles;
+    const int ny = (int)gridDim.y;
+    const KtRange<int> kr = split_ktiles<int>(p.K >> 6, ny, blockIdx.y);
+    const int kt0 = kr.kt0, kt1 = kr.kt1;
     if (kt0 >= kt1) return;
     const int nt = kt1 - kt0;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -511,7 +506,7 @@ __global__ __launch_bounds__(256, 2) void gemm32_n64f_kernel(N64FBatch batch) {
     const bool live = mj < p.M && 16 * wave + j < batch.rpw;
     const bool wave_on = 16 * wave < batch.rpw;                     // (wave-uniform) a wave past the tile only helps staging the weights
     const bool gated = p.gate != nullptr;
-    const float gv = gated ? 1.0f / (1.0f + __expf(-p.gate[0] / 0.1f)) : 1.0f;
+    const float gv = gated ? gate_of(p.gate) : 1.0f;
     const float ca = gated ? gv : 1.f, cb = gated ? 1.f - gv : 1.f;
     const bool has_b = p.type == 1;
     const float cp = p.prev ? (p.type == 0 ? cb : 1.f) : 0.f;
@@ -617,11 +612,11 @@ __global__ __launch_bounds__(256, 2) void gemm32_n64f_kernel(N64FBatch batch) {
 struct K64Prob {
     const float* A; const float* W; const float* bias; const float* resid; float* C; int64_t M; int32_t N, lda, ldw, ldc, ldr;
     // GATE variant (the dF product of a gated SANB step with the fusion's backward folded in, launch_gemm32_k64_gate):
-    //   dF = acc + resid;   dtheta += <dF, ga - go> g (1 - g) / 0.1   (go null: zeros);   C = dF * (scale_prev ? 1 - g : 1), if store
+    //   dF = acc + resid;   dtheta += gate_grad(<dF, ga - go>, g)   (go null: zeros);   C = dF * (scale_prev ? 1 - g : 1), if store
     const float* gate; const float* ga; const float* go; int64_t ldga, ldgo; float* dgate; int32_t scale_prev, store;
     float* d2; int64_t ldd2; int32_t d2_is_b;      // optional second output  d2 = (d2_is_b ? 1 - g : g) · dF  (Versa: gradient wrt the dim-aligned tap)
 };
-struct K64Batch { K64Prob p[4]; };
+struct K64Batch { K64Prob p[K64_MAXP]; };
 
 template <bool TBV, bool GATE = false>
 __global__ __launch_bounds__(256, 2) void gemm32_k64_kernel(K64Batch batch, int nblk) {
@@ -660,7 +655,7 @@ __global__ __launch_bounds__(256, 2) void gemm32_k64_kernel(K64Batch batch, int 
     }
     const bool has_r = p.resid != nullptr, has_b = p.bias != nullptr;
     float gpart = 0.f, gval = 0.f;
-    if constexpr (GATE) gval = 1.0f / (1.0f + __expf(-p.gate[0] / 0.1f));
+    if constexpr (GATE) gval = gate_of(p.gate);
     const float cdp = (GATE && p.scale_prev) ? 1.f - gval : 1.f;
     const float cgo = (GATE && p.go) ? 1.f : 0.f;
     const float cd2 = GATE ? (p.d2_is_b ? 1.f - gval : gval) : 0.f;
@@ -758,16 +753,16 @@ __global__ __launch_bounds__(256, 2) void gemm32_k64_kernel(K64Batch batch, int 
         gpart = wave_sum(gpart);
         if (lane == 0) gred[wave] = gpart;
         __syncthreads();
-        if (tid == 0) atomicAdd(p.dgate, ((gred[0] + gred[1]) + (gred[2] + gred[3])) * gval * (1.f - gval) / 0.1f);
+        if (tid == 0) atomicAdd(p.dgate, gate_grad((gred[0] + gred[1]) + (gred[2] + gred[3]), gval));
     }
 }
 
-// column sums: out[n] += sum_m X[m][n]  (bias gradients); up to 4 problems per launch
+// column sums: out[n] += sum_m X[m][n]  (bias gradients); up to COLSUM_MAXP problems per launch
 struct ColsumBatch {
-    const float* X[4];
-    float* out[4];
-    int64_t M[4];
-    int32_t N[4], ld[4];
+    const float* X[COLSUM_MAXP];
+    float* out[COLSUM_MAXP];
+    int64_t M[COLSUM_MAXP];
+    int32_t N[COLSUM_MAXP], ld[COLSUM_MAXP];
 };
 __global__ __launch_bounds__(256) void colsum_kernel(ColsumBatch b, int rows_per_block) {
     __shared__ float part[4][64];
@@ -881,9 +876,12 @@ constexpr int (*g_tiled[8])(const Gemm32Batch&, dim3, int, int, bool, bool, hipS
     launch_flags<0>, launch_flags<G32_TA>, launch_flags<G32_TB>, launch_flags<G32_TA | G32_TB>,
     launch_flags<G32_ACCUM>, launch_flags<G32_TA | G32_ACCUM>, launch_flags<G32_TB | G32_ACCUM>, launch_flags<G32_TA | G32_TB | G32_ACCUM>};
 
-// The K-splits that own a non-empty K range: the kernels give split y the K-tiles [y, y + 1) * ceil(ktiles / splits) and a split whose
-// range is empty writes nothing — its partial would be read uninitialised by the reducer.
-int nonempty_splits(int64_t ktiles, int splits) { return (int)ceil_div(ktiles, ceil_div(ktiles, (int64_t)splits)); }
+// The K-splits that own a non-empty K range (split_ktiles: the leading ones); the partial of an empty one would be read uninitialised
+int nonempty_splits(int64_t ktiles, int splits) {
+    int n = 0;
+    while (n < splits && split_ktiles<int64_t>(ktiles, splits, n).kt0 < split_ktiles<int64_t>(ktiles, splits, n).kt1) ++n;
+    return n;
+}
 
 // Split-K partials -> C.  The caller has filled rb.p (the problem as the reducer sees it: C, bias, residual, act_src), rb.P, rb.stride
 // and rb.cs; `splitk` is the launch's split count (a problem with a shorter K than its launch mates owns fewer of them).
@@ -918,7 +916,7 @@ void gemm32_set_scratch(float* ws, size_t floats) { g_scratch = ws; g_scratch_fl
 static int g_use_n64f = 1;
 IISAN_DEV_KNOB(gemm32_n64f, g_use_n64f);
 bool gemm32_n64f_ok(const N64FDesc* d, int n) {
-    if (!g_use_n64f || n < 1 || n > 3) return false;
+    if (!g_use_n64f || n < 1 || n > N64F_MAXP) return false;
     for (int i = 0; i < n; ++i) {
         const N64FDesc& q = d[i];
         const FuseOperands& f = q.f;
@@ -1021,10 +1019,27 @@ static void fill_k64(K64Batch& kb, const Gemm32Prob* probs, int nprob) {
         k.lda = q.lda; k.ldw = q.ldb; k.ldc = q.ldc; k.ldr = q.ldr;
     }
 }
+// The one launch of gemm32_k64_kernel: W stored [64, N] (tb) or [N, 64]; gate: the gate-fused epilogue (W [64, N] only).
+static int launch_k64(const K64Batch& kb, const K64Grid& g, int nprob, bool tb, bool gate, hipStream_t s) {
+    // dynamic LDS = the W slice.  The [N, 64] layout stages 64 nblk rows of 68 floats, the [64, N] layout 64 rows of 64 nblk + 4: four
+    // pad floats per 64 against four per 64 nblk — the first is never the smaller, and the plain route launches both layouts with it
+    const size_t lds = (gate ? (size_t)64 * (64 * g.nblk + 4) : (size_t)64 * g.nblk * 68) * sizeof(float);
+    static OncePerDevice attr;
+    if (attr.first())
+        for (const void* k : {(const void*)gemm32_k64_kernel<false>, (const void*)gemm32_k64_kernel<true>, (const void*)gemm32_k64_kernel<true, true>})
+            IISAN_HIP_OK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 68 * 4));
+    ++g_cnt_k64;
+    const dim3 grid((unsigned)g.rt, (unsigned)g.ny, (unsigned)nprob);
+    if (gate) hipLaunchKernelGGL((gemm32_k64_kernel<true, true>), grid, dim3(256), lds, s, kb, g.nblk);
+    else if (tb) hipLaunchKernelGGL(gemm32_k64_kernel<true>, grid, dim3(256), lds, s, kb, g.nblk);
+    else hipLaunchKernelGGL(gemm32_k64_kernel<false>, grid, dim3(256), lds, s, kb, g.nblk);
+    IISAN_LAUNCH_OK();
+    return IISAN_OK;
+}
 static int g_use_k64_gate = 1;
 IISAN_DEV_KNOB(gemm32_k64_gate, g_use_k64_gate);
 bool gemm32_k64_gate_ok(const Gemm32Prob* probs, const K64Gate* gates, int nprob) {
-    if (!g_use_k64 || !g_use_k64_gate || nprob < 1 || nprob > 4) return false;
+    if (!g_use_k64 || !g_use_k64_gate || nprob < 1 || nprob > K64_MAXP) return false;
     for (int i = 0; i < nprob; ++i) {
         const K64Gate& g = gates[i];
         if (!k64_shape_ok(probs[i]) || !probs[i].resid || !g.gate || !g.ga || !g.dgate || (g.ldga & 3) || (g.go && (g.ldgo & 3)) || (g.d2 && ((g.ldd2 & 3) || ((uintptr_t)g.d2 & 15))) ||
@@ -1048,15 +1063,7 @@ static int launch_gemm32_k64_gate_impl(const Gemm32Prob* probs, const K64Gate* g
     }
     const K64Grid g = k64_grid(probs, nprob);
     IISAN_CHECK_SHAPE(g.rt < (1ll << 31), "gemm32: grid too large");
-    const dim3 grid((unsigned)g.rt, (unsigned)g.ny, (unsigned)nprob);
-    const size_t lds = (size_t)64 * (64 * g.nblk + 4) * sizeof(float);
-    static OncePerDevice attr;
-    if (attr.first())
-        IISAN_HIP_OK(hipFuncSetAttribute((const void*)gemm32_k64_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 68 * 4));
-    ++g_cnt_k64;
-    hipLaunchKernelGGL((gemm32_k64_kernel<true, true>), grid, dim3(256), lds, s, kb, g.nblk);
-    IISAN_LAUNCH_OK();
-    return IISAN_OK;
+    return launch_k64(kb, g, nprob, true, true, s);
 }
 
 // ---- launch_gemm32: plan, then run ---------------------------------------------------------------------------------------------
@@ -1115,7 +1122,7 @@ static Gemm32Plan plan_gemm32(const Gemm32Prob* probs, int nprob, int flags, siz
         // towers and [1408, 1024] x [1024 -> 1024] for the inter-modal one) used to go to the tiled kernel as a whole — one K-tile per
         // workgroup for the K = 64 members: 68.6 us for 46 MB of output (round 6).  The K = 64 members get their own launch.
         if (nk64 > 0 && nk64 < nprob) { pl.kernel = G32K_SPLIT_K64; pl.nk64 = nk64; return pl; }
-        if (nk64 == nprob && nprob <= 4) {       // (K64Batch holds four)
+        if (nk64 == nprob && nprob <= K64_MAXP) {
             const K64Grid g = k64_grid(probs, nprob);
             if (g.rt >= (1ll << 31)) { iisan_set_error("gemm32: grid too large"); return pl; }
             pl.kernel = G32K_K64; pl.nblk = g.nblk; pl.gx = g.rt; pl.gy = g.ny; pl.gz = nprob;
@@ -1220,19 +1227,7 @@ static int launch_gemm32_impl(const Gemm32Prob* probs, int nprob, int flags, hip
     if (pl.kernel == G32K_K64) {
         K64Batch kb{};
         fill_k64(kb, probs, nprob);
-        // the [N, 64] layout stages 64 nblk rows of 68 floats, the [64, N] layout 64 rows of 64 nblk + 4: four pad floats per 64
-        // against four per 64 nblk — the first is never the smaller, and both instantiations are launched with it
-        const size_t lds = (size_t)64 * pl.nblk * 68 * sizeof(float);
-        static OncePerDevice attr;
-        if (attr.first()) {
-            IISAN_HIP_OK(hipFuncSetAttribute((const void*)gemm32_k64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 68 * 4));
-            IISAN_HIP_OK(hipFuncSetAttribute((const void*)gemm32_k64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 68 * 4));
-        }
-        ++g_cnt_k64;
-        if (flags & G32_TB) hipLaunchKernelGGL(gemm32_k64_kernel<true>, grid, dim3(256), lds, s, kb, pl.nblk);
-        else hipLaunchKernelGGL(gemm32_k64_kernel<false>, grid, dim3(256), lds, s, kb, pl.nblk);
-        IISAN_LAUNCH_OK();
-        return IISAN_OK;
+        return launch_k64(kb, K64Grid{pl.gx, pl.nblk, pl.gy}, nprob, (flags & G32_TB) != 0, false, s);
     }
     // place the partials: split y of problem i writes its raw product at C + y * ksplit_stride of the scratch
     Gemm32Batch b{};
@@ -1262,7 +1257,8 @@ static int launch_gemm32_impl(const Gemm32Prob* probs, int nprob, int flags, hip
         int n = 0;
         for (int i = 0; i < nprob; ++i)
             if (probs[i].colsum_a) { X[n] = probs[i].A; O[n] = probs[i].colsum_a; Ms[n] = probs[i].K; Ns[n] = (int32_t)probs[i].M; lds[n] = probs[i].lda; ++n; }
-        for (int i = 0; i < n; i += 4) IISAN_TRY(launch_colsum(X + i, O + i, Ms + i, Ns + i, lds + i, n - i < 4 ? n - i : 4, s));
+        for (int i = 0; i < n; i += COLSUM_MAXP)
+            IISAN_TRY(launch_colsum(X + i, O + i, Ms + i, Ns + i, lds + i, n - i < COLSUM_MAXP ? n - i : COLSUM_MAXP, s));
     }
     if (pl.scratch == G32S_NONE) return IISAN_OK;
     ReduceBatch rb{};
@@ -1331,7 +1327,7 @@ int launch_gemm32_k64_gate(const Gemm32Prob* probs, const K64Gate* gates, int np
 
 int launch_colsum(const float* const* X, float* const* out, const int64_t* M, const int32_t* N, const int32_t* ld,
                   int nprob, hipStream_t s) {
-    IISAN_CHECK_SHAPE(nprob >= 1 && nprob <= 4, "colsum: 1..4 problems per launch");
+    IISAN_CHECK_SHAPE(nprob >= 1 && nprob <= COLSUM_MAXP, "colsum: 1..%d problems per launch", COLSUM_MAXP);
     ColsumBatch b{};
     int64_t maxM = 0;
     int maxN = 0;

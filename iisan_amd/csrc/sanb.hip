@@ -26,7 +26,6 @@ constexpr int RD = 64;             // adapter bottleneck (cfg->down)
 constexpr int UST = RD + 4;        // LDS row stride of the [16, 64] buffer: 16-byte aligned rows, 4 banks apart
 constexpr int NT = 256;            // threads per workgroup (4 waves), three workgroups per CU (LDS: 3 x 53.5 KB)
 
-__device__ __forceinline__ float gate_of(const float* theta) { return 1.0f / (1.0f + __expf(-theta[0] / 0.1f)); }
 __device__ __forceinline__ f4 mfma16(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 // v_mfma_f32_16x16x4_f32: lane l holds A[i = l&15][k = l>>4], B[k = l>>4][j = l&15]; C/D register r = row 4*(l>>4)+r, column l&15
 
@@ -356,7 +355,7 @@ __global__ __launch_bounds__(NT, 3) void sanb_bwd_kernel(SanbArgs args) {
         gate_part = wave_sum(gate_part);
         if (lane == 0) red[wave] = gate_part;
         __syncthreads();
-        if (tid == 0) atomicAdd(t.dgate, (red[0] + red[1] + red[2] + red[3]) * g * (1.f - g) / 0.1f);
+        if (tid == 0) atomicAdd(t.dgate, gate_grad(red[0] + red[1] + red[2] + red[3], g));
     }
 }
 

@@ -36,8 +36,6 @@ struct FuseArgs {
     int64_t M;
 };
 
-__device__ __forceinline__ float gate_of(const float* theta) { return 1.0f / (1.0f + __expf(-theta[0] / 0.1f)); }
-
 __global__ __launch_bounds__(256) void fuse_fwd_kernel(FuseArgs args) {
     const FuseTower& t = args.t[blockIdx.y];
     const int d4 = t.D / 4;
@@ -121,7 +119,7 @@ __global__ __launch_bounds__(256) void fuse_bwd_kernel(FuseArgs args) {
     part = wave_sum(part);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(t.dgate, (red[0] + red[1] + red[2] + red[3]) * g * (1.f - g) / 0.1f);
+    if (threadIdx.x == 0) atomicAdd(t.dgate, gate_grad(red[0] + red[1] + red[2] + red[3], g));
 }
 
 // ---- static description of one configuration -----------------------------------------------------------------
@@ -345,8 +343,8 @@ int gemm_group(const Gemm32Prob* pr, int n, int flags, const SideBufs& b, hipStr
             } else ++i;
         }
     }
-    for (int i = 0; i < nr; i += 4)          // (a launch takes four problems: Gemm32Batch)
-        IISAN_TRY(launch_gemm32(rest + i, nr - i < 4 ? nr - i : 4, flags & ~G32_HINT_B_EXACT16, s));
+    for (int i = 0; i < nr; i += K64_MAXP)   // (not G32_MAXP: a chunk that turns out all K = 64 must fit K64Batch)
+        IISAN_TRY(launch_gemm32(rest + i, nr - i < K64_MAXP ? nr - i : K64_MAXP, flags & ~G32_HINT_B_EXACT16, s));
     return IISAN_OK;
 }
 

@@ -62,6 +62,10 @@ def test_gemm32_vs_torch(lib, case):
     ref = (A.t() if ta else A).double() @ (B if tb else B.t()).double()
     Ad, Bd, bd = A.cuda(), B.cuda(), bias.cuda()
     C = torch.empty(M, N, device="cuda")
+    # the plain product (no bias, no ReLU, no accumulate) in every layout: the only run of A stored [K, M] with B stored [N, K]
+    _lib.check(lib.iisan_gemm32(Ad.data_ptr(), Bd.data_ptr(), None, C.data_ptr(), M, N, K, ta, tb, 0, 0, _stream()), "gemm32 plain")
+    torch.cuda.synchronize()
+    _close(C, ref, 1e-5, 1e-5, f"gemm32 plain, layout ta={ta} tb={tb} {case}")
     if not ta:
         _lib.check(lib.iisan_gemm32(Ad.data_ptr(), Bd.data_ptr(), bd.data_ptr(), C.data_ptr(), M, N, K, ta, tb, 1, 0, _stream()), "gemm32")
         torch.cuda.synchronize()
