@@ -226,7 +226,9 @@ __global__ __launch_bounds__(256, 2) void attention16_kernel(const typename T::e
 // softmax statistics by wave shuffles), phase 2 lanes over (4 keys x 16 four-dim groups) streaming V rows.
 // HBM-bound: reads K and V once (2 * S * 128 B per pair).  P is rounded to the 16-bit operand type before the PV
 // product and the sum uses the unrounded values, as in the MFMA kernel above.
-template <typename T>
+// SROW = length of a wave's score row in LDS: 256 (S <= 256: the towers at 224 pixels / short titles) or 1024 (256 < S <= 1024) — the same
+// arithmetic in the same order, a lane sums SROW / 64 probabilities before the wave reduction.
+template <typename T, int SROW>
 __global__ __launch_bounds__(256) void attention_cls_kernel(const typename T::elem* __restrict__ qkv,
                                                             const float* __restrict__ key_bias,
                                                             typename T::elem* __restrict__ ctx, int64_t pairs, int S, int heads,
@@ -234,7 +236,7 @@ __global__ __launch_bounds__(256) void attention_cls_kernel(const typename T::el
     typedef typename T::elem E;
     typedef typename T::v8 V8;
     typedef typename T::v4 V4;
-    __shared__ float sP[4][256];
+    __shared__ float sP[4][SROW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t pair = (int64_t)blockIdx.x * 4 + wave;
     if (pair >= pairs) return;
@@ -280,7 +282,7 @@ __global__ __launch_bounds__(256) void attention_cls_kernel(const typename T::el
             a += __shfl_xor(a, 4, 64);
             if (key >= S) a = -INFINITY;
             else if (kbv[u] < 0.f) a = MASK_RAW;
-            if (kc == 0 && key < 256) sP[wave][key] = a;
+            if (kc == 0 && key < SROW) sP[wave][key] = a;
             mx = fmaxf(mx, a);
         }
     }
@@ -290,7 +292,7 @@ __global__ __launch_bounds__(256) void attention_cls_kernel(const typename T::el
     const float c2 = 0.18033688011112042f;
     float sum = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < SROW / 64; ++i) {
         const int key = lane + 64 * i;
         const float a = key < S ? sP[wave][key] : -INFINITY;
         const float p = __builtin_amdgcn_exp2f((a - mx) * c2);      // -inf -> 0 for the structural pad keys
@@ -372,6 +374,9 @@ int launch_attention16(int dtype16, const void* qkv, const float* key_bias, void
     IISAN_CHECK_SHAPE(items > 0 && S > 0 && heads > 0, "attention16: empty problem");
     IISAN_CHECK_SHAPE(items * heads < (1ll << 31), "attention16: grid too large");
     IISAN_CHECK_SHAPE((int64_t)S * heads * 64 < (1ll << 31), "attention16: item of %d x %d elements too large", S, heads * 64);
+    IISAN_CHECK_SHAPE(S <= 1024, "attention16: sequence length %d > 1024 not supported", S);
+    // past the last rung of the tile ladder (14 key tiles): the streaming-softmax kernel, whose working set does not grow with S (attn16_long.hip)
+    if (S > 224) return launch_attention16_long(dtype16, qkv, key_bias, ctx, items, S, heads, s);
     // ViT (no key_bias, 13 key tiles): K / V staged by LDS-DMA, V read transposed (attn16_dma.hip; dev switch attn_route)
     if (attention16_dma_routed(key_bias, S)) return launch_attention16_dma(dtype16, qkv, ctx, items, S, heads, s);
     return dtype16 == IISAN_BF16 ? launch_t<BF16>(qkv, key_bias, ctx, items, S, heads, s)
@@ -380,13 +385,17 @@ int launch_attention16(int dtype16, const void* qkv, const float* key_bias, void
 
 int launch_attention_cls16(int dtype16, const void* qkv, const float* key_bias, void* ctx_cls, int64_t items, int S, int heads,
                            hipStream_t s, const void* q_cls) {
-    IISAN_CHECK_SHAPE(items > 0 && S > 0 && S <= 256 && heads > 0, "attention_cls16: unsupported problem (S=%d)", S);
+    IISAN_CHECK_SHAPE(items > 0 && S > 0 && heads > 0, "attention_cls16: unsupported problem (S=%d)", S);
+    IISAN_CHECK_SHAPE(S <= 1024, "attention_cls16: sequence length %d > 1024 not supported", S);
     const int64_t pairs = items * heads;
+    IISAN_CHECK_SHAPE(ceil_div(pairs, 4) < (1ll << 31), "attention_cls16: grid too large");
     dim3 grid((unsigned)ceil_div(pairs, 4)), block(256);
-    if (dtype16 == IISAN_BF16)
-        hipLaunchKernelGGL(attention_cls_kernel<BF16>, grid, block, 0, s, (const __bf16*)qkv, key_bias, (__bf16*)ctx_cls, pairs, S, heads, (const __bf16*)q_cls);
-    else
-        hipLaunchKernelGGL(attention_cls_kernel<F16>, grid, block, 0, s, (const _Float16*)qkv, key_bias, (_Float16*)ctx_cls, pairs, S, heads, (const _Float16*)q_cls);
+    // a score row of 256 keys as before, or of 1,024 (16 KB of LDS per workgroup instead of 4)
+#define IISAN_CLS_CASE(T, E, SROW) \
+    hipLaunchKernelGGL((attention_cls_kernel<T, SROW>), grid, block, 0, s, (const E*)qkv, key_bias, (E*)ctx_cls, pairs, S, heads, (const E*)q_cls)
+    if (dtype16 == IISAN_BF16) { if (S <= 256) IISAN_CLS_CASE(BF16, __bf16, 256); else IISAN_CLS_CASE(BF16, __bf16, 1024); }
+    else { if (S <= 256) IISAN_CLS_CASE(F16, _Float16, 256); else IISAN_CLS_CASE(F16, _Float16, 1024); }
+#undef IISAN_CLS_CASE
     IISAN_LAUNCH_OK();
     return IISAN_OK;
 }

@@ -1,5 +1,6 @@
 // The per-block arithmetic the three MFMA attention kernels share (device only):
-//   attention16_kernel (attn16.hip), attention16_dma_kernel (attn16_dma.hip), attention16_drop_kernel (bert_drop.hip).
+//   attention16_kernel (attn16.hip), attention16_dma_kernel (attn16_dma.hip), attention16_drop_kernel (bert_drop.hip);
+//   attention16_long_kernel (attn16_long.hip) runs the same pieces per 128-key chunk, with the chunk form of the row softmax it defines.
 // A block = 16 queries of one (item, head) in one wave.  Scores are computed TRANSPOSED, S^T = K · Q^T, on v_mfma_f32_16x16x32: a lane
 // (j = lane & 15, g = lane >> 4) holds, for ONE query j, keys 16 t + 4 g + r of score tile t in sc[t][r] — so the softmax row reduction is a
 // per-lane loop plus two xor-shuffles (16, 32), and the exponentiated registers are ALREADY in B-operand layout for O^T = V^T · P^T.

@@ -393,6 +393,8 @@ int launch_stream_stats_finalize(const float* rowpart, int nslots, int64_t Mpad,
                                  int64_t items, int Ttok, hipStream_t s, bool x16_blk32 = false);     // x16_blk32: the stream is block-major
 int launch_attention16(int dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int S,
                        int heads, hipStream_t s);
+// attn16_long.hip: streaming softmax over 128-key chunks, any 1 <= S <= 1024; launch_attention16 sends 224 < S <= 1024 there
+int launch_attention16_long(int dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int S, int heads, hipStream_t s);
 // attn16_dma.hip: the ViT shape (no key_bias, 192 < S <= 208) with K / V staged by LDS-DMA; `routed` = launch_attention16 sends this
 // problem there under the dev switch attn_route
 bool attention16_dma_routed(const float* key_bias, int S);

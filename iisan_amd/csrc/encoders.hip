@@ -441,7 +441,8 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
     const int D = w->hidden, F = w->mlp, P = (w->image / w->patch) * (w->image / w->patch), T = P + 1;
     const int pd = w->channels * w->patch * w->patch;
     IISAN_CHECK_SHAPE(pd % 64 == 0, "vit: patch vector length %d must be a multiple of 64", pd);
-    IISAN_CHECK_SHAPE(T <= 224, "vit: %d tokens per image > 224 not supported", T);
+    // (past 224 tokens the attention steps run the streaming-softmax kernel, attn16_long.hip; everything else takes T as it comes)
+    IISAN_CHECK_SHAPE(T <= 1024, "vit: %d tokens per image > 1024 not supported", T);
     const int64_t Mc = (chunk_items > 0 && chunk_items < M) ? chunk_items : M;
     WsCarver c(ws, ws_bytes);
     EncBufs b;
@@ -539,7 +540,11 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
     const uint64_t seed = dropping ? drop->seed : 0;
     IISAN_CHECK_SHAPE(M > 0, "bert_forward_taps: M must be positive");
     IISAN_TRY(check_common(w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
-    IISAN_CHECK_SHAPE(words >= 1 && words <= w->max_pos && words <= 224, "bert: %d words unsupported", words);
+    IISAN_CHECK_SHAPE(words >= 1 && words <= w->max_pos && words <= 1024, "bert: %d words unsupported (at most max_pos = %d positions, and 1024)", words,
+                      w->max_pos);
+    // ... and the train-mode attention kernel keeps a whole head in LDS (bert_drop.hip): refused here, before any launch, never a silent fall-back
+    IISAN_CHECK_SHAPE(!(dropping && words > 224), "bert dropout: no train-mode attention kernel past 224 words, titles of %d words run in eval mode only "
+                      "(drop == NULL or both probabilities 0)", words);
     const int D = w->hidden, F = w->mlp, T = words;
     const int64_t Mc = (chunk_items > 0 && chunk_items < M) ? chunk_items : M;
     WsCarver c(ws, ws_bytes);

@@ -362,11 +362,18 @@ int iisan_layernorm(int32_t dtype16, const float* x, const float* g, const float
                     void* out16, float* out32, int64_t rows, int32_t width, void* stream);
 /* softmax(QK^T/sqrt(64) + key_bias)V per (item, head); qkv 16-bit HEAD-MAJOR [items, H, 3 (q|k|v), S, 64] (what the QKV
  * GEMM epilogue of the encoders writes); ctx 16-bit token-major [items*S, H*64];
- * key_bias fp32 [items,S] or NULL (values < 0 mark masked keys) */
+ * key_bias fp32 [items,S] or NULL (values < 0 mark masked keys).
+ * 1 <= S <= 1024: up to 224 tokens a whole head's K and V sit in LDS (csrc/attn16.hip, attn16_dma.hip); 224 < S <= 1024 runs the
+ * streaming-softmax kernel below.  S > 1024: IISAN_EBADSHAPE, nothing launched. */
 int iisan_attention16(int32_t dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int32_t S,
                       int32_t heads, void* stream);
+/* the same arithmetic by the streaming-softmax kernel (csrc/attn16_long.hip: keys in chunks of 128, running maximum / sum / context per
+ * query row) at ANY 1 <= S <= 1024 — what iisan_attention16 launches past 224 tokens, reachable below that for tests and timing */
+int iisan_attention16_long(int32_t dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int32_t S,
+                           int32_t heads, void* stream);
 /* the same for the CLS query (token 0) of every item only: ctx_cls 16-bit [items, H*64].  Used by the encoder executors
- * in the last live block, where only `hidden_states[i][:, 0]` is consumed (Code_Uncached/model/model.py:210-213) */
+ * in the last live block, where only `hidden_states[i][:, 0]` is consumed (Code_Uncached/model/model.py:210-213).
+ * 1 <= S <= 1024 (a score row of 256 keys per wave up to S = 256, of 1,024 beyond); S > 1024: IISAN_EBADSHAPE, nothing launched. */
 int iisan_attention_cls16(int32_t dtype16, const void* qkv, const float* key_bias, void* ctx_cls, int64_t items,
                           int32_t S, int32_t heads, void* stream);
 /* iisan_attention16 (cls_only == 0) / iisan_attention_cls16 (cls_only != 0; the query is token 0 of the q block) with the
