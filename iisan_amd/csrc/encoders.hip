@@ -174,10 +174,13 @@ int max_tap(const int32_t* tap_layers, int n) {
 }
 
 int check_common(int hidden, int layers, int heads, int mlp, int n_taps, const int32_t* tap_layers) {
-    // the widths the row kernels are instantiated at (rowops.hip): ViT-B / BERT-base and ViT-L / BERT-large
-    IISAN_CHECK_SHAPE(hidden == 768 || hidden == 1024, "encoder hidden size %d not supported: the supported widths are 768 (12 heads) "
-                      "and 1024 (16 heads)", hidden);
-    IISAN_CHECK_SHAPE(heads > 0 && hidden == heads * 64, "encoder head_dim must be 64 (hidden %d, heads %d; supported: 768 / 12 and 1024 / 16)", hidden, heads);
+    // the widths the row kernels are instantiated at (rowops.hip): ViT-B / BERT-base, ViT-L / BERT-large, and the narrow towers — BERT-tiny
+    // (128), ViT-tiny (192), BERT-mini (256), ViT-small (384)
+    IISAN_CHECK_SHAPE(hidden == 768 || hidden == 1024 || hidden == 128 || hidden == 192 || hidden == 256 || hidden == 384,
+                      "encoder hidden size %d not supported: the supported widths are 768 (12 heads) and 1024 (16 heads), "
+                      "and 128, 192, 256, 384 (2, 3, 4, 6 heads)", hidden);
+    IISAN_CHECK_SHAPE(heads > 0 && hidden == heads * 64, "encoder head_dim must be 64 (hidden %d, heads %d; supported: 768 / 12 and 1024 / 16, "
+                      "128 / 2, 192 / 3, 256 / 4, 384 / 6)", hidden, heads);
     IISAN_CHECK_SHAPE(layers >= 1 && layers <= IISAN_MAX_LAYERS, "encoder layers %d out of range", layers);
     IISAN_CHECK_SHAPE(mlp % 128 == 0, "encoder mlp size %d must be a multiple of 128", mlp);
     IISAN_CHECK_SHAPE(n_taps >= 1 && tap_layers, "need at least one tap layer");
@@ -192,8 +195,8 @@ IISAN_DEV_KNOB(full_blocks, g_full_blocks);
 IISAN_DEV_KNOB(resid32, g_resid32);
 IISAN_DEV_KNOB(ln_fold, g_ln_fold);
 IISAN_DEV_KNOB(blk32, g_blk32);
-// (the LayerNorm-folded routes — fold_ln_weights, the stream statistics, the block-major stream — are 768 wide: a 1024-wide tower runs
-//  on the LayerNorm-image route whatever ln_fold says, and asks for no folded set)
+// (the LayerNorm-folded routes — fold_ln_weights, the stream statistics, the block-major stream — are 768 wide: a 1024-wide tower and the
+//  narrow ones (128 - 384) run on the LayerNorm-image route whatever ln_fold says, and ask for no folded set)
 static int vit_fold_layers(const iisan_vit_weights* w) {
     return (!g_resid32 && g_ln_fold && w->dtype16 == IISAN_F16 && w->hidden == 768) ? w->layers : 0;
 }
@@ -256,7 +259,7 @@ enum VitStrategy {
 // residual adds in the epilogues of the O / FC2 products likewise — for every chunk size of this call (the last chunk may be shorter)
 VitStrategy vit_strategy(const iisan_vit_weights* w, const EncBufs& b, int live, bool full_blocks, int64_t M, int64_t Mc, int T) {
     if (g_resid32) return VS_RESID32;
-    if (!b.Wf || live == 0 || w->hidden != 768) return VS_IMAGE;       // (hidden 1024: b.Wf is null already — vit_fold_layers)
+    if (!b.Wf || live == 0 || w->hidden != 768) return VS_IMAGE;       // (any other width: b.Wf is null already — vit_fold_layers)
     const int dt = w->dtype16, D = w->hidden, F = w->mlp;
     bool fold = true, stream = g_ln_fold >= 2;
     for (int64_t mc : {Mc, M % Mc == 0 ? Mc : M % Mc}) {
@@ -533,7 +536,7 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
     const bool dropping = drop && (drop->hidden_p > 0.f || drop->attn_p > 0.f);
     // never a silent fall-back to eval mode: the row kernels have train-mode instantiations for the mixed stream only
     IISAN_CHECK_SHAPE(!(dropping && g_resid32), "bert dropout: no train-mode instantiation for the fp32 residual stream of the dev switch resid32 = 1");
-    // ... and for 768-wide rows only (rowops.hip): tap caches of the wide towers are built in eval mode
+    // ... and for 768-wide rows only (rowops.hip): tap caches of the wide and the narrow towers are built in eval mode
     IISAN_CHECK_SHAPE(!(dropping && w->hidden != 768), "bert dropout: no train-mode instantiation at this width, hidden size %d runs in eval mode only "
                       "(drop == NULL or both probabilities 0)", w->hidden);
     const float hp = dropping ? drop->hidden_p : 0.f, ap = dropping ? drop->attn_p : 0.f;

@@ -20,9 +20,16 @@ namespace {
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_BYTES = BM * BK * 2;       // 16 KiB per operand tile
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;   // A + W
+constexpr int RAG_N_END = 768;                // a ragged last column tile (N % 128 == 64) is served below this N (gemm16_route)
 
-template <typename T, int EPI>
+// RAG: N % 128 == 64 — the last column tile holds 64 live columns (the 192- and 576-column products of a 192-wide tower).  Its upper 64
+// W rows do not exist and the weights may END there: the staging address of such a row is clamped to the last row of W (as attn16_dma.hip
+// clamps its pad rows), so nothing is read past the allocation and the slots those lanes fill are never multiplied.  wave_n == 1 owns the
+// dead columns: it stages and meets every barrier, skips its MFMAs (a wave-uniform branch), reads no bias and stores nothing.  A template
+// flag, so that the whole-tile instantiations keep their instruction streams (profiles/narrow_towers.md).
+template <typename T, int EPI, bool RAG = false>
 __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
+    static_assert(!RAG || EPI != EPI_F32, "EPI_F32 has its own ragged tile: its W image is padded to whole tiles");
     typedef typename T::v8 V8;
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE_BYTES];
 
@@ -49,7 +56,9 @@ __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
         for (int j = 0; j < 4; ++j) {
             const int q = (wave * 4 + j) * 8 + (lane >> 3);
             a_off[j] = (int64_t)q * p.lda * 2 + slog * 16;
-            w_off[j] = (int64_t)nperm(q) * p.ldw * 2 + slog * 16;
+            int wq = nperm(q);
+            if constexpr (RAG) wq = n0 + wq < p.N ? wq : p.N - 1 - n0;       // a row past the end of W: read its last row instead
+            w_off[j] = (int64_t)wq * p.ldw * 2 + slog * 16;
         }
     }
     auto stage = [&](int kt, int buf) {
@@ -74,6 +83,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
     const int frow = lane & 15, fg = lane >> 4, fsw = lane & 7;
     const int xrow_off = (wave_m * 64 + frow) * 128;
     const int wrow_off = (wave_n * 64 + frow) * 128;
+    const bool dead = RAG && n0 + wave_n * 64 >= p.N;      // wave-uniform: this wave's 64 columns lie beyond N
 
     int nk = p.K / BK, k_first = 0;
     if constexpr (EPI == EPI_F32) {                   // split-K: blockIdx.y owns a contiguous range of K-tiles
@@ -97,6 +107,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
         const char* sW = sA + TILE_BYTES;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
+            if (RAG && dead) break;                        // (no fragment reads, no MFMAs: the accumulators stay zero and are never stored)
             const int slot = ((kk * 4 + fg) ^ fsw) << 4;
             V8 xf[4], wf[2][2];
 #pragma unroll
@@ -124,6 +135,9 @@ __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
             const int n = n0 + wave_n * 64 + nb * 32 + 8 * fg;
+            if constexpr (RAG) {
+                if (n + 8 > p.N) continue;                 // N % 8 == 0: a lane's 8 columns are all in or all out (no bias read either)
+            }
             float v[8];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -201,17 +215,19 @@ __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
 
 template <typename T>
 int launch_t(int mode, const Gemm16Args& a, hipStream_t s) {
-    const int64_t tiles = ceil_div(a.M, BM) * (a.N / BN);
+    const int64_t tiles = ceil_div(a.M, BM) * ceil_div(a.N, BN);
     dim3 grid((unsigned)tiles), block(256);
+    const bool rag = a.N % BN != 0;       // (gemm16_route: N % 128 == 64 then)
+#define V1_CASE(E)                                                                                                             \
+    case E:                                                                                                                    \
+        if (rag) hipLaunchKernelGGL((gemm16_kernel<T, E, true>), grid, block, 0, s, a);                                        \
+        else hipLaunchKernelGGL((gemm16_kernel<T, E>), grid, block, 0, s, a);                                                  \
+        break
     switch (mode) {
-        case EPI_OUT16: hipLaunchKernelGGL((gemm16_kernel<T, EPI_OUT16>), grid, block, 0, s, a); break;
-        case EPI_GELU16: hipLaunchKernelGGL((gemm16_kernel<T, EPI_GELU16>), grid, block, 0, s, a); break;
-        case EPI_RESID32: hipLaunchKernelGGL((gemm16_kernel<T, EPI_RESID32>), grid, block, 0, s, a); break;
-        case EPI_PATCH32: hipLaunchKernelGGL((gemm16_kernel<T, EPI_PATCH32>), grid, block, 0, s, a); break;
-        case EPI_QKVH16: hipLaunchKernelGGL((gemm16_kernel<T, EPI_QKVH16>), grid, block, 0, s, a); break;
-        case EPI_PATCH16: hipLaunchKernelGGL((gemm16_kernel<T, EPI_PATCH16>), grid, block, 0, s, a); break;
+        V1_CASE(EPI_OUT16); V1_CASE(EPI_GELU16); V1_CASE(EPI_RESID32); V1_CASE(EPI_PATCH32); V1_CASE(EPI_QKVH16); V1_CASE(EPI_PATCH16);
         default: iisan_set_error("gemm16: bad epilogue mode %d", mode); return IISAN_EBADSHAPE;
     }
+#undef V1_CASE
     IISAN_LAUNCH_OK();
     return IISAN_OK;
 }
@@ -279,8 +295,11 @@ static int reject(const char* what, int mode, const Gemm16Args& a) {
 int gemm16_route(int dtype16, int mode, const Gemm16Args& a) {
     if (mode < EPI_OUT16 || mode > EPI_STREAM16 || mode == EPI_F32) return reject("bad epilogue mode", mode, a);     // (EPI_F32: launch_gemm16_f32)
     if (!(a.M > 0 && a.N > 0 && a.K > 0)) return reject("empty problem", mode, a);
-    if (!(a.N % BN == 0 && a.K % BK == 0)) return reject("N must be a multiple of 128 and K of 64", mode, a);
-    if (!(ceil_div(a.M, BM) * (a.N / BN) < (1ll << 31))) return reject("grid too large", mode, a);
+    // N % 128 == 64 below RAG_N_END: a ragged last column tile, on the 128x128 kernel alone (both 256x256 kernels turn down N % 256 != 0) — the
+    // 192- and 576-column products of a 192-wide tower.  From 768 columns on every supported width is a multiple of 128 and a ragged N is refused
+    if (!((a.N % BN == 0 || (a.N % 64 == 0 && a.N < RAG_N_END)) && a.K % BK == 0))
+        return reject("N must be a multiple of 128 (below 768: of 64) and K of 64", mode, a);
+    if (!(ceil_div(a.M, BM) * ceil_div(a.N, BN) < (1ll << 31))) return reject("grid too large", mode, a);
     if (mode == EPI_PATCH32 && !(a.patch_P > 0 && a.pos)) return reject("patch mode needs P and pos", mode, a);
     if (mode == EPI_PATCH16 && !(a.patch_P > 0)) return reject("patch mode needs P", mode, a);
     if (mode == EPI_RESID32 && !a.resid) return reject("residual mode needs resid", mode, a);

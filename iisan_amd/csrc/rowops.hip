@@ -2,17 +2,38 @@
 // Roofline: HBM (one read + one write of each row); one wave64 per row, 16-byte lane accesses,
 // wavefront-shuffle reductions, fp32 statistics (two-pass mean / centred variance in registers).
 // The row width D is a template parameter of the LayerNorm / embedding kernels (D / 256 pieces per lane: 3 at 768 — ViT-B, BERT-base —
-// 4 at 1024 — ViT-L, BERT-large); their names keep the 768 they were written for.  The kernels of the ViT's product route
+// 4 at 1024 — ViT-L, BERT-large); their names keep the 768 they were written for.  Below 768 (128, 192, 256, 384: BERT-tiny, ViT-tiny,
+// BERT-mini, ViT-small) a row takes fewer lanes, a compile-time quantity beside the piece count (row_lpr / row_np below), and several
+// rows share a wave.  The kernels of the ViT's product route
 // (fold_ln_weights, stream_stats_finalize, the MX_STAT / MX_BLK32 operand sets) are 768 wide only.
 // Train-mode dropout of the BERT tower (opt-in, bert_drop.hip) runs the SAME three kernels — layernorm768_mixed_kernel,
 // layernorm768_kernel, bert_embed_ln_kernel — with a keep functor as trailing template parameter and kernel argument (RowKeep,
 // common.h): the keep factor multiplies the 16-bit delta as it is added, or the embedding's LayerNorm output before it is rounded.  The
 // default RowKeepNone is empty and every use sits under `if constexpr (KEEP::on)`: the eval-mode instantiations compile to the
 // instruction stream they had without it (tools/isa_compare.py --ignore-arg RowKeepNone; profiles/rowops_shared_body.md).  RowKeep is
-// instantiated only where the BERT executor launches it, 768 wide: a launcher given a RowKeep for anything else refuses.
+// instantiated only where the BERT executor launches it, 768 wide (no other width has one): a launcher given a RowKeep for anything else refuses.
 #include "common.h"
 
 namespace {
+
+// How a row of D elements lies over the lanes: D = LPR * NP * VEC — LPR lanes per row (a power of two), NP pieces of VEC elements (one
+// 16-byte access of the narrowest operand) per lane.  `full` = the lanes a row gets from 768 on (a whole wave in the fp32 kernels, half a
+// wave in the mixed one): D / (full * VEC) pieces there (3 at 768, 4 at 1024).  Below that a row gets fewer lanes and several rows share a
+// wave — fp32 kernels: 128 = 32 x 1, 192 = 16 x 3, 256 = 64 x 1, 384 = 32 x 3; mixed kernel: 16 x 1, 8 x 3, 32 x 1, 16 x 3 — with NP in
+// {1, 3}, every access still 16 bytes per lane and the xor reductions log2(LPR) steps.
+constexpr int row_np(int D, int vec, int full) { return D % (full * vec) == 0 ? D / (full * vec) : ((D / vec) % 3 == 0 ? 3 : 1); }
+constexpr int row_lpr(int D, int vec, int full) { return D / vec / row_np(D, vec, full); }
+constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
+constexpr bool row_width_ok(int D, int vec, int full) {
+    const int np = row_np(D, vec, full), lpr = row_lpr(D, vec, full);
+    return lpr * np * vec == D && lpr >= 8 && lpr <= full && (lpr & (lpr - 1)) == 0 && np >= 1 && np <= 4;
+}
+template <int LPR>
+__device__ __forceinline__ float row_sum(float v) {          // over the LPR lanes of a row (LPR = 64: wave_sum)
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 // ---- (residual add +) LayerNorm over rows of D fp32 (HF nn.LayerNorm, eps inside the sqrt) ----------------------
 // v = x + delta16 (delta optional: the 16-bit output of the preceding O / FC2 GEMM, so the fp32 read-modify-write of
@@ -31,10 +52,11 @@ __global__ __launch_bounds__(256) void layernorm768_kernel(const float* x, const
                                                            float* out32, int64_t rows, KEEP keep = KEEP()) {
     constexpr bool D1 = V & 1, D2 = (V & 2) != 0, SUM = (V & 4) != 0, LN = (V & 8) != 0;
     static_assert(!KEEP::on || (D1 && !D2 && !SUM && LN), "train mode: x = LN(x + keep * delta) alone (delta2 is never dropped)");
-    constexpr int NP = D / 256;        // 4-element pieces per lane of the wave: 3 (768) or 4 (1024)
-    static_assert(D % 256 == 0 && NP >= 1 && NP <= 4, "row width: a multiple of 256, at most 1024 (the row lives in registers)");
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    constexpr int NP = row_np(D, 4, 64), LPR = row_lpr(D, 4, 64), PW = LPR * 4;        // 4-element pieces per lane: 3 (768) or 4 (1024) over a whole wave
+    static_assert(row_width_ok(D, 4, 64), "row width: LPR * NP * 4 with LPR a power of two, at most 1024 (the row lives in registers)");
+    static_assert(!KEEP::on || D == 768, "train mode: 768 wide only");
+    const int lane = threadIdx.x & (LPR - 1);
+    const int64_t row = (int64_t)blockIdx.x * (256 / LPR) + (threadIdx.x / LPR);       // (every lane of a row leaves together)
     if (row >= rows) return;
     // The fp32 residual stream and the 16-bit deltas are read once and not touched again for gigabytes: non-temporal
     // accesses (measured: 220.7 -> 201.8 us average per launch over a step's 49 launches)
@@ -43,20 +65,20 @@ __global__ __launch_bounds__(256) void layernorm768_kernel(const float* x, const
     typename T::v4 d1[NP], d2[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        v[i] = __builtin_nontemporal_load((const f4*)(xr + i * 256 + lane * 4));
-        if (D1) d1[i] = __builtin_nontemporal_load((const typename T::v4*)(delta + row * D + i * 256 + lane * 4));
-        if (D2) d2[i] = __builtin_nontemporal_load((const typename T::v4*)(delta2 + row * D + i * 256 + lane * 4));
+        v[i] = __builtin_nontemporal_load((const f4*)(xr + i * PW + lane * 4));
+        if (D1) d1[i] = __builtin_nontemporal_load((const typename T::v4*)(delta + row * D + i * PW + lane * 4));
+        if (D2) d2[i] = __builtin_nontemporal_load((const typename T::v4*)(delta2 + row * D + i * PW + lane * 4));
     }
     f4 gg[NP], bb[NP];
     if (LN) {
 #pragma unroll
-        for (int i = 0; i < NP; ++i) { gg[i] = *(const f4*)(g + i * 256 + lane * 4); bb[i] = *(const f4*)(b + i * 256 + lane * 4); }
+        for (int i = 0; i < NP; ++i) { gg[i] = *(const f4*)(g + i * PW + lane * 4); bb[i] = *(const f4*)(b + i * PW + lane * 4); }
     }
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         if constexpr (KEEP::on) {
-            const uint64_t idx = keep.index(row, D, i * 256 + lane * 4);
+            const uint64_t idx = keep.index(row, D, i * PW + lane * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[i][e] += keep(idx + e) * T::to_f32(d1[i][e]);
         } else if (D1) {
@@ -67,11 +89,11 @@ __global__ __launch_bounds__(256) void layernorm768_kernel(const float* x, const
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[i][e] += T::to_f32(d2[i][e]);
         }
-        if (SUM) __builtin_nontemporal_store(v[i], (f4*)(sum32 + row * D + i * 256 + lane * 4));
+        if (SUM) __builtin_nontemporal_store(v[i], (f4*)(sum32 + row * D + i * PW + lane * 4));
         s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
     }
     if (!LN) return;
-    const float mean = wave_sum(s) * (1.0f / (float)D);
+    const float mean = row_sum<LPR>(s) * (1.0f / (float)D);
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NP; ++i)
@@ -80,10 +102,10 @@ __global__ __launch_bounds__(256) void layernorm768_kernel(const float* x, const
             const float d = v[i][e] - mean;
             q += d * d;
         }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / (float)D) + eps);
+    const float rstd = rsqrtf(row_sum<LPR>(q) * (1.0f / (float)D) + eps);
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        const int c = i * 256 + lane * 4;
+        const int c = i * PW + lane * 4;
         f4 y;
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] = (v[i][e] - mean) * rstd * gg[i][e] + bb[i][e];
@@ -124,36 +146,40 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
                    RESY = (V & MX_RESY) != 0, SRC32 = (V & MX_SRC32) != 0, CLSONLY = (V & MX_CLSONLY) != 0, POSROW = (V & MX_POSROW) != 0,
                    STAT = (V & MX_STAT) != 0, ALIAS = (V & MX_ALIAS) != 0, BLK32 = (V & MX_BLK32) != 0;
     static_assert(!BLK32 || (STAT && SRC32), "block-major stream: written by the ViT's first add only (the products do the rest)");
-    constexpr int NP = D / 256;        // 8-element pieces per lane of the half-wave: 3 (768) or 4 (1024)
-    static_assert(D % 256 == 0 && NP >= 1 && NP <= 4, "row width: a multiple of 256, at most 1024 (the row lives in registers)");
+    // 8-element pieces per lane: 3 (768) or 4 (1024) over half a wave.  TPW tokens per workgroup: 8 from 768 on, 8 * 32 / LPR below
+    constexpr int NP = row_np(D, 8, 32), LPR = row_lpr(D, 8, 32), PW = LPR * 8, TPW = 256 / LPR, TSH = ilog2(TPW);
+    static_assert(row_width_ok(D, 8, 32), "row width: LPR * NP * 8 with LPR a power of two, at most 1024 (the row lives in registers)");
     static_assert(D == 768 || !(STAT || BLK32), "the product route's stream (row statistics, block-major rows) is 768 wide");
+    static_assert(!KEEP::on || D == 768, "train mode: 768 wide only");
     static_assert(!KEEP::on || (V & ~MX_ALIAS) == (MX_D1 | MX_LN | MX_RESY), "train mode: x = LN(x + keep * delta) alone (delta2 is never dropped)");
     typedef typename T::v8 V8;
-    const int lane = threadIdx.x & 31, half = threadIdx.x >> 5;          // 8 half-waves per workgroup
+    const int lane = threadIdx.x & (LPR - 1), half = threadIdx.x / LPR;  // TPW rows per workgroup (8 half-waves from 768 on)
     int64_t item;
     int tok;
     if (CLSONLY) {
-        item = (int64_t)blockIdx.x * 8 + half; tok = 0;
+        item = (int64_t)blockIdx.x * TPW + half; tok = 0;
         if (item >= items) return;
     } else {
-        const int bpi = (Ttok + 7) >> 3;
+        // a workgroup = TPW consecutive tokens of ONE item (bpi workgroups per item, the last one ragged: tok >= Ttok leaves): no row of
+        // it crosses the item boundary, and the CLS row is the one with tok == 0 — no division per lane
+        const int bpi = (Ttok + TPW - 1) >> TSH;
         item = blockIdx.x / bpi;
-        tok = (int)(blockIdx.x - item * bpi) * 8 + half;
+        tok = (int)(blockIdx.x - item * bpi) * TPW + half;
         if (tok >= Ttok) return;
     }
     const int64_t row = item * Ttok + tok;
-    const bool cls = tok == 0;                                            // uniform within the half-wave
+    const bool cls = tok == 0;                                            // uniform within the LPR lanes of a row
     V8 d1[NP], d2[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        if (D1) d1[i] = __builtin_nontemporal_load((const V8*)(delta + row * D + i * 256 + lane * 8));
-        if (D2) d2[i] = __builtin_nontemporal_load((const V8*)(delta2 + row * D + i * 256 + lane * 8));
+        if (D1) d1[i] = __builtin_nontemporal_load((const V8*)(delta + row * D + i * PW + lane * 8));
+        if (D2) d2[i] = __builtin_nontemporal_load((const V8*)(delta2 + row * D + i * PW + lane * 8));
     }
     float v[NP][8];
     if (cls) {
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
-            const f4 a = *(const f4*)(xc + item * D + i * 256 + lane * 8), c = *(const f4*)(xc + item * D + i * 256 + lane * 8 + 4);
+            const f4 a = *(const f4*)(xc + item * D + i * PW + lane * 8), c = *(const f4*)(xc + item * D + i * PW + lane * 8 + 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[i][e] = a[e]; v[i][4 + e] = c[e]; }
         }
@@ -161,15 +187,15 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             const int64_t srow = POSROW ? (int64_t)tok : row;            // POSROW: the position-embedding table (L2-resident), by token
-            const f4 a = POSROW ? *(const f4*)(x32 + srow * D + i * 256 + lane * 8) : __builtin_nontemporal_load((const f4*)(x32 + srow * D + i * 256 + lane * 8));
-            const f4 c = POSROW ? *(const f4*)(x32 + srow * D + i * 256 + lane * 8 + 4) : __builtin_nontemporal_load((const f4*)(x32 + srow * D + i * 256 + lane * 8 + 4));
+            const f4 a = POSROW ? *(const f4*)(x32 + srow * D + i * PW + lane * 8) : __builtin_nontemporal_load((const f4*)(x32 + srow * D + i * PW + lane * 8));
+            const f4 c = POSROW ? *(const f4*)(x32 + srow * D + i * PW + lane * 8 + 4) : __builtin_nontemporal_load((const f4*)(x32 + srow * D + i * PW + lane * 8 + 4));
 #pragma unroll
             for (int e = 0; e < 4; ++e) { v[i][e] = a[e]; v[i][4 + e] = c[e]; }
         }
     } else {
         h8 xh[NP];
 #pragma unroll
-        for (int i = 0; i < NP; ++i) xh[i] = __builtin_nontemporal_load((const h8*)(x16 + row * D + i * 256 + lane * 8));
+        for (int i = 0; i < NP; ++i) xh[i] = __builtin_nontemporal_load((const h8*)(x16 + row * D + i * PW + lane * 8));
 #pragma unroll
         for (int i = 0; i < NP; ++i)
 #pragma unroll
@@ -179,16 +205,16 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
     // ROUNDED row (what the product multiplies); val is rounded in place
     auto put_resid = [&](int i, float (&val)[8]) {
         if (cls) {
-            *(f4*)(xc + item * D + i * 256 + lane * 8) = (f4){val[0], val[1], val[2], val[3]};
-            *(f4*)(xc + item * D + i * 256 + lane * 8 + 4) = (f4){val[4], val[5], val[6], val[7]};
+            *(f4*)(xc + item * D + i * PW + lane * 8) = (f4){val[0], val[1], val[2], val[3]};
+            *(f4*)(xc + item * D + i * PW + lane * 8 + 4) = (f4){val[4], val[5], val[6], val[7]};
         }
         if ((!cls || STAT) && !ALIAS) {
             h8 o;
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (_Float16)val[e];
             // read again by the GEMM that follows (MX_BLK32: block-major, common.h — the lane's 8 columns are one 16-byte granule of it)
-            if (STAT) *(h8*)(x16 + (BLK32 ? blk32_byte(row, i * 256 + lane * 8, D) >> 1 : row * D + i * 256 + lane * 8)) = o;
-            else __builtin_nontemporal_store(o, (h8*)(x16 + row * D + i * 256 + lane * 8));
+            if (STAT) *(h8*)(x16 + (BLK32 ? blk32_byte(row, i * PW + lane * 8, D) >> 1 : row * D + i * PW + lane * 8)) = o;
+            else __builtin_nontemporal_store(o, (h8*)(x16 + row * D + i * PW + lane * 8));
             if (STAT) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) val[e] = (float)o[e];
@@ -200,7 +226,7 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         if constexpr (KEEP::on) {
-            const uint64_t idx = keep.index(row, D, i * 256 + lane * 8);
+            const uint64_t idx = keep.index(row, D, i * PW + lane * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[i][e] += keep(idx + e) * T::to_f32(d1[i][e]);
         } else if (D1 && use_d) {
@@ -216,9 +242,9 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
         for (int e = 0; e < 8; ++e) s += v[i][e];
     }
     if (!LN && !STAT) return;
-    auto sum32 = [](float t) {          // over the 32 lanes of the half-wave
+    auto sum32 = [](float t) {          // over the LPR lanes of the row (32: the half-wave)
 #pragma unroll
-        for (int o = 16; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        for (int o = LPR / 2; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
         return t;
     };
     const float mean = sum32(s) * (1.0f / (float)D);
@@ -237,7 +263,7 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
     }
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        const int c = i * 256 + lane * 8;
+        const int c = i * PW + lane * 8;
         const f4 g0 = *(const f4*)(g + c), g1 = *(const f4*)(g + c + 4), b0 = *(const f4*)(b + c), b1 = *(const f4*)(b + c + 4);
         float y[8];
 #pragma unroll
@@ -333,10 +359,11 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __res
                                                             _Float16* __restrict__ X16, float* __restrict__ Xc,
                                                             const int64_t* __restrict__ index = nullptr, int64_t rows = 0,
                                                             KEEP keep = KEEP()) {
-    constexpr int NP = D / 256;
-    static_assert(D % 256 == 0 && NP >= 1 && NP <= 4, "row width: a multiple of 256, at most 1024");
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    constexpr int NP = row_np(D, 4, 64), LPR = row_lpr(D, 4, 64), PW = LPR * 4;        // as layernorm768_kernel
+    static_assert(row_width_ok(D, 4, 64), "row width: LPR * NP * 4 with LPR a power of two, at most 1024");
+    static_assert(!KEEP::on || D == 768, "train mode: 768 wide only");
+    const int lane = threadIdx.x & (LPR - 1);
+    const int64_t row = (int64_t)blockIdx.x * (256 / LPR) + (threadIdx.x / LPR);
     if (row >= M * W) return;
     const int64_t m = row / W;
     const int t = (int)(row % W);
@@ -358,13 +385,13 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __res
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        const int c = i * 256 + lane * 4;
+        const int c = i * PW + lane * 4;
         const f4 a = *(const f4*)(wr + c), p2 = *(const f4*)(pr + c), ty = *(const f4*)(type0 + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[i][e] = a[e] + p2[e] + ty[e];
         s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
     }
-    const float mean = wave_sum(s) * (1.0f / (float)D);
+    const float mean = row_sum<LPR>(s) * (1.0f / (float)D);
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NP; ++i)
@@ -373,10 +400,10 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __res
             const float d = v[i][e] - mean;
             q += d * d;
         }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / (float)D) + eps);
+    const float rstd = rsqrtf(row_sum<LPR>(q) * (1.0f / (float)D) + eps);
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        const int c = i * 256 + lane * 4;
+        const int c = i * PW + lane * 4;
         const f4 gg = *(const f4*)(g + c), bb = *(const f4*)(b + c);
         f4 y;
         typename T::v4 o;
@@ -429,13 +456,30 @@ __global__ void cast16_kernel(const float* __restrict__ src, typename T::elem* _
 
 }  // namespace
 
-// width: 768 or 1024 (the two instantiated row widths; anything else is IISAN_EBADSHAPE)
+// The instantiated row widths: 768 / 1024 (ViT-B / BERT-base, ViT-L / BERT-large) and the narrow towers' 128, 192, 256, 384 (BERT-tiny, ViT-tiny,
+// BERT-mini, ViT-small).  The refusal names the width it was given and 768 and 1024 first.
+static bool row_width_instantiated(int w) { return w == 768 || w == 1024 || w == 128 || w == 192 || w == 256 || w == 384; }
+#define ROW_WIDTH_MSG "row width %d not instantiated (768 and 1024 are, and 128, 192, 256, 384)"
+// one switch over the widths: X(W, A) is the launch at the compile-time width W (A: whatever else the launch is a template of)
+#define ROW_WIDTH_SWITCH(width, X, A)                                                                                         \
+    switch (width) {                                                                                                           \
+        case 128: X(128, A); break;                                                                                            \
+        case 192: X(192, A); break;                                                                                            \
+        case 256: X(256, A); break;                                                                                            \
+        case 384: X(384, A); break;                                                                                            \
+        case 768: X(768, A); break;                                                                                            \
+        default: X(1024, A); break;                                                                                            \
+    }
+
+// width: one of the instantiated row widths (anything else is IISAN_EBADSHAPE)
 int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, const void* delta16b, const float* g,
                              const float* b, float eps, float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s,
                              const RowKeep* keep) {
-    IISAN_CHECK_SHAPE(width == 768 || width == 1024, "layernorm: row width %d not instantiated (768 and 1024 are)", width);
+    IISAN_CHECK_SHAPE(row_width_instantiated(width), "layernorm: " ROW_WIDTH_MSG, width);
     if (rows <= 0) return IISAN_OK;
-    dim3 grid((unsigned)ceil_div(rows, 4)), block(256);
+    const int64_t blocks = ceil_div(rows, (int64_t)(256 / row_lpr(width, 4, 64)));       // 4 rows per workgroup from 768 on, up to 16 below
+    IISAN_CHECK_SHAPE(blocks < (1ll << 31), "layernorm: grid too large");
+    dim3 grid((unsigned)blocks), block(256);
     const int v = (delta16 ? 1 : 0) | (delta16b ? 2 : 0) | (sum32 ? 4 : 0) | (g ? 8 : 0);
 #define LN768_LAUNCH(TT, EL, V, W)                                                                                             \
     hipLaunchKernelGGL((layernorm768_kernel<TT, V, W>), grid, block, 0, s, x, (const EL*)delta16, (const EL*)delta16b, g, b, eps, sum32, (EL*)out16, out32, rows)
@@ -448,18 +492,17 @@ int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, c
         IISAN_LAUNCH_OK();
         return IISAN_OK;
     }
+#define LN768_AT(W, V)                                                                                                         \
+    if (dtype16 == IISAN_BF16) LN768_LAUNCH(BF16, __bf16, V, W); else LN768_LAUNCH(F16, _Float16, V, W)
 #define LN768_CASE(V)                                                                                                          \
     case V:                                                                                                                    \
-        if (width == 768) {                                                                                                    \
-            if (dtype16 == IISAN_BF16) LN768_LAUNCH(BF16, __bf16, V, 768); else LN768_LAUNCH(F16, _Float16, V, 768);           \
-        } else {                                                                                                               \
-            if (dtype16 == IISAN_BF16) LN768_LAUNCH(BF16, __bf16, V, 1024); else LN768_LAUNCH(F16, _Float16, V, 1024);         \
-        }                                                                                                                      \
+        ROW_WIDTH_SWITCH(width, LN768_AT, V)                                                                                   \
         break
     switch (v) {
         LN768_CASE(0); LN768_CASE(1); LN768_CASE(2); LN768_CASE(3); LN768_CASE(4); LN768_CASE(5); LN768_CASE(6); LN768_CASE(7);
         LN768_CASE(8); LN768_CASE(9); LN768_CASE(10); LN768_CASE(11); LN768_CASE(12); LN768_CASE(13); LN768_CASE(14); LN768_CASE(15);
     }
+#undef LN768_AT
 #undef LN768_CASE
 #undef LN768_KEEP
 #undef LN768_LAUNCH
@@ -468,15 +511,16 @@ int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, c
 }
 
 
-// mixed-precision residual stream (layernorm768_mixed_kernel): V = MX_* flags of the operands that exist; width 768 or 1024 — the
-// operand sets of the LayerNorm-image routes exist at both, those of the product route (MX_STAT, MX_BLK32) at 768 only
+// mixed-precision residual stream (layernorm768_mixed_kernel): V = MX_* flags of the operands that exist; the operand sets of the
+// LayerNorm-image routes exist at every instantiated width, those of the product route (MX_STAT, MX_BLK32) at 768 only
 int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, float* xc, const void* delta16, const void* delta16b,
                               const float* g, const float* b, float eps, void* out16, int64_t items, int Ttok, int width, hipStream_t s,
                               float* stat, const RowKeep* keep) {
-    IISAN_CHECK_SHAPE(width == 768 || width == 1024, "layernorm768_mixed: row width %d not instantiated (768 and 1024 are)", width);
+    IISAN_CHECK_SHAPE(row_width_instantiated(width), "layernorm768_mixed: " ROW_WIDTH_MSG, width);
     if (items <= 0) return IISAN_OK;
     IISAN_CHECK_SHAPE(!(V & MX_STAT) || stat, "layernorm768_mixed: MX_STAT needs the statistics buffer");
-    const int64_t blocks = (V & MX_CLSONLY) ? ceil_div(items, 8) : items * ((Ttok + 7) / 8);
+    const int tpw = 256 / row_lpr(width, 8, 32);          // tokens (CLS-only: items) per workgroup: 8 from 768 on, up to 32 below
+    const int64_t blocks = (V & MX_CLSONLY) ? ceil_div(items, (int64_t)tpw) : items * ((Ttok + tpw - 1) / tpw);
     IISAN_CHECK_SHAPE(blocks < (1ll << 31), "layernorm768_mixed: grid too large");
     dim3 grid((unsigned)blocks), block(256);
 #define MX_LAUNCH(TT, EL, VV, W)                                                                                               \
@@ -501,13 +545,11 @@ int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, f
         if (dtype16 == IISAN_BF16) MX_LAUNCH(BF16, __bf16, VV, 768); else MX_LAUNCH(F16, _Float16, VV, 768);                   \
         IISAN_LAUNCH_OK();                                                                                                     \
         return IISAN_OK
+#define MX_AT(W, VV)                                                                                                           \
+    if (dtype16 == IISAN_BF16) MX_LAUNCH(BF16, __bf16, VV, W); else MX_LAUNCH(F16, _Float16, VV, W)
 #define MX_CASE(VV)                                                                                                            \
     case VV:                                                                                                                   \
-        if (width == 768) {                                                                                                    \
-            if (dtype16 == IISAN_BF16) MX_LAUNCH(BF16, __bf16, VV, 768); else MX_LAUNCH(F16, _Float16, VV, 768);               \
-        } else {                                                                                                               \
-            if (dtype16 == IISAN_BF16) MX_LAUNCH(BF16, __bf16, VV, 1024); else MX_LAUNCH(F16, _Float16, VV, 1024);             \
-        }                                                                                                                      \
+        ROW_WIDTH_SWITCH(width, MX_AT, VV)                                                                                     \
         IISAN_LAUNCH_OK();                                                                                                     \
         return IISAN_OK
     switch (V) {
@@ -525,6 +567,7 @@ int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, f
         MX_CASE768(MX_D1 | MX_RESV | MX_CLSONLY);          // ViT closing add of the CLS rows when x + dO is in the stream already
         default: break;
     }
+#undef MX_AT
 #undef MX_CASE
 #undef MX_CASE768
 #undef MX_KEEP
@@ -579,13 +622,13 @@ int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M,
     return IISAN_OK;
 }
 
-// one launcher for the direct (index == null) and the indexed form; width 768 or 1024
+// one launcher for the direct (index == null) and the indexed form; width: one of the instantiated row widths
 template <bool IDX>
 static int bert_embed_ln_any(int dtype16, const int64_t* text, int64_t rows, const int64_t* index, const float* word, const float* pos,
                              const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
                              int64_t M, int W, int vocab, int width, hipStream_t s, void* X16, float* Xc, const RowKeep* keep) {
-    IISAN_CHECK_SHAPE(width == 768 || width == 1024, "bert_embed_ln: row width %d not instantiated (768 and 1024 are)", width);
-    dim3 grid((unsigned)ceil_div(M * W, 4)), block(256);
+    IISAN_CHECK_SHAPE(row_width_instantiated(width), "bert_embed_ln: " ROW_WIDTH_MSG, width);
+    dim3 grid((unsigned)ceil_div(M * W, (int64_t)(256 / row_lpr(width, 4, 64)))), block(256);
 #define EMBED_LAUNCH(TT, EL, WD)                                                                                               \
     hipLaunchKernelGGL((bert_embed_ln_kernel<TT, IDX, WD>), grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (EL*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows)
 #define EMBED_KEEP(TT, EL)                                                                                                     \
@@ -594,10 +637,11 @@ static int bert_embed_ln_any(int dtype16, const int64_t* text, int64_t rows, con
         IISAN_CHECK_SHAPE(width == 768, "bert_embed_ln: no train-mode instantiation at row width %d", width);
         if (dtype16 == IISAN_BF16) EMBED_KEEP(BF16, __bf16); else EMBED_KEEP(F16, _Float16);
         iisan_count_bert_drop();
-    } else if (width == 768) {
-        if (dtype16 == IISAN_BF16) EMBED_LAUNCH(BF16, __bf16, 768); else EMBED_LAUNCH(F16, _Float16, 768);
     } else {
-        if (dtype16 == IISAN_BF16) EMBED_LAUNCH(BF16, __bf16, 1024); else EMBED_LAUNCH(F16, _Float16, 1024);
+#define EMBED_AT(WD, TT)                                                                                                       \
+    if (dtype16 == IISAN_BF16) EMBED_LAUNCH(BF16, __bf16, WD); else EMBED_LAUNCH(TT, _Float16, WD)
+        ROW_WIDTH_SWITCH(width, EMBED_AT, F16)
+#undef EMBED_AT
     }
 #undef EMBED_KEEP
 #undef EMBED_LAUNCH

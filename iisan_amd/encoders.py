@@ -96,7 +96,7 @@ class PackedVit(_PackedEncoder):
         s.patch_w, s.patch_b = self._m16("patch_w"), self._v32("patch_b")
         s.cls_token, s.pos_emb = self._v32("cls_token"), self._v32("pos_emb")
         # LayerNorm 1 / 2 folded into the QKV / FC1 weights once, here, instead of at the start of every forward call — where the
-        # executor has that route (fp16 operands, hidden 768; 0 bytes otherwise: a 1024-wide tower keeps no fp32 masters)
+        # executor has that route (fp16 operands, hidden 768; 0 bytes otherwise: a 1024-wide or a narrow tower keeps no fp32 masters)
         lib = _lib.load()
         nbytes = lib.iisan_vit_fold_bytes(C.byref(s))
         self._layers(s, cfg.layers, masters=nbytes > 0)

@@ -28,8 +28,10 @@ from . import dp, ops
 @torch.no_grad()
 def build_tap_cache(model, images: torch.Tensor, text: torch.Tensor, batch: int = 256) -> Tuple[torch.Tensor, torch.Tensor]:
     """CLS taps of every hidden state for a catalogue: ([N, Lc+1, Dc], [N, Lt+1, Dt]) fp32 on the inputs' device.  The widths are
-    the towers' own hidden sizes (768 or 1024; the two towers may differ), not the side network's: a 24-layer ViT-L/16 gives the
-    [N, 25, 1024] image taps of the Versa variant.  Always eval mode (no tower dropout)."""
+    the towers' own hidden sizes (768 or 1024, or the narrow towers' 128, 192, 256, 384; the two towers may differ), not the side
+    network's: a 24-layer ViT-L/16 gives the [N, 25, 1024] image taps of the Versa variant, `weights.VIT_TINY` / `weights.BERT_TINY` the
+    [N, 13, 192] / [N, 3, 128] taps of its edge configuration (`Code_Cached_Asym/preprocess_edge_small.py`).  Always eval mode (no tower
+    dropout)."""
     enc = model.mm_encoder
     cvs, txs = [], []
     for i in range(0, images.shape[0], batch):

@@ -75,6 +75,13 @@ BERT_BASE = BertConfig()
 # the towers whose taps the Versa variant consumes (`Code_Cached_Asym/parameters.py`: text_embedding_dim 1024, text_layers 24)
 VIT_LARGE = VitConfig(hidden=1024, layers=24, heads=16, mlp=4096)
 BERT_LARGE = BertConfig(hidden=1024, layers=24, heads=16, mlp=4096)
+# the edge towers (`Code_Cached_Asym/preprocess_edge_small.py` caches the per-layer CLS rows of `prajjwal1/bert-tiny` and
+# `WinKawaks/vit-tiny-patch16-224`) and their next sizes up (`WinKawaks/vit-small-patch16-224`, `prajjwal1/bert-mini`): 64-wide heads
+# like every tower here, hidden 128 - 384 (`vit_from_hf` / `bert_from_hf` read every shape off the state dict)
+VIT_TINY = VitConfig(hidden=192, layers=12, heads=3, mlp=768)
+VIT_SMALL = VitConfig(hidden=384, layers=12, heads=6, mlp=1536)
+BERT_TINY = BertConfig(hidden=128, layers=2, heads=2, mlp=512, vocab=30522, eps=1e-12)
+BERT_MINI = BertConfig(hidden=256, layers=4, heads=4, mlp=1024, vocab=30522, eps=1e-12)
 
 
 def _normal(rs: np.random.RandomState, shape, std: float) -> torch.Tensor:

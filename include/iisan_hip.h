@@ -47,11 +47,13 @@ const char* iisan_last_error(void);
 /* ------------------------------------------------------------------------------------------------------------
  * Frozen encoders (no-grad).  Weights are packed once by the host (iisan_amd/encoders.py): matrices in the 16-bit
  * operand type, [out,in] row-major exactly like torch.nn.Linear.weight; vectors in fp32.
- * Hidden size D = 64 * heads with D = 768 (ViT-B/16, BERT-base: 12 heads) or D = 1024 (ViT-L/16, BERT-large: 16 heads); any other
- * width is IISAN_EBADSHAPE before any launch.  The taps are D wide — the tower's own width, not the side network's.
- * D = 1024 runs on the LayerNorm-image route of both executors (mixed fp16 / fp32-CLS residual stream; dev switch resid32 works
- * too).  The LayerNorm-folded route of the ViT executor (folded weights, stream epilogues, block-major stream) is 768 wide only:
- * at D = 1024 iisan_vit_fold_bytes is 0, `folded` is ignored, and the dev switch ln_fold selects nothing.
+ * Hidden size D = 64 * heads with D = 768 (ViT-B/16, BERT-base: 12 heads) or D = 1024 (ViT-L/16, BERT-large: 16 heads), or one of the
+ * narrow towers' D = 128 (BERT-tiny: 2 heads), 192 (ViT-tiny: 3), 256 (BERT-mini: 4), 384 (ViT-small: 6); any other width (512 and
+ * 1280 among them) is IISAN_EBADSHAPE before any launch.  The taps are D wide — the tower's own width, not the side network's.
+ * Every D other than 768 runs on the LayerNorm-image route of both executors (mixed fp16 / fp32-CLS residual stream; dev switch
+ * resid32 works too), in eval mode only (iisan_bert_forward_taps_dropout: drop == NULL or both probabilities 0).  The
+ * LayerNorm-folded route of the ViT executor (folded weights, stream epilogues, block-major stream) is 768 wide only: at any other D
+ * iisan_vit_fold_bytes is 0, `folded` is ignored, and the dev switch ln_fold selects nothing.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct {
     const void* qkv_w;  const float* qkv_b;   /* [3D,D] 16-bit, [3D]  (q;k;v stacked)                          */
@@ -102,7 +104,7 @@ typedef struct {
  * array.  `chunk_items` (0 = whole batch) bounds the activation working set. */
 /* The folded weights of `w` (LayerNorm 1 / 2 of every layer folded into qkv_w / fc1_w: gamma-scaled, centred, fp16, rounded
  * sum-preservingly from the fp32 masters when the layer has them, + the folded biases): [layers][(3D + F) x D] fp16, then
- * [layers][3D + F] fp32.  0 bytes when the executor would not use them (bf16 operands; hidden size 1024). */
+ * [layers][3D + F] fp32.  0 bytes when the executor would not use them (bf16 operands; any hidden size other than 768). */
 size_t iisan_vit_fold_bytes(const iisan_vit_weights* w);
 int iisan_vit_fold_layernorm(const iisan_vit_weights* w, void* folded, size_t bytes, void* stream);
 /* fp16 operands (dtype16 = IISAN_F16), production sizes: the executor folds LayerNorm 1 / 2 of every block into the QKV / FC1
@@ -350,13 +352,15 @@ int iisan_adam_step(float* p, const float* g, float* m, float* v, int64_t n, con
  * ---------------------------------------------------------------------------------------------------------- */
 /* C = epilogue(A[M,K] · W[N,K]^T + bias): 16-bit operands, fp32 accumulate.
  * mode 0: out16 = acc+bias     1: out16 = gelu_erf(acc+bias)     2: out32 = acc+bias+resid32 (resid may alias out)
- * A must be readable for ceil(M/256)*256 rows (tiles are loaded whole; rows >= M are never stored). */
+ * A must be readable for ceil(M/256)*256 rows (tiles are loaded whole; rows >= M are never stored).
+ * K % 64 == 0; N % 128 == 0, or N % 64 == 0 below 768 (the 192- and 576-column products of a 192-wide tower: a ragged last column
+ * tile on the 128x128 kernel, W and bias read for rows / entries 0..N-1 only).  Anything else: IISAN_EBADSHAPE. */
 int iisan_gemm16(int32_t dtype16, int32_t mode, const void* A, const void* W, const float* bias, void* out,
                  const float* resid, int64_t M, int32_t N, int32_t K, void* stream);
 /* LayerNorm over rows of width 768: out16 (nullable) / out32 (nullable) */
 int iisan_layernorm768(int32_t dtype16, const float* x, const float* g, const float* b, float eps,
                        void* out16, float* out32, int64_t rows, void* stream);
-/* The same over rows of `width` elements, width 768 or 1024 — the two row widths the encoders' row kernels are built for
+/* The same over rows of `width` elements, width 768 or 1024, or 128, 192, 256, 384 — the row widths the encoders' row kernels are built for
  * (ViT-B / BERT-base, ViT-L / BERT-large).  Any other width: IISAN_EBADSHAPE, nothing launched.  At width 768 it is the call above. */
 int iisan_layernorm(int32_t dtype16, const float* x, const float* g, const float* b, float eps,
                     void* out16, float* out32, int64_t rows, int32_t width, void* stream);
