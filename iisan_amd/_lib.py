@@ -108,6 +108,7 @@ SIGNATURES = {
     "iisan_gemm32_plan": (i32, [C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), i32, i32, i64, i32, C.POINTER(i32)]),
     "iisan_inbatch_ce_route": (i32, [i64, i32]),
     "iisan_inbatch_ce_route_e": (i32, [i64, i32, i32]),
+    "iisan_encoder_plan": (i32, [i32, i32, i32, i32, i32, i32, i64, i64, i32, i32, i32]),
     # DEV section: the library's only process-global state (development switches + measurement hooks)
     "iisan_dev_set": (i32, [C.c_char_p, i64]),
     "iisan_dev_get": (i64, [C.c_char_p]),

@@ -357,6 +357,7 @@ bool gemm16_h256_applicable(int mode, const Gemm16Args& a);      // gemm16_h256.
 int launch_gemm16_h256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s);
 int launch_gemm16_f32(const Gemm16Args& a, int ksplit, hipStream_t s);      // gemm16.hip: fp32 output of the 128x128 kernel (split.hip)
 // `width` of the row kernels below: 768 or 1024, or 128, 192, 256, 384 (the instantiated widths; anything else: IISAN_EBADSHAPE)
+bool row_width_instantiated(int width);     // rowops.hip; the encoder executors accept a tower of exactly these hidden sizes
 int launch_layernorm768(int dtype16, const float* x, const float* g, const float* b, float eps, void* out16,
                         float* out32, int64_t rows, int width, hipStream_t s);
 // x (+ delta16) -> [sum32 = x + delta] -> LayerNorm -> out16 / out32 (any output may be null; g == null: no LayerNorm)

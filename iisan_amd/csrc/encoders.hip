@@ -45,6 +45,15 @@ int g_ln_fold = 2;
 // formula.  0: row-major everywhere (the A/B handle and the tests' reference route: the same kernels, the same arithmetic, bit-equal
 // results).
 int g_blk32 = 2;
+// process-wide OVERRIDE of the weights structs' `full_blocks` field (bench.py, tests; not declared in include/iisan_hip.h):
+// 1 = run every block of the tower on every token, as the reference does
+int g_full_blocks = 0;
+
+// A call runs in chunks of Mc items; its last chunk may be shorter.  Mc and `last` are the only two chunk sizes a call has.
+struct Chunks {
+    int64_t Mc, last;
+    Chunks(int64_t M, int64_t chunk_items) : Mc((chunk_items > 0 && chunk_items < M) ? chunk_items : M), last(Mc > 0 && M % Mc ? M % Mc : Mc) {}
+};
 
 size_t carve(WsCarver& c, EncBufs& b, int64_t tokens, int64_t items, int D, int F, int64_t kb_elems, int fold_layers = 0, bool fold_ws = true) {
     const int64_t Tp = ceil_div(tokens, 256) * 256;     // GEMM A operands are read in 256-row tiles
@@ -72,100 +81,79 @@ size_t carve(WsCarver& c, EncBufs& b, int64_t tokens, int64_t items, int D, int 
     return c.off;
 }
 
-Gemm16Args gemm_args(int mode, const void* A, int K, const void* W, const float* bias, void* out, int N, int64_t M, int qkv_S = 0,
-                     int qkv_heads = 0, int qkv_which0 = 0, const float* rowstat = nullptr) {
-    Gemm16Args a{};
-    a.A = A; a.W = W; a.bias = bias; a.out = out;
-    a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldo = N;
-    a.qkv_S = qkv_S; a.qkv_heads = qkv_heads; a.qkv_which0 = qkv_which0;
-    a.rowstat = rowstat;
-    return a;
-}
+// One 16-bit product: its epilogue mode and its Gemm16Args with everything but the operand pointers.  rowstat / rowpart point at WANTED
+// where the product takes them: gemm16_route asks only whether they are there, Chunk::launch puts the workspace buffers in their place.
+struct Product { int mode; Gemm16Args a; };
+float WANTED;
 
-// F1 block-major?  Decided once per call: only when BOTH products — FC1 (GELU, `rowstat`: LayerNorm in its epilogue) and FC2 (`fc2_mode`:
-// EPI_OUT16 or EPI_STREAM16) — run on gemm16_h256 with the flag for every chunk size of the call (the last chunk may be shorter)
-bool f1_blk32(int dt, int D, int F, int64_t M, int64_t Mc, int T, const float* rowstat, int fc2_mode, float* rowpart) {
-    if (g_blk32 < 1) return false;
-    for (int64_t mc : {Mc, M % Mc == 0 ? Mc : M % Mc}) {
-        const int64_t tok = mc * T;
-        Gemm16Args f1 = gemm_args(EPI_GELU16, nullptr, D, nullptr, nullptr, nullptr, F, tok, 0, 0, 0, rowstat);
-        Gemm16Args f2 = gemm_args(fc2_mode, nullptr, F, nullptr, nullptr, nullptr, D, tok, fc2_mode == EPI_STREAM16 ? T : 0);
-        f1.out_blk32 = 1;
-        f2.a_blk32 = 1; f2.rowpart = rowpart;
-        if (gemm16_route(dt, EPI_GELU16, f1) != G16_H256 || gemm16_route(dt, fc2_mode, f2) != G16_H256) return false;
+// The products of one call, each described ONCE: a probe hands a description to gemm16_route, a launch adds the pointers to the same
+// description.  The layout decisions of the call are fields, so the probe of a decision is a copy with that decision switched on.
+struct Products {
+    int dt, D, F, T, heads;
+    bool ln = false;        // QKV / FC1 read the stream and apply LayerNorm in their epilogues (VS_FOLD, VS_STREAM)
+    bool stream = false;    // O / FC2 add into the stream in their epilogues (VS_STREAM)
+    bool f1blk = false;     // F1, the FC1 -> FC2 intermediate of the all-token blocks, is block-major
+    bool xblk = false;      // ... and so is the ViT stream X16 (VS_STREAM only)
+
+    // out [M, N] = A [M, K] W^T, natural leading dimensions: the products of the CLS tail (one row per item) as they are
+    static Product plain(int mode, int K, int N, int64_t M) {
+        Product p{mode, {}};
+        p.a.M = M; p.a.N = N; p.a.K = K; p.a.lda = K; p.a.ldw = K; p.a.ldo = N;
+        return p;
     }
-    return true;
-}
-
-// The ViT stream block-major?  Only on the product route (VS_STREAM) with F1 block-major, and only when every product that touches the
-// stream takes the flags for every chunk size of the call: QKV and FC1 (A), O and FC2 (read-modify-write), the K/V product of a CLS-only
-// last block (A)
-bool x16_blk32(int dt, int D, int F, int heads, int64_t M, int64_t Mc, int T, bool full_blocks, const float* rowstat, float* rowpart) {
-    if (g_blk32 < 2) return false;
-    for (int64_t mc : {Mc, M % Mc == 0 ? Mc : M % Mc}) {
-        const int64_t tok = mc * T;
-        Gemm16Args q = gemm_args(EPI_QKVH16, nullptr, D, nullptr, nullptr, nullptr, 3 * D, tok, T, heads, 0, rowstat);
-        Gemm16Args kv = gemm_args(EPI_QKVH16, nullptr, D, nullptr, nullptr, nullptr, 2 * D, tok, T, heads, 1, rowstat);
-        Gemm16Args f1 = gemm_args(EPI_GELU16, nullptr, D, nullptr, nullptr, nullptr, F, tok, 0, 0, 0, rowstat);
-        Gemm16Args o = gemm_args(EPI_STREAM16, nullptr, D, nullptr, nullptr, nullptr, D, tok, T), f2 = gemm_args(EPI_STREAM16, nullptr, F, nullptr, nullptr, nullptr, D, tok, T);
-        q.a_blk32 = kv.a_blk32 = f1.a_blk32 = f1.out_blk32 = o.out_blk32 = f2.a_blk32 = f2.out_blk32 = 1;
-        o.rowpart = f2.rowpart = rowpart;
-        auto h256 = [&](int mode, const Gemm16Args& a) { return gemm16_route(dt, mode, a) == G16_H256; };
-        if (!(h256(EPI_QKVH16, q) && h256(EPI_GELU16, f1) && h256(EPI_STREAM16, o) && h256(EPI_STREAM16, f2) && (full_blocks || h256(EPI_QKVH16, kv))))
-            return false;
+    // q | k | v from `which0` on, head-major (1: K and V alone, the CLS-only last block)
+    Product qkv(int64_t tok, int which0 = 0) const {
+        Product p = plain(EPI_QKVH16, D, (3 - which0) * D, tok);
+        p.a.qkv_S = T; p.a.qkv_heads = heads; p.a.qkv_which0 = which0;
+        p.a.rowstat = ln ? &WANTED : nullptr; p.a.a_blk32 = xblk;
+        return p;
     }
-    return true;
-}
+    Product fc1(int64_t tok) const {
+        Product p = plain(EPI_GELU16, D, F, tok);
+        p.a.rowstat = ln ? &WANTED : nullptr; p.a.a_blk32 = xblk; p.a.out_blk32 = f1blk;
+        return p;
+    }
+    // O (K = D) and FC2 (K = F, A = F1): a 16-bit delta, or x += A W^T + bias in the stream with the row sums of the new rows
+    Product to_stream(int K, int64_t tok, bool a_blk) const {
+        Product p = plain(stream ? EPI_STREAM16 : EPI_OUT16, K, D, tok);
+        p.a.a_blk32 = a_blk;
+        if (stream) { p.a.qkv_S = T; p.a.rowpart = &WANTED; p.a.out_blk32 = xblk; }
+        return p;
+    }
+    Product o(int64_t tok) const { return to_stream(D, tok, false); }
+    Product fc2(int64_t tok) const { return to_stream(F, tok, f1blk); }
+    // patch embedding of `rows` patch vectors of length pd, P per image: fp32 token rows (+ the position table, a pointer) or 16-bit rows
+    static Product patch(bool fp32, int pd, int D, int64_t rows, int P) {
+        Product p = plain(fp32 ? EPI_PATCH32 : EPI_PATCH16, pd, D, rows);
+        p.a.patch_P = P;
+        return p;
+    }
 
-// the FC1 -> FC2 pair of an all-token block: F1 = GELU(A W1^T + b1) (rowstat: LayerNorm in the epilogue), out = F1 W2^T + b2
-int gemm_fc1(int dt, const void* A, int D, const void* W, const float* bias, const float* rowstat, void* F1, int F, int64_t M, bool f1blk, hipStream_t s,
-             bool a_blk = false) {
-    Gemm16Args a = gemm_args(EPI_GELU16, A, D, W, bias, F1, F, M, 0, 0, 0, rowstat);
-    a.out_blk32 = f1blk; a.a_blk32 = a_blk;
-    return launch_gemm16(dt, EPI_GELU16, a, s);
-}
-int gemm_fc2(int dt, const void* F1, int F, const void* W, const float* bias, void* out, int D, int64_t M, bool f1blk, hipStream_t s) {
-    Gemm16Args a = gemm_args(EPI_OUT16, F1, F, W, bias, out, D, M);
-    a.a_blk32 = f1blk;
-    return launch_gemm16(dt, EPI_OUT16, a, s);
-}
-
-int gemm(int dt, int mode, const void* A, int K, const void* W, const float* bias, void* out, int N, const float* resid,
-         int64_t M, hipStream_t s, const float* pos = nullptr, int patch_P = 0, int qkv_S = 0, int qkv_heads = 0,
-         int qkv_which0 = 0) {
-    Gemm16Args a = gemm_args(mode, A, K, W, bias, out, N, M, qkv_S, qkv_heads, qkv_which0);
-    a.resid = resid; a.pos = pos; a.patch_P = patch_P;
-    return launch_gemm16(dt, mode, a, s);
-}
-
-// LN(x) W^T + b with the LayerNorm in the epilogue: A = the stream, W / bias = the folded set, rowstat = the rows' rstd
-int gemm_ln(int dt, int mode, const void* X16, int K, const void* Wf, const float* bf, const float* rs, void* out, int N,
-            int64_t M, hipStream_t s, int qkv_S = 0, int qkv_heads = 0, int qkv_which0 = 0, bool x_blk = false) {
-    Gemm16Args a = gemm_args(mode, X16, K, Wf, bf, out, N, M, qkv_S, qkv_heads, qkv_which0, rs);
-    a.a_blk32 = x_blk;       // the stream is block-major
-    return launch_gemm16(dt, mode, a, s);
-}
-
-// Last live block: K and V for every token (head-major; the q third of the buffer is left untouched), Q for the CLS rows
-// only.  Hc (in) / Qc (out) are compact [mc, D] 16-bit views: Hc = the CLS rows of the block's 16-bit input H.
-int kv_all_q_cls(int dt, const iisan_layer_weights& L, const void* H, void* QKV, const void* Hc, void* Qc, int64_t tok,
-                 int64_t mc, int T, int heads, int D, hipStream_t s) {
-    const size_t e16 = 2;
-    IISAN_TRY(gemm(dt, EPI_QKVH16, H, D, (const char*)L.qkv_w + (size_t)D * D * e16, L.qkv_b + D, QKV, 2 * D, nullptr, tok, s,
-                   nullptr, 0, T, heads, 1));
-    IISAN_TRY(gemm(dt, EPI_OUT16, Hc, D, L.qkv_w, L.qkv_b, Qc, D, nullptr, mc, s));
-    return IISAN_OK;
-}
+    // Every product of `list` (P_* bits) on gemm16_h256, for every chunk size of the call?  LayerNorm and the residual add in the epilogue and
+    // the block-major operands exist on that kernel alone, and a buffer has ONE layout per call: a product that another kernel would take
+    // (gemm16_route: small chunks, forced variants) turns the decision down for the whole call.
+    enum { P_QKV = 1, P_KV = 2, P_FC1 = 4, P_O = 8, P_FC2 = 16 };
+    bool all_h256(const Chunks& c, int list) const {
+        for (int64_t mc : {c.Mc, c.last}) {
+            const Product all[] = {qkv(mc * T), qkv(mc * T, 1), fc1(mc * T), o(mc * T), fc2(mc * T)};
+            for (int i = 0; i < 5; ++i)
+                if ((list >> i & 1) && gemm16_route(dt, all[i].mode, all[i].a) != G16_H256) return false;
+        }
+        return true;
+    }
+    // F1 block-major?  Only when both products of the pair take the flag.
+    bool f1_blk32(const Chunks& c) const {
+        Products t = *this;
+        t.f1blk = true;
+        return g_blk32 >= 1 && t.all_h256(c, P_FC1 | P_FC2);
+    }
+};
 
 int tap_index(const int32_t* tap_layers, int n, int layer) {
     for (int k = 0; k < n; ++k)
         if (tap_layers[k] == layer) return k;
     return -1;
 }
-
-// process-wide OVERRIDE of the weights structs' `full_blocks` field (bench.py, tests; not declared in include/iisan_hip.h):
-// 1 = run every block of the tower on every token, as the reference does
-int g_full_blocks = 0;
 
 int max_tap(const int32_t* tap_layers, int n) {
     int m = 0;
@@ -174,9 +162,8 @@ int max_tap(const int32_t* tap_layers, int n) {
 }
 
 int check_common(int hidden, int layers, int heads, int mlp, int n_taps, const int32_t* tap_layers) {
-    // the widths the row kernels are instantiated at (rowops.hip): ViT-B / BERT-base, ViT-L / BERT-large, and the narrow towers — BERT-tiny
-    // (128), ViT-tiny (192), BERT-mini (256), ViT-small (384)
-    IISAN_CHECK_SHAPE(hidden == 768 || hidden == 1024 || hidden == 128 || hidden == 192 || hidden == 256 || hidden == 384,
+    // ViT-B / BERT-base, ViT-L / BERT-large, and the narrow towers — BERT-tiny (128), ViT-tiny (192), BERT-mini (256), ViT-small (384)
+    IISAN_CHECK_SHAPE(row_width_instantiated(hidden),
                       "encoder hidden size %d not supported: the supported widths are 768 (12 heads) and 1024 (16 heads), "
                       "and 128, 192, 256, 384 (2, 3, 4, 6 heads)", hidden);
     IISAN_CHECK_SHAPE(heads > 0 && hidden == heads * 64, "encoder head_dim must be 64 (hidden %d, heads %d; supported: 768 / 12 and 1024 / 16, "
@@ -188,6 +175,62 @@ int check_common(int hidden, int layers, int heads, int mlp, int n_taps, const i
         IISAN_CHECK_SHAPE(tap_layers[k] >= 0 && tap_layers[k] <= layers, "tap layer %d outside 0..%d", tap_layers[k], layers);
     return IISAN_OK;
 }
+// (past 224 tokens the attention steps run the streaming-softmax kernel, attn16_long.hip; everything else takes T as it comes)
+int vit_check_tokens(int T) {
+    IISAN_CHECK_SHAPE(T <= 1024, "vit: %d tokens per image > 1024 not supported", T);
+    return IISAN_OK;
+}
+int bert_check_words(int words, int max_pos) {
+    IISAN_CHECK_SHAPE(words >= 1 && words <= max_pos && words <= 1024, "bert: %d words unsupported (at most max_pos = %d positions, and 1024)", words, max_pos);
+    return IISAN_OK;
+}
+
+// The LayerNorm-folded routes — fold_ln_weights, the stream statistics, the block-major stream — take fp16 operands and are 768 wide: a
+// bf16 tower, a 1024-wide one and the narrow ones (128 - 384) run on the LayerNorm-image route whatever ln_fold says, and ask for no folded set
+bool vit_fold_routes(int dtype16, int hidden) { return dtype16 == IISAN_F16 && hidden == 768; }
+
+// One chunk of a forward: mc items from item m0 of the call on, tok = mc * T token rows, tp = their rows of the tap tensor
+struct Chunk : Products {
+    const EncBufs& b; hipStream_t s; float eps;
+    bool mixed;     // fp32 CLS rows in Xc + a 16-bit stream for the other rows; false: the whole stream fp32 in X (dev knob resid32)
+    int64_t m0, mc, tok; float* tp; int n_taps;
+
+    // the description of a product + its pointers
+    int launch(Product p, const void* A, const void* W, const float* bias, void* out) const {
+        p.a.A = A; p.a.W = W; p.a.bias = bias; p.a.out = out;
+        if (p.a.rowstat) p.a.rowstat = b.RS;
+        if (p.a.rowpart) p.a.rowpart = b.RP;
+        return launch_gemm16(dt, p.mode, p.a, s);
+    }
+    // the CLS rows of the current hidden state — rows of X at stride T, or the compact CLS stream itself — into tap slot k of n
+    int gather_cls(float* out, int n, int k) const {
+        return mixed ? launch_gather_cls(b.Xc, out, mc, 1, D, n, k, s) : launch_gather_cls(b.X, out, mc, T, D, n, k, s);
+    }
+    int tap(int k) const { return gather_cls(tp, n_taps, k); }
+
+    // The last LIVE block when later blocks are dead code, once the tower has put K / V of every token into QKV (head-major; the q third of the
+    // buffer is left untouched) and the CLS rows of the block's 16-bit input into Cls: only the CLS token's output is consumed, so Q, attention,
+    // O, both adds, FC1 and FC2 run on one row per item; the result, hidden state l + 1 (before any final LayerNorm), goes to
+    // tap k.  The towers differ in the attention launch (attn_drop: the train-mode kernel) and in the adds — pre-LN: x += delta, LN2 in front
+    // of FC1; post_ln: x = LN(x + keep * delta) with ln1 / ln2.
+    int cls_tail(const iisan_layer_weights& L, const float* key_bias, const DropCfg* attn_drop, bool post_ln, const RowKeep* keep1,
+                 const RowKeep* keep2, int k) const {
+        void* Qc = (char*)b.Cls + (size_t)b.Mcp * D * 2;       // compact [mc, D] 16-bit views in their own scratch: CLS rows of the input, their Q
+        IISAN_TRY(launch(plain(EPI_OUT16, D, D, mc), b.Cls, L.qkv_w, L.qkv_b, Qc));
+        if (attn_drop) IISAN_TRY(launch_attention16_drop(dt, b.QKV, key_bias, b.H, mc, T, heads, *attn_drop, m0, true, Qc, s));
+        else IISAN_TRY(launch_attention_cls16(dt, b.QKV, key_bias, b.H, mc, T, heads, s, Qc));
+        float* Xc = (float*)b.QKV;      // free once the CLS attention has run (stream order)
+        IISAN_TRY(launch(plain(EPI_OUT16, D, D, mc), b.H, L.o_w, L.o_b, b.D16));
+        IISAN_TRY(gather_cls(Xc, 1, 0));
+        if (post_ln) IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln1_w, L.ln1_b, eps, nullptr, b.H, Xc, mc, D, s, keep1));
+        else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, eps, Xc, b.H, nullptr, mc, D, s));
+        IISAN_TRY(launch(plain(EPI_GELU16, D, F, mc), b.H, L.fc1_w, L.fc1_b, b.F1));
+        IISAN_TRY(launch(plain(EPI_OUT16, F, D, mc), b.F1, L.fc2_w, L.fc2_b, b.D16));
+        if (post_ln) IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, eps, nullptr, nullptr, Xc, mc, D, s, keep2));
+        else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, nullptr, nullptr, eps, Xc, nullptr, nullptr, mc, D, s));
+        return launch_gather_cls(Xc, tp, mc, 1, D, n_taps, k, s);
+    }
+};
 
 }  // namespace
 
@@ -195,10 +238,8 @@ IISAN_DEV_KNOB(full_blocks, g_full_blocks);
 IISAN_DEV_KNOB(resid32, g_resid32);
 IISAN_DEV_KNOB(ln_fold, g_ln_fold);
 IISAN_DEV_KNOB(blk32, g_blk32);
-// (the LayerNorm-folded routes — fold_ln_weights, the stream statistics, the block-major stream — are 768 wide: a 1024-wide tower and the
-//  narrow ones (128 - 384) run on the LayerNorm-image route whatever ln_fold says, and ask for no folded set)
 static int vit_fold_layers(const iisan_vit_weights* w) {
-    return (!g_resid32 && g_ln_fold && w->dtype16 == IISAN_F16 && w->hidden == 768) ? w->layers : 0;
+    return (!g_resid32 && g_ln_fold && vit_fold_routes(w->dtype16, w->hidden)) ? w->layers : 0;
 }
 // the folded set of one tower: [layers][(3D + F) x D] fp16, then [layers][3D + F] fp32 (the caller's `folded` buffer or the workspace)
 static size_t vit_fold_w_elems(const iisan_vit_weights* w) { return (size_t)(3 * w->hidden + w->mlp) * w->hidden; }
@@ -219,7 +260,7 @@ static int vit_fold_all(const iisan_vit_weights* w, int layers, bool last_fc1, c
 }
 
 extern "C" size_t iisan_vit_fold_bytes(const iisan_vit_weights* w) {
-    if (w->dtype16 != IISAN_F16 || w->hidden != 768) return 0;
+    if (!vit_fold_routes(w->dtype16, w->hidden)) return 0;
     return (size_t)w->layers * (vit_fold_w_elems(w) * 2 + (size_t)(3 * w->hidden + w->mlp) * 4);
 }
 
@@ -234,62 +275,68 @@ extern "C" int iisan_vit_fold_layernorm(const iisan_vit_weights* w, void* folded
     return vit_fold_all(w, w->layers, true, (char*)folded, (float*)((char*)folded + (size_t)w->layers * vit_fold_w_elems(w) * 2), (hipStream_t)stream);
 }
 
-extern "C" size_t iisan_vit_forward_taps_ws_bytes(const iisan_vit_weights* w, int64_t M, int64_t chunk_items) {
-    const int64_t Mc = (chunk_items > 0 && chunk_items < M) ? chunk_items : M;
+// the workspace of a ViT call that runs in chunks of Mc items (c.off: its size)
+static void vit_carve(WsCarver& c, EncBufs& b, const iisan_vit_weights* w, int64_t Mc) {
     const int P = (w->image / w->patch) * (w->image / w->patch);
     const int pd = w->channels * w->patch * w->patch;
+    carve(c, b, Mc * (P + 1), Mc, w->hidden, w->mlp > pd ? w->mlp : pd, 0, vit_fold_layers(w), w->folded == nullptr);
+}
+
+extern "C" size_t iisan_vit_forward_taps_ws_bytes(const iisan_vit_weights* w, int64_t M, int64_t chunk_items) {
     WsCarver c(nullptr, 0);
     EncBufs b;
-    return carve(c, b, Mc * (P + 1), Mc, w->hidden, w->mlp > pd ? w->mlp : pd, 0, vit_fold_layers(w), w->folded == nullptr);
+    vit_carve(c, b, w, Chunks(M, chunk_items).Mc);
+    return c.off;
 }
 
 namespace {
 
-// How one call carries the residual stream of the pre-LN tower; decided once per call (vit_strategy).  Each strategy is three steps of
-// VitChunk, every one a complete launch list: `open` (the stream becomes hidden state l; LN1), a full block, `close` (the last hidden
-// state, when it is tapped).
+// How one call carries the residual stream of the pre-LN tower; decided once per call (vit_plan).  Each strategy is three steps of
+// VitChunk (VIT_STEPS): `open` (the stream becomes hidden state l; LN1), `mid` (between the O and the FC1 product of an all-token block:
+// LN2) and `close` (the last hidden state, when it is tapped).  The products around them are those of Products under the strategy's flags.
 enum VitStrategy {
     VS_RESID32,     // dev knob resid32: the whole stream fp32 in X, LayerNorm images in H
     VS_IMAGE,       // mixed stream (fp16 rows in X16, fp32 CLS rows in Xc), LayerNorm images in H: ln_fold = 0, bf16 operands, small batches
     VS_FOLD,        // mixed stream, no image: the add kernels leave rstd per row, the QKV / FC1 products apply LayerNorm (ln_fold = 1)
     VS_STREAM,      // ... and no add kernels: the O / FC2 products add into the stream in their epilogues (ln_fold = 2, the product route)
 };
+struct VitPlan {
+    VitStrategy st;
+    bool folds;     // the call folds the LayerNorms into the weights itself (the weights struct carries no folded set)
+};
 
-// LayerNorm in the epilogues of the QKV / FC1 products (g_ln_fold) only where those products run on the kernel that has it, and the
-// residual adds in the epilogues of the O / FC2 products likewise — for every chunk size of this call (the last chunk may be shorter)
-VitStrategy vit_strategy(const iisan_vit_weights* w, const EncBufs& b, int live, bool full_blocks, int64_t M, int64_t Mc, int T) {
-    if (g_resid32) return VS_RESID32;
-    if (!b.Wf || live == 0 || w->hidden != 768) return VS_IMAGE;       // (any other width: b.Wf is null already — vit_fold_layers)
-    const int dt = w->dtype16, D = w->hidden, F = w->mlp;
-    bool fold = true, stream = g_ln_fold >= 2;
-    for (int64_t mc : {Mc, M % Mc == 0 ? Mc : M % Mc}) {
-        const int64_t tok = mc * T;
-        auto h256 = [&](int mode, const Gemm16Args& a) { return gemm16_route(dt, mode, a) == G16_H256; };
-        fold = fold && h256(EPI_QKVH16, gemm_args(EPI_QKVH16, nullptr, D, nullptr, nullptr, nullptr, 3 * D, tok, T, w->heads, 0, b.RS)) &&
-               h256(EPI_GELU16, gemm_args(EPI_GELU16, nullptr, D, nullptr, nullptr, nullptr, F, tok, 0, 0, 0, b.RS)) &&
-               (full_blocks || h256(EPI_QKVH16, gemm_args(EPI_QKVH16, nullptr, D, nullptr, nullptr, nullptr, 2 * D, tok, T, w->heads, 1, b.RS)));
-        Gemm16Args o = gemm_args(EPI_STREAM16, nullptr, D, nullptr, nullptr, nullptr, D, tok, T), f = gemm_args(EPI_STREAM16, nullptr, F, nullptr, nullptr, nullptr, D, tok, T);
-        o.rowpart = f.rowpart = b.RP;
-        stream = stream && h256(EPI_STREAM16, o) && h256(EPI_STREAM16, f);
+// The strategy and the two layouts of a ViT call, left in p.  LayerNorm in the epilogues of the QKV / FC1 products (g_ln_fold) only where
+// those products run on the kernel that has it, and the residual adds in the epilogues of the O / FC2 products likewise.  The stream is
+// block-major only on the product route, with F1 block-major, and only when every product that touches it takes the flags: QKV and FC1 (A),
+// O and FC2 (read-modify-write), the K/V product of a CLS-only last block (A).
+VitPlan vit_plan(Products& p, int live, bool full_blocks, bool folded, const Chunks& c) {
+    if (g_resid32) return {VS_RESID32, false};
+    const int reads = Products::P_QKV | Products::P_FC1 | (full_blocks ? 0 : Products::P_KV), adds = Products::P_O | Products::P_FC2;
+    Products t = p;
+    t.ln = true;
+    if (live > 0 && g_ln_fold && vit_fold_routes(p.dt, p.D) && t.all_h256(c, reads)) {
+        p = t;
+        t.stream = true;
+        if (g_ln_fold >= 2 && t.all_h256(c, adds)) p = t;
     }
-    return !fold ? VS_IMAGE : stream ? VS_STREAM : VS_FOLD;
+    t = p;
+    t.f1blk = t.xblk = true;
+    if (g_blk32 >= 2 && p.stream && t.all_h256(c, reads | adds)) p = t;
+    else p.f1blk = p.f1_blk32(c);
+    const VitStrategy st = !p.ln ? VS_IMAGE : p.stream ? VS_STREAM : VS_FOLD;
+    return {st, st >= VS_FOLD && !folded};
 }
 
 constexpr int MX_ADD_STAT = MX_D1 | MX_RESV | MX_STAT;       // x += d (fp16 stream, fp32 CLS rows); row statistics
 
-// One chunk of a ViT forward: mc items, tok = mc * T token rows, tp = their rows of the tap tensor.
+// One chunk of a ViT forward.
 // The O / FC2 products of resid32 / image / fold emit 16-bit DELTAS (dO in D16, dF in D16b); the residual add is fused into a later
 // LayerNorm kernel (HBM-bound) instead of a read-modify-write GEMM epilogue.  Pre-LN tower, resid32 / image: LN2 computes LN(x + dO)
 // WITHOUT writing x back; the next open step adds both deltas, (x + dO) + dF in fp32 — the same value — and writes x once per block
 // instead of twice.
-struct VitChunk {
-    const iisan_vit_weights* w; const EncBufs& b; VitStrategy st; hipStream_t s;
-    int dt, D, F, T, heads; float eps;
-    int64_t mc, tok; float* tp; int n_taps;
-    bool f1blk;     // F1 of the full blocks is block-major (f1_blk32, decided once per call)
-    bool xblk;      // ... and so is the stream X16 (x16_blk32; VS_STREAM only)
+struct VitChunk : Chunk {
+    const iisan_vit_weights* w;
 
-    bool mixed() const { return st != VS_RESID32; }
     const iisan_layer_weights& layer(int l) const { return w->layer[l]; }
     // the folded set of layer l (vit_fold_all)
     char* Wf_qkv(int l) const { return (char*)b.Wf + (size_t)l * (3 * D + F) * D * 2; }
@@ -304,30 +351,20 @@ struct VitChunk {
         else IISAN_TRY(launch_vit_im2col(dt, img, img_u8, b.F1, mc, w->channels, w->image, w->patch, s));
         // patch embedding: resid32 = fp32 token rows with the position embedding added (128x128 kernel); mixed = 16-bit rows on the
         // production GEMM (gemm16_h256, 0.40 against 0.59 ms at bs = 128), the position table is added by block 0's open step
-        if (mixed()) IISAN_TRY(gemm(dt, EPI_PATCH16, b.F1, pd, w->patch_w, w->patch_b, b.D16b, D, nullptr, mc * P, s, nullptr, P));
-        else IISAN_TRY(gemm(dt, EPI_PATCH32, b.F1, pd, w->patch_w, w->patch_b, b.X, D, nullptr, mc * P, s, w->pos_emb, P));
+        Product pe = patch(!mixed, pd, D, mc * P, P);
+        pe.a.pos = mixed ? nullptr : w->pos_emb;
+        IISAN_TRY(launch(pe, b.F1, w->patch_w, w->patch_b, mixed ? b.D16b : (void*)b.X));
         // CLS rows: cls + pos[0] — into the fp32 stream (token-major) or into the compact fp32 CLS stream
-        return launch_vit_cls_rows(mixed() ? b.Xc : b.X, w->cls_token, w->pos_emb, mc, mixed() ? 1 : T, D, s);
+        return launch_vit_cls_rows(mixed ? b.Xc : b.X, w->cls_token, w->pos_emb, mc, mixed ? 1 : T, D, s);
     }
-    // the tapped rows of the current hidden state: CLS rows of X (stride T) or the compact CLS stream itself
-    int tap(int k) const { return mixed() ? launch_gather_cls(b.Xc, tp, mc, 1, D, n_taps, k, s) : launch_gather_cls(b.X, tp, mc, T, D, n_taps, k, s); }
-
     // ---- VS_RESID32 ------------------------------------------------------------------------------------------------------------
     int open_resid32(int l) const {     // x += dO + dF of block l - 1 ; h = LN1(x)
         const iisan_layer_weights& L = layer(l);
         if (l == 0) return launch_add2_layernorm768(dt, b.X, nullptr, nullptr, L.ln1_w, L.ln1_b, eps, nullptr, b.H, nullptr, tok, D, s);
         return launch_add2_layernorm768(dt, b.X, b.D16, b.D16b, L.ln1_w, L.ln1_b, eps, b.X, b.H, nullptr, tok, D, s);
     }
-    int full_resid32(int l) const {
-        const iisan_layer_weights& L = layer(l);
-        IISAN_TRY(gemm(dt, EPI_QKVH16, b.H, D, L.qkv_w, L.qkv_b, b.QKV, 3 * D, nullptr, tok, s, nullptr, 0, T, heads));
-        IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
-        IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
-        // h = LN2(x + dO)   (x itself is updated by the next open step)
-        IISAN_TRY(launch_add_layernorm768(dt, b.X, b.D16, L.ln2_w, L.ln2_b, eps, nullptr, b.H, nullptr, tok, D, s));
-        IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, tok, s));
-        return gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, nullptr, tok, s);
-    }
+    // h = LN2(x + dO)   (x itself is updated by the next open step)
+    int mid_resid32(int l) const { return launch_add_layernorm768(dt, b.X, b.D16, layer(l).ln2_w, layer(l).ln2_b, eps, nullptr, b.H, nullptr, tok, D, s); }
     int close_resid32() const { return launch_add2_layernorm768(dt, b.X, b.D16, b.D16b, nullptr, nullptr, eps, b.X, nullptr, nullptr, tok, D, s); }
 
     // ---- VS_IMAGE ----------------------------------------------------------------------------------------------------------------
@@ -337,16 +374,8 @@ struct VitChunk {
             return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_LN, w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, L.ln1_w, L.ln1_b, eps, b.H, mc, T, D, s);
         return launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_LN, nullptr, b.X16, b.Xc, b.D16, b.D16b, L.ln1_w, L.ln1_b, eps, b.H, mc, T, D, s);
     }
-    int full_image(int l) const {
-        const iisan_layer_weights& L = layer(l);
-        IISAN_TRY(gemm(dt, EPI_QKVH16, b.H, D, L.qkv_w, L.qkv_b, b.QKV, 3 * D, nullptr, tok, s, nullptr, 0, T, heads));
-        IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
-        IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
-        // h = LN2(x + dO)   (x itself is updated by the next open step)
-        IISAN_TRY(launch_layernorm768_mixed(dt, MX_D1 | MX_LN, nullptr, b.X16, b.Xc, b.D16, nullptr, L.ln2_w, L.ln2_b, eps, b.H, mc, T, D, s));
-        IISAN_TRY(gemm_fc1(dt, b.H, D, L.fc1_w, L.fc1_b, nullptr, b.F1, F, tok, f1blk, s));
-        return gemm_fc2(dt, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, tok, f1blk, s);
-    }
+    // h = LN2(x + dO)   (x itself is updated by the next open step)
+    int mid_image(int l) const { return launch_layernorm768_mixed(dt, MX_D1 | MX_LN, nullptr, b.X16, b.Xc, b.D16, nullptr, layer(l).ln2_w, layer(l).ln2_b, eps, b.H, mc, T, D, s); }
     // only the CLS rows of the last hidden state are consumed
     int close_image() const { return launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, b.D16, b.D16b, nullptr, nullptr, eps, nullptr, mc, T, D, s); }
 
@@ -354,80 +383,57 @@ struct VitChunk {
     int patches_to_stream() const {     // position table + 16-bit patch embedding -> fp16 stream of the patch rows (the CLS rows are in Xc already)
         return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_ADD_STAT | (xblk ? MX_BLK32 : 0), w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, D, s, b.RS);
     }
-    int open_fold(int l) const {
-        if (l == 0) return patches_to_stream();
-        // x += dF of block l - 1 (x + dO is in the stream already: that block wrote it in its LN2 step)
-        return launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, D, s, b.RS);
-    }
-    int full_fold(int l) const {
-        const iisan_layer_weights& L = layer(l);
-        IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l), bf_qkv(l), b.RS, b.QKV, 3 * D, tok, s, T, heads));
-        IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
-        IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
-        // x += dO (written: the FC1 product reads the stream); LN2 in the FC1 product's epilogue
-        IISAN_TRY(launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, b.D16, nullptr, nullptr, nullptr, eps, nullptr, mc, T, D, s, b.RS));
-        IISAN_TRY(gemm_fc1(dt, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, f1blk, s));
-        return gemm_fc2(dt, b.F1, F, L.fc2_w, L.fc2_b, b.D16b, D, tok, f1blk, s);
-    }
+    // x += d in the stream; rstd of the new rows
+    int add_stat(const void* d) const { return launch_layernorm768_mixed(dt, MX_ADD_STAT, nullptr, b.X16, b.Xc, d, nullptr, nullptr, nullptr, eps, nullptr, mc, T, D, s, b.RS); }
+    // x += dF of block l - 1 (x + dO is in the stream already: that block wrote it in its mid step)
+    int open_fold(int l) const { return l == 0 ? patches_to_stream() : add_stat(b.D16b); }
+    // x += dO (written: the FC1 product reads the stream); LN2 in the FC1 product's epilogue
+    int mid_fold(int) const { return add_stat(b.D16); }
     // x + dO is in the stream: the CLS rows take dF
     int close_fold() const { return launch_layernorm768_mixed(dt, MX_D1 | MX_RESV | MX_CLSONLY, nullptr, b.X16, b.Xc, b.D16b, nullptr, nullptr, nullptr, eps, nullptr, mc, T, D, s); }
 
-    // ---- VS_STREAM: ... and the O / FC2 products add into the stream and leave its row statistics --------------------------------------
-    // x += A W^T + bias in the stream (fp16 rows in place, the CLS rows' fp32 stream through the finalize step); rstd of the new rows
-    int gemm_stream(const void* A, int K, const void* W, const float* bias, bool a_blk = false) const {
-        Gemm16Args a = gemm_args(EPI_STREAM16, A, K, W, bias, b.X16, D, tok, T);
-        a.rowpart = b.RP; a.a_blk32 = a_blk; a.out_blk32 = xblk;
-        IISAN_TRY(launch_gemm16(dt, EPI_STREAM16, a, s));
-        return launch_stream_stats_finalize(b.RP, D / 64, ceil_div(tok, 256) * 256, b.X16, b.Xc, b.RS, eps, mc, T, s, xblk);
-    }
-    int open_stream(int l) const {
-        if (l == 0) return patches_to_stream();
-        return IISAN_OK;        // the FC2 product of block l - 1 added into the stream and left its statistics
-    }
-    int full_stream(int l) const {
-        const iisan_layer_weights& L = layer(l);
-        IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l), bf_qkv(l), b.RS, b.QKV, 3 * D, tok, s, T, heads, 0, xblk));
-        IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
-        IISAN_TRY(gemm_stream(b.H, D, L.o_w, L.o_b));
-        IISAN_TRY(gemm_fc1(dt, b.X16, D, Wf_fc1(l), bf_fc1(l), b.RS, b.F1, F, tok, f1blk, s, xblk));
-        return gemm_stream(b.F1, F, L.fc2_w, L.fc2_b, f1blk);
-    }
+    // ---- VS_STREAM: ... and the O / FC2 products add into the stream and leave its row statistics: no step but the first ------------------
+    int open_stream(int l) const { return l == 0 ? patches_to_stream() : IISAN_OK; }
+    int mid_stream(int) const { return IISAN_OK; }
     int close_stream() const { return IISAN_OK; }       // the stream is the last hidden state already
 
-    // ---- the last LIVE block when later blocks are dead code: only the CLS token's output is consumed.  K/V are computed for every token,
-    // but attention, O, LN2, FC1, FC2 and the closing residual add run on one row per item; its output goes to tap k
+    // ---- the blocks: every product as Products describes it under the strategy ------------------------------------------------------------
+    // the A operand of the QKV / FC1 products: the LayerNorm image against the tower's weights, or the stream itself against the folded set
+    const void* act() const { return ln ? b.X16 : b.H; }
+    // an O / FC2 product: its 16-bit delta into `d`; VS_STREAM: x += A W^T + bias in the stream instead (fp16 rows in place, the CLS rows'
+    // fp32 stream through the finalize step) and rstd of the new rows
+    int delta(const Product& p, const void* A, const void* W, const float* bias, void* d) const {
+        if (!stream) return launch(p, A, W, bias, d);
+        IISAN_TRY(launch(p, A, W, bias, b.X16));
+        return launch_stream_stats_finalize(b.RP, D / 64, ceil_div(tok, 256) * 256, b.X16, b.Xc, b.RS, eps, mc, T, s, xblk);
+    }
+    int full_block(int l, int (VitChunk::*mid)(int) const) const {
+        const iisan_layer_weights& L = layer(l);
+        IISAN_TRY(launch(qkv(tok), act(), ln ? Wf_qkv(l) : L.qkv_w, ln ? bf_qkv(l) : L.qkv_b, b.QKV));
+        IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
+        IISAN_TRY(delta(o(tok), b.H, L.o_w, L.o_b, b.D16));
+        IISAN_TRY((this->*mid)(l));
+        IISAN_TRY(launch(fc1(tok), act(), ln ? Wf_fc1(l) : L.fc1_w, ln ? bf_fc1(l) : L.fc1_b, b.F1));
+        return delta(fc2(tok), b.F1, L.fc2_w, L.fc2_b, b.D16b);
+    }
+    // the CLS-only last live block (Chunk::cls_tail); its output goes to tap k
     int cls_block(int l, int k) const {
         const iisan_layer_weights& L = layer(l);
-        // CLS rows only: compact [mc, D] 16-bit views in their own scratch
-        void* Hc = b.Cls;
-        void* Qc = (char*)b.Cls + (size_t)b.Mcp * D * 2;
-        if (st == VS_FOLD || st == VS_STREAM) {
-            // K / V of every token from the stream (LN1 in the epilogue); the CLS rows' LN1 image from their fp32 stream
-            IISAN_TRY(launch_layernorm768(dt, b.Xc, L.ln1_w, L.ln1_b, eps, Hc, nullptr, mc, D, s));
-            IISAN_TRY(gemm_ln(dt, EPI_QKVH16, b.X16, D, Wf_qkv(l) + (size_t)D * D * 2, bf_qkv(l) + D, b.RS, b.QKV, 2 * D, tok, s, T, heads, 1, xblk));
-            IISAN_TRY(gemm(dt, EPI_OUT16, Hc, D, L.qkv_w, L.qkv_b, Qc, D, nullptr, mc, s));
-        } else {
-            IISAN_TRY(launch_gather_rows16(b.H, Hc, mc, T, D, s));            // CLS rows of LN1(x)
-            IISAN_TRY(kv_all_q_cls(dt, L, b.H, b.QKV, Hc, Qc, tok, mc, T, heads, D, s));
-        }
-        IISAN_TRY(launch_attention_cls16(dt, b.QKV, nullptr, b.H, mc, T, heads, s, Qc));
-        float* Xc = (float*)b.QKV;      // free once the CLS attention has run (stream order)
-        IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, mc, s));
-        if (mixed()) IISAN_TRY(launch_gather_cls(b.Xc, Xc, mc, 1, D, 1, 0, s)); else IISAN_TRY(launch_gather_cls(b.X, Xc, mc, T, D, 1, 0, s));
-        IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, eps, Xc, b.H, nullptr, mc, D, s));
-        IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, mc, s));
-        IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, nullptr, mc, s));
-        IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, nullptr, nullptr, eps, Xc, nullptr, nullptr, mc, D, s));
-        return launch_gather_cls(Xc, tp, mc, 1, D, n_taps, k, s);     // hidden state `live` (before any final LayerNorm)
+        // the CLS rows' LN1 image: from their fp32 stream, or gathered from the image of every row
+        if (ln) IISAN_TRY(launch_layernorm768(dt, b.Xc, L.ln1_w, L.ln1_b, eps, b.Cls, nullptr, mc, D, s));
+        else IISAN_TRY(launch_gather_rows16(b.H, b.Cls, mc, T, D, s));
+        // K / V of every token (ln: from the stream, LN1 in the epilogue): the last two thirds of the QKV weights
+        IISAN_TRY(launch(qkv(tok, 1), act(), (ln ? Wf_qkv(l) : (const char*)L.qkv_w) + (size_t)D * D * 2, (ln ? bf_qkv(l) : L.qkv_b) + D, b.QKV));
+        return cls_tail(L, nullptr, nullptr, false, nullptr, nullptr, k);
     }
 };
 
 // the three steps of every strategy, indexed by VitStrategy
-const struct { int (VitChunk::*open)(int) const; int (VitChunk::*full)(int) const; int (VitChunk::*close)() const; } VIT_STEPS[] = {
-    {&VitChunk::open_resid32, &VitChunk::full_resid32, &VitChunk::close_resid32},
-    {&VitChunk::open_image, &VitChunk::full_image, &VitChunk::close_image},
-    {&VitChunk::open_fold, &VitChunk::full_fold, &VitChunk::close_fold},
-    {&VitChunk::open_stream, &VitChunk::full_stream, &VitChunk::close_stream},
+const struct { int (VitChunk::*open)(int) const; int (VitChunk::*mid)(int) const; int (VitChunk::*close)() const; } VIT_STEPS[] = {
+    {&VitChunk::open_resid32, &VitChunk::mid_resid32, &VitChunk::close_resid32},
+    {&VitChunk::open_image, &VitChunk::mid_image, &VitChunk::close_image},
+    {&VitChunk::open_fold, &VitChunk::mid_fold, &VitChunk::close_fold},
+    {&VitChunk::open_stream, &VitChunk::mid_stream, &VitChunk::close_stream},
 };
 
 }  // namespace
@@ -441,35 +447,33 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
     IISAN_CHECK_SHAPE(M > 0, "vit_forward_taps: M must be positive");
     IISAN_TRY(check_common(w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
     IISAN_CHECK_SHAPE(w->patch % 8 == 0 && w->image % w->patch == 0, "vit: patch %d / image %d unsupported", w->patch, w->image);
-    const int D = w->hidden, F = w->mlp, P = (w->image / w->patch) * (w->image / w->patch), T = P + 1;
+    const int D = w->hidden, T = (w->image / w->patch) * (w->image / w->patch) + 1;
     const int pd = w->channels * w->patch * w->patch;
     IISAN_CHECK_SHAPE(pd % 64 == 0, "vit: patch vector length %d must be a multiple of 64", pd);
-    // (past 224 tokens the attention steps run the streaming-softmax kernel, attn16_long.hip; everything else takes T as it comes)
-    IISAN_CHECK_SHAPE(T <= 1024, "vit: %d tokens per image > 1024 not supported", T);
-    const int64_t Mc = (chunk_items > 0 && chunk_items < M) ? chunk_items : M;
-    WsCarver c(ws, ws_bytes);
+    IISAN_TRY(vit_check_tokens(T));
+    const Chunks c(M, chunk_items);
+    WsCarver cv(ws, ws_bytes);
     EncBufs b;
-    carve(c, b, Mc * T, Mc, D, F > pd ? F : pd, 0, vit_fold_layers(w), w->folded == nullptr);
+    vit_carve(cv, b, w, c.Mc);
     if (w->folded && b.RS) {       // the caller folded once (iisan_vit_fold_layernorm)
         b.Wf = const_cast<void*>(w->folded);
         b.Bf = (float*)((char*)b.Wf + (size_t)w->layers * vit_fold_w_elems(w) * 2);
     }
-    if (c.overflow || !ws) {
-        iisan_set_error("vit_forward_taps: workspace too small (%zu < %zu)", ws_bytes, c.off);
+    if (cv.overflow || !ws) {
+        iisan_set_error("vit_forward_taps: workspace too small (%zu < %zu)", ws_bytes, cv.off);
         return IISAN_EWORKSPACE;
     }
     const bool full_blocks = g_full_blocks || w->full_blocks;
     // Blocks after the deepest tapped hidden state are dead code (Versa configurations tap a prefix of the tower)
     const int live = full_blocks ? w->layers : max_tap(tap_layers, n_taps);
-    const VitStrategy st = vit_strategy(w, b, live, full_blocks, M, Mc, T);
-    const auto& step = VIT_STEPS[st];
-    const bool xblk = st == VS_STREAM && x16_blk32(w->dtype16, D, F, w->heads, M, Mc, T, full_blocks, b.RS, b.RP);
-    const bool f1blk = xblk || (st != VS_RESID32 && f1_blk32(w->dtype16, D, F, M, Mc, T, st >= VS_FOLD ? b.RS : nullptr, st == VS_STREAM ? EPI_STREAM16 : EPI_OUT16, b.RP));
-    if (st >= VS_FOLD && !w->folded) IISAN_TRY(vit_fold_all(w, live, full_blocks, (char*)b.Wf, b.Bf, s));
+    Products p{w->dtype16, D, w->mlp, T, w->heads};
+    const VitPlan plan = vit_plan(p, live, full_blocks, w->folded != nullptr, c);
+    const auto& step = VIT_STEPS[plan.st];
+    if (plan.folds) IISAN_TRY(vit_fold_all(w, live, full_blocks, (char*)b.Wf, b.Bf, s));
     const int64_t img_elems = (int64_t)w->channels * w->image * w->image;
-    for (int64_t m0 = 0; m0 < M; m0 += Mc) {
-        const int64_t mc = (M - m0 < Mc) ? M - m0 : Mc;
-        const VitChunk ch{w, b, st, s, w->dtype16, D, F, T, w->heads, w->eps, mc, mc * T, taps + m0 * n_taps * D, n_taps, f1blk, xblk};
+    for (int64_t m0 = 0; m0 < M; m0 += c.Mc) {
+        const int64_t mc = (M - m0 < c.Mc) ? M - m0 : c.Mc;
+        const VitChunk ch{{p, b, s, w->eps, plan.st != VS_RESID32, m0, mc, mc * T, taps + m0 * n_taps * D, n_taps}, w};
         if (index) IISAN_TRY(ch.embed(images, 1, index + m0, rows));
         else IISAN_TRY(ch.embed(img_u8 ? (const void*)((const uint8_t*)images + m0 * img_elems) : (const void*)((const float*)images + m0 * img_elems), img_u8));
         int k = tap_index(tap_layers, n_taps, 0);
@@ -478,7 +482,7 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
             IISAN_TRY((ch.*step.open)(l));       // -> the stream is hidden state l
             k = tap_index(tap_layers, n_taps, l);
             if (k >= 0 && l > 0) IISAN_TRY(ch.tap(k));
-            if (l + 1 < live || full_blocks) IISAN_TRY((ch.*step.full)(l));
+            if (l + 1 < live || full_blocks) IISAN_TRY(ch.full_block(l, step.mid));
             else IISAN_TRY(ch.cls_block(l, tap_index(tap_layers, n_taps, live)));
         }
         k = full_blocks ? tap_index(tap_layers, n_taps, w->layers) : -1;
@@ -514,16 +518,82 @@ extern "C" int iisan_vit_forward_taps_u8_indexed(const iisan_vit_weights* w, con
 }
 
 extern "C" size_t iisan_bert_forward_taps_ws_bytes(const iisan_bert_weights* w, int64_t M, int32_t words, int64_t chunk_items) {
-    const int64_t Mc = (chunk_items > 0 && chunk_items < M) ? chunk_items : M;
+    const int64_t Mc = Chunks(M, chunk_items).Mc;
     WsCarver c(nullptr, 0);
     EncBufs b;
     return carve(c, b, Mc * words, Mc, w->hidden, w->mlp, Mc * words);
 }
 
+namespace {
+
+// What a BERT call decides before its first launch, beside p.f1blk.  Post-LN tower: the stream IS the LayerNorm output.  resid32: X fp32
+// [tok, D]; mixed: Xc fp32 (CLS rows) + X16 fp16.  alias: with fp16 operands the 16-bit image the products read and the fp16 stream are the same
+// values: one buffer, written once (g_ln_fold; the add + LayerNorm kernels move 6 instead of 8 bytes per element)
+struct BertPlan { bool mixed, alias; };
+BertPlan bert_plan(Products& p, const Chunks& c) {
+    p.f1blk = p.f1_blk32(c);
+    const bool mixed = !g_resid32;
+    return {mixed, mixed && p.dt == IISAN_F16 && g_ln_fold != 0};
+}
+
+// One chunk of a BERT forward.  Eval mode (dropping = false) is the launch sequence below with null keeps; in train mode the attention kernel of
+// bert_drop.hip takes the place of the eval-mode one, and the embedding and add + LayerNorm steps run their train-mode instantiations (a RowKeep
+// instead of null; rowops.hip) — sites 0, 1 + 3l, 2 + 3l, 3 + 3l and their indices: include/iisan_hip.h, iisan_bert_dropout
+struct BertChunk : Chunk {
+    const iisan_bert_weights* w; bool alias, dropping; float hp, ap; uint64_t seed;
+
+    void* img() const { return alias ? b.X16 : b.H; }       // the 16-bit image of the stream: the A operand of the QKV / FC1 products
+    // train mode: the keep functor of a hidden site, local row r of the launch = token row m0 * T + r * rs of the whole call (rs = 1: the rows of
+    // the chunk; rs = T: compact CLS rows, the masks of token row t = 0 of the all-token execution); eval: null
+    struct Keep {
+        RowKeep rk; bool on;
+        operator const RowKeep*() const { return on ? &rk : nullptr; }
+    };
+    Keep keep(int site, int rs) const { return {RowKeep{make_drop(seed, site, hp), m0 * T, rs}, dropping}; }
+    DropCfg attn_drop(int l) const { return make_drop(seed, 1 + 3 * l, ap); }
+
+    // index != null: `text` is a resident table [rows, 2W] and item m of the chunk is its row index[m0 + m]
+    int embed(const int64_t* text, const int64_t* index, int64_t rows) const {
+        const Keep k = keep(0, 1);
+        if (index) return launch_bert_embed_ln_indexed(dt, text, rows, index + m0, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b, w->eps,
+                                                       mixed ? nullptr : b.X, img(), b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc, k);
+        return launch_bert_embed_ln(dt, text + m0 * 2 * T, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b, w->eps,
+                                    mixed ? nullptr : b.X, img(), b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc, k);
+    }
+    // x = LN(x + delta): stream and 16-bit image out
+    int add_ln(const float* g, const float* be, int site) const {
+        const Keep k = keep(site, 1);
+        return mixed ? launch_layernorm768_mixed(dt, MX_D1 | MX_LN | MX_RESY | (alias ? MX_ALIAS : 0), nullptr, b.X16, b.Xc, b.D16, nullptr, g, be, eps, img(), mc, T, D, s, nullptr, k)
+                     : launch_add_layernorm768(dt, b.X, b.D16, g, be, eps, nullptr, b.H, b.X, tok, D, s);
+    }
+    int full_block(int l) const {
+        const iisan_layer_weights& L = w->layer[l];
+        // a = LN(x + O(attn(x)))
+        IISAN_TRY(launch(qkv(tok), img(), L.qkv_w, L.qkv_b, b.QKV));
+        if (dropping) IISAN_TRY(launch_attention16_drop(dt, b.QKV, b.KB, b.H, mc, T, heads, attn_drop(l), m0, false, nullptr, s));
+        else IISAN_TRY(launch_attention16(dt, b.QKV, b.KB, b.H, mc, T, heads, s));
+        IISAN_TRY(launch(o(tok), b.H, L.o_w, L.o_b, b.D16));
+        IISAN_TRY(add_ln(L.ln1_w, L.ln1_b, 2 + 3 * l));
+        // x = LN(a + FC2(gelu(FC1 a)))
+        IISAN_TRY(launch(fc1(tok), img(), L.fc1_w, L.fc1_b, b.F1));
+        IISAN_TRY(launch(fc2(tok), b.F1, L.fc2_w, L.fc2_b, b.D16));
+        return add_ln(L.ln2_w, L.ln2_b, 3 + 3 * l);
+    }
+    // the CLS-only last live block (Chunk::cls_tail).  Post-LN tower: the block input is the 16-bit image of x, so its CLS rows are gathered directly
+    int cls_block(int l, int k) const {
+        const iisan_layer_weights& L = w->layer[l];
+        IISAN_TRY(launch_gather_rows16(img(), b.Cls, mc, T, D, s));
+        IISAN_TRY(launch(qkv(tok, 1), img(), (const char*)L.qkv_w + (size_t)D * D * 2, L.qkv_b + D, b.QKV));
+        const DropCfg ad = attn_drop(l);
+        const Keep k1 = keep(2 + 3 * l, T), k2 = keep(3 + 3 * l, T);
+        return cls_tail(L, b.KB, dropping ? &ad : nullptr, true, k1, k2, k);
+    }
+};
+
+}  // namespace
+
 // index != null: `text` is a resident table [rows, 2W] and slot m reads row index[m] (the chunk loop offsets the index, never the table)
-// drop: null or both probabilities 0 = eval mode, the launch sequence below unchanged; otherwise the attention kernel of bert_drop.hip takes
-// the place of the eval-mode one, and the embedding and add + LayerNorm steps run their train-mode instantiations (a RowKeep instead of
-// null; rowops.hip) — sites and indices: include/iisan_hip.h, iisan_bert_dropout
+// drop: null or both probabilities 0 = eval mode; otherwise train mode (BertChunk)
 static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* text, int64_t M, int32_t words,
                                   const int32_t* tap_layers, int32_t n_taps, float* taps, int64_t chunk_items,
                                   void* ws, size_t ws_bytes, void* stream, const int64_t* index = nullptr, int64_t rows = 0,
@@ -539,91 +609,38 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
     // ... and for 768-wide rows only (rowops.hip): tap caches of the wide and the narrow towers are built in eval mode
     IISAN_CHECK_SHAPE(!(dropping && w->hidden != 768), "bert dropout: no train-mode instantiation at this width, hidden size %d runs in eval mode only "
                       "(drop == NULL or both probabilities 0)", w->hidden);
-    const float hp = dropping ? drop->hidden_p : 0.f, ap = dropping ? drop->attn_p : 0.f;
-    const uint64_t seed = dropping ? drop->seed : 0;
     IISAN_CHECK_SHAPE(M > 0, "bert_forward_taps: M must be positive");
     IISAN_TRY(check_common(w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
-    IISAN_CHECK_SHAPE(words >= 1 && words <= w->max_pos && words <= 1024, "bert: %d words unsupported (at most max_pos = %d positions, and 1024)", words,
-                      w->max_pos);
+    IISAN_TRY(bert_check_words(words, w->max_pos));
     // ... and the train-mode attention kernel keeps a whole head in LDS (bert_drop.hip): refused here, before any launch, never a silent fall-back
     IISAN_CHECK_SHAPE(!(dropping && words > 224), "bert dropout: no train-mode attention kernel past 224 words, titles of %d words run in eval mode only "
                       "(drop == NULL or both probabilities 0)", words);
-    const int D = w->hidden, F = w->mlp, T = words;
-    const int64_t Mc = (chunk_items > 0 && chunk_items < M) ? chunk_items : M;
-    WsCarver c(ws, ws_bytes);
+    const int D = w->hidden, T = words;
+    const Chunks c(M, chunk_items);
+    WsCarver cv(ws, ws_bytes);
     EncBufs b;
-    carve(c, b, Mc * T, Mc, D, F, Mc * T);
-    if (c.overflow || !ws) {
-        iisan_set_error("bert_forward_taps: workspace too small (%zu < %zu)", ws_bytes, c.off);
+    carve(cv, b, c.Mc * T, c.Mc, D, w->mlp, c.Mc * T);
+    if (cv.overflow || !ws) {
+        iisan_set_error("bert_forward_taps: workspace too small (%zu < %zu)", ws_bytes, cv.off);
         return IISAN_EWORKSPACE;
     }
-    const int dt = w->dtype16;
-    const bool f1blk = f1_blk32(dt, D, F, M, Mc, T, nullptr, EPI_OUT16, nullptr);      // F1 of the all-token blocks block-major
-    for (int64_t m0 = 0; m0 < M; m0 += Mc) {
-        const int64_t mc = (M - m0 < Mc) ? M - m0 : Mc;
-        const int64_t tok = mc * T;
-        float* tp = taps + m0 * n_taps * D;
-        const bool mixed = !g_resid32;
-        // post-LN tower: the stream IS the LayerNorm output.  resid32: X fp32 [tok, D]; mixed: Xc fp32 (CLS rows) + X16 fp16.  With fp16
-        // operands the 16-bit image the products read and the fp16 stream are the same values: one buffer, written once (g_ln_fold; the add +
-        // LayerNorm kernels move 6 instead of 8 bytes per element)
-        const bool alias = mixed && dt == IISAN_F16 && g_ln_fold;
-        void* IMG = alias ? b.X16 : b.H;
-        // train mode: the keep functor of a hidden site, local row r of the launch = token row r0 + r * rs of the whole call; eval: null
-        RowKeep rk;
-        auto keep = [&](int site, int64_t r0, int rs) -> const RowKeep* {
-            if (!dropping) return nullptr;
-            rk = RowKeep{make_drop(seed, site, hp), r0, rs};
-            return &rk;
-        };
-        if (index) IISAN_TRY(launch_bert_embed_ln_indexed(dt, text, rows, index + m0, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b,
-                                                          w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc, keep(0, m0 * T, 1)));
-        else IISAN_TRY(launch_bert_embed_ln(dt, text + m0 * 2 * words, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b,
-                                            w->eps, mixed ? nullptr : b.X, IMG, b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc, keep(0, m0 * T, 1)));
-        auto tap = [&](int k) { return mixed ? launch_gather_cls(b.Xc, tp, mc, 1, D, n_taps, k, s) : launch_gather_cls(b.X, tp, mc, T, D, n_taps, k, s); };
-        // x = LN(x + delta): stream and 16-bit image out
-        auto add_ln = [&](const float* g, const float* be, int site) {
-            return mixed ? launch_layernorm768_mixed(dt, MX_D1 | MX_LN | MX_RESY | (alias ? MX_ALIAS : 0), nullptr, b.X16, b.Xc, b.D16, nullptr, g, be, w->eps, IMG, mc, T, D, s,
-                                                     nullptr, keep(site, m0 * T, 1))
-                         : launch_add_layernorm768(dt, b.X, b.D16, g, be, w->eps, nullptr, b.H, b.X, tok, D, s);
-        };
+    Products p{w->dtype16, D, w->mlp, T, w->heads};
+    const BertPlan plan = bert_plan(p, c);
+    const bool full_blocks = g_full_blocks || w->full_blocks;
+    const int live = full_blocks ? w->layers : max_tap(tap_layers, n_taps);     // see the ViT executor
+    for (int64_t m0 = 0; m0 < M; m0 += c.Mc) {
+        const int64_t mc = (M - m0 < c.Mc) ? M - m0 : c.Mc;
+        const BertChunk ch{{p, b, s, w->eps, plan.mixed, m0, mc, mc * T, taps + m0 * n_taps * D, n_taps}, w, plan.alias, dropping,
+                           dropping ? drop->hidden_p : 0.f, dropping ? drop->attn_p : 0.f, dropping ? drop->seed : 0};
+        IISAN_TRY(ch.embed(text, index, rows));
         int k = tap_index(tap_layers, n_taps, 0);
-        if (k >= 0) IISAN_TRY(tap(k));
-        const bool full_blocks = g_full_blocks || w->full_blocks;
-        const int live = full_blocks ? w->layers : max_tap(tap_layers, n_taps);     // see the ViT executor
+        if (k >= 0) IISAN_TRY(ch.tap(k));
         for (int l = 0; l < live; ++l) {
-            const iisan_layer_weights& L = w->layer[l];
-            // a = LN(x + O(attn(x)))
-            if (l + 1 < live || full_blocks) {
-                IISAN_TRY(gemm(dt, EPI_QKVH16, IMG, D, L.qkv_w, L.qkv_b, b.QKV, 3 * D, nullptr, tok, s, nullptr, 0, T, w->heads));
-                if (dropping) IISAN_TRY(launch_attention16_drop(dt, b.QKV, b.KB, b.H, mc, T, w->heads, make_drop(seed, 1 + 3 * l, ap), m0, false, nullptr, s));
-                else IISAN_TRY(launch_attention16(dt, b.QKV, b.KB, b.H, mc, T, w->heads, s));
-                IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, tok, s));
-                IISAN_TRY(add_ln(L.ln1_w, L.ln1_b, 2 + 3 * l));
-                // x = LN(a + FC2(gelu(FC1 a)))
-                IISAN_TRY(gemm_fc1(dt, IMG, D, L.fc1_w, L.fc1_b, nullptr, b.F1, F, tok, f1blk, s));
-                IISAN_TRY(gemm_fc2(dt, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, tok, f1blk, s));
-                IISAN_TRY(add_ln(L.ln2_w, L.ln2_b, 3 + 3 * l));
-                k = tap_index(tap_layers, n_taps, l + 1);
-                if (k >= 0) IISAN_TRY(tap(k));
-            } else {
-                // post-LN tower: the block input H is the 16-bit image of X, so the CLS rows of H are gathered directly
-                void* Hc = b.Cls;
-                void* Qc = (char*)b.Cls + (size_t)b.Mcp * D * 2;
-                IISAN_TRY(launch_gather_rows16(IMG, Hc, mc, T, D, s));
-                IISAN_TRY(kv_all_q_cls(dt, L, IMG, b.QKV, Hc, Qc, tok, mc, T, w->heads, D, s));
-                float* Xc = (float*)b.QKV;
-                if (dropping) IISAN_TRY(launch_attention16_drop(dt, b.QKV, b.KB, b.H, mc, T, w->heads, make_drop(seed, 1 + 3 * l, ap), m0, true, Qc, s));
-                else IISAN_TRY(launch_attention_cls16(dt, b.QKV, b.KB, b.H, mc, T, w->heads, s, Qc));
-                IISAN_TRY(gemm(dt, EPI_OUT16, b.H, D, L.o_w, L.o_b, b.D16, D, nullptr, mc, s));
-                if (mixed) IISAN_TRY(launch_gather_cls(b.Xc, Xc, mc, 1, D, 1, 0, s)); else IISAN_TRY(launch_gather_cls(b.X, Xc, mc, T, D, 1, 0, s));
-                // (train mode: the masks of token row t = 0 of the all-token execution — compact row r is token row (m0 + r) T)
-                IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln1_w, L.ln1_b, w->eps, nullptr, b.H, Xc, mc, D, s, keep(2 + 3 * l, m0 * T, T)));
-                IISAN_TRY(gemm(dt, EPI_GELU16, b.H, D, L.fc1_w, L.fc1_b, b.F1, F, nullptr, mc, s));
-                IISAN_TRY(gemm(dt, EPI_OUT16, b.F1, F, L.fc2_w, L.fc2_b, b.D16, D, nullptr, mc, s));
-                IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, w->eps, nullptr, nullptr, Xc, mc, D, s, keep(3 + 3 * l, m0 * T, T)));
-                k = tap_index(tap_layers, n_taps, live);
-                IISAN_TRY(launch_gather_cls(Xc, tp, mc, 1, D, n_taps, k, s));
+            k = tap_index(tap_layers, n_taps, l + 1);
+            if (l + 1 == live && !full_blocks) IISAN_TRY(ch.cls_block(l, k));
+            else {
+                IISAN_TRY(ch.full_block(l));
+                if (k >= 0) IISAN_TRY(ch.tap(k));
             }
         }
     }
@@ -655,4 +672,24 @@ extern "C" int iisan_bert_forward_taps_dropout(const iisan_bert_weights* w, cons
     IISAN_CHECK_SHAPE(M > 0, "bert dropout: M must be positive");
     return bert_forward_taps_impl(w, text_or_table, M, words, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream, index,
                                   index ? rows : 0, drop);
+}
+
+// The decisions vit_forward_taps_impl / bert_forward_taps_impl take before their first launch, for the towers' own shapes and no weights: the
+// refusals that depend on these inputs, then vit_plan / bert_plan themselves.  `layers` is the shortest tower that has the tap.
+extern "C" int32_t iisan_encoder_plan(int32_t tower, int32_t dtype16, int32_t hidden, int32_t heads, int32_t mlp, int32_t tokens, int64_t M,
+                                      int64_t chunk_items, int32_t deepest_tap, int32_t full_blocks, int32_t folded) {
+    IISAN_CHECK_SHAPE(tower == IISAN_TOWER_VIT || tower == IISAN_TOWER_BERT, "encoder_plan: tower %d is neither ViT (0) nor BERT (1)", tower);
+    IISAN_CHECK_SHAPE(M > 0, "encoder_plan: M must be positive");
+    const int layers = deepest_tap > 1 ? deepest_tap : 1;
+    IISAN_TRY(check_common(hidden, layers, heads, mlp, 1, &deepest_tap));
+    IISAN_TRY(tower == IISAN_TOWER_VIT ? vit_check_tokens(tokens) : bert_check_words(tokens, tokens));
+    const bool full = g_full_blocks || full_blocks;
+    const Chunks c(M, chunk_items);
+    Products p{dtype16, hidden, mlp, tokens, heads};
+    if (tower == IISAN_TOWER_BERT) {
+        const BertPlan plan = bert_plan(p, c);
+        return (plan.mixed ? 1 : 0) | (plan.alias ? 2 : 0) | (p.f1blk ? 4 : 0);
+    }
+    const VitPlan plan = vit_plan(p, full ? layers : deepest_tap, full, folded != 0, c);
+    return (int32_t)plan.st | (p.f1blk ? 4 : 0) | (p.xblk ? 8 : 0) | (plan.folds ? 16 : 0);
 }

@@ -458,7 +458,7 @@ __global__ void cast16_kernel(const float* __restrict__ src, typename T::elem* _
 
 // The instantiated row widths: 768 / 1024 (ViT-B / BERT-base, ViT-L / BERT-large) and the narrow towers' 128, 192, 256, 384 (BERT-tiny, ViT-tiny,
 // BERT-mini, ViT-small).  The refusal names the width it was given and 768 and 1024 first.
-static bool row_width_instantiated(int w) { return w == 768 || w == 1024 || w == 128 || w == 192 || w == 256 || w == 384; }
+bool row_width_instantiated(int w) { return w == 768 || w == 1024 || w == 128 || w == 192 || w == 256 || w == 384; }
 #define ROW_WIDTH_MSG "row width %d not instantiated (768 and 1024 are, and 128, 192, 256, 384)"
 // one switch over the widths: X(W, A) is the launch at the compile-time width W (A: whatever else the launch is a template of)
 #define ROW_WIDTH_SWITCH(width, X, A)                                                                                         \

@@ -66,6 +66,16 @@ class _PackedEncoder:
         self._keep.append(t)
         return _ptr(t)
 
+    def _taps_call(self, name: str, head, M: int, tap_layers: Sequence[int], chunk_items: int, ws_bytes: int, device, extra=()):
+        """One `*_forward_taps*` call: allocates the taps [M, len(tap_layers), D] and a workspace of ws_bytes, calls the entry point `name`
+        with (weights, *head, tap array, n_taps, taps, chunk_items, *extra, workspace, its size, stream) and raises on a non-zero code."""
+        taps = torch.empty((M, len(tap_layers), self.cfg.hidden), dtype=torch.float32, device=device)
+        tl = (C.c_int32 * len(tap_layers))(*tap_layers)
+        ws = self.ws.get(ws_bytes, device)
+        _lib.check(getattr(_lib.load(), name)(C.byref(self.struct), *head, tl, len(tap_layers), _ptr(taps), chunk_items, *extra,
+                                              _ptr(ws), ws.numel(), _stream()), name)
+        return taps
+
     def _layers(self, struct, n_layers: int, masters: bool = False):
         """masters: also keep the fp32 originals of qkv_w / fc1_w on the device (`iisan_layer_weights.qkv_w32 / fc1_w32`): the ViT
         executor folds its LayerNorms into these two matrices and then rounds to fp16 once, not twice."""
@@ -126,15 +136,9 @@ class PackedVit(_PackedEncoder):
         assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous()
         assert images.shape[1:] == (cfg.channels, cfg.image, cfg.image), images.shape
         M = images.shape[0]
-        taps = torch.empty((M, len(tap_layers), cfg.hidden), dtype=torch.float32, device=images.device)
-        tl = (C.c_int32 * len(tap_layers))(*tap_layers)
         nbytes = lib.iisan_vit_forward_taps_ws_bytes(C.byref(self.struct), M, chunk_items)
-        ws = self.ws.get(nbytes, images.device)
-        fn = lib.iisan_vit_forward_taps_u8 if images.dtype == torch.uint8 else lib.iisan_vit_forward_taps
-        _lib.check(fn(C.byref(self.struct), _ptr(images), M, tl, len(tap_layers), _ptr(taps),
-                      chunk_items, _ptr(ws), ws.numel(), _stream()), "iisan_vit_forward_taps")
-        return taps
-
+        return self._taps_call("iisan_vit_forward_taps_u8" if images.dtype == torch.uint8 else "iisan_vit_forward_taps", (_ptr(images), M),
+                               M, tap_layers, chunk_items, nbytes, images.device)
 
     def forward_taps_indexed(self, catalogue_u8: torch.Tensor, index: torch.Tensor, tap_layers: Sequence[int],
                              chunk_items: int = 0) -> torch.Tensor:
@@ -148,14 +152,9 @@ class PackedVit(_PackedEncoder):
         assert index.is_cuda and index.device == catalogue_u8.device and index.dtype == torch.int64
         assert index.dim() == 1 and index.is_contiguous(), index.shape
         M = index.shape[0]
-        taps = torch.empty((M, len(tap_layers), cfg.hidden), dtype=torch.float32, device=index.device)
-        tl = (C.c_int32 * len(tap_layers))(*tap_layers)
         nbytes = lib.iisan_vit_forward_taps_ws_bytes(C.byref(self.struct), M, chunk_items)
-        ws = self.ws.get(nbytes, index.device)
-        _lib.check(lib.iisan_vit_forward_taps_u8_indexed(C.byref(self.struct), _ptr(catalogue_u8), catalogue_u8.shape[0], _ptr(index), M,
-                                                         tl, len(tap_layers), _ptr(taps), chunk_items, _ptr(ws), ws.numel(),
-                                                         _stream()), "iisan_vit_forward_taps_u8_indexed")
-        return taps
+        return self._taps_call("iisan_vit_forward_taps_u8_indexed", (_ptr(catalogue_u8), catalogue_u8.shape[0], _ptr(index), M),
+                               M, tap_layers, chunk_items, nbytes, index.device)
 
 
 class PackedBert(_PackedEncoder):
@@ -183,19 +182,11 @@ class PackedBert(_PackedEncoder):
         lib = _lib.load()
         assert text.is_cuda and text.dtype == torch.int64 and text.is_contiguous() and text.shape[1] % 2 == 0
         M, words = text.shape[0], text.shape[1] // 2
-        taps = torch.empty((M, len(tap_layers), self.cfg.hidden), dtype=torch.float32, device=text.device)
-        tl = (C.c_int32 * len(tap_layers))(*tap_layers)
         nbytes = lib.iisan_bert_forward_taps_ws_bytes(C.byref(self.struct), M, words, chunk_items)
-        ws = self.ws.get(nbytes, text.device)
         if dropout is not None:
-            _lib.check(lib.iisan_bert_forward_taps_dropout(C.byref(self.struct), _ptr(text), 0, None, M, words, tl, len(tap_layers),
-                                                           _ptr(taps), chunk_items, C.byref(self._drop_struct(dropout)), _ptr(ws),
-                                                           ws.numel(), _stream()), "iisan_bert_forward_taps_dropout")
-            return taps
-        _lib.check(lib.iisan_bert_forward_taps(C.byref(self.struct), _ptr(text), M, words, tl, len(tap_layers),
-                                               _ptr(taps), chunk_items, _ptr(ws), ws.numel(), _stream()),
-                   "iisan_bert_forward_taps")
-        return taps
+            return self._taps_call("iisan_bert_forward_taps_dropout", (_ptr(text), 0, None, M, words), M, tap_layers, chunk_items, nbytes,
+                                   text.device, extra=(C.byref(self._drop_struct(dropout)),))
+        return self._taps_call("iisan_bert_forward_taps", (_ptr(text), M, words), M, tap_layers, chunk_items, nbytes, text.device)
 
     def forward_taps_indexed(self, table: torch.Tensor, index: torch.Tensor, tap_layers: Sequence[int],
                              chunk_items: int = 0, dropout=None) -> torch.Tensor:
@@ -208,16 +199,9 @@ class PackedBert(_PackedEncoder):
         assert index.is_cuda and index.device == table.device and index.dtype == torch.int64
         assert index.dim() == 1 and index.is_contiguous(), index.shape
         M, words = index.shape[0], table.shape[1] // 2
-        taps = torch.empty((M, len(tap_layers), self.cfg.hidden), dtype=torch.float32, device=index.device)
-        tl = (C.c_int32 * len(tap_layers))(*tap_layers)
         nbytes = lib.iisan_bert_forward_taps_ws_bytes(C.byref(self.struct), M, words, chunk_items)
-        ws = self.ws.get(nbytes, index.device)
+        head = (_ptr(table), table.shape[0], _ptr(index), M, words)
         if dropout is not None:
-            _lib.check(lib.iisan_bert_forward_taps_dropout(C.byref(self.struct), _ptr(table), table.shape[0], _ptr(index), M, words, tl,
-                                                           len(tap_layers), _ptr(taps), chunk_items, C.byref(self._drop_struct(dropout)),
-                                                           _ptr(ws), ws.numel(), _stream()), "iisan_bert_forward_taps_dropout")
-            return taps
-        _lib.check(lib.iisan_bert_forward_taps_indexed(C.byref(self.struct), _ptr(table), table.shape[0], _ptr(index), M, words, tl,
-                                                       len(tap_layers), _ptr(taps), chunk_items, _ptr(ws), ws.numel(), _stream()),
-                   "iisan_bert_forward_taps_indexed")
-        return taps
+            return self._taps_call("iisan_bert_forward_taps_dropout", head, M, tap_layers, chunk_items, nbytes, index.device,
+                                   extra=(C.byref(self._drop_struct(dropout)),))
+        return self._taps_call("iisan_bert_forward_taps_indexed", head, M, tap_layers, chunk_items, nbytes, index.device)

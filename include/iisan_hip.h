@@ -451,6 +451,17 @@ int32_t iisan_gemm32_plan(const int64_t* M, const int32_t* N, const int64_t* K, 
 int32_t iisan_inbatch_ce_route(int64_t bs, int32_t S);
 /* the same at embedding width E (iisan_inbatch_ce_route is the E = 64 call): never 3 at E > 64; -1 for a shape or width outside the limits */
 int32_t iisan_inbatch_ce_route_e(int64_t bs, int32_t S, int32_t E);
+/* host-side query: what iisan_vit_forward_taps* / iisan_bert_forward_taps* decide once per call, before their first launch, under the current
+ * dev switches (resid32, ln_fold, blk32, full_blocks, gemm16_variant) — the executors' own decision code, asked without weights or a
+ * workspace.  tokens: per item (patches + 1 / words); deepest_tap: the largest tap layer of the call; full_blocks: the weights struct's field;
+ * folded: the weights struct carries a folded set (iisan_vit_fold_layernorm).  Negative = the executors refuse these sizes (iisan_last_error).
+ * ViT: bits 0-1 how the residual stream is carried (0 fp32 stream of resid32, 1 mixed stream + LayerNorm images, 2 LayerNorm in the QKV / FC1
+ * epilogues, 3 ... and the residual adds in the O / FC2 epilogues), 4 = the FC1 -> FC2 intermediate is block-major, 8 = the stream is, 16 = the
+ * call folds the LayerNorm weights itself.  BERT: 1 = mixed stream, 2 = stream and 16-bit image share one buffer, 4 = block-major FC1 -> FC2. */
+#define IISAN_TOWER_VIT 0
+#define IISAN_TOWER_BERT 1
+int32_t iisan_encoder_plan(int32_t tower, int32_t dtype16, int32_t hidden, int32_t heads, int32_t mlp, int32_t tokens, int64_t M,
+                           int64_t chunk_items, int32_t deepest_tap, int32_t full_blocks, int32_t folded);
 
 /* ------------------------------------------------------------------------------------------------------------
  * DEV section — process-wide development switches and measurement hooks.  NOT part of the product contract: a

@@ -531,6 +531,83 @@ def test_gemm32_plan_table():
             assert rc == want[0] and tuple(out) == want, (probs, flags, scratch, colsum, knobs, rc, tuple(out), want)
 
 
+def test_encoder_plan_table():
+    """What the two encoder executors decide once per call, before their first launch (encoders.hip: vit_plan / bert_plan, asked through
+    `iisan_encoder_plan` without weights, workspace or device), as a literal table.  ViT: R = fp32 stream of the dev switch resid32, I = mixed
+    stream + LayerNorm images, F = LayerNorm in the QKV / FC1 epilogues, S = ... and the residual adds in the O / FC2 epilogues; then f = the
+    FC1 -> FC2 intermediate is block-major, x = the stream is, w = the call folds the LayerNorm weights itself.  BERT: M = mixed stream (P: fp32),
+    a = stream and 16-bit image share a buffer, f as above.  ! = the executors refuse the sizes.  Columns: gemm16_variant 0, then 4, each under
+    ln_fold 0 / 1 / 2 x blk32 0 / 1 / 2; then resid32 = 1 under gemm16_variant 0 and 4.  Expected values: recorded from the three probe functions
+    this plan replaced (vit_strategy, f1_blk32, x16_blk32, called as the executors called them, in an instrumented build of the parent commit);
+    they agree with every anchor derived by hand from that code, asserted again below.  The routes depend on `iisan_cu_count` through
+    gemm16_route's half-a-tile-per-CU rule at 256 compute units: an MI355X, and what the library assumes where no device is visible."""
+    from iisan_amd import _lib
+    lib = _lib.load()
+    VIT, BERT, F16, BF16 = 0, 1, 0, 1
+    knobs = [dict(ln_fold=l, blk32=b, gemm16_variant=v) for v in (0, 4) for l in (0, 1, 2) for b in (0, 1, 2)] + \
+            [dict(resid32=1, gemm16_variant=v) for v in (0, 4)]
+    # (tower, dtype16, hidden, heads, mlp, tokens, M, chunk_items, deepest tap, full_blocks, folded set supplied) -> plan under each knob set
+    table = [
+        ((0, 0, 768, 12, 3072, 197, 1408, 0, 12, 0, 1), "I If If F Ff Ff S Sf Sfx I If If F Ff Ff S Sf Sfx R R"),
+        ((0, 0, 768, 12, 3072, 197, 1408, 1000, 12, 0, 1), "I If If F Ff Ff S Sf Sfx I If If F Ff Ff S Sf Sfx R R"),
+        ((1, 0, 768, 12, 3072, 30, 1408, 0, 12, 0, 0), "M Mf Mf Ma Maf Maf Ma Maf Maf M Mf Mf Ma Maf Maf Ma Maf Maf Pf Pf"),
+        ((1, 0, 768, 12, 3072, 30, 1408, 1000, 12, 0, 0), "M Mf Mf Ma Maf Maf Ma Maf Maf M Mf Mf Ma Maf Maf Ma Maf Maf Pf Pf"),
+        ((0, 1, 768, 12, 3072, 197, 1408, 0, 12, 0, 1), "I If If I If If I If If I If If I If If I If If R R"),
+        ((0, 1, 768, 12, 3072, 197, 1408, 1000, 12, 0, 1), "I If If I If If I If If I If If I If If I If If R R"),
+        ((1, 1, 768, 12, 3072, 30, 1408, 0, 12, 0, 0), "M Mf Mf M Mf Mf M Mf Mf M Mf Mf M Mf Mf M Mf Mf Pf Pf"),
+        ((1, 1, 768, 12, 3072, 30, 1408, 1000, 12, 0, 0), "M Mf Mf M Mf Mf M Mf Mf M Mf Mf M Mf Mf M Mf Mf Pf Pf"),
+        ((0, 0, 768, 12, 3072, 197, 1408, 0, 12, 0, 0), "I If If Fw Ffw Ffw Sw Sfw Sfxw I If If Fw Ffw Ffw Sw Sfw Sfxw R R"),
+        ((0, 0, 768, 12, 3072, 197, 4, 0, 12, 0, 1), "I I I I I I I I I I If If F Ff Ff S Sf Sfx R R"),
+        ((1, 0, 768, 12, 3072, 30, 4, 0, 12, 0, 0), "M M M Ma Ma Ma Ma Ma Ma M Mf Mf Ma Maf Maf Ma Maf Maf P Pf"),
+        ((0, 0, 768, 12, 3072, 577, 1408, 0, 12, 0, 1), "I If If F Ff Ff S Sf Sfx I If If F Ff Ff S Sf Sfx R R"),
+        ((1, 0, 768, 12, 3072, 577, 1408, 0, 12, 0, 0), "M Mf Mf Ma Maf Maf Ma Maf Maf M Mf Mf Ma Maf Maf Ma Maf Maf Pf Pf"),
+        ((0, 0, 1024, 16, 4096, 197, 1408, 0, 24, 0, 1), "I If If I If If I If If I If If I If If I If If R R"),
+        ((0, 0, 384, 6, 1536, 197, 1408, 0, 12, 0, 1), "I I I I I I I I I I I I I I I I I I R R"),
+        ((0, 0, 192, 3, 768, 197, 1408, 0, 12, 0, 1), "I I I I I I I I I I I I I I I I I I R R"),
+        ((1, 0, 1024, 16, 4096, 30, 1408, 0, 24, 0, 0), "M Mf Mf Ma Maf Maf Ma Maf Maf M Mf Mf Ma Maf Maf Ma Maf Maf Pf Pf"),
+        ((1, 0, 256, 4, 1024, 30, 1408, 0, 4, 0, 0), "M Mf Mf Ma Maf Maf Ma Maf Maf M Mf Mf Ma Maf Maf Ma Maf Maf Pf Pf"),
+        ((1, 0, 128, 2, 512, 30, 1408, 0, 2, 0, 0), "M M M Ma Ma Ma Ma Ma Ma M M M Ma Ma Ma Ma Ma Ma P P"),
+        ((0, 0, 768, 12, 3072, 197, 1408, 0, 0, 0, 1), "I If If I If If I If If I If If I If If I If If R R"),
+        ((1, 0, 768, 12, 3072, 30, 1408, 0, 0, 0, 0), "M Mf Mf Ma Maf Maf Ma Maf Maf M Mf Mf Ma Maf Maf Ma Maf Maf Pf Pf"),
+        ((0, 0, 768, 12, 3072, 197, 1408, 0, 6, 0, 1), "I If If F Ff Ff S Sf Sfx I If If F Ff Ff S Sf Sfx R R"),
+        ((0, 0, 768, 12, 3072, 197, 1408, 0, 6, 1, 1), "I If If F Ff Ff S Sf Sfx I If If F Ff Ff S Sf Sfx R R"),
+        ((0, 0, 768, 12, 3072, 197, 1408, 1000, 6, 1, 1), "I If If F Ff Ff S Sf Sfx I If If F Ff Ff S Sf Sfx R R"),
+        ((1, 0, 768, 12, 3072, 30, 1408, 0, 6, 1, 0), "M Mf Mf Ma Maf Maf Ma Maf Maf M Mf Mf Ma Maf Maf Ma Maf Maf Pf Pf"),
+        ((0, 0, 768, 12, 3072, 1025, 1408, 0, 12, 0, 1), "! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! !"),
+        ((1, 0, 768, 12, 3072, 0, 1408, 0, 12, 0, 0), "! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! !"),
+        ((0, 0, 768, 12, 3072, 197, 0, 0, 12, 0, 1), "! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! !"),
+        ((0, 0, 512, 8, 2048, 197, 1408, 0, 12, 0, 1), "! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! ! !"),
+    ]
+
+    def code(tower, w):
+        if w < 0:
+            return "!"
+        if tower == VIT:
+            return "RIFS"[w & 3] + ("f" if w & 4 else "") + ("x" if w & 8 else "") + ("w" if w & 16 else "")
+        return ("M" if w & 1 else "P") + ("a" if w & 2 else "") + ("f" if w & 4 else "")
+
+    def plan(case, **kn):
+        with _lib.dev(**kn):
+            return code(case[0], lib.iisan_encoder_plan(*case))
+
+    for case, want in table:
+        got = [plan(case, **kn) for kn in knobs]
+        assert got == want.split(), (case, " ".join(got), want)
+    # the anchors: ViT-B and BERT-base at the bs = 128 headline batch of 1,408 items
+    vit = lambda dt=F16, hidden=768, heads=12, M=1408, tap=12: (VIT, dt, hidden, heads, 4 * hidden, 197, M, 0, tap, 0, 1)
+    assert plan(vit()) == "Sfx"
+    assert plan(vit(BF16)) == "If"                                   # LayerNorm in the epilogue is fp16 only
+    assert plan(vit(), resid32=1) == "R"
+    for hidden, heads in ((1024, 16), (384, 6), (192, 3)):
+        assert plan(vit(hidden=hidden, heads=heads))[0] == "I"       # the folded routes are 768 wide
+    assert plan(vit(), ln_fold=0) == "If" and plan(vit(), ln_fold=1) == "Ff"
+    assert plan(vit(), blk32=0) == "S" and plan(vit(), blk32=1) == "Sf"
+    assert plan(vit(tap=0))[0] == "I"                                # taps [0] only: no live block
+    assert plan(vit(M=4)) == "I"                                     # below half a tile per CU the products run on the 128x128 kernel
+    bert = lambda dt: (BERT, dt, 768, 12, 3072, 30, 1408, 0, 12, 0, 0)
+    assert plan(bert(F16)) == "Maf" and plan(bert(BF16)) == "Mf"
+
+
 def test_tools_compile_and_name_only_declared_entry_points():
     """a development tool that still iterated a table the ABI clean-up had removed died silently in every child process.  Every
     script under tools/ must byte-compile, and every `iisan_*` entry point it names must be one the loader binds (`_lib.SIGNATURES` =
