@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libiisan_hip.so")
 
 IISAN_F16, IISAN_BF16, IISAN_F32 = 0, 1, 2
+IISAN_WIN_TRAIN, IISAN_WIN_EVAL, IISAN_WIN_INPUT = 0, 1, 2
 MAX_LAYERS, MAX_SIDE = 48, 16
 
 vp, i32, i64, f32, u64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
@@ -83,6 +84,9 @@ SIGNATURES = {
     "iisan_score_rank": (i32, [vp, vp, i64, i64, i32, vp, i32, vp, vp, vp]),
     "iisan_score_topk_ws_bytes": (sz, [i64, i64, i32]),
     "iisan_score_topk": (i32, [vp, vp, i64, i64, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "iisan_user_windows": (i32, [vp, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, i64, i32, vp, vp]),
+    "iisan_user_history": (i32, [vp, vp, i64, vp, i64, i32, vp, vp]),
+    "iisan_rank_histogram": (i32, [vp, i64, i32, vp, vp]),
     "iisan_adam_step": (i32, [vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(f32), i32, i32, f32, f32, f32, f32, vp]),
     "iisan_gemm16": (i32, [i32, i32, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
     "iisan_layernorm768": (i32, [i32, vp, vp, vp, f32, vp, vp, i64, vp]),

@@ -14,6 +14,8 @@
   (768: ViT-B / BERT-base; 1024: ViT-L / BERT-large — the widths `Code_Cached_Asym/preprocess_*.py` caches for Versa).
 * `item_table_from_store` / `build_tap_cache_from_store`  the same two over an item store (`iisan_amd.itemstore`): id ranges
   through the indexed encoder entries, no image batch on the host or the device.
+* `evaluate_ranks_from_store` / `recommend_topk_from_store` / `eval_metrics_from_store`  the eval routes over a user store
+  (`iisan_amd.userstore`): windows, masks, targets and exclusion lists of a user batch are built on the device by user number.
 """
 from __future__ import annotations
 
@@ -210,12 +212,16 @@ def evaluate_ranks(model, item_emb: torch.Tensor, eval_seqs: Sequence[Sequence[i
     model.train(was_training)
     ranks = torch.cat(out)
     ranks = dp.gather_concat(ranks, U) if world > 1 else ranks
-    # `iisan_score_rank` reports -1 for a target outside 1..item_num; the reference indexes the score row with it and raises
-    # IndexError (metrics.py:206) — so does this, after the gather, on every rank alike
     if bool((ranks < 1).any()):
-        bad = torch.nonzero(ranks < 1).flatten()[:8].tolist()
-        raise IndexError(f"evaluate_ranks: target item id outside 1..{item_emb.shape[0] - 1} for users {bad}")
+        _raise_invalid_targets(ranks, item_emb)
     return ranks
+
+
+def _raise_invalid_targets(ranks: torch.Tensor, item_emb: torch.Tensor):
+    """`iisan_score_rank` reports -1 for a target outside 1..item_num; the reference indexes the score row with it and raises
+    IndexError (metrics.py:206) — so do the eval routes, after the gather, on every rank alike."""
+    bad = torch.nonzero(ranks < 1).flatten()[:8].tolist()
+    raise IndexError(f"evaluate_ranks: target item id outside 1..{item_emb.shape[0] - 1} for users {bad}")
 
 
 @torch.no_grad()
@@ -254,6 +260,108 @@ def recommend_topk(model, item_emb: torch.Tensor, input_seqs: Sequence[Sequence[
             fill = excl[:k - free]
             ids_c[r, free:free + len(fill)] = torch.tensor(fill, dtype=torch.int32)
         ids = ids_c.to(dev)
+    if world > 1:
+        ids, sc = dp.gather_concat(ids, U), dp.gather_concat(sc, U)
+    return ids, sc
+
+
+def _ranks_from_store(model, item_emb, users, max_seq_len, batch, rank, world) -> torch.Tensor:
+    """The gathered ranks of `evaluate_ranks_from_store`, invalid targets (-1) still in them."""
+    from . import userstore
+    U = users.n_users
+    item_emb = ops._f32c(item_emb)
+    hs = max(1, min(users.max_hist, HIST_MAX))
+    idx = users.eval_index(rank, world, batch)
+    first = userstore.shard_range(U, rank, world, batch)[0]
+    # the long-history users of this shard, by position in it (host arithmetic on the store's short list; the tail that repeats user
+    # U - 1 to fill the last batch is cut off by the gather and needs no correction)
+    long_pos = [(int(u) - first, int(u)) for u in users.long_users if first <= int(u) < first + idx.numel()]
+    was_training = model.training
+    model.eval()
+    out = []
+    try:
+        for i in range(0, idx.numel(), batch):
+            ib = idx[i:i + batch]
+            _, m, tgt, x = users.windows(userstore.EVAL, max_seq_len, ib, item_emb)    # x == item_emb[tokens], metrics.py:214
+            prec = model.user_encoder(x, m, None)[:, -1].contiguous()                  # metrics.py:216
+            r = ops.score_rank(prec, item_emb, users.history(ib, hs), tgt)
+            for k, u in long_pos:
+                if i <= k < i + batch:
+                    r[k - i] = _rank_long_history(prec[k - i:k - i + 1], item_emb, users.host.history(u).tolist(), users.host.target(u))
+            out.append(r)
+    finally:
+        model.train(was_training)
+    ranks = torch.cat(out)
+    return dp.gather_concat(ranks, U) if world > 1 else ranks
+
+
+@torch.no_grad()
+def evaluate_ranks_from_store(model, item_emb: torch.Tensor, users, max_seq_len: int, batch: int = 1024, rank: int = 0,
+                              world: int = 1) -> torch.Tensor:
+    """`evaluate_ranks` over a `userstore.UserStore` built from (`eval_seq`, `user_history`): the same kernels on the same values — bit-equal
+    ranks — with the token windows, masks, targets, exclusion matrix and `item_emb[tokens]` of every user batch built on the device from
+    the resident sequences.  The user shard is the `dp.sequential_shard` range made on the device; no per-user host work, no per-batch
+    host-to-device copy (users with more than HIST_MAX excluded items are corrected as in `evaluate_ranks`)."""
+    ranks = _ranks_from_store(model, item_emb, users, max_seq_len, batch, rank, world)
+    if bool((ranks < 1).any()):
+        _raise_invalid_targets(ranks, item_emb)
+    return ranks
+
+
+@torch.no_grad()
+def eval_metrics_from_store(model, item_emb: torch.Tensor, users, max_seq_len: int, batch: int = 1024, rank: int = 0, world: int = 1,
+                            topk: int = 10) -> Tuple[float, float]:
+    """(Hit@k, nDCG@k) = `hit_ndcg(evaluate_ranks(...), topk)` without the rank vector leaving the device: `iisan_rank_histogram` counts the
+    ranks 1..k, and k + 2 integers come back.  Hit@k = sum of counts[1..k] / U; nDCG@k = sum of counts[r] / log2(r + 1) / U in float64.
+    An invalid target raises the IndexError of `evaluate_ranks`."""
+    import math
+    ranks = _ranks_from_store(model, item_emb, users, max_seq_len, batch, rank, world)
+    counts = ops.rank_histogram(ranks, topk).cpu().tolist()
+    if counts[0] > 0:
+        _raise_invalid_targets(ranks, item_emb)
+    U = users.n_users
+    return sum(counts[1:topk + 1]) / U, sum(counts[r] / math.log2(r + 1) for r in range(1, topk + 1)) / U
+
+
+@torch.no_grad()
+def recommend_topk_from_store(model, item_emb: torch.Tensor, users, max_seq_len: int, k: int = 10, batch: int = 1024, rank: int = 0,
+                              world: int = 1, holdout: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`recommend_topk` over a `userstore.UserStore`: bit-equal ids and scores.  The store's sequences are the encoder's inputs (INPUT
+    windows); with `holdout` the last item of every sequence is held out as in the reference's eval protocol (EVAL windows: a store built
+    from `eval_seq` serves both this and `evaluate_ranks_from_store`).  The whole exclusion list of every user is applied
+    (`iisan_score_topk` takes any stride), as `recommend_topk` does."""
+    from . import userstore
+    U = users.n_users
+    item_emb = ops._f32c(item_emb)
+    hs = max(1, users.max_hist)
+    idx = users.eval_index(rank, world, batch)
+    first = userstore.shard_range(U, rank, world, batch)[0]
+    mode = userstore.EVAL if holdout else userstore.INPUT
+    n_items = item_emb.shape[0] - 1
+    was_training = model.training
+    model.eval()
+    ids_out, sc_out = [], []
+    try:
+        for i in range(0, idx.numel(), batch):
+            ib = idx[i:i + batch]
+            _, m, _, x = users.windows(mode, max_seq_len, ib, item_emb)
+            prec = model.user_encoder(x, m, None)[:, -1].contiguous()                    # metrics.py:214-216
+            ids, sc = ops.score_topk(prec, item_emb, users.history(ib, hs), k)
+            ids_out.append(ids)
+            sc_out.append(sc)
+    finally:
+        model.train(was_training)
+    ids, sc = torch.cat(ids_out), torch.cat(sc_out)
+    if n_items - hs < k:
+        # fewer than k items outside some user's history: the -inf (history) items follow in ascending id order (`recommend_topk`), from
+        # the store's host copy of the lists
+        ids_c = ids.cpu()
+        for r in torch.nonzero((ids_c == 0).any(dim=1)).flatten().tolist():
+            excl = sorted({int(c) for c in users.host.history(min(first + r, U - 1)) if 1 <= int(c) <= n_items})
+            free = int((ids_c[r] != 0).sum())
+            fill = excl[:k - free]
+            ids_c[r, free:free + len(fill)] = torch.tensor(fill, dtype=torch.int32)
+        ids = ids_c.to(ids.device)
     if world > 1:
         ids, sc = dp.gather_concat(ids, U), dp.gather_concat(sc, U)
     return ids, sc

@@ -436,6 +436,20 @@ def score_topk(prec_last: torch.Tensor, item_emb: torch.Tensor, history: torch.T
     return ids, scores
 
 
+def rank_histogram(ranks: torch.Tensor, k: int, counts: torch.Tensor = None) -> torch.Tensor:
+    """int64 [k + 2] += histogram of int32 ranks [U] (`iisan_rank_histogram`): [0] ranks < 1, [r] rank r (1 <= r <= k), [k + 1] ranks > k.
+    `counts` None: a zeroed vector is made; given, it is accumulated into."""
+    lib = _lib.load()
+    _need_cuda(ranks, counts)
+    ranks = ranks.to(torch.int32).contiguous()
+    if counts is None:
+        counts = torch.zeros(max(k, 0) + 2, dtype=torch.int64, device=ranks.device)
+    elif counts.dtype != torch.int64 or counts.numel() != k + 2 or not counts.is_contiguous():
+        raise _lib.IisanHipError(f"rank_histogram: counts must be a contiguous int64 [{k + 2}]")
+    _lib.check(lib.iisan_rank_histogram(ranks.data_ptr(), ranks.numel(), k, counts.data_ptr(), _stream()), "iisan_rank_histogram")
+    return counts
+
+
 def adam_step(p, g, m, v, seg_end: Sequence[int], seg_lr: Sequence[float], step: int, grad_scale: float = 1.0,
               beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
     lib = _lib.load()

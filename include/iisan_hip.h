@@ -338,6 +338,37 @@ int iisan_score_topk(const float* prec, const float* item_emb, int64_t U, int64_
                      void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Device-resident user store: the user side of a batch built on the device (csrc/users.hip) — what
+ * Code_Uncached/data_utils/dataset.py:65-92 (train) and :183-189 (eval) build per user on the host.  User sequences live in CSR form:
+ * seq_off int64 [n_users + 1], seq_items int32 [nnz] (item ids 1..item_num); exclusion lists in a second CSR of the same form.
+ * user_index int64 [B] on the device names the batch's users, duplicates and any order allowed; a value outside [0, n_users) is a PADDING
+ * ROW: nothing of the store is read for it and its ids, mask, target and history are all zero (iisan_score_rank then reports -1 for it,
+ * as for any invalid target).  With L the length of a user's sequence:
+ * ---------------------------------------------------------------------------------------------------------- */
+#define IISAN_WIN_TRAIN 0   /* ids [B, S+1]: the last min(L, S+1) items right-aligned, zeros in front;
+                               log_mask[b, j] = 1 for j >= S+1-min(L, S+1), j < S   (dataset.py:66-72)                              */
+#define IISAN_WIN_EVAL  1   /* sequence = inputs + target: target[b] = last item; ids [B, S] = the min(L-1, S) items before it,
+                               right-aligned; log_mask 1 on them   (dataset.py:183-189)                                             */
+#define IISAN_WIN_INPUT 2   /* every item is an input: ids [B, S] = the last min(L, S), log_mask 1 on them; no target               */
+/* ids int64, log_mask fp32 [B, S] (every mode), target int32 [B]: required in EVAL mode, optional otherwise (written 0 when given).
+ * x (nullable; EVAL / INPUT modes only) fp32 [B, S, E]: x[b, j] = item_emb[ids[b, j]] for item_emb fp32 [n_items_plus1, E] — a padded
+ * position copies ROW 0 of the table (what indexing the table with the padded ids gives), an id outside [0, n_items_plus1) is not
+ * dereferenced and yields a zero row.  Every element of every output given is written.
+ * Limits (IISAN_EBADSHAPE before any launch, the message names the argument): B >= 1, 1 <= S <= 63, no null pointer among those the mode
+ * needs, x only with item_emb and not in TRAIN mode, E % 4 == 0, item_emb and x 16-byte aligned. */
+int iisan_user_windows(const int64_t* seq_off, const int32_t* seq_items, int64_t n_users,
+                       const int64_t* user_index, int64_t B, int32_t S, int32_t mode,
+                       int64_t* ids, float* log_mask, int32_t* target,
+                       const float* item_emb, int64_t n_items_plus1, int32_t E, float* x, void* stream);
+/* history int32 [B, hist_stride] = the first min(len, hist_stride) entries of each user's exclusion list, padded with 0 — the `history`
+ * operand of iisan_score_rank / iisan_score_topk.  B >= 1, hist_stride >= 1. */
+int iisan_user_history(const int64_t* hist_off, const int32_t* hist_items, int64_t n_users,
+                       const int64_t* user_index, int64_t B, int32_t hist_stride, int32_t* history, void* stream);
+/* counts int64 [K + 2] += histogram of ranks int32 [U] (the caller zeroes it): counts[0] ranks < 1 (invalid targets), counts[r] rank r for
+ * 1 <= r <= K, counts[K + 1] ranks > K.  Integer adds only: the result does not depend on the launch's schedule.  U >= 1, 1 <= K <= 64. */
+int iisan_rank_histogram(const int32_t* ranks, int64_t U, int32_t K, int64_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Fused Adam over a flat fp32 parameter buffer with per-segment learning rates (torch.optim.Adam defaults, the
  * optimiser of Code_Uncached/run.py:323-336).  seg_end (host, int64[n_seg]) are exclusive end offsets: element i takes
  * seg_lr[s] for the first s with i < seg_end[s].  IISAN_EBADSHAPE unless n > 0, 1 <= n_seg <= 8, step >= 1, seg_end is
