@@ -93,6 +93,7 @@ SIGNATURES = {
     "iisan_layernorm": (i32, [i32, vp, vp, vp, f32, vp, vp, i64, i32, vp]),
     "iisan_attention16": (i32, [i32, vp, vp, vp, i64, i32, i32, vp]),
     "iisan_attention16_long": (i32, [i32, vp, vp, vp, i64, i32, i32, vp]),
+    "iisan_attention16_hd80": (i32, [i32, vp, vp, vp, i64, i32, i32, vp]),
     "iisan_attention_cls16": (i32, [i32, vp, vp, vp, i64, i32, i32, vp]),
     "iisan_attention16_dropout": (i32, [i32, vp, vp, vp, i64, i32, i32, f32, u64, i32, i32, vp]),
     "iisan_gemm32": (i32, [vp, vp, vp, vp, i64, i32, i64, i32, i32, i32, i32, vp]),

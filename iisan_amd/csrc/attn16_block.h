@@ -1,6 +1,7 @@
 // The per-block arithmetic the three MFMA attention kernels share (device only):
 //   attention16_kernel (attn16.hip), attention16_dma_kernel (attn16_dma.hip), attention16_drop_kernel (bert_drop.hip);
-//   attention16_long_kernel (attn16_long.hip) runs the same pieces per 128-key chunk, with the chunk form of the row softmax it defines.
+//   attention16_long_kernel (attn16_long.hip) and attention16_hd80_kernel (attn16_hd80.hip: 80-wide heads) run the same pieces per 128-key
+//   chunk, with the chunk form of the row softmax below.
 // A block = 16 queries of one (item, head) in one wave.  Scores are computed TRANSPOSED, S^T = K · Q^T, on v_mfma_f32_16x16x32: a lane
 // (j = lane & 15, g = lane >> 4) holds, for ONE query j, keys 16 t + 4 g + r of score tile t in sc[t][r] — so the softmax row reduction is a
 // per-lane loop plus two xor-shuffles (16, 32), and the exponentiated registers are ALREADY in B-operand layout for O^T = V^T · P^T.
@@ -84,6 +85,38 @@ __device__ __forceinline__ float attn_row_softmax(f4 (&sc)[NT16], Keep keep) {
     sum += __shfl_xor(sum, 16, 64);
     sum += __shfl_xor(sum, 32, 64);
     return 1.0f / sum;
+}
+
+// Chunk form of attn_row_softmax (the streaming-softmax kernels, attn16_long.hip and attn16_hd80.hip; c2 = log2(e) / sqrt(head width)): sc (raw, limited scores of one query row over ONE chunk) becomes p = exp2(sc c2 - ms_new) with
+// ms_new = max(ms_old, c2 * chunk maximum); returns ms_new and the chunk's row sum of the unrounded p.  Same instruction diet as the row
+// form: two max chains, four sum chains, one fma and the bare v_exp_f32 per score.
+struct AttnChunkStat { float ms, sum; };
+template <int NT16>
+__device__ __forceinline__ AttnChunkStat attn_chunk_softmax(f4 (&sc)[NT16], float ms_old, const float c2 = ATTN_C2) {
+    float mx0 = -INFINITY, mx1 = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < NT16; ++t) {
+        if (t & 1) mx1 = fmaxf(fmaxf(mx1, sc[t][0]), fmaxf(sc[t][1], fmaxf(sc[t][2], sc[t][3])));
+        else mx0 = fmaxf(fmaxf(mx0, sc[t][0]), fmaxf(sc[t][1], fmaxf(sc[t][2], sc[t][3])));
+    }
+    float mx = fmaxf(mx0, mx1);
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float ms = fmaxf(ms_old, mx * c2);
+    const float mxs = -ms;
+    f4 sum4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < NT16; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float p = __builtin_amdgcn_exp2f(fmaf(sc[t][r], c2, mxs));      // exactly 0 on all-masked rows (MASK_RAW c2 is exact)
+            sum4[r] += p;
+            sc[t][r] = p;
+        }
+    float sum = (sum4[0] + sum4[1]) + (sum4[2] + sum4[3]);
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    return {ms, sum};
 }
 
 // ---- P, rounded to the operand type -----------------------------------------------------------------------------------------------------

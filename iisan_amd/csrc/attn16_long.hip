@@ -37,38 +37,6 @@ constexpr int LONG_CHUNK = LONG_NT * 16;
 constexpr int LONG_NQ = ATTN_LONG_NQ;
 constexpr int LONG_MAX_S = 1024;
 
-// Chunk form of attn_row_softmax: sc (raw, limited scores of one query row over ONE chunk) becomes p = exp2(sc c2 - ms_new) with
-// ms_new = max(ms_old, c2 * chunk maximum); returns ms_new and the chunk's row sum of the unrounded p.  Same instruction diet as the row
-// form: two max chains, four sum chains, one fma and the bare v_exp_f32 per score.
-struct AttnChunkStat { float ms, sum; };
-template <int NT16>
-__device__ __forceinline__ AttnChunkStat attn_chunk_softmax(f4 (&sc)[NT16], float ms_old) {
-    float mx0 = -INFINITY, mx1 = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < NT16; ++t) {
-        if (t & 1) mx1 = fmaxf(fmaxf(mx1, sc[t][0]), fmaxf(sc[t][1], fmaxf(sc[t][2], sc[t][3])));
-        else mx0 = fmaxf(fmaxf(mx0, sc[t][0]), fmaxf(sc[t][1], fmaxf(sc[t][2], sc[t][3])));
-    }
-    float mx = fmaxf(mx0, mx1);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float ms = fmaxf(ms_old, mx * ATTN_C2);
-    const float mxs = -ms;
-    f4 sum4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < NT16; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float p = __builtin_amdgcn_exp2f(fmaf(sc[t][r], ATTN_C2, mxs));      // exactly 0 on all-masked rows (MASK_RAW c2 is exact)
-            sum4[r] += p;
-            sc[t][r] = p;
-        }
-    float sum = (sum4[0] + sum4[1]) + (sum4[2] + sum4[3]);
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    return {ms, sum};
-}
-
 // grid = (items * heads, query ranges), 256 threads.  Registers: 4 x (Q 8 + context 16 + statistics 2) per wave's blocks, one chunk's scores
 // (32), the next chunk's K / V rows (32), K / V^T fragments: 222 VGPRs, no scratch (tests/test_isa_long_attention.py); LDS 35,328 B.
 template <typename T>

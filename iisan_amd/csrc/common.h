@@ -356,7 +356,7 @@ int launch_gemm16_s256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s
 bool gemm16_h256_applicable(int mode, const Gemm16Args& a);      // gemm16_h256.hip
 int launch_gemm16_h256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s);
 int launch_gemm16_f32(const Gemm16Args& a, int ksplit, hipStream_t s);      // gemm16.hip: fp32 output of the 128x128 kernel (split.hip)
-// `width` of the row kernels below: 768 or 1024, or 128, 192, 256, 384 (the instantiated widths; anything else: IISAN_EBADSHAPE)
+// `width` of the row kernels below: 768 or 1024, or 128, 192, 256, 384, or 1280 (the instantiated widths; anything else: IISAN_EBADSHAPE)
 bool row_width_instantiated(int width);     // rowops.hip; the encoder executors accept a tower of exactly these hidden sizes
 int launch_layernorm768(int dtype16, const float* x, const float* g, const float* b, float eps, void* out16,
                         float* out32, int64_t rows, int width, hipStream_t s);
@@ -396,6 +396,8 @@ int launch_attention16(int dtype16, const void* qkv, const float* key_bias, void
                        int heads, hipStream_t s);
 // attn16_long.hip: streaming softmax over 128-key chunks, any 1 <= S <= 1024; launch_attention16 sends 224 < S <= 1024 there
 int launch_attention16_long(int dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int S, int heads, hipStream_t s);
+// attn16_hd80.hip: the same streaming softmax for 80-wide heads (ViT-H/14); qkv ROW-MAJOR [items * S, 3 * heads * 80] (an EPI_OUT16 product)
+int launch_attention16_hd80(int dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int S, int heads, hipStream_t s);
 // attn16_dma.hip: the ViT shape (no key_bias, 192 < S <= 208) with K / V staged by LDS-DMA; `routed` = launch_attention16 sends this
 // problem there under the dev switch attn_route
 bool attention16_dma_routed(const float* key_bias, int S);
@@ -404,6 +406,8 @@ int launch_attention16_dma(int dtype16, const void* qkv, void* ctx, int64_t item
 int launch_attention_cls16(int dtype16, const void* qkv, const float* key_bias, void* ctx_cls, int64_t items, int S,
                            int heads, hipStream_t s, const void* q_cls = nullptr);   // q_cls: [items, heads*64] 16-bit CLS queries
 // embedding and tap steps of the encoder executors (rowops.hip)
+// columns of a patch row in the patch matrix / the packed patch weight: C p p, zero-padded to a multiple of 64 when p % 8 != 0 (p = 14: 588 -> 640)
+int vit_patch_ld(int C, int p);
 int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64_t M, int C, int R, int p, hipStream_t s);
 // item m = row index[m] of a resident uint8 catalogue [rows, C, R, R]; values outside [0, rows) = padding (zero fragment, no read)
 int launch_vit_im2col_indexed(int dtype16, const uint8_t* catalogue, int64_t rows, const int64_t* index, void* out, int64_t M, int C,

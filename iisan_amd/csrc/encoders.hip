@@ -13,7 +13,7 @@ struct EncBufs {
     void* X16;      // [Tp, D] fp16: residual stream of the non-CLS rows (mixed mode)
     float* Xc;      // [Mcp, D] fp32: residual stream of the CLS rows, compact (mixed mode) = the hidden states' tapped rows
     void* H;        // [Tp, D] 16-bit: LayerNorm output, reused as the attention context
-    void* QKV;      // [Tp, 3D] 16-bit
+    void* QKV;      // [Tp, 3D] 16-bit: head-major per item (EPI_QKVH16); 80-wide heads: row-major, the output of a plain product
     void* F1;       // [Tp, max(F, patch_dim)] 16-bit: GELU(FC1) (and the patch matrix during embedding)
     void* D16;      // [Tp, D] 16-bit: output of the O GEMM (a residual DELTA, added to the fp32 stream by LayerNorm kernels)
     void* D16b;     // [Tp, D] 16-bit: output of the FC2 GEMM
@@ -94,6 +94,9 @@ struct Products {
     bool stream = false;    // O / FC2 add into the stream in their epilogues (VS_STREAM)
     bool f1blk = false;     // F1, the FC1 -> FC2 intermediate of the all-token blocks, is block-major
     bool xblk = false;      // ... and so is the ViT stream X16 (VS_STREAM only)
+    // 80-wide heads (ViT-H/14, hidden 1280 = 16 x 80): QKV is a plain row-major product (no GEMM epilogue knows a head width but 64), the
+    // attention runs attn16_hd80.hip, and there is no CLS-only form of the last live block: it runs on every token
+    bool hd80() const { return D == heads * 80; }
 
     // out [M, N] = A [M, K] W^T, natural leading dimensions: the products of the CLS tail (one row per item) as they are
     static Product plain(int mode, int K, int N, int64_t M) {
@@ -103,6 +106,7 @@ struct Products {
     }
     // q | k | v from `which0` on, head-major (1: K and V alone, the CLS-only last block)
     Product qkv(int64_t tok, int which0 = 0) const {
+        if (hd80()) return plain(EPI_OUT16, D, 3 * D, tok);     // q | k | v only: VitChunk::cls_block, the one caller of which0 = 1, refuses this head width
         Product p = plain(EPI_QKVH16, D, (3 - which0) * D, tok);
         p.a.qkv_S = T; p.a.qkv_heads = heads; p.a.qkv_which0 = which0;
         p.a.rowstat = ln ? &WANTED : nullptr; p.a.a_blk32 = xblk;
@@ -161,13 +165,15 @@ int max_tap(const int32_t* tap_layers, int n) {
     return m;
 }
 
-int check_common(int hidden, int layers, int heads, int mlp, int n_taps, const int32_t* tap_layers) {
-    // ViT-B / BERT-base, ViT-L / BERT-large, and the narrow towers — BERT-tiny (128), ViT-tiny (192), BERT-mini (256), ViT-small (384)
-    IISAN_CHECK_SHAPE(row_width_instantiated(hidden),
+int check_common(bool vit, int hidden, int layers, int heads, int mlp, int n_taps, const int32_t* tap_layers) {
+    // ViT-B / BERT-base, ViT-L / BERT-large, and the narrow towers — BERT-tiny (128), ViT-tiny (192), BERT-mini (256), ViT-small (384);
+    // on the ViT executor alone ViT-H/14: 1280 as 16 heads of 80 (1280 as 20 heads of 64 is no tower the reference caches, and stays refused)
+    const bool huge = vit && hidden == 1280 && heads == 16;
+    IISAN_CHECK_SHAPE(huge || (hidden != 1280 && row_width_instantiated(hidden)),
                       "encoder hidden size %d not supported: the supported widths are 768 (12 heads) and 1024 (16 heads), "
-                      "and 128, 192, 256, 384 (2, 3, 4, 6 heads)", hidden);
-    IISAN_CHECK_SHAPE(heads > 0 && hidden == heads * 64, "encoder head_dim must be 64 (hidden %d, heads %d; supported: 768 / 12 and 1024 / 16, "
-                      "128 / 2, 192 / 3, 256 / 4, 384 / 6)", hidden, heads);
+                      "and 128, 192, 256, 384 (2, 3, 4, 6 heads); the ViT executor also takes 1280 as 16 heads of 80", hidden);
+    IISAN_CHECK_SHAPE(huge || (heads > 0 && hidden == heads * 64), "encoder head_dim must be 64 (hidden %d, heads %d; supported: 768 / 12 and 1024 / 16, "
+                      "128 / 2, 192 / 3, 256 / 4, 384 / 6; ViT only: 1280 / 16, head_dim 80)", hidden, heads);
     IISAN_CHECK_SHAPE(layers >= 1 && layers <= IISAN_MAX_LAYERS, "encoder layers %d out of range", layers);
     IISAN_CHECK_SHAPE(mlp % 128 == 0, "encoder mlp size %d must be a multiple of 128", mlp);
     IISAN_CHECK_SHAPE(n_taps >= 1 && tap_layers, "need at least one tap layer");
@@ -186,7 +192,7 @@ int bert_check_words(int words, int max_pos) {
 }
 
 // The LayerNorm-folded routes — fold_ln_weights, the stream statistics, the block-major stream — take fp16 operands and are 768 wide: a
-// bf16 tower, a 1024-wide one and the narrow ones (128 - 384) run on the LayerNorm-image route whatever ln_fold says, and ask for no folded set
+// bf16 tower, a 1024- or 1280-wide one and the narrow ones (128 - 384) run on the LayerNorm-image route whatever ln_fold says, and ask for no folded set
 bool vit_fold_routes(int dtype16, int hidden) { return dtype16 == IISAN_F16 && hidden == 768; }
 
 // One chunk of a forward: mc items from item m0 of the call on, tok = mc * T token rows, tp = their rows of the tap tensor
@@ -278,7 +284,7 @@ extern "C" int iisan_vit_fold_layernorm(const iisan_vit_weights* w, void* folded
 // the workspace of a ViT call that runs in chunks of Mc items (c.off: its size)
 static void vit_carve(WsCarver& c, EncBufs& b, const iisan_vit_weights* w, int64_t Mc) {
     const int P = (w->image / w->patch) * (w->image / w->patch);
-    const int pd = w->channels * w->patch * w->patch;
+    const int pd = vit_patch_ld(w->channels, w->patch);
     carve(c, b, Mc * (P + 1), Mc, w->hidden, w->mlp > pd ? w->mlp : pd, 0, vit_fold_layers(w), w->folded == nullptr);
 }
 
@@ -346,7 +352,7 @@ struct VitChunk : Chunk {
 
     // index != null: `img` is a resident uint8 catalogue of `rows` images and item m of the chunk is its row index[m]
     int embed(const void* img, int img_u8, const int64_t* index = nullptr, int64_t rows = 0) const {
-        const int P = T - 1, pd = w->channels * w->patch * w->patch;
+        const int P = T - 1, pd = vit_patch_ld(w->channels, w->patch);      // (588 -> 640 columns at patch 14: zeros in F1 and in patch_w)
         if (index) IISAN_TRY(launch_vit_im2col_indexed(dt, (const uint8_t*)img, rows, index, b.F1, mc, w->channels, w->image, w->patch, s));
         else IISAN_TRY(launch_vit_im2col(dt, img, img_u8, b.F1, mc, w->channels, w->image, w->patch, s));
         // patch embedding: resid32 = fp32 token rows with the position embedding added (128x128 kernel); mixed = 16-bit rows on the
@@ -410,7 +416,8 @@ struct VitChunk : Chunk {
     int full_block(int l, int (VitChunk::*mid)(int) const) const {
         const iisan_layer_weights& L = layer(l);
         IISAN_TRY(launch(qkv(tok), act(), ln ? Wf_qkv(l) : L.qkv_w, ln ? bf_qkv(l) : L.qkv_b, b.QKV));
-        IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
+        if (hd80()) IISAN_TRY(launch_attention16_hd80(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
+        else IISAN_TRY(launch_attention16(dt, b.QKV, nullptr, b.H, mc, T, heads, s));
         IISAN_TRY(delta(o(tok), b.H, L.o_w, L.o_b, b.D16));
         IISAN_TRY((this->*mid)(l));
         IISAN_TRY(launch(fc1(tok), act(), ln ? Wf_fc1(l) : L.fc1_w, ln ? bf_fc1(l) : L.fc1_b, b.F1));
@@ -418,6 +425,9 @@ struct VitChunk : Chunk {
     }
     // the CLS-only last live block (Chunk::cls_tail); its output goes to tap k
     int cls_block(int l, int k) const {
+        // the K / V product, the CLS attention kernel and the CLS tail are written for 64-wide heads: the executor runs the last live block of an
+        // 80-wide-head tower on every token and never comes here
+        IISAN_CHECK_SHAPE(!hd80(), "vit: no CLS-only form of the last live block for 80-wide heads (hidden %d, heads %d)", D, heads);
         const iisan_layer_weights& L = layer(l);
         // the CLS rows' LN1 image: from their fp32 stream, or gathered from the image of every row
         if (ln) IISAN_TRY(launch_layernorm768(dt, b.Xc, L.ln1_w, L.ln1_b, eps, b.Cls, nullptr, mc, D, s));
@@ -445,10 +455,13 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
                                  void* ws, size_t ws_bytes, void* stream, const int64_t* index = nullptr, int64_t rows = 0) {
     hipStream_t s = (hipStream_t)stream;
     IISAN_CHECK_SHAPE(M > 0, "vit_forward_taps: M must be positive");
-    IISAN_TRY(check_common(w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
-    IISAN_CHECK_SHAPE(w->patch % 8 == 0 && w->image % w->patch == 0, "vit: patch %d / image %d unsupported", w->patch, w->image);
+    IISAN_TRY(check_common(true, w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
+    // patch sides: the multiples of 8, and 14 (ViT-H/14) through the padded patch extraction
+    IISAN_CHECK_SHAPE((w->patch % 8 == 0 || w->patch == 14) && w->patch > 0 && w->image % w->patch == 0, "vit: patch %d / image %d unsupported", w->patch, w->image);
     const int D = w->hidden, T = (w->image / w->patch) * (w->image / w->patch) + 1;
-    const int pd = w->channels * w->patch * w->patch;
+    // a patch side that is a multiple of 8 takes its patch vector as it is; 14 is zero-padded to a multiple of 64 by the patch
+    // extraction, and patch_w carries the same padding (vit_patch_ld)
+    const int pd = vit_patch_ld(w->channels, w->patch);
     IISAN_CHECK_SHAPE(pd % 64 == 0, "vit: patch vector length %d must be a multiple of 64", pd);
     IISAN_TRY(vit_check_tokens(T));
     const Chunks c(M, chunk_items);
@@ -467,7 +480,9 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
     // Blocks after the deepest tapped hidden state are dead code (Versa configurations tap a prefix of the tower)
     const int live = full_blocks ? w->layers : max_tap(tap_layers, n_taps);
     Products p{w->dtype16, D, w->mlp, T, w->heads};
-    const VitPlan plan = vit_plan(p, live, full_blocks, w->folded != nullptr, c);
+    // 80-wide heads: the last live block has no CLS-only form and runs on every token (1 / 32 of a ViT-H)
+    const bool all_tokens = full_blocks || p.hd80();
+    const VitPlan plan = vit_plan(p, live, all_tokens, w->folded != nullptr, c);
     const auto& step = VIT_STEPS[plan.st];
     if (plan.folds) IISAN_TRY(vit_fold_all(w, live, full_blocks, (char*)b.Wf, b.Bf, s));
     const int64_t img_elems = (int64_t)w->channels * w->image * w->image;
@@ -482,10 +497,11 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
             IISAN_TRY((ch.*step.open)(l));       // -> the stream is hidden state l
             k = tap_index(tap_layers, n_taps, l);
             if (k >= 0 && l > 0) IISAN_TRY(ch.tap(k));
-            if (l + 1 < live || full_blocks) IISAN_TRY(ch.full_block(l, step.mid));
+            if (l + 1 < live || all_tokens) IISAN_TRY(ch.full_block(l, step.mid));
             else IISAN_TRY(ch.cls_block(l, tap_index(tap_layers, n_taps, live)));
         }
-        k = full_blocks ? tap_index(tap_layers, n_taps, w->layers) : -1;
+        // (full_blocks: live = the whole tower.  live = 0: no block has run, tap 0 is written above and there is nothing to close)
+        k = all_tokens && live > 0 ? tap_index(tap_layers, n_taps, live) : -1;
         if (k >= 0) {
             IISAN_TRY((ch.*step.close)());
             IISAN_TRY(ch.tap(k));
@@ -610,7 +626,7 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
     IISAN_CHECK_SHAPE(!(dropping && w->hidden != 768), "bert dropout: no train-mode instantiation at this width, hidden size %d runs in eval mode only "
                       "(drop == NULL or both probabilities 0)", w->hidden);
     IISAN_CHECK_SHAPE(M > 0, "bert_forward_taps: M must be positive");
-    IISAN_TRY(check_common(w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
+    IISAN_TRY(check_common(false, w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
     IISAN_TRY(bert_check_words(words, w->max_pos));
     // ... and the train-mode attention kernel keeps a whole head in LDS (bert_drop.hip): refused here, before any launch, never a silent fall-back
     IISAN_CHECK_SHAPE(!(dropping && words > 224), "bert dropout: no train-mode attention kernel past 224 words, titles of %d words run in eval mode only "
@@ -681,7 +697,7 @@ extern "C" int32_t iisan_encoder_plan(int32_t tower, int32_t dtype16, int32_t hi
     IISAN_CHECK_SHAPE(tower == IISAN_TOWER_VIT || tower == IISAN_TOWER_BERT, "encoder_plan: tower %d is neither ViT (0) nor BERT (1)", tower);
     IISAN_CHECK_SHAPE(M > 0, "encoder_plan: M must be positive");
     const int layers = deepest_tap > 1 ? deepest_tap : 1;
-    IISAN_TRY(check_common(hidden, layers, heads, mlp, 1, &deepest_tap));
+    IISAN_TRY(check_common(tower == IISAN_TOWER_VIT, hidden, layers, heads, mlp, 1, &deepest_tap));
     IISAN_TRY(tower == IISAN_TOWER_VIT ? vit_check_tokens(tokens) : bert_check_words(tokens, tokens));
     const bool full = g_full_blocks || full_blocks;
     const Chunks c(M, chunk_items);
@@ -690,6 +706,6 @@ extern "C" int32_t iisan_encoder_plan(int32_t tower, int32_t dtype16, int32_t hi
         const BertPlan plan = bert_plan(p, c);
         return (plan.mixed ? 1 : 0) | (plan.alias ? 2 : 0) | (p.f1blk ? 4 : 0);
     }
-    const VitPlan plan = vit_plan(p, full ? layers : deepest_tap, full, folded != 0, c);
-    return (int32_t)plan.st | (p.f1blk ? 4 : 0) | (p.xblk ? 8 : 0) | (plan.folds ? 16 : 0);
+    const VitPlan plan = vit_plan(p, full ? layers : deepest_tap, full || p.hd80(), folded != 0, c);
+    return (int32_t)plan.st | (p.f1blk ? 4 : 0) | (p.xblk ? 8 : 0) | (plan.folds ? 16 : 0) | (p.hd80() ? 32 : 0);
 }

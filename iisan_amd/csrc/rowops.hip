@@ -2,7 +2,7 @@
 // Roofline: HBM (one read + one write of each row); one wave64 per row, 16-byte lane accesses,
 // wavefront-shuffle reductions, fp32 statistics (two-pass mean / centred variance in registers).
 // The row width D is a template parameter of the LayerNorm / embedding kernels (D / 256 pieces per lane: 3 at 768 — ViT-B, BERT-base —
-// 4 at 1024 — ViT-L, BERT-large); their names keep the 768 they were written for.  Below 768 (128, 192, 256, 384: BERT-tiny, ViT-tiny,
+// 4 at 1024 — ViT-L, BERT-large — 5 at 1280 — ViT-H/14, the ViT executor only); their names keep the 768 they were written for.  Below 768 (128, 192, 256, 384: BERT-tiny, ViT-tiny,
 // BERT-mini, ViT-small) a row takes fewer lanes, a compile-time quantity beside the piece count (row_lpr / row_np below), and several
 // rows share a wave.  The kernels of the ViT's product route
 // (fold_ln_weights, stream_stats_finalize, the MX_STAT / MX_BLK32 operand sets) are 768 wide only.
@@ -26,7 +26,7 @@ constexpr int row_lpr(int D, int vec, int full) { return D / vec / row_np(D, vec
 constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
 constexpr bool row_width_ok(int D, int vec, int full) {
     const int np = row_np(D, vec, full), lpr = row_lpr(D, vec, full);
-    return lpr * np * vec == D && lpr >= 8 && lpr <= full && (lpr & (lpr - 1)) == 0 && np >= 1 && np <= 4;
+    return lpr * np * vec == D && lpr >= 8 && lpr <= full && (lpr & (lpr - 1)) == 0 && np >= 1 && np <= 5;
 }
 template <int LPR>
 __device__ __forceinline__ float row_sum(float v) {          // over the LPR lanes of a row (LPR = 64: wave_sum)
@@ -335,6 +335,46 @@ __global__ __launch_bounds__(256) void vit_im2col_kernel(const SRC* __restrict__
     }
 }
 
+// The same for a patch side that is no multiple of 8 (ViT-H/14: p = 14, C p p = 588): the patch row is ZERO-PADDED to `ldp` columns, the next
+// multiple of 64 (640), as the packed patch weight is, so the patch-embedding product keeps K % 64 == 0.  One thread = 8 consecutive
+// columns of the padded row (one 16-byte store), each read on its own: a run of 8 columns crosses pixel rows of 14.  The arithmetic per pixel
+// — the two __fdiv_rn of the uint8 source, the zero fragment of an indexed pad slot — is that of the kernel above.
+template <typename T, typename SRC, bool IDX = false>
+__global__ __launch_bounds__(256) void vit_im2col_pad_kernel(const SRC* __restrict__ img, typename T::elem* __restrict__ out,
+                                                             int64_t M, int C, int R, int p, int ldp,
+                                                             const int64_t* __restrict__ index = nullptr, int64_t rows = 0) {
+    const int pd = C * p * p, per_row = ldp / 8;
+    const int gp = R / p;
+    const int64_t total = M * gp * gp * per_row;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int t = (int)(i % per_row);
+        const int64_t pr = i / per_row;        // patch row index = m*P + py*gp + px
+        const int64_t m = pr / (gp * gp);
+        const int pp = (int)(pr % (gp * gp)), py = pp / gp, px = pp % gp;
+        int64_t sm = m;
+        bool pad = false;
+        if constexpr (IDX) {
+            sm = index[m];
+            pad = (uint64_t)sm >= (uint64_t)rows;       // negative or >= rows: never loaded
+            if (pad) sm = 0;
+        }
+        typename T::v8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int col = t * 8 + e;
+            float a = 0.f;
+            if (col < pd && !(IDX && pad)) {            // columns pd .. ldp - 1: the zero padding
+                const int c = col / (p * p), rem = col % (p * p), iy = rem / p, ix = rem % p;
+                const SRC v = img[((sm * C + c) * R + (py * p + iy)) * (int64_t)R + px * p + ix];
+                if constexpr (sizeof(SRC) == 4) a = v;
+                else a = __fdiv_rn(__fdiv_rn((float)v, 255.0f) - 0.5f, 0.5f);
+            }
+            o[e] = T::from_f32(a);
+        }
+        *(typename T::v8*)(out + pr * (int64_t)ldp + t * 8) = o;
+    }
+}
+
 // CLS rows of the token matrix: X[m*T] = cls + pos[0]
 __global__ void vit_cls_rows_kernel(float* __restrict__ X, const float* __restrict__ cls, const float* __restrict__ pos,
                                     int64_t M, int T, int D) {
@@ -458,10 +498,13 @@ __global__ void cast16_kernel(const float* __restrict__ src, typename T::elem* _
 
 // The instantiated row widths: 768 / 1024 (ViT-B / BERT-base, ViT-L / BERT-large) and the narrow towers' 128, 192, 256, 384 (BERT-tiny, ViT-tiny,
 // BERT-mini, ViT-small).  The refusal names the width it was given and 768 and 1024 first.
-bool row_width_instantiated(int w) { return w == 768 || w == 1024 || w == 128 || w == 192 || w == 256 || w == 384; }
-#define ROW_WIDTH_MSG "row width %d not instantiated (768 and 1024 are, and 128, 192, 256, 384)"
-// one switch over the widths: X(W, A) is the launch at the compile-time width W (A: whatever else the launch is a template of)
-#define ROW_WIDTH_SWITCH(width, X, A)                                                                                         \
+// 1280 (ViT-H/14: five pieces per lane) is instantiated like the others; the executors take it on the ViT alone (encoders.hip, check_common).
+bool row_width_instantiated(int w) { return w == 768 || w == 1024 || w == 128 || w == 192 || w == 256 || w == 384 || w == 1280; }
+#define ROW_WIDTH_MSG "row width %d not instantiated (768 and 1024 are, and 128, 192, 256, 384, 1280)"
+// one switch over the widths: X(W, A) is the launch at the compile-time width W (A: whatever else the launch is a template of).
+// ROW_WIDTH_SWITCH_64: the widths of the towers with 64-wide heads, ViT and BERT — what the BERT-only kernels are instantiated at (the BERT
+// embedding, the post-LN operand sets of the mixed kernel); ROW_WIDTH_SWITCH: those and 1280, for the kernels the ViT executor launches.
+#define ROW_WIDTH_SWITCH_64(width, X, A)                                                                                      \
     switch (width) {                                                                                                           \
         case 128: X(128, A); break;                                                                                            \
         case 192: X(192, A); break;                                                                                            \
@@ -470,6 +513,8 @@ bool row_width_instantiated(int w) { return w == 768 || w == 1024 || w == 128 ||
         case 768: X(768, A); break;                                                                                            \
         default: X(1024, A); break;                                                                                            \
     }
+#define ROW_WIDTH_SWITCH(width, X, A)                                                                                         \
+    if ((width) == 1280) { X(1280, A); } else ROW_WIDTH_SWITCH_64(width, X, A)
 
 // width: one of the instantiated row widths (anything else is IISAN_EBADSHAPE)
 int launch_add2_layernorm768(int dtype16, const float* x, const void* delta16, const void* delta16b, const float* g,
@@ -552,14 +597,20 @@ int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, f
         ROW_WIDTH_SWITCH(width, MX_AT, VV)                                                                                     \
         IISAN_LAUNCH_OK();                                                                                                     \
         return IISAN_OK
+#define MX_CASE_BERT(VV)                                                                                                       \
+    case VV:                                                                                                                   \
+        if (width == 1280) break;                                                                                              \
+        ROW_WIDTH_SWITCH_64(width, MX_AT, VV)                                                                                  \
+        IISAN_LAUNCH_OK();                                                                                                     \
+        return IISAN_OK
     switch (V) {
         MX_CASE(MX_SRC32 | MX_RESV | MX_LN);               // ViT block 0, LN1: fp32 embeddings -> fp16 stream + LN image
         MX_CASE(MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_LN);   // ViT block 0, LN1: position table + 16-bit patch embedding -> stream + image
         MX_CASE(MX_D1 | MX_LN);                            // ViT LN2: LN(x + dO), x not written
         MX_CASE(MX_D1 | MX_D2 | MX_RESV | MX_LN);          // ViT LN1: x += dO + dF; LN
         MX_CASE(MX_D1 | MX_D2 | MX_RESV | MX_CLSONLY);     // ViT closing add of the CLS rows (the last hidden state)
-        MX_CASE(MX_D1 | MX_LN | MX_RESY);                  // BERT: x = LN(x + d)
-        MX_CASE(MX_D1 | MX_LN | MX_RESY | MX_ALIAS);       // BERT, fp16 operands: ... and the image IS the stream
+        MX_CASE_BERT(MX_D1 | MX_LN | MX_RESY);             // BERT: x = LN(x + d) (no BERT is 1280 wide)
+        MX_CASE_BERT(MX_D1 | MX_LN | MX_RESY | MX_ALIAS);  // BERT, fp16 operands: ... and the image IS the stream
         // LayerNorm applied by the consuming product (Gemm16Args::rowstat): the stream and the row statistics only — 768 wide
         MX_CASE768(MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_STAT);   // ViT block 0
         MX_CASE768(MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_STAT | MX_BLK32);   // ... into a block-major stream
@@ -569,6 +620,7 @@ int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, f
     }
 #undef MX_AT
 #undef MX_CASE
+#undef MX_CASE_BERT
 #undef MX_CASE768
 #undef MX_KEEP
 #undef MX_LAUNCH
@@ -586,7 +638,29 @@ int launch_layernorm768(int dtype16, const float* x, const float* g, const float
     return launch_add_layernorm768(dtype16, x, nullptr, g, b, eps, nullptr, out16, out32, rows, width, s);
 }
 
+// columns of a patch row in the patch matrix (and of a row of the packed patch weight): C p p, zero-padded to a multiple of 64 where the
+// patch side is no multiple of 8
+int vit_patch_ld(int C, int p) { return p % 8 == 0 ? C * p * p : (int)ceil_div(C * p * p, 64) * 64; }
+
 int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64_t M, int C, int R, int p, hipStream_t s) {
+    if (p % 8 != 0) {
+        const int ldp = vit_patch_ld(C, p);
+        const int64_t total = M * (R / p) * (R / p) * (ldp / 8);
+        const unsigned grid = (unsigned)(ceil_div(total, 256) < 262144 ? ceil_div(total, 256) : 262144);
+        if (img_u8) {
+            if (dtype16 == IISAN_BF16)
+                hipLaunchKernelGGL((vit_im2col_pad_kernel<BF16, uint8_t>), dim3(grid), dim3(256), 0, s, (const uint8_t*)img, (__bf16*)out, M, C, R, p, ldp);
+            else
+                hipLaunchKernelGGL((vit_im2col_pad_kernel<F16, uint8_t>), dim3(grid), dim3(256), 0, s, (const uint8_t*)img, (_Float16*)out, M, C, R, p, ldp);
+        } else {
+            if (dtype16 == IISAN_BF16)
+                hipLaunchKernelGGL((vit_im2col_pad_kernel<BF16, float>), dim3(grid), dim3(256), 0, s, (const float*)img, (__bf16*)out, M, C, R, p, ldp);
+            else
+                hipLaunchKernelGGL((vit_im2col_pad_kernel<F16, float>), dim3(grid), dim3(256), 0, s, (const float*)img, (_Float16*)out, M, C, R, p, ldp);
+        }
+        IISAN_LAUNCH_OK();
+        return IISAN_OK;
+    }
     const int64_t total = M * (R / p) * (R / p) * (C * p * p / 8);
     const unsigned grid = (unsigned)(ceil_div(total, 256) < 262144 ? ceil_div(total, 256) : 262144);
     if (img_u8) {
@@ -606,6 +680,17 @@ int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64
 
 int launch_vit_im2col_indexed(int dtype16, const uint8_t* catalogue, int64_t rows, const int64_t* index, void* out, int64_t M, int C,
                               int R, int p, hipStream_t s) {
+    if (p % 8 != 0) {
+        const int ldp = vit_patch_ld(C, p);
+        const int64_t total = M * (R / p) * (R / p) * (ldp / 8);
+        const unsigned grid = (unsigned)(ceil_div(total, 256) < 262144 ? ceil_div(total, 256) : 262144);
+        if (dtype16 == IISAN_BF16)
+            hipLaunchKernelGGL((vit_im2col_pad_kernel<BF16, uint8_t, true>), dim3(grid), dim3(256), 0, s, catalogue, (__bf16*)out, M, C, R, p, ldp, index, rows);
+        else
+            hipLaunchKernelGGL((vit_im2col_pad_kernel<F16, uint8_t, true>), dim3(grid), dim3(256), 0, s, catalogue, (_Float16*)out, M, C, R, p, ldp, index, rows);
+        IISAN_LAUNCH_OK();
+        return IISAN_OK;
+    }
     const int64_t total = M * (R / p) * (R / p) * (C * p * p / 8);
     const unsigned grid = (unsigned)(ceil_div(total, 256) < 262144 ? ceil_div(total, 256) : 262144);
     if (dtype16 == IISAN_BF16)
@@ -627,7 +712,7 @@ template <bool IDX>
 static int bert_embed_ln_any(int dtype16, const int64_t* text, int64_t rows, const int64_t* index, const float* word, const float* pos,
                              const float* type0, const float* g, const float* b, float eps, float* X, void* H, float* key_bias,
                              int64_t M, int W, int vocab, int width, hipStream_t s, void* X16, float* Xc, const RowKeep* keep) {
-    IISAN_CHECK_SHAPE(row_width_instantiated(width), "bert_embed_ln: " ROW_WIDTH_MSG, width);
+    IISAN_CHECK_SHAPE(row_width_instantiated(width) && width != 1280, "bert_embed_ln: " ROW_WIDTH_MSG " — 1280 on the ViT's kernels only", width);
     dim3 grid((unsigned)ceil_div(M * W, (int64_t)(256 / row_lpr(width, 4, 64)))), block(256);
 #define EMBED_LAUNCH(TT, EL, WD)                                                                                               \
     hipLaunchKernelGGL((bert_embed_ln_kernel<TT, IDX, WD>), grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (EL*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows)
@@ -640,7 +725,7 @@ static int bert_embed_ln_any(int dtype16, const int64_t* text, int64_t rows, con
     } else {
 #define EMBED_AT(WD, TT)                                                                                                       \
     if (dtype16 == IISAN_BF16) EMBED_LAUNCH(BF16, __bf16, WD); else EMBED_LAUNCH(TT, _Float16, WD)
-        ROW_WIDTH_SWITCH(width, EMBED_AT, F16)
+        ROW_WIDTH_SWITCH_64(width, EMBED_AT, F16)
 #undef EMBED_AT
     }
 #undef EMBED_KEEP

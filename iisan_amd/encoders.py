@@ -103,6 +103,8 @@ class PackedVit(_PackedEncoder):
         s = _lib.VitWeights()
         s.hidden, s.layers, s.heads, s.mlp = cfg.hidden, cfg.layers, cfg.heads, cfg.mlp
         s.image, s.patch, s.channels, s.dtype16, s.eps = cfg.image, cfg.patch, cfg.channels, dtype16, cfg.eps
+        if cfg.patch_ld != cfg.patch_dim:      # patch 14: rows zero-padded like the patch matrix (include/iisan_hip.h)
+            self._w = dict(w, patch_w=torch.nn.functional.pad(w["patch_w"].float(), (0, cfg.patch_ld - cfg.patch_dim)))
         s.patch_w, s.patch_b = self._m16("patch_w"), self._v32("patch_b")
         s.cls_token, s.pos_emb = self._v32("cls_token"), self._v32("pos_emb")
         # LayerNorm 1 / 2 folded into the QKV / FC1 weights once, here, instead of at the start of every forward call — where the

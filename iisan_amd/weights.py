@@ -52,6 +52,12 @@ class VitConfig:
     def patch_dim(self) -> int:
         return self.channels * self.patch * self.patch
 
+    @property
+    def patch_ld(self) -> int:
+        """Columns of a row of the PACKED patch weight (and of the patch matrix): `patch_dim`, zero-padded to the next multiple of 64
+        when the patch side is no multiple of 8 (patch 14: 588 -> 640), so that the patch-embedding product keeps K % 64 == 0."""
+        return self.patch_dim if self.patch % 8 == 0 else -(-self.patch_dim // 64) * 64
+
 
 @dataclass(frozen=True)
 class BertConfig:
@@ -80,6 +86,9 @@ BERT_LARGE = BertConfig(hidden=1024, layers=24, heads=16, mlp=4096)
 # like every tower here, hidden 128 - 384 (`vit_from_hf` / `bert_from_hf` read every shape off the state dict)
 VIT_TINY = VitConfig(hidden=192, layers=12, heads=3, mlp=768)
 VIT_SMALL = VitConfig(hidden=384, layers=12, heads=6, mlp=1536)
+# ViT-H/14 (`Code_Cached_Asym/preprocess_vectors_vit_large.py:111` caches the CLS rows of all 33 hidden states of
+# `google/vit-huge-patch14-224-in21k`): 16 heads of 80, 14-pixel patches (257 tokens at 224 pixels, a patch vector of 588)
+VIT_HUGE = VitConfig(hidden=1280, layers=32, heads=16, mlp=5120, patch=14)
 BERT_TINY = BertConfig(hidden=128, layers=2, heads=2, mlp=512, vocab=30522, eps=1e-12)
 BERT_MINI = BertConfig(hidden=256, layers=4, heads=4, mlp=1024, vocab=30522, eps=1e-12)
 

@@ -48,12 +48,19 @@ const char* iisan_last_error(void);
  * Frozen encoders (no-grad).  Weights are packed once by the host (iisan_amd/encoders.py): matrices in the 16-bit
  * operand type, [out,in] row-major exactly like torch.nn.Linear.weight; vectors in fp32.
  * Hidden size D = 64 * heads with D = 768 (ViT-B/16, BERT-base: 12 heads) or D = 1024 (ViT-L/16, BERT-large: 16 heads), or one of the
- * narrow towers' D = 128 (BERT-tiny: 2 heads), 192 (ViT-tiny: 3), 256 (BERT-mini: 4), 384 (ViT-small: 6); any other width (512 and
- * 1280 among them) is IISAN_EBADSHAPE before any launch.  The taps are D wide — the tower's own width, not the side network's.
+ * narrow towers' D = 128 (BERT-tiny: 2 heads), 192 (ViT-tiny: 3), 256 (BERT-mini: 4), 384 (ViT-small: 6).  The ViT executor alone also takes
+ * ViT-H/14: D = 1280 as 16 heads of 80, 14-pixel patches (below).  Any other width or pair (512; 1280 with 20 heads; 1280 on the BERT
+ * executor) is IISAN_EBADSHAPE before any launch.  The taps are D wide — the tower's own width, not the side network's.
  * Every D other than 768 runs on the LayerNorm-image route of both executors (mixed fp16 / fp32-CLS residual stream; dev switch
  * resid32 works too), in eval mode only (iisan_bert_forward_taps_dropout: drop == NULL or both probabilities 0).  The
  * LayerNorm-folded route of the ViT executor (folded weights, stream epilogues, block-major stream) is 768 wide only: at any other D
  * iisan_vit_fold_bytes is 0, `folded` is ignored, and the dev switch ln_fold selects nothing.
+ * ViT-H/14 (hidden 1280, heads 16): the QKV product is a plain row-major one and the attention of every block is iisan_attention16_hd80
+ * (csrc/attn16_hd80.hip); the tower has NO CLS-only form of the last live block — that block runs on every token like the others (1 / 32
+ * of a 32-layer tower; blocks past the deepest tap are still not run) — and iisan_encoder_plan says so (bit 32).
+ * Patch sides: the multiples of 8, and 14 (any other side is IISAN_EBADSHAPE).  At 14 the patch vector of C*P*P (588) elements is
+ * zero-padded to the next multiple of 64 (640) in the patch matrix, and patch_w must carry the same padding: [D, 640] with columns
+ * 588..639 zero (iisan_amd/encoders.py pads it).
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct {
     const void* qkv_w;  const float* qkv_b;   /* [3D,D] 16-bit, [3D]  (q;k;v stacked)                          */
@@ -74,7 +81,7 @@ typedef struct {
     int32_t dtype16;
     float   eps;
     int32_t full_blocks;                      /* dead-work policy, see below: 0 = default, 1 = every block on every token */
-    const void*  patch_w;                     /* [D, C*P*P] 16-bit (Conv2d kernel flattened (c,py,px))          */
+    const void*  patch_w;                     /* [D, C*P*P] 16-bit (Conv2d kernel flattened (c,py,px)); P % 8 != 0: rows zero-padded to a multiple of 64 */
     const float* patch_b;                     /* [D]                                                            */
     const float* cls_token;                   /* [D]                                                            */
     const float* pos_emb;                     /* [T, D], T = (image/patch)^2 + 1                                */
@@ -391,8 +398,8 @@ int iisan_gemm16(int32_t dtype16, int32_t mode, const void* A, const void* W, co
 /* LayerNorm over rows of width 768: out16 (nullable) / out32 (nullable) */
 int iisan_layernorm768(int32_t dtype16, const float* x, const float* g, const float* b, float eps,
                        void* out16, float* out32, int64_t rows, void* stream);
-/* The same over rows of `width` elements, width 768 or 1024, or 128, 192, 256, 384 — the row widths the encoders' row kernels are built for
- * (ViT-B / BERT-base, ViT-L / BERT-large).  Any other width: IISAN_EBADSHAPE, nothing launched.  At width 768 it is the call above. */
+/* The same over rows of `width` elements, width 768 or 1024, or 128, 192, 256, 384, or 1280 — the row widths the encoders' row kernels are built for
+ * (ViT-B / BERT-base, ViT-L / BERT-large, the narrow towers, ViT-H/14).  Any other width: IISAN_EBADSHAPE, nothing launched.  At width 768 it is the call above. */
 int iisan_layernorm(int32_t dtype16, const float* x, const float* g, const float* b, float eps,
                     void* out16, float* out32, int64_t rows, int32_t width, void* stream);
 /* softmax(QK^T/sqrt(64) + key_bias)V per (item, head); qkv 16-bit HEAD-MAJOR [items, H, 3 (q|k|v), S, 64] (what the QKV
@@ -405,6 +412,11 @@ int iisan_attention16(int32_t dtype16, const void* qkv, const float* key_bias, v
 /* the same arithmetic by the streaming-softmax kernel (csrc/attn16_long.hip: keys in chunks of 128, running maximum / sum / context per
  * query row) at ANY 1 <= S <= 1024 — what iisan_attention16 launches past 224 tokens, reachable below that for tests and timing */
 int iisan_attention16_long(int32_t dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int32_t S,
+                           int32_t heads, void* stream);
+/* 80-wide heads (ViT-H/14; csrc/attn16_hd80.hip): softmax(QK^T/sqrt(80) + key_bias)V by the same streaming softmax, 1 <= S <= 1024.
+ * qkv 16-bit ROW-MAJOR [items*S, 3*H*80] — the output of a plain product: Q, K, V of head h at columns h*80, H*80 + h*80, 2*H*80 + h*80 —
+ * ctx 16-bit token-major [items*S, H*80]; key_bias as in iisan_attention16.  S > 1024: IISAN_EBADSHAPE, nothing launched. */
+int iisan_attention16_hd80(int32_t dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int32_t S,
                            int32_t heads, void* stream);
 /* the same for the CLS query (token 0) of every item only: ctx_cls 16-bit [items, H*64].  Used by the encoder executors
  * in the last live block, where only `hidden_states[i][:, 0]` is consumed (Code_Uncached/model/model.py:210-213).
@@ -488,7 +500,8 @@ int32_t iisan_inbatch_ce_route_e(int64_t bs, int32_t S, int32_t E);
  * folded: the weights struct carries a folded set (iisan_vit_fold_layernorm).  Negative = the executors refuse these sizes (iisan_last_error).
  * ViT: bits 0-1 how the residual stream is carried (0 fp32 stream of resid32, 1 mixed stream + LayerNorm images, 2 LayerNorm in the QKV / FC1
  * epilogues, 3 ... and the residual adds in the O / FC2 epilogues), 4 = the FC1 -> FC2 intermediate is block-major, 8 = the stream is, 16 = the
- * call folds the LayerNorm weights itself.  BERT: 1 = mixed stream, 2 = stream and 16-bit image share one buffer, 4 = block-major FC1 -> FC2. */
+ * call folds the LayerNorm weights itself, 32 = 80-wide heads (hidden 1280, heads 16): row-major QKV, iisan_attention16_hd80, and the last live
+ * block runs on every token instead of on the CLS rows.  BERT: 1 = mixed stream, 2 = stream and 16-bit image share one buffer, 4 = block-major FC1 -> FC2. */
 #define IISAN_TOWER_VIT 0
 #define IISAN_TOWER_BERT 1
 int32_t iisan_encoder_plan(int32_t tower, int32_t dtype16, int32_t hidden, int32_t heads, int32_t mlp, int32_t tokens, int64_t M,
