@@ -1,7 +1,7 @@
 // The per-block arithmetic the three MFMA attention kernels share (device only):
 //   attention16_kernel (attn16.hip), attention16_dma_kernel (attn16_dma.hip), attention16_drop_kernel (bert_drop.hip);
-//   attention16_long_kernel (attn16_long.hip) and attention16_hd80_kernel (attn16_hd80.hip: 80-wide heads) run the same pieces per 128-key
-//   chunk, with the chunk form of the row softmax below.
+//   the streaming-softmax body (attn16_stream.h: one chunk walk behind attention16_long_kernel, attn16_long.hip, and attention16_hd80_kernel,
+//   attn16_hd80.hip: 80-wide heads) runs the same pieces per 128-key chunk, with the chunk form of the row softmax below.
 // A block = 16 queries of one (item, head) in one wave.  Scores are computed TRANSPOSED, S^T = K · Q^T, on v_mfma_f32_16x16x32: a lane
 // (j = lane & 15, g = lane >> 4) holds, for ONE query j, keys 16 t + 4 g + r of score tile t in sc[t][r] — so the softmax row reduction is a
 // per-lane loop plus two xor-shuffles (16, 32), and the exponentiated registers are ALREADY in B-operand layout for O^T = V^T · P^T.
@@ -87,7 +87,7 @@ __device__ __forceinline__ float attn_row_softmax(f4 (&sc)[NT16], Keep keep) {
     return 1.0f / sum;
 }
 
-// Chunk form of attn_row_softmax (the streaming-softmax kernels, attn16_long.hip and attn16_hd80.hip; c2 = log2(e) / sqrt(head width)): sc (raw, limited scores of one query row over ONE chunk) becomes p = exp2(sc c2 - ms_new) with
+// Chunk form of attn_row_softmax (the streaming-softmax body, attn16_stream.h; c2 = log2(e) / sqrt(head width)): sc (raw, limited scores of one query row over ONE chunk) becomes p = exp2(sc c2 - ms_new) with
 // ms_new = max(ms_old, c2 * chunk maximum); returns ms_new and the chunk's row sum of the unrounded p.  Same instruction diet as the row
 // form: two max chains, four sum chains, one fma and the bare v_exp_f32 per score.
 struct AttnChunkStat { float ms, sum; };

@@ -1,70 +1,30 @@
-"""Attention past 224 tokens: the streaming-softmax kernel (csrc/attn16_long.hip) behind `iisan_attention16`, the 1,024-key score row of
-`iisan_attention_cls16`, the `iisan_attention16_long` primitive below the old limit, and the routing between the kernels.
+"""Attention past 224 tokens: the streaming-softmax kernel (the chunk walk of csrc/attn16_stream.h in the 64-wide geometry of
+csrc/attn16_long.hip) behind `iisan_attention16`, the 1,024-key score row of `iisan_attention_cls16`, the `iisan_attention16_long`
+primitive below the old limit and around the 16-query block and the 128-key chunk, and the routing between the kernels.
 
-Reference and input recipe are those of tests/test_gpu_primitives.py::test_attention16_vs_torch (float64 softmax of the same 16-bit
-operands, `randn * 1.5`), the bound is the project's own 2.5 * TOL[dt] * max|ref| (P and O each rounded once to 16 bits; the fp32 rescale
-of the running sum and context adds nothing at that scale).  Measured values: profiles/long_sequences.md."""
+Reference, input recipe, the guarded launch and the bound 2.5 * TOL[dt] * max|ref| are those of tests/attn_stream_io.py, shared with the
+80-wide geometry (tests/test_gpu_vit_huge_attention.py).  Measured values: profiles/long_sequences.md."""
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+import attn_stream_io as aio  # noqa: E402
+from attn_stream_io import TOL  # noqa: E402
 from iisan_amd import _lib  # noqa: E402
 
-T16 = {0: torch.float16, 1: torch.bfloat16}
-TOL = {0: 2e-3, 1: 1.6e-2}       # relative to the output scale: one 16-bit rounding of the result
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _attn_ref(qkv, key_bias, items, S, heads):
-    D = heads * 64
-    x = qkv.double().view(items, S, 3, heads, 64)
-    q, k, v = (x[:, :, i].transpose(1, 2) for i in range(3))
-    s = q @ k.transpose(-1, -2) / 8.0
-    if key_bias is not None:
-        masked = (key_bias < 0)[:, None, None, :]
-        s = torch.where(masked, torch.full_like(s, torch.finfo(torch.float32).min), s)
-    p = torch.softmax(s, -1)
-    return (p @ v).transpose(1, 2).reshape(items * S, D)
-
-
-def _problem(dt, items, S, heads, masked, seed=None):
-    g = torch.Generator().manual_seed(S * 13 + heads if seed is None else seed)
-    D = heads * 64
-    qkv = (torch.randn(items * S, 3 * D, generator=g) * 1.5).to(T16[dt])
-    kb = None
-    if masked:
-        kb = torch.zeros(items, S)
-        for i in range(items):
-            n = int(torch.randint(1, S + 1, (1,), generator=g))
-            kb[i, n:] = -1.0
-        kb[0, :] = -1.0                       # an all-masked (padding) item attends uniformly
-    return qkv, kb
-
-
-def _head_major(qkv, items, S, heads):
-    return qkv.view(items, S, 3, heads, 64).permute(0, 3, 2, 1, 4).contiguous().cuda()
+_stream = aio.stream
 
 
 def _run(lib, entry, dt, qkvd, kbd, items, S, heads, rows):
-    """One launch of `entry` into a buffer with a guard row behind it."""
-    D = heads * 64
-    out = torch.full((rows + 1, D), 7.0, dtype=T16[dt], device="cuda")
-    _lib.check(getattr(lib, entry)(dt, qkvd.data_ptr(), kbd.data_ptr() if kbd is not None else None, out.data_ptr(), items, S, heads,
-                                   _stream()), entry)
-    torch.cuda.synchronize()
-    assert (out[rows] == 7.0).all(), f"{entry}: wrote behind its output"
-    return out[:rows].cpu().double()
+    return aio.run(lib, entry, dt, qkvd, kbd, items, S, heads, rows).cpu().double()
 
 
 def _check_both_entries(lib, dt, qkv, kb, items, S, heads, what):
     D = heads * 64
-    ref = _attn_ref(qkv, kb, items, S, heads)
-    tol = 2.5 * TOL[dt] * ref.abs().max().item()     # P and O are both rounded to 16 bit
-    qkvd, kbd = _head_major(qkv, items, S, heads), (kb.cuda() if kb is not None else None)
+    ref = aio.attn_ref(qkv, kb, items, S, heads)
+    tol = aio.bound(dt, ref)
+    qkvd, kbd = aio.head_major(qkv, items, S, heads), (kb.cuda() if kb is not None else None)
     got = _run(lib, "iisan_attention16", dt, qkvd, kbd, items, S, heads, items * S)
     err = (got - ref).abs().max().item()
     got_cls = _run(lib, "iisan_attention_cls16", dt, qkvd, kbd, items, S, heads, items)
@@ -91,7 +51,7 @@ LONG_CASES = [(2, 225, 2, False),      # first length over the old limit
 @pytest.mark.parametrize("case", LONG_CASES)
 def test_long_attention_vs_float64(lib, dt, case):
     items, S, heads, masked = case
-    qkv, kb = _problem(dt, items, S, heads, masked)
+    qkv, kb = aio.problem(dt, items, S, heads, masked=masked)
     _lib.dev_set("count:attn16_long", 0)
     _check_both_entries(lib, dt, qkv, kb, items, S, heads, str(case))
     assert _lib.dev_get("count:attn16_long") == 1          # iisan_attention16 ran the streaming kernel; the CLS entry has its own
@@ -105,7 +65,7 @@ def test_long_attention_mask_shapes(lib, dt, S):
     """Item 0: keys 0..199 masked (whole chunks of uniform weights that must vanish exactly when the first real key arrives); item 1: only
     key S - 1 real; item 2: real keys only in a middle chunk (masked chunks before and behind); item 3: all masked = the mean of V."""
     items, heads = 4, 2
-    qkv, _ = _problem(dt, items, S, heads, False, seed=S + 5)
+    qkv, _ = aio.problem(dt, items, S, heads, seed=S + 5)
     kb = torch.full((items, S), -1.0)
     kb[0, 200:] = 0.0
     kb[1, S - 1] = 0.0
@@ -127,14 +87,17 @@ def test_long_attention_mask_shapes(lib, dt, S):
 # ---- 3. the streaming kernel below the old limit ---------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("dt", [0, 1])
-@pytest.mark.parametrize("case", [(3, 197, 12, False), (5, 30, 12, True), (2, 224, 2, False)])
+@pytest.mark.parametrize("case", [(3, 197, 12, False), (5, 30, 12, True), (2, 224, 2, False),
+                                  # around the 16-query block and around the 128-key chunk, as the 80-wide geometry is run
+                                  (2, 1, 2, False), (2, 15, 2, False), (2, 16, 2, False), (1, 17, 2, False),
+                                  (2, 127, 2, False), (2, 128, 2, False), (1, 129, 3, False)])
 def test_long_kernel_below_the_old_limit(lib, dt, case):
     items, S, heads, masked = case
-    qkv, kb = _problem(dt, items, S, heads, masked)
-    ref = _attn_ref(qkv, kb, items, S, heads)
-    tol = 2.5 * TOL[dt] * ref.abs().max().item()
+    qkv, kb = aio.problem(dt, items, S, heads, masked=masked)
+    ref = aio.attn_ref(qkv, kb, items, S, heads)
+    tol = aio.bound(dt, ref)
     _lib.dev_set("count:attn16_long", 0)
-    got = _run(lib, "iisan_attention16_long", dt, _head_major(qkv, items, S, heads), kb.cuda() if kb is not None else None, items, S, heads,
+    got = _run(lib, "iisan_attention16_long", dt, aio.head_major(qkv, items, S, heads), kb.cuda() if kb is not None else None, items, S, heads,
                items * S)
     assert _lib.dev_get("count:attn16_long") == 1
     err = (got - ref).abs().max().item()

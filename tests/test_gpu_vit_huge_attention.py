@@ -1,54 +1,33 @@
-"""`iisan_attention16_hd80` (csrc/attn16_hd80.hip): streaming-softmax attention for 80-wide heads on row-major QKV, against float64.
+"""`iisan_attention16_hd80`: streaming-softmax attention for 80-wide heads on row-major QKV (the chunk walk of csrc/attn16_stream.h in the
+geometry of csrc/attn16_hd80.hip), against float64.
 
-Reference, input recipe and bound are those of tests/test_gpu_attention_long.py: float64 softmax of the same 16-bit operands (`randn * 1.5`),
-max|err| <= 2.5 * TOL[dt] * max|ref| (P and O each rounded once to 16 bits).  Shapes: around the 16-row query block (1, 15, 16, 17), around
-the 128-key chunk (127, 128, 129), the tower's own 257 tokens with its 16 heads, and 577 / 1,024 (three query ranges, eight chunks).
+Reference, input recipe, the guarded launch and the bound 2.5 * TOL[dt] * max|ref| are those of tests/attn_stream_io.py, shared with the
+64-wide geometry (tests/test_gpu_attention_long.py).  Shapes: around the 16-row query block (1, 15, 16, 17), around the 128-key chunk
+(127, 128, 129), the tower's own 257 tokens with its 16 heads, and 577 / 1,024 (three query ranges, eight chunks).
 Measured values: profiles/vit_huge.md."""
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+import attn_stream_io as aio  # noqa: E402
 from iisan_amd import _lib  # noqa: E402
 
-T16 = {0: torch.float16, 1: torch.bfloat16}
-TOL = {0: 2e-3, 1: 1.6e-2}       # relative to the output scale: one 16-bit rounding of the result
 HD = 80
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _attn_ref(qkv, key_bias, items, S, heads):
-    x = qkv.double().view(items, S, 3, heads, HD)
-    q, k, v = (x[:, :, i].transpose(1, 2) for i in range(3))
-    s = q @ k.transpose(-1, -2) / (HD ** 0.5)
-    if key_bias is not None:
-        masked = (key_bias < 0)[:, None, None, :]
-        s = torch.where(masked, torch.full_like(s, torch.finfo(torch.float32).min), s)
-    return (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(items * S, heads * HD)
+_stream = aio.stream
 
 
 def _problem(dt, items, S, heads, seed=None):
-    g = torch.Generator().manual_seed(S * 13 + heads if seed is None else seed)
-    return (torch.randn(items * S, 3 * heads * HD, generator=g) * 1.5).to(T16[dt])
+    return aio.problem(dt, items, S, heads, HD, seed=seed)[0]
 
 
 def _run(lib, dt, qkvd, kbd, items, S, heads):
-    """One launch into a buffer with a guard row behind it."""
-    rows, D = items * S, heads * HD
-    out = torch.full((rows + 1, D), 7.0, dtype=T16[dt], device="cuda")
-    _lib.check(lib.iisan_attention16_hd80(dt, qkvd.data_ptr(), kbd.data_ptr() if kbd is not None else None, out.data_ptr(), items, S, heads,
-                                          _stream()), "iisan_attention16_hd80")
-    torch.cuda.synchronize()
-    assert (out[rows] == 7.0).all(), "attention16_hd80 wrote behind its output"
-    return out[:rows]
+    return aio.run(lib, "iisan_attention16_hd80", dt, qkvd, kbd, items, S, heads, items * S, HD)
 
 
 def _check(lib, dt, qkv, kb, items, S, heads, what):
-    ref = _attn_ref(qkv, kb, items, S, heads)
-    tol = 2.5 * TOL[dt] * ref.abs().max().item()
+    ref = aio.attn_ref(qkv, kb, items, S, heads, HD)
+    tol = aio.bound(dt, ref)
     got = _run(lib, dt, qkv.cuda(), kb.cuda() if kb is not None else None, items, S, heads).cpu().double()
     err = (got - ref).abs().max().item()
     print(f"attention16_hd80 {what} dt={dt}: max err {err:.3e} (bound {tol:.3e})")
@@ -79,13 +58,15 @@ def test_hd80_attention_mask_shapes(lib, dt, S):
     """Item 0: a masked prefix spanning whole chunks (keys 0 .. 127 at S = 129, 0 .. 255 at S = 300: uniform weights that must vanish exactly
     when the first real key arrives); item 1: only the last key real — its row is V of that key; item 2: all masked — every chunk keeps the
     running maximum at MASK_RAW c2, the rescale factor between chunks is exp2(0) = 1, and the row is softmax of equal scores like the
-    reference's; item 3: a mask that ends inside a chunk."""
-    items, heads = 4, 2
+    reference's; item 3: a mask that ends inside a chunk; item 4: real keys only in one middle chunk (masked chunks before and behind)."""
+    items, heads = 5, 2
     qkv = _problem(dt, items, S, heads, seed=S + 5)
     kb = torch.full((items, S), -1.0)
     kb[0, 128 * ((S - 1) // 128):] = 0.0
     kb[1, S - 1] = 0.0
     kb[3, :S // 2 + 3] = 0.0
+    mid = 128 * ((S // 128) // 2)
+    kb[4, mid:mid + 128] = 0.0
     got, ref, tol = _check(lib, dt, qkv, kb, items, S, heads, f"mask shapes S={S}")
     D = heads * HD
     v = qkv.double().view(items, S, 3, heads, HD)[:, :, 2].reshape(items, S, D)

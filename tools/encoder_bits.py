@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """Bit fingerprint of the frozen-encoder executors: one SHA-256 of the tap bytes per case, over toy towers and every route the
-executors choose between.  Seeded and self-contained, so two builds of the library can be compared line by line:
+executors choose between.  Seeded and self-contained (this one file: copy it into a checkout of the parent if the parent lacks a case),
+so two builds of the library can be compared line by line:
 
     python3 tools/encoder_bits.py > child.txt        (and the same in a checkout of the parent)        diff parent.txt child.txt
+
+IISAN_LIB=path fingerprints another build of the library with this tree's Python.
 
 Cases: the two-block hidden-768 towers of tests/golden_io.py on 70 items (whole, and in chunks of 32 whose last one holds 6), fp16 and
 bf16, under gemm16_variant 0 / 4 x ln_fold 0 / 1 / 2 x full_blocks 0 / 1, and under resid32 = 1; a tapped prefix; the ViT from fp32
 pixels, uint8 pixels and the indexed uint8 catalogue; BERT direct and indexed, in eval mode and with train-mode dropout; toy towers at
-hidden 192 / 128, 384 / 256 and 1024; and one tower each past 224 tokens (a 256-pixel image at patch 16, titles of 226 words)."""
+hidden 192 / 128, 384 / 256 and 1024; one tower each past 224 tokens (a 256-pixel image at patch 16, titles of 226 words); the two-layer
+hidden-1,280 toy ViT-H/14 of tests/vit_huge_io.py (80-wide heads), fp16 and bf16; and the two streaming-softmax attention primitives
+directly, `iisan_attention16_long` and `iisan_attention16_hd80`, at S = 17 / 129 / 257 / 577 / 1,024 with 2 heads, unmasked and under
+the random-length mask of the tests (tests/attn_stream_io.py)."""
 import hashlib
 import os
 import sys
@@ -17,8 +23,13 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import attn_stream_io as aio  # noqa: E402
 import golden_io as gio  # noqa: E402
+import vit_huge_io as vio  # noqa: E402
 from iisan_amd import _lib, encoders, weights  # noqa: E402
+
+if os.environ.get("IISAN_LIB"):            # another build of the library (the parent's, copied aside)
+    _lib.LIB_PATH = os.path.abspath(os.environ["IISAN_LIB"])
 
 ITEMS = 70
 DTYPES = (("fp16", _lib.IISAN_F16), ("bf16", _lib.IISAN_BF16))
@@ -50,7 +61,7 @@ def knobs(**kw):
 
 def main():
     assert torch.cuda.is_available(), "encoder_bits: needs the GPU"
-    _lib.load()
+    lib = _lib.load()
     out = []
 
     def emit(name, *tensors):
@@ -110,6 +121,22 @@ def main():
                         tag = f"{name} v{variant} fb{fb} c{chunk}"
                         emit(f"vit {tag}", vit.forward_taps(images, [0, 1, 2], chunk_items=chunk))
                         emit(f"bert {tag}", bert.forward_taps(text, [0, 1, 2], chunk_items=chunk))
+        # 80-wide heads: the toy ViT-H/14 (17 tokens, 16 heads of 80)
+        for dname, dt in DTYPES:
+            knobs()
+            vit = encoders.PackedVit(weights.make_vit_weights(vio.GEOM_VIT, seed=vio.GEOM_SEED_W), vio.GEOM_VIT, "cuda", dt)
+            x = vio.images(vio.GEOM_ITEMS, vio.GEOM_VIT.image, vio.GEOM_SEED_X).cuda()
+            emit(f"vit huge {dname}", vit.forward_taps(x, [0, 1, 2]))
+        # the streaming-softmax primitives themselves
+        for entry, hd, lay in (("iisan_attention16_long", 64, aio.head_major), ("iisan_attention16_hd80", 80, None)):
+            for dname, dt in DTYPES:
+                for S in (17, 129, 257, 577, 1024):
+                    for masked in (False, True):
+                        items, heads = 3, 2
+                        qkv, kb = aio.problem(dt, items, S, heads, hd, masked=masked)
+                        qkvd = lay(qkv, items, S, heads, hd) if lay else qkv.cuda()
+                        ctx = aio.run(lib, entry, dt, qkvd, kb.cuda() if masked else None, items, S, heads, items * S, hd)
+                        emit(f"{entry} {dname} S{S} {'masked' if masked else 'plain'}", ctx.view(torch.int16))
     finally:
         _lib.dev_reset()
     print(f"# {len(out)} cases, all {hashlib.sha256(chr(10).join(out).encode()).hexdigest()}")

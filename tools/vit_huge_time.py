@@ -38,6 +38,8 @@ def _event_us(fn, reps):
 def attention(a):
     import torch
     from iisan_amd import _lib
+    if os.environ.get("IISAN_LIB"):            # another build of the library (the parent's, copied aside), timed beside this one
+        _lib.LIB_PATH = os.path.abspath(os.environ["IISAN_LIB"])
     lib = _lib.load()
     s = torch.cuda.current_stream().cuda_stream
     items, S = a.attn_items, 257
