@@ -12,12 +12,16 @@
 // and one item-row load feeds two MFMAs: the table is read once per 32 users (1.9 GB) and item splits across blockIdx.y
 // fill the chip, partial counts meeting in `ranks` through integer atomics (exact, order-free).
 //
-// Exactness: a rank is a count of comparisons `score(c) > score(target)`; every score of a user — the target's, its history
-// items', every other item's — comes out of the SAME 16-MFMA chain with the same contraction order (lane group g contracts
-// k = 16g .. 16g+15; the four groups meet in the MFMA's own fixed reduction), so equal inputs give equal bits wherever the
-// item sits in a tile.  The target's and the history items' scores are taken from the diagonal of extra tiles whose row i
-// is "the h-th item of user i".  History: a history item contributes with score -inf instead of its raw score; if the
-// target itself is in the history its score is -inf as well (metrics.py:204-205: reproduced, not fixed).
+// Exactness: a rank is a count of comparisons `score(c) > score(target)`, and every score of a user — the target's, its history
+// items', every other item's, in the rank kernel and in the top-k kernel — is made by ONE piece of code: `tile_scores`, the chain
+// of 16 MFMAs per 64 features with one contraction order (lane group g contracts k = 16g .. 16g+15; the four groups meet in the
+// MFMA's own fixed reduction), on row fragments that only `load_row16` and user fragments that only `load_user_frags` build: equal
+// inputs give equal bits wherever the item sits in a tile, by construction.  (The walk over the table's tiles stays written out in
+// both kernels: as one shared function it cost the rank kernel 22 % at EW = 128 and 192, profiles/eval_shared_walk.md.)  The
+// target's and the history items' scores are taken from the diagonal of extra tiles whose row i is "the h-th item of user i".
+// History: a history item contributes with score -inf instead of its raw score; if the target itself is in the history its score
+// is -inf as well (metrics.py:204-205: reproduced, not fixed).
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
@@ -57,6 +61,19 @@ __device__ __forceinline__ void load_row16(const float* __restrict__ row, int g,
         for (int v = 0; v < 4; ++v) a[4 * nb + v] = *(const f4*)(row + 64 * nb + 16 * g + 4 * v);
 }
 
+// the vectors of users u0 .. u0 + 31 as B fragments: lane (j, g) holds prec[u0 + 16u + j][16g .. 16g+15] of every block, zero rows past U
+template <int NE>
+__device__ __forceinline__ void load_user_frags(const float* __restrict__ prec, int u0, int U, int j, int g, f4 (&b)[2][4 * NE]) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int uu = u0 + 16 * u + j;
+        if (uu < U) load_row16<NE>(prec + (int64_t)uu * (64 * NE), g, b[u]);
+        else
+#pragma unroll
+            for (int v = 0; v < 4 * NE; ++v) b[u][v] = (f4){0.f, 0.f, 0.f, 0.f};
+    }
+}
+
 template <int NE>
 __global__ __launch_bounds__(256) void score_rank_mfma_kernel(const float* __restrict__ prec, const float* __restrict__ item_emb,
                                                               int n_items, const int32_t* __restrict__ history, int hist_stride,
@@ -70,16 +87,8 @@ __global__ __launch_bounds__(256) void score_rank_mfma_kernel(const float* __res
     const int j = lane & 15, g = lane >> 4;
     const int u0 = blockIdx.x * UB;
 
-    // the users' vectors as B fragments: lane (j, g) holds prec[u0 + 16u + j][16g .. 16g+15]
     f4 b[2][4 * NE];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int uu = u0 + 16 * u + j;
-        if (uu < U) load_row16<NE>(prec + (int64_t)uu * (64 * NE), g, b[u]);
-        else
-#pragma unroll
-            for (int v = 0; v < 4 * NE; ++v) b[u][v] = (f4){0.f, 0.f, 0.f, 0.f};
-    }
+    load_user_frags<NE>(prec, u0, U, j, g, b);
     if (threadIdx.x < UB) {
         const int uu = u0 + (int)threadIdx.x;
         int t = uu < U ? target[uu] : 0;
@@ -295,14 +304,7 @@ __global__ __launch_bounds__(256) void score_topk_kernel(const float* __restrict
     const int u0 = blockIdx.x * UB;
 
     f4 b[2][4 * NE];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int uu = u0 + 16 * u + j;
-        if (uu < U) load_row16<NE>(prec + (int64_t)uu * (64 * NE), g, b[u]);
-        else
-#pragma unroll
-            for (int v = 0; v < 4 * NE; ++v) b[u][v] = (f4){0.f, 0.f, 0.f, 0.f};
-    }
+    load_user_frags<NE>(prec, u0, U, j, g, b);
     if (hist_stride <= TK_HS)
         for (int i = threadIdx.x; i < UB * hist_stride; i += 256) {
             const int x = i / hist_stride, h = i - x * hist_stride;
@@ -421,10 +423,17 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const tkey* __restrict__
     for (int r = (nv < k ? nv : k) + lane; r < k; r += 64) { ids[(int64_t)u * k + r] = 0; if (scores) scores[(int64_t)u * k + r] = -INFINITY; }
 }
 
+// Launch geometry for a wanted number of item splits: 32-user blocks x the splits that hold a tile, `per` whole tiles each (tiles_per_split)
+struct ScoreGrid { int ublocks, splits, per; };
+static ScoreGrid score_grid(int64_t U, int64_t n_items_plus1, int64_t want) {
+    const int64_t n_tiles = ceil_div(n_items_plus1, 16), per = ceil_div(n_tiles, want < 1 ? 1 : want);
+    return {(int)ceil_div(U, UB), (int)ceil_div(n_tiles, per), (int)per};
+}
+
 // item splits of the top-k launch: two workgroups per CU fit (73 KiB of LDS each).  Longer item streams per wave mean fewer appended
 // candidates (a stream's threshold is its own k-th best), more splits mean better-filled rounds: among 1 .. 8 splits (more only when
 // there are fewer user blocks than workgroup slots) the count with the best-filled last round wins, ties to the fewer splits.
-static int topk_splits(int64_t U, int64_t n_items_plus1) {
+static ScoreGrid topk_grid(int64_t U, int64_t n_items_plus1) {
     const int64_t ublocks = ceil_div(U, UB), n_tiles = ceil_div(n_items_plus1, 16), slots = (int64_t)2 * iisan_cu_count();
     int64_t cap = n_tiles / 64;                                  // at least 16 tiles (256 items) per wave
     if (cap > TK_MAX_SPLITS) cap = TK_MAX_SPLITS;
@@ -441,11 +450,10 @@ static int topk_splits(int64_t U, int64_t n_items_plus1) {
         best = ceil_div(slots, ublocks);
         if (best > cap) best = cap;
     }
-    const int64_t per = ceil_div(n_tiles, best);
-    return (int)ceil_div(n_tiles, per);
+    return score_grid(U, n_items_plus1, best);
 }
 
-// The run-time width as the NE template argument: f(integral_constant<int, 1 .. 4>), after score_width let it through
+// The run-time width as the NE template argument: f(integral_constant<int, 1 .. 4>), after check_score_problem let it through
 template <class F>
 void with_ne(int E, F&& f) {
     switch (E / 64) {
@@ -456,7 +464,16 @@ void with_ne(int E, F&& f) {
     }
 }
 #define SC_NE decltype(ne)::value
-bool score_width(int E) { return E > 0 && E <= 256 && E % 64 == 0; }
+
+// What both entries ask of a problem (`name`: the entry's message prefix; k = 1 for the rank entry, whose outputs are one per user)
+int check_score_problem(const char* name, const float* prec, const float* item_emb, int64_t U, int64_t n_items_plus1, int E, int hist_stride,
+                        int64_t k) {
+    IISAN_CHECK_SHAPE(E > 0 && E <= 256 && E % 64 == 0, "%s: embedding_dim must be 64, 128, 192 or 256 (got %d)", name, E);
+    IISAN_CHECK_SHAPE(U > 0 && n_items_plus1 > 1 && hist_stride >= 0, "%s: empty problem", name);
+    IISAN_CHECK_SHAPE(U < (1ll << 31) - UB && n_items_plus1 < (1ll << 31) - 16 && U * k < (1ll << 31), "%s: problem too large for 32-bit indices", name);
+    IISAN_CHECK_SHAPE((((uintptr_t)prec | (uintptr_t)item_emb) & 15) == 0, "%s: prec and item_emb must be 16-byte aligned", name);
+    return IISAN_OK;
+}
 
 }  // namespace
 
@@ -464,24 +481,15 @@ extern "C" int iisan_score_rank(const float* prec, const float* item_emb, int64_
                                 const int32_t* history, int32_t hist_stride, const int32_t* target, int32_t* ranks,
                                 void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    IISAN_CHECK_SHAPE(score_width(E), "score_rank: embedding_dim must be 64, 128, 192 or 256 (got %d)", E);
-    IISAN_CHECK_SHAPE(U > 0 && n_items_plus1 > 1 && hist_stride >= 0, "score_rank: empty problem");
+    if (int rc = check_score_problem("score_rank", prec, item_emb, U, n_items_plus1, E, hist_stride, 1)) return rc;
     IISAN_CHECK_SHAPE(hist_stride <= MAXH, "score_rank: at most %d history entries per user (got %d)", MAXH, hist_stride);
-    IISAN_CHECK_SHAPE(U < (1ll << 31) - UB && n_items_plus1 < (1ll << 31) - 16, "score_rank: problem too large for 32-bit indices");
-    IISAN_CHECK_SHAPE((((uintptr_t)prec | (uintptr_t)item_emb) & 15) == 0, "score_rank: prec and item_emb must be 16-byte aligned");
-    const int ublocks = (int)ceil_div(U, UB);
-    const int n_tiles = (int)ceil_div(n_items_plus1, 16);
     // item splits: about four workgroups per CU in total, at least 16 tiles (4 per wave) each
-    int splits = (int)ceil_div((int64_t)4 * iisan_cu_count(), ublocks);
-    if (splits > n_tiles / 16) splits = n_tiles / 16;
-    if (splits < 1) splits = 1;
-    const int per = (int)ceil_div(n_tiles, splits);
-    splits = (int)ceil_div(n_tiles, per);
+    const ScoreGrid g = score_grid(U, n_items_plus1, std::min(ceil_div((int64_t)4 * iisan_cu_count(), ceil_div(U, UB)), ceil_div(n_items_plus1, 16) / 16));
     hipLaunchKernelGGL(zero_ranks_kernel, dim3((unsigned)ceil_div(U, 256)), dim3(256), 0, s, ranks, U);
     IISAN_LAUNCH_OK();
     with_ne(E, [&](auto ne) {
-        hipLaunchKernelGGL(score_rank_mfma_kernel<SC_NE>, dim3((unsigned)ublocks, (unsigned)splits), dim3(256), 0, s, prec, item_emb,
-                           (int)n_items_plus1, history, hist_stride, target, ranks, (int)U, per);
+        hipLaunchKernelGGL(score_rank_mfma_kernel<SC_NE>, dim3((unsigned)g.ublocks, (unsigned)g.splits), dim3(256), 0, s, prec, item_emb,
+                           (int)n_items_plus1, history, hist_stride, target, ranks, (int)U, g.per);
     });
     IISAN_LAUNCH_OK();
     return IISAN_OK;
@@ -489,7 +497,7 @@ extern "C" int iisan_score_rank(const float* prec, const float* item_emb, int64_
 
 extern "C" size_t iisan_score_topk_ws_bytes(int64_t U, int64_t n_items_plus1, int32_t k) {
     if (U <= 0 || n_items_plus1 <= 1 || k <= 0) return 0;
-    const int splits = topk_splits(U, n_items_plus1);
+    const int splits = topk_grid(U, n_items_plus1).splits;
     return splits > 1 ? align_up((size_t)splits * (size_t)U * (size_t)k * sizeof(tkey), 256) : 0;
 }
 
@@ -497,35 +505,29 @@ extern "C" int iisan_score_topk(const float* prec, const float* item_emb, int64_
                                 const int32_t* history, int32_t hist_stride, int32_t k, int32_t* topk_ids, float* topk_scores,
                                 void* ws, size_t ws_bytes, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    IISAN_CHECK_SHAPE(score_width(E), "score_topk: embedding_dim must be 64, 128, 192 or 256 (got %d)", E);
-    IISAN_CHECK_SHAPE(U > 0 && n_items_plus1 > 1 && hist_stride >= 0, "score_topk: empty problem");
+    if (int rc = check_score_problem("score_topk", prec, item_emb, U, n_items_plus1, E, hist_stride, k)) return rc;
     IISAN_CHECK_SHAPE(k >= 1 && k <= TK_MAX, "score_topk: k must be in 1..%d (got %d)", TK_MAX, k);
     IISAN_CHECK_SHAPE(hist_stride == 0 || history, "score_topk: hist_stride %d without a history array", hist_stride);
-    IISAN_CHECK_SHAPE(U < (1ll << 31) - UB && n_items_plus1 < (1ll << 31) - 16 && U * k < (1ll << 31), "score_topk: problem too large for 32-bit indices");
-    IISAN_CHECK_SHAPE((((uintptr_t)prec | (uintptr_t)item_emb) & 15) == 0, "score_topk: prec and item_emb must be 16-byte aligned");
-    const int ublocks = (int)ceil_div(U, UB);
-    const int n_tiles = (int)ceil_div(n_items_plus1, 16);
-    const int splits = topk_splits(U, n_items_plus1);
-    const int per = (int)ceil_div(n_tiles, splits);
+    const ScoreGrid g = topk_grid(U, n_items_plus1);
     const size_t need = iisan_score_topk_ws_bytes(U, n_items_plus1, k);
     if (ws_bytes < need || (need && !ws)) {
         iisan_set_error("score_topk: workspace too small (%zu < %zu)", ws_bytes, need);
         return IISAN_EWORKSPACE;
     }
-    if (splits == 1) {
+    // one split writes ids / scores itself; several leave their lists in the workspace for the merge
+    auto launch = [&](auto direct) {
+        constexpr bool DIRECT = decltype(direct)::value;
         with_ne(E, [&](auto ne) {
-            hipLaunchKernelGGL((score_topk_kernel<true, SC_NE>), dim3((unsigned)ublocks, 1), dim3(256), 0, s, prec, item_emb, (int)n_items_plus1, history,
-                               hist_stride, (int)U, per, k, (tkey*)nullptr, topk_ids, topk_scores);
+            hipLaunchKernelGGL((score_topk_kernel<DIRECT, SC_NE>), dim3((unsigned)g.ublocks, (unsigned)g.splits), dim3(256), 0, s, prec, item_emb,
+                               (int)n_items_plus1, history, hist_stride, (int)U, g.per, k, DIRECT ? (tkey*)nullptr : (tkey*)ws, topk_ids, topk_scores);
         });
+    };
+    if (g.splits == 1) launch(std::true_type{});
+    else launch(std::false_type{});
+    IISAN_LAUNCH_OK();
+    if (g.splits > 1) {
+        hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)U), dim3(64), 0, s, (const tkey*)ws, g.splits, (int)U, k, topk_ids, topk_scores);
         IISAN_LAUNCH_OK();
-        return IISAN_OK;
     }
-    with_ne(E, [&](auto ne) {
-        hipLaunchKernelGGL((score_topk_kernel<false, SC_NE>), dim3((unsigned)ublocks, (unsigned)splits), dim3(256), 0, s, prec, item_emb, (int)n_items_plus1,
-                           history, hist_stride, (int)U, per, k, (tkey*)ws, topk_ids, topk_scores);
-    });
-    IISAN_LAUNCH_OK();
-    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)U), dim3(64), 0, s, (const tkey*)ws, splits, (int)U, k, topk_ids, topk_scores);
-    IISAN_LAUNCH_OK();
     return IISAN_OK;
 }

@@ -24,7 +24,14 @@ from typing import List, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import dp, ops
+from . import dp, ops, userstore
+from .userstore import HIST_MAX, _ragged  # noqa: F401  (the rank route reads `evaluate.HIST_MAX` when called: tests set it here)
+
+
+def _all_layers(enc, cv_device, text_device):
+    """The tap lists "every hidden state" (the embeddings and each layer's output) of the image and the text tower."""
+    text = enc.bert_encoder.text_encoders["title"]
+    return range(enc.cv_encoder.packed(cv_device).cfg.layers + 1), range(text.packed(text_device).cfg.layers + 1)
 
 
 @torch.no_grad()
@@ -38,11 +45,24 @@ def build_tap_cache(model, images: torch.Tensor, text: torch.Tensor, batch: int 
     cvs, txs = [], []
     for i in range(0, images.shape[0], batch):
         img, txt = images[i:i + batch].contiguous(), text[i:i + batch].contiguous()
-        Lc = enc.cv_encoder.packed(img.device).cfg.layers
-        Lt = enc.bert_encoder.text_encoders["title"].packed(txt.device).cfg.layers
-        cvs.append(enc.cv_encoder.forward_taps(img, range(Lc + 1)))
-        txs.append(enc.bert_encoder.forward_taps(txt, range(Lt + 1)))
+        cv_layers, text_layers = _all_layers(enc, img.device, txt.device)
+        cvs.append(enc.cv_encoder.forward_taps(img, cv_layers))
+        txs.append(enc.bert_encoder.forward_taps(txt, text_layers))
     return torch.cat(cvs), torch.cat(txs)
+
+
+def _shard_and_gather(model, N: int, rank: int, world: int, device, item3_of) -> torch.Tensor:
+    """Rows 0..N-1 of the item table, each rank fusing the `item3_of(lo, hi)` blocks of its contiguous shard lo..hi-1, gathered on all."""
+    per = (N + world - 1) // world
+    lo, hi = min(rank * per, N), min((rank + 1) * per, N)
+    rows = [model.fuse_item3(item3) for item3 in item3_of(lo, hi)]
+    emb = model.com_dense.weight.shape[0]
+    mine = torch.cat(rows) if rows else torch.empty(0, emb, device=device)
+    if world == 1:
+        return mine
+    pad = torch.zeros(per, emb, device=mine.device)
+    pad[:mine.shape[0]] = mine
+    return dp.gather_concat(pad, per * world)[:N]
 
 
 @torch.no_grad()
@@ -50,21 +70,11 @@ def item_table(model, images_or_taps: torch.Tensor, text_or_taps: torch.Tensor, 
                world: int = 1) -> torch.Tensor:
     """Item embedding table `com_dense(cat(cv, text, mm))` (modality 'inter': `com_dense(mm)`) [N, emb] for items 0..N-1
     (row 0 = the padding item)."""
-    N = images_or_taps.shape[0]
-    per = (N + world - 1) // world
-    lo, hi = min(rank * per, N), min((rank + 1) * per, N)
-    rows = []
-    for i in range(lo, hi, batch):
-        j = min(i + batch, hi)
-        item3, _ = model.mm_encoder.forward_item3(images_or_taps[i:j].contiguous(), text_or_taps[i:j].contiguous())
-        rows.append(model.fuse_item3(item3))
-    emb = model.com_dense.weight.shape[0]
-    mine = torch.cat(rows) if rows else torch.empty(0, emb, device=images_or_taps.device)
-    if world == 1:
-        return mine
-    pad = torch.zeros(per, emb, device=mine.device)
-    pad[:mine.shape[0]] = mine
-    return dp.gather_concat(pad, per * world)[:N]
+    def item3_of(lo, hi):
+        for i in range(lo, hi, batch):
+            j = min(i + batch, hi)
+            yield model.mm_encoder.forward_item3(images_or_taps[i:j].contiguous(), text_or_taps[i:j].contiguous())[0]
+    return _shard_and_gather(model, images_or_taps.shape[0], rank, world, images_or_taps.device, item3_of)
 
 
 def _store_batches(model, store, lo: int, hi: int, batch: int):
@@ -89,10 +99,9 @@ def build_tap_cache_from_store(model, store, batch: int = 256) -> Tuple[torch.Te
     enc = model.mm_encoder
     cvs, txs = [], []
     for cat, txt, index in _store_batches(model, store, 0, store.rows, batch):
-        Lc = enc.cv_encoder.packed(index.device).cfg.layers
-        Lt = enc.bert_encoder.text_encoders["title"].packed(index.device).cfg.layers
-        cvs.append(enc.cv_encoder.forward_taps_indexed(cat, index, range(Lc + 1)))
-        txs.append(enc.bert_encoder.forward_taps_indexed(txt, index, range(Lt + 1)))
+        cv_layers, text_layers = _all_layers(enc, index.device, index.device)
+        cvs.append(enc.cv_encoder.forward_taps_indexed(cat, index, cv_layers))
+        txs.append(enc.bert_encoder.forward_taps_indexed(txt, index, text_layers))
     if hasattr(store, "release"):
         store.release()
     return torch.cat(cvs), torch.cat(txs)
@@ -102,30 +111,12 @@ def build_tap_cache_from_store(model, store, batch: int = 256) -> Tuple[torch.Te
 def item_table_from_store(model, store, batch: int = 512, rank: int = 0, world: int = 1) -> torch.Tensor:
     """`item_table` over the catalogue of an item store: [N+1, emb] for item ids 0..N (row 0 = the padding item), the same values
     as `item_table` on the materialised catalogue at the same `batch`."""
-    N = store.rows
-    per = (N + world - 1) // world
-    lo, hi = min(rank * per, N), min((rank + 1) * per, N)
-    rows = []
-    for cat, txt, index in _store_batches(model, store, lo, hi, batch):
-        item3, _ = model.mm_encoder.forward_item3_indexed(cat, txt, index)
-        rows.append(model.fuse_item3(item3))
-    if hasattr(store, "release"):
-        store.release()
-    emb = model.com_dense.weight.shape[0]
-    mine = torch.cat(rows) if rows else torch.empty(0, emb, device=store.device)
-    if world == 1:
-        return mine
-    pad = torch.zeros(per, emb, device=mine.device)
-    pad[:mine.shape[0]] = mine
-    return dp.gather_concat(pad, per * world)[:N]
-
-
-def _ragged(rows, n):
-    """(flat int64 array, lengths, end offsets) of a list of n integer sequences."""
-    import itertools
-    lens = np.fromiter((len(r) for r in rows), dtype=np.int64, count=n)
-    flat = np.fromiter(itertools.chain.from_iterable(rows), dtype=np.int64, count=int(lens.sum()))
-    return flat, lens, np.cumsum(lens)
+    def item3_of(lo, hi):
+        for cat, txt, index in _store_batches(model, store, lo, hi, batch):
+            yield model.mm_encoder.forward_item3_indexed(cat, txt, index)[0]
+        if hasattr(store, "release"):
+            store.release()
+    return _shard_and_gather(model, store.rows, rank, world, store.device, item3_of)
 
 
 def _pack_users(seqs: Sequence[Sequence[int]], histories: Sequence[Sequence[int]], max_seq_len: int, hist_stride: int):
@@ -153,9 +144,6 @@ def _pack_users(seqs: Sequence[Sequence[int]], histories: Sequence[Sequence[int]
     return torch.from_numpy(tok), torch.from_numpy(lm), torch.from_numpy(hist), torch.from_numpy(tgt.astype(np.int32))
 
 
-HIST_MAX = 256      # exclusion-list entries per user that iisan_score_rank takes in one launch (csrc/score.hip: MAXH)
-
-
 def _rank_long_history(prec_u: torch.Tensor, item_emb: torch.Tensor, history: Sequence[int], target: int) -> int:
     """Exact rank of ONE user whose exclusion list exceeds HIST_MAX entries, from launches of `iisan_score_rank` alone.
     With R(H) the kernel's rank under exclusion set H and T0 = {target} if the target is itself excluded (its score is then -inf in
@@ -178,40 +166,135 @@ def _rank_long_history(prec_u: torch.Tensor, item_emb: torch.Tensor, history: Se
     return int(r[0] + (r[1:] - r[0]).sum())
 
 
+# A rank's share of the users, from host lists or from a `UserStore`.  Either source has `n_users`; `count`, the shard's length
+# (`dp.sequential_shard`); `hs`, the width of the exclusion matrix; `batch(i, j, item_emb)` = (x = item_emb[tokens], mask, exclusion matrix,
+# targets | None) of shard positions i..j-1, on the device; on the host `user(position)` and, per user number, `history(u)` (the FULL
+# exclusion list) and `target(u)`; `long`, the (position, user) pairs whose list exceeds `cap`, the entries per user a batch may carry
+# (None: any) — iisan_score_rank keeps them in LDS (include/iisan_hip.h: hist_stride <= 256).  Such users (the reference masks histories of
+# any length, metrics.py:198-207) keep their first `cap` entries in the batched pass and are re-ranked exactly by `_rank_long_history`.
+
+class _ListUsers:
+    """Host lists: the shard is packed once by `_pack_users`, a batch is its slices shipped to the device.  `targets` False: `seqs` are the
+    encoder's inputs alone (`recommend_topk`)."""
+
+    def __init__(self, seqs, histories, max_seq_len, cap, rank, world, batch, targets=True):
+        self.n_users, self.seqs, self.full = len(seqs), seqs, histories
+        self.idx = dp.sequential_shard(self.n_users, rank, world, batch) if world > 1 else list(range(self.n_users))
+        self.count = len(self.idx)
+        long_users = {u for u in range(self.n_users) if len(histories[u]) > cap} if cap else set()
+        if long_users:
+            histories = list(histories)
+            for u in long_users:
+                histories[u] = histories[u][:cap]
+        self.long = [(k, u) for k, u in enumerate(self.idx) if u in long_users] if long_users else []
+        self.hs = max(1, max((len(h) for h in histories), default=1))
+        rows = [seqs[i] for i in self.idx] if targets else [list(seqs[i]) + [0] for i in self.idx]
+        self.tok, self.lm, self.hist, tgt = _pack_users(rows, [histories[i] for i in self.idx], max_seq_len, self.hs)
+        self.tgt = tgt if targets else None
+
+    def batch(self, i, j, item_emb):
+        dev = item_emb.device
+        x = item_emb[self.tok[i:j].to(dev)]                          # == com_dense(cat(tables[tokens])), metrics.py:214
+        return x, self.lm[i:j].to(dev), self.hist[i:j].to(dev), None if self.tgt is None else self.tgt[i:j].to(dev)
+
+    def user(self, pos):
+        return self.idx[pos]
+
+    def history(self, u):
+        return self.full[u]
+
+    def target(self, u):
+        return int(self.seqs[u][-1])
+
+
+class _StoreUsers:
+    """A `userstore.UserStore`: a batch is a slice of the shard's user numbers (made on the device), its windows, masks, targets, exclusion
+    matrix and `item_emb[tokens]` are built there; the host answers from the store's CSR copy."""
+
+    def __init__(self, users, max_seq_len, mode, cap, rank, world, batch):
+        self.users, self.n_users, self.S, self.mode = users, users.n_users, max_seq_len, mode
+        self.hs = max(1, min(users.max_hist, cap) if cap else users.max_hist)
+        self.idx = users.eval_index(rank, world, batch)
+        self.first, self.count = userstore.shard_range(self.n_users, rank, world, batch)[0], self.idx.numel()
+        # (the tail that repeats user U - 1 to fill the last batch is cut off by the gather and needs no correction)
+        self.long = [(int(u) - self.first, int(u)) for u in users.long_users if self.first <= int(u) < self.first + self.count] if cap else []
+
+    def batch(self, i, j, item_emb):
+        ib = self.idx[i:j]
+        _, m, tgt, x = self.users.windows(self.mode, self.S, ib, item_emb)
+        return x, m, self.users.history(ib, self.hs), tgt
+
+    def user(self, pos):
+        return min(self.first + pos, self.n_users - 1)
+
+    def history(self, u):
+        return self.users.host.history(u).tolist()
+
+    def target(self, u):
+        return self.users.host.target(u)
+
+
+def _rank_loop(model, item_emb, src, batch, world) -> torch.Tensor:
+    """The gathered ranks of a user source, invalid targets (-1) still in them."""
+    was_training = model.training
+    model.eval()
+    out = []
+    try:
+        for i in range(0, src.count, batch):
+            x, m, hist, tgt = src.batch(i, i + batch, item_emb)
+            prec = model.user_encoder(x, m, None)[:, -1].contiguous()   # metrics.py:216
+            r = ops.score_rank(prec, item_emb, hist, tgt)
+            for k, u in src.long:
+                if i <= k < i + batch:
+                    r[k - i] = _rank_long_history(prec[k - i:k - i + 1], item_emb, src.history(u), src.target(u))
+            out.append(r)
+    finally:
+        model.train(was_training)
+    ranks = torch.cat(out)
+    return dp.gather_concat(ranks, src.n_users) if world > 1 else ranks
+
+
+def _topk_loop(model, item_emb, src, k, batch, world) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The gathered top-k lists (ids, scores) of a user source."""
+    was_training = model.training
+    model.eval()
+    ids_out, sc_out = [], []
+    try:
+        for i in range(0, src.count, batch):
+            x, m, hist, _ = src.batch(i, i + batch, item_emb)
+            prec = model.user_encoder(x, m, None)[:, -1].contiguous()   # metrics.py:214-216
+            ids, sc = ops.score_topk(prec, item_emb, hist, k)
+            ids_out.append(ids)
+            sc_out.append(sc)
+    finally:
+        model.train(was_training)
+    ids, sc = torch.cat(ids_out), torch.cat(sc_out)
+    n_items = item_emb.shape[0] - 1
+    if n_items - src.hs < k:
+        ids = _fill_short_lists(ids, k, n_items, lambda row: src.history(src.user(row)))
+    if world > 1:
+        ids, sc = dp.gather_concat(ids, src.n_users), dp.gather_concat(sc, src.n_users)
+    return ids, sc
+
+
+def _fill_short_lists(ids: torch.Tensor, k: int, n_items: int, history_of_row) -> torch.Tensor:
+    """Fewer than k items outside some user's history: the reference's argsort lists the -inf (history) items next — for a stable sort in
+    ascending id order — and the kernel leaves those slots 0 (include/iisan_hip.h).  `history_of_row(r)`: the exclusion list of row r."""
+    ids_c = ids.cpu()
+    for r in torch.nonzero((ids_c == 0).any(dim=1)).flatten().tolist():
+        excl = sorted({int(c) for c in history_of_row(r) if 1 <= int(c) <= n_items})
+        free = int((ids_c[r] != 0).sum())
+        fill = excl[:k - free]
+        ids_c[r, free:free + len(fill)] = torch.tensor(fill, dtype=torch.int32)
+    return ids_c.to(ids.device)
+
+
 @torch.no_grad()
 def evaluate_ranks(model, item_emb: torch.Tensor, eval_seqs: Sequence[Sequence[int]], histories: Sequence[Sequence[int]],
                    max_seq_len: int, batch: int = 1024, rank: int = 0, world: int = 1) -> torch.Tensor:
     """1-based rank of every user's target (int32 [U], identical on all ranks).  `eval_seqs[u]` = history + target
     (`eval_seq`), `histories[u]` = items to exclude (`user_history`, metrics.py:204-205)."""
-    U = len(eval_seqs)
-    # iisan_score_rank keeps a user's exclusion list in LDS (include/iisan_hip.h: hist_stride <= 256).  Users with longer lists (the
-    # reference masks histories of any length, metrics.py:198-207) keep their first 256 entries in the batched pass and are re-ranked
-    # exactly by `_rank_long_history` below — a few more launches of the same kernel, no other arithmetic (ADVICE r4).
-    long_users = [u for u in range(U) if len(histories[u]) > HIST_MAX]
-    if long_users:
-        histories = list(histories)
-        full = {u: histories[u] for u in long_users}
-        for u in long_users:
-            histories[u] = full[u][:HIST_MAX]
-    hs = max(1, max(len(h) for h in histories))
-    idx = dp.sequential_shard(U, rank, world, batch) if world > 1 else list(range(U))
-    tok, lm, hist, tgt = _pack_users([eval_seqs[i] for i in idx], [histories[i] for i in idx], max_seq_len, hs)
-    dev = item_emb.device
-    was_training = model.training
-    model.eval()
-    out = []
-    for i in range(0, len(idx), batch):
-        t, m = tok[i:i + batch].to(dev), lm[i:i + batch].to(dev)
-        x = item_emb[t]                                            # == com_dense(cat(tables[tokens])), metrics.py:214
-        prec = model.user_encoder(x, m, None)[:, -1].contiguous()   # metrics.py:216
-        r = ops.score_rank(prec, item_emb, hist[i:i + batch].to(dev), tgt[i:i + batch].to(dev))
-        for k in range(i, min(i + batch, len(idx))):
-            if long_users and idx[k] in full:
-                r[k - i] = _rank_long_history(prec[k - i:k - i + 1], item_emb, full[idx[k]], int(tgt[k]))
-        out.append(r)
-    model.train(was_training)
-    ranks = torch.cat(out)
-    ranks = dp.gather_concat(ranks, U) if world > 1 else ranks
+    ranks = _rank_loop(model, item_emb, _ListUsers(eval_seqs, histories, max_seq_len, HIST_MAX, rank, world, batch), batch, world)
     if bool((ranks < 1).any()):
         _raise_invalid_targets(ranks, item_emb)
     return ranks
@@ -233,66 +316,12 @@ def recommend_topk(model, item_emb: torch.Tensor, input_seqs: Sequence[Sequence[
     `max_seq_len` are used, `dataset.py:183-189`; for the reference's eval protocol `eval_seq[u][:-1]`), `histories[u]` = the items
     scored -inf.  Ties towards the lower item id (a stable argsort).  Consistent with `evaluate_ranks`: a target it ranks r <= k is
     `ids[u, r-1]`.  The [U, N] score matrix never exists (`iisan_score_topk`)."""
-    U = len(input_seqs)
-    hs = max(1, max((len(h) for h in histories), default=1))
-    idx = dp.sequential_shard(U, rank, world, batch) if world > 1 else list(range(U))
-    tok, lm, hist, _ = _pack_users([list(input_seqs[i]) + [0] for i in idx], [histories[i] for i in idx], max_seq_len, hs)
-    dev = item_emb.device
-    n_items = item_emb.shape[0] - 1
-    was_training = model.training
-    model.eval()
-    ids_out, sc_out = [], []
-    for i in range(0, len(idx), batch):
-        t, m = tok[i:i + batch].to(dev), lm[i:i + batch].to(dev)
-        prec = model.user_encoder(item_emb[t], m, None)[:, -1].contiguous()          # metrics.py:214-216
-        ids, sc = ops.score_topk(prec, item_emb, hist[i:i + batch].to(dev), k)
-        ids_out.append(ids)
-        sc_out.append(sc)
-    model.train(was_training)
-    ids, sc = torch.cat(ids_out), torch.cat(sc_out)
-    if n_items - hs < k:
-        # fewer than k items outside some user's history: the reference's argsort lists the -inf (history) items next — for a stable
-        # sort in ascending id order — and the kernel leaves those slots 0 (include/iisan_hip.h)
-        ids_c = ids.cpu()
-        for r in torch.nonzero((ids_c == 0).any(dim=1)).flatten().tolist():
-            excl = sorted({int(c) for c in histories[idx[r]] if 1 <= int(c) <= n_items})
-            free = int((ids_c[r] != 0).sum())
-            fill = excl[:k - free]
-            ids_c[r, free:free + len(fill)] = torch.tensor(fill, dtype=torch.int32)
-        ids = ids_c.to(dev)
-    if world > 1:
-        ids, sc = dp.gather_concat(ids, U), dp.gather_concat(sc, U)
-    return ids, sc
+    return _topk_loop(model, item_emb, _ListUsers(input_seqs, histories, max_seq_len, None, rank, world, batch, targets=False), k, batch, world)
 
 
 def _ranks_from_store(model, item_emb, users, max_seq_len, batch, rank, world) -> torch.Tensor:
     """The gathered ranks of `evaluate_ranks_from_store`, invalid targets (-1) still in them."""
-    from . import userstore
-    U = users.n_users
-    item_emb = ops._f32c(item_emb)
-    hs = max(1, min(users.max_hist, HIST_MAX))
-    idx = users.eval_index(rank, world, batch)
-    first = userstore.shard_range(U, rank, world, batch)[0]
-    # the long-history users of this shard, by position in it (host arithmetic on the store's short list; the tail that repeats user
-    # U - 1 to fill the last batch is cut off by the gather and needs no correction)
-    long_pos = [(int(u) - first, int(u)) for u in users.long_users if first <= int(u) < first + idx.numel()]
-    was_training = model.training
-    model.eval()
-    out = []
-    try:
-        for i in range(0, idx.numel(), batch):
-            ib = idx[i:i + batch]
-            _, m, tgt, x = users.windows(userstore.EVAL, max_seq_len, ib, item_emb)    # x == item_emb[tokens], metrics.py:214
-            prec = model.user_encoder(x, m, None)[:, -1].contiguous()                  # metrics.py:216
-            r = ops.score_rank(prec, item_emb, users.history(ib, hs), tgt)
-            for k, u in long_pos:
-                if i <= k < i + batch:
-                    r[k - i] = _rank_long_history(prec[k - i:k - i + 1], item_emb, users.host.history(u).tolist(), users.host.target(u))
-            out.append(r)
-    finally:
-        model.train(was_training)
-    ranks = torch.cat(out)
-    return dp.gather_concat(ranks, U) if world > 1 else ranks
+    return _rank_loop(model, ops._f32c(item_emb), _StoreUsers(users, max_seq_len, userstore.EVAL, HIST_MAX, rank, world, batch), batch, world)
 
 
 @torch.no_grad()
@@ -330,41 +359,8 @@ def recommend_topk_from_store(model, item_emb: torch.Tensor, users, max_seq_len:
     windows); with `holdout` the last item of every sequence is held out as in the reference's eval protocol (EVAL windows: a store built
     from `eval_seq` serves both this and `evaluate_ranks_from_store`).  The whole exclusion list of every user is applied
     (`iisan_score_topk` takes any stride), as `recommend_topk` does."""
-    from . import userstore
-    U = users.n_users
-    item_emb = ops._f32c(item_emb)
-    hs = max(1, users.max_hist)
-    idx = users.eval_index(rank, world, batch)
-    first = userstore.shard_range(U, rank, world, batch)[0]
-    mode = userstore.EVAL if holdout else userstore.INPUT
-    n_items = item_emb.shape[0] - 1
-    was_training = model.training
-    model.eval()
-    ids_out, sc_out = [], []
-    try:
-        for i in range(0, idx.numel(), batch):
-            ib = idx[i:i + batch]
-            _, m, _, x = users.windows(mode, max_seq_len, ib, item_emb)
-            prec = model.user_encoder(x, m, None)[:, -1].contiguous()                    # metrics.py:214-216
-            ids, sc = ops.score_topk(prec, item_emb, users.history(ib, hs), k)
-            ids_out.append(ids)
-            sc_out.append(sc)
-    finally:
-        model.train(was_training)
-    ids, sc = torch.cat(ids_out), torch.cat(sc_out)
-    if n_items - hs < k:
-        # fewer than k items outside some user's history: the -inf (history) items follow in ascending id order (`recommend_topk`), from
-        # the store's host copy of the lists
-        ids_c = ids.cpu()
-        for r in torch.nonzero((ids_c == 0).any(dim=1)).flatten().tolist():
-            excl = sorted({int(c) for c in users.host.history(min(first + r, U - 1)) if 1 <= int(c) <= n_items})
-            free = int((ids_c[r] != 0).sum())
-            fill = excl[:k - free]
-            ids_c[r, free:free + len(fill)] = torch.tensor(fill, dtype=torch.int32)
-        ids = ids_c.to(ids.device)
-    if world > 1:
-        ids, sc = dp.gather_concat(ids, U), dp.gather_concat(sc, U)
-    return ids, sc
+    src = _StoreUsers(users, max_seq_len, userstore.EVAL if holdout else userstore.INPUT, None, rank, world, batch)
+    return _topk_loop(model, ops._f32c(item_emb), src, k, batch, world)
 
 
 def hit_ndcg(ranks: torch.Tensor, topk: int = 10) -> Tuple[float, float]:

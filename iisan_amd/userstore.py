@@ -9,11 +9,12 @@ eval routes) the user encoder's input `item_emb[ids]` in one launch each.  `eval
 `Dataset` / `DistributedSampler` of a Cached or item-store epoch.
 
 The host keeps the CSR arrays it was built from (numpy, a few bytes per interaction): the exclusion lists longer than
-`evaluate.HIST_MAX` are re-ranked from them (`evaluate._rank_long_history`), and so is the tail of a top-k list with fewer than k items
+`HIST_MAX` are re-ranked from them (`evaluate._rank_long_history`), and so is the tail of a top-k list with fewer than k items
 outside a user's history.
 """
 from __future__ import annotations
 
+import itertools
 import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
@@ -26,6 +27,14 @@ from . import _lib
 __all__ = ["UserStore", "HostUsers", "pack_users", "epoch_index_host", "shard_range", "TRAIN", "EVAL", "INPUT"]
 
 TRAIN, EVAL, INPUT = _lib.IISAN_WIN_TRAIN, _lib.IISAN_WIN_EVAL, _lib.IISAN_WIN_INPUT      # include/iisan_hip.h; 1 <= S <= 63
+HIST_MAX = 256      # exclusion-list entries per user that iisan_score_rank takes in one launch (csrc/score.hip: MAXH)
+
+
+def _ragged(rows, n):
+    """(flat int64 array, lengths, end offsets) of a list of n integer sequences."""
+    lens = np.fromiter((len(r) for r in rows), dtype=np.int64, count=n)
+    flat = np.fromiter(itertools.chain.from_iterable(rows), dtype=np.int64, count=int(lens.sum()))
+    return flat, lens, np.cumsum(lens)
 
 
 @dataclass
@@ -38,7 +47,7 @@ class HostUsers:
     hist_items: Optional[np.ndarray]
     min_len: int                        # shortest sequence (0 for an empty store)
     max_hist: int                       # longest exclusion list
-    long_users: np.ndarray              # int64, ascending: users whose exclusion list exceeds evaluate.HIST_MAX
+    long_users: np.ndarray              # int64, ascending: users whose exclusion list exceeds HIST_MAX
 
     def sequence(self, u: int) -> np.ndarray:
         return self.seq_items[self.seq_off[u]:self.seq_off[u + 1]]
@@ -65,7 +74,6 @@ def _rows(x, what: str):
 
 
 def _csr(rows, what: str, item_num: Optional[int]):
-    from .evaluate import _ragged
     n = len(rows)
     flat, lens, ends = _ragged(rows, n)
     if flat.size:
@@ -84,7 +92,6 @@ def _csr(rows, what: str, item_num: Optional[int]):
 def pack_users(seqs, histories=None, item_num: Optional[int] = None) -> HostUsers:
     """CSR form of `seqs` (and `histories`) with the store's validation: ValueError for a negative id, for an id above `item_num` when it
     is given, and for `histories` that do not list every user."""
-    from .evaluate import HIST_MAX
     rows = _rows(seqs, "seqs")
     off, items, lens = _csr(rows, "seqs", item_num)
     hoff = hitems = None

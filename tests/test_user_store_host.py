@@ -113,6 +113,37 @@ def test_shard_rule_equals_sequential_shard(U, world, batch):
         assert cat[:U] == list(range(U))
 
 
+class _RaisingEncoder(torch.nn.Module):
+    """A model whose user encoder fails: what an eval route leaves behind when a batch raises."""
+
+    def user_encoder(self, x, mask, local_rank):
+        raise RuntimeError("user encoder failed")
+
+
+@pytest.mark.parametrize("training", [True, False])
+def test_a_raise_inside_an_eval_loop_leaves_the_models_mode_as_it_was(training):
+    item_emb = torch.arange(20, dtype=torch.float32).view(5, 4)
+    for route in (lambda m: evaluate.evaluate_ranks(m, item_emb, [[1, 2, 3]], [[1, 2]], 4),
+                  lambda m: evaluate.recommend_topk(m, item_emb, [[1, 2]], [[1, 2]], 4, k=2)):
+        model = _RaisingEncoder().train(training)
+        with pytest.raises(RuntimeError, match="user encoder failed"):
+            route(model)
+        assert model.training is training
+
+
+def test_fill_short_lists_appends_the_history_in_ascending_id_order():
+    """k = 4 over items 1..5: the slots the kernel left 0 take the user's in-range, distinct history ids, ascending (the reference's stable
+    argsort lists the -inf items there); a full list is not touched, a list stays short when the history has too few such ids."""
+    ids = torch.tensor([[4, 2, 5, 1],            # no empty slot
+                        [3, 5, 0, 0],            # two: history [4, 1, 2] -> 1, 2
+                        [2, 0, 0, 0]],           # three: history [0, 9, 5, 3, 5] -> 3, 5 (0 is padding, 9 is above the table, 5 twice)
+                       dtype=torch.int32)
+    hist = [[3], [4, 1, 2], [0, 9, 5, 3, 5]]
+    out = evaluate._fill_short_lists(ids, 4, 5, lambda row: hist[row])
+    assert out.dtype == torch.int32
+    assert out.tolist() == [[4, 2, 5, 1], [3, 5, 1, 2], [2, 3, 5, 0]]
+
+
 def test_new_symbols_are_bound():
     for name, n_args in (("iisan_user_windows", 15), ("iisan_user_history", 8), ("iisan_rank_histogram", 5)):
         assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == n_args
