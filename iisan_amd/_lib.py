@@ -12,6 +12,8 @@ LIB_PATH = os.path.join(_HERE, "libiisan_hip.so")
 
 IISAN_F16, IISAN_BF16, IISAN_F32 = 0, 1, 2
 IISAN_WIN_TRAIN, IISAN_WIN_EVAL, IISAN_WIN_INPUT = 0, 1, 2
+IISAN_TOWER_VIT, IISAN_TOWER_BERT, IISAN_TOWER_CLIP = 0, 1, 2
+EPI_OUT16, EPI_GELU16, EPI_QGELU16 = 0, 1, 8      # epilogue modes of iisan_gemm16 (include/iisan_hip.h)
 MAX_LAYERS, MAX_SIDE = 48, 16
 
 vp, i32, i64, f32, u64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
@@ -26,7 +28,9 @@ class VitWeights(C.Structure):
     _fields_ = [("hidden", i32), ("layers", i32), ("heads", i32), ("mlp", i32),
                 ("image", i32), ("patch", i32), ("channels", i32), ("dtype16", i32), ("eps", f32), ("full_blocks", i32),
                 ("patch_w", vp), ("patch_b", vp), ("cls_token", vp), ("pos_emb", vp),
-                ("layer", LayerWeights * MAX_LAYERS), ("folded", vp)]
+                ("layer", LayerWeights * MAX_LAYERS), ("folded", vp),
+                # CLIP vision towers (all zero = a plain ViT): pre-LayerNorm, MLP activation (0 erf-GELU, 1 quick-GELU), uint8 statistics
+                ("pre_ln_w", vp), ("pre_ln_b", vp), ("act", i32), ("norm_mean", f32 * 3), ("norm_std", f32 * 3)]
 
 
 class BertWeights(C.Structure):

@@ -205,6 +205,40 @@ __device__ __forceinline__ void gelu_erf_fast2xN(f2* x) {
     }
 }
 __device__ __forceinline__ void gelu_erf_fast2x8(f2 (&x)[8]) { gelu_erf_fast2xN<8>(x); }
+// quick-GELU, the MLP activation of the OpenAI CLIP towers (EPI_QGELU16):  x * sigmoid(1.702 x) = x / (1 + 2^(-1.702 log2(e) x)),  as
+// v_mul + v_exp_f32 + v_add + v_rcp_f32 + v_mul.  A transcendental issues in 8 cycles where an fma takes 4, so a pair costs 3 packed
+// + 4 transcendental instructions = 44 issue cycles against the 15 x 4 = 60 of gelu_erf_fast2xN, with ONE temporary per pair.  A fit in
+// the style of gelu_erf_fast was not taken: the tail of the sigmoid is e^(-1.702 a), not a Gaussian — a e^(-1.702 a) falls below 1.7e-6
+// only from a = 10 on, so the polynomial would have to cover twice the range of the erf fit — and it keeps |x| and the polynomial live
+// per pair, registers the 256x256 FC1 epilogue does not have.  Max |error| against float64 over [-12, 12] in fp32 arithmetic: 7.4e-7
+// (at x = 8.6, where an ulp of the result is 9.5e-7), and 1.38e-6 with v_exp_f32 and v_rcp_f32 each taken 1 ulp off in the worst
+// direction (tools/qgelu_err.py) — inside the 1.7e-6 of gelu_erf_fast.  Saturation is exact: 2^t overflows to inf, 1 / inf = 0 and
+// x * 0 = -0 for x << 0;  2^t underflows to 0 and x / 1 = x for x >> 0.
+constexpr float QGELU_K = -2.45546696f;       // -1.702 * log2(e)
+__device__ __forceinline__ float quick_gelu(float x) {
+    float y = x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * QGELU_K));
+    // The product is an fp32 value of its own.  Left to itself hipcc fuses it with the fp16 conversion that follows in the 128x128
+    // epilogue (`v_fma_mixlo_f16`, whatever the contraction setting) — one rounding where the packed form below has two, and the two
+    // kernel families stop agreeing bit for bit (seen on a CLIP-B/32 batch: 8e-5 between their taps)
+    asm volatile("" : "+v"(y));
+    return y;
+}
+// The same on NP pairs, step by step across the pairs like gelu_erf_fast2xN: the packed steps are v_pk_mul_f32 / v_pk_add_f32, and the
+// transcendentals of a step are 2 NP independent instructions
+template <int NP>
+__device__ __forceinline__ void quick_gelu2xN(f2* x) {
+    f2 t[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) t[k] = x[k] * (f2)QGELU_K;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) { t[k][0] = __builtin_amdgcn_exp2f(t[k][0]); t[k][1] = __builtin_amdgcn_exp2f(t[k][1]); }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) t[k] = t[k] + (f2)1.0f;
+#pragma unroll
+    for (int k = 0; k < NP; ++k) { t[k][0] = __builtin_amdgcn_rcpf(t[k][0]); t[k][1] = __builtin_amdgcn_rcpf(t[k][1]); }
+#pragma unroll
+    for (int k = 0; k < NP; ++k) x[k] = x[k] * t[k];
+}
 // d/dx gelu_erf
 __device__ __forceinline__ float gelu_erf_grad(float x) {
     const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
@@ -335,7 +369,10 @@ struct Gemm16Args {
 __host__ __device__ static inline int64_t blk32_byte(int64_t m, int64_t c, int64_t C) {
     return ((m >> 5) * (C >> 5) + (c >> 5)) * 2048 + ((c >> 3) & 1) * 1024 + (((c >> 4) & 1) * 32 + (m & 31)) * 16 + (c & 7) * 2;
 }
-enum { EPI_OUT16 = 0, EPI_GELU16 = 1, EPI_RESID32 = 2, EPI_PATCH32 = 3, EPI_QKVH16 = 4, EPI_F32 = 5, EPI_PATCH16 = 6, EPI_STREAM16 = 7 };
+enum { EPI_OUT16 = 0, EPI_GELU16 = 1, EPI_RESID32 = 2, EPI_PATCH32 = 3, EPI_QKVH16 = 4, EPI_F32 = 5, EPI_PATCH16 = 6, EPI_STREAM16 = 7, EPI_QGELU16 = 8 };
+// EPI_QGELU16: EPI_GELU16 with quick_gelu in place of the erf form (the FC1 product of a CLIP tower) — the 128x128 kernel and gemm16_h256, plain
+// or with a block-major output; no LayerNorm in the epilogue (rowstat) and no block-major A operand (the folded route does not serve CLIP).
+// gemm16_s256, the dev-only race screen, does not have it: gemm16_route sends such a product to the 128x128 kernel under variant 3.
 // EPI_STREAM16 (gemm16_h256 only, fp16, N = ldo): the residual add of a pre-LN tower in the epilogue — out IS the fp16 stream x [Mpad, N],
 // read and written in place: x[m] = fp16(x[m] + acc[m] + bias), and `rowpart` [N / 64][Mpad] (sum, sum of squares) receives every
 // row's statistics over each 64-column slice (reduced in a fixed order by stream_stats_finalize, rowops.hip).  Rows m = item * qkv_S
@@ -355,6 +392,8 @@ bool gemm16_s256_applicable(int mode, const Gemm16Args& a);      // gemm16_s256.
 int launch_gemm16_s256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s);
 bool gemm16_h256_applicable(int mode, const Gemm16Args& a);      // gemm16_h256.hip
 int launch_gemm16_h256(int dtype16, int mode, const Gemm16Args& a, hipStream_t s);
+// gemm16_h256_qgelu.hip: the EPI_QGELU16 instantiations of gemm16_h256_kernel (row-major or block-major output, by a.out_blk32)
+int launch_gemm16_h256_qgelu(int dtype16, const Gemm16Args& a, hipStream_t s);
 int launch_gemm16_f32(const Gemm16Args& a, int ksplit, hipStream_t s);      // gemm16.hip: fp32 output of the 128x128 kernel (split.hip)
 // `width` of the row kernels below: 768 or 1024, or 128, 192, 256, 384, or 1280 (the instantiated widths; anything else: IISAN_EBADSHAPE)
 bool row_width_instantiated(int width);     // rowops.hip; the encoder executors accept a tower of exactly these hidden sizes
@@ -408,10 +447,15 @@ int launch_attention_cls16(int dtype16, const void* qkv, const float* key_bias, 
 // embedding and tap steps of the encoder executors (rowops.hip)
 // columns of a patch row in the patch matrix / the packed patch weight: C p p, zero-padded to a multiple of 64 when p % 8 != 0 (p = 14: 588 -> 640)
 int vit_patch_ld(int C, int p);
-int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64_t M, int C, int R, int p, hipStream_t s);
+// norm (host, null = none): mean[3] | std[3] of a uint8 source, (p / 255 - mean) / std in place of the reference's (.5, .5) transform
+int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64_t M, int C, int R, int p, hipStream_t s, const float* norm = nullptr);
 // item m = row index[m] of a resident uint8 catalogue [rows, C, R, R]; values outside [0, rows) = padding (zero fragment, no read)
 int launch_vit_im2col_indexed(int dtype16, const uint8_t* catalogue, int64_t rows, const int64_t* index, void* out, int64_t M, int C,
-                              int R, int p, hipStream_t s);
+                              int R, int p, hipStream_t s, const float* norm = nullptr);
+// CLIP opening step (rowops.hip, clip_open_kernel): x0 = LN_pre(pos + patch embedding | cls + pos[0] in xc) -> the mixed stream (x16 / xc),
+// and LN1(x0) -> out16, one launch
+int launch_clip_open(int dtype16, const float* pos, void* x16, float* xc, const void* patch16, const float* pre_g, const float* pre_b,
+                     const float* g, const float* b, float eps, void* out16, int64_t items, int Ttok, int width, hipStream_t s);
 int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M, int T, int D, hipStream_t s);
 // keep (train mode): the keep factor multiplies the fp32 LayerNorm output before it is rounded or stored — width 768
 int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, const float* pos, const float* type0,

@@ -90,6 +90,7 @@ float WANTED;
 // description.  The layout decisions of the call are fields, so the probe of a decision is a copy with that decision switched on.
 struct Products {
     int dt, D, F, T, heads;
+    int act;                // MLP activation of the tower (iisan_vit_weights::act): 0 erf-GELU, 1 quick-GELU — the epilogue mode of every FC1 product
     bool ln = false;        // QKV / FC1 read the stream and apply LayerNorm in their epilogues (VS_FOLD, VS_STREAM)
     bool stream = false;    // O / FC2 add into the stream in their epilogues (VS_STREAM)
     bool f1blk = false;     // F1, the FC1 -> FC2 intermediate of the all-token blocks, is block-major
@@ -97,6 +98,7 @@ struct Products {
     // 80-wide heads (ViT-H/14, hidden 1280 = 16 x 80): QKV is a plain row-major product (no GEMM epilogue knows a head width but 64), the
     // attention runs attn16_hd80.hip, and there is no CLS-only form of the last live block: it runs on every token
     bool hd80() const { return D == heads * 80; }
+    int fc1_mode() const { return act ? EPI_QGELU16 : EPI_GELU16; }
 
     // out [M, N] = A [M, K] W^T, natural leading dimensions: the products of the CLS tail (one row per item) as they are
     static Product plain(int mode, int K, int N, int64_t M) {
@@ -113,7 +115,7 @@ struct Products {
         return p;
     }
     Product fc1(int64_t tok) const {
-        Product p = plain(EPI_GELU16, D, F, tok);
+        Product p = plain(fc1_mode(), D, F, tok);
         p.a.rowstat = ln ? &WANTED : nullptr; p.a.a_blk32 = xblk; p.a.out_blk32 = f1blk;
         return p;
     }
@@ -192,8 +194,10 @@ int bert_check_words(int words, int max_pos) {
 }
 
 // The LayerNorm-folded routes — fold_ln_weights, the stream statistics, the block-major stream — take fp16 operands and are 768 wide: a
-// bf16 tower, a 1024- or 1280-wide one and the narrow ones (128 - 384) run on the LayerNorm-image route whatever ln_fold says, and ask for no folded set
-bool vit_fold_routes(int dtype16, int hidden) { return dtype16 == IISAN_F16 && hidden == 768; }
+// bf16 tower, a 1024- or 1280-wide one and the narrow ones (128 - 384) run on the LayerNorm-image route whatever ln_fold says, and ask for no folded set.
+// So does a CLIP tower at every width: patches_to_stream has no pre-LayerNorm and the <.., LNA> FC1 epilogue no quick-GELU twin
+bool vit_fold_routes(int dtype16, int hidden, bool clip) { return dtype16 == IISAN_F16 && hidden == 768 && !clip; }
+bool vit_is_clip(const iisan_vit_weights* w) { return w->pre_ln_w != nullptr || w->act != 0; }
 
 // One chunk of a forward: mc items from item m0 of the call on, tok = mc * T token rows, tp = their rows of the tap tensor
 struct Chunk : Products {
@@ -230,7 +234,7 @@ struct Chunk : Products {
         IISAN_TRY(gather_cls(Xc, 1, 0));
         if (post_ln) IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln1_w, L.ln1_b, eps, nullptr, b.H, Xc, mc, D, s, keep1));
         else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, eps, Xc, b.H, nullptr, mc, D, s));
-        IISAN_TRY(launch(plain(EPI_GELU16, D, F, mc), b.H, L.fc1_w, L.fc1_b, b.F1));
+        IISAN_TRY(launch(plain(fc1_mode(), D, F, mc), b.H, L.fc1_w, L.fc1_b, b.F1));
         IISAN_TRY(launch(plain(EPI_OUT16, F, D, mc), b.F1, L.fc2_w, L.fc2_b, b.D16));
         if (post_ln) IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, L.ln2_w, L.ln2_b, eps, nullptr, nullptr, Xc, mc, D, s, keep2));
         else IISAN_TRY(launch_add_layernorm768(dt, Xc, b.D16, nullptr, nullptr, eps, Xc, nullptr, nullptr, mc, D, s));
@@ -245,7 +249,7 @@ IISAN_DEV_KNOB(resid32, g_resid32);
 IISAN_DEV_KNOB(ln_fold, g_ln_fold);
 IISAN_DEV_KNOB(blk32, g_blk32);
 static int vit_fold_layers(const iisan_vit_weights* w) {
-    return (!g_resid32 && g_ln_fold && vit_fold_routes(w->dtype16, w->hidden)) ? w->layers : 0;
+    return (!g_resid32 && g_ln_fold && vit_fold_routes(w->dtype16, w->hidden, vit_is_clip(w))) ? w->layers : 0;
 }
 // the folded set of one tower: [layers][(3D + F) x D] fp16, then [layers][3D + F] fp32 (the caller's `folded` buffer or the workspace)
 static size_t vit_fold_w_elems(const iisan_vit_weights* w) { return (size_t)(3 * w->hidden + w->mlp) * w->hidden; }
@@ -266,13 +270,13 @@ static int vit_fold_all(const iisan_vit_weights* w, int layers, bool last_fc1, c
 }
 
 extern "C" size_t iisan_vit_fold_bytes(const iisan_vit_weights* w) {
-    if (!vit_fold_routes(w->dtype16, w->hidden)) return 0;
+    if (!vit_fold_routes(w->dtype16, w->hidden, vit_is_clip(w))) return 0;
     return (size_t)w->layers * (vit_fold_w_elems(w) * 2 + (size_t)(3 * w->hidden + w->mlp) * 4);
 }
 
 extern "C" int iisan_vit_fold_layernorm(const iisan_vit_weights* w, void* folded, size_t bytes, void* stream) {
     const size_t need = iisan_vit_fold_bytes(w);
-    IISAN_CHECK_SHAPE(need > 0, "vit_fold_layernorm: fp16 operands and hidden size 768 only");
+    IISAN_CHECK_SHAPE(need > 0, "vit_fold_layernorm: fp16 operands and hidden size 768 only, and no CLIP tower");
     if (!folded || bytes < need) {
         iisan_set_error("vit_fold_layernorm: buffer too small (%zu < %zu)", bytes, need);
         return IISAN_EWORKSPACE;
@@ -315,12 +319,12 @@ struct VitPlan {
 // those products run on the kernel that has it, and the residual adds in the epilogues of the O / FC2 products likewise.  The stream is
 // block-major only on the product route, with F1 block-major, and only when every product that touches it takes the flags: QKV and FC1 (A),
 // O and FC2 (read-modify-write), the K/V product of a CLS-only last block (A).
-VitPlan vit_plan(Products& p, int live, bool full_blocks, bool folded, const Chunks& c) {
+VitPlan vit_plan(Products& p, int live, bool full_blocks, bool folded, const Chunks& c, bool clip) {
     if (g_resid32) return {VS_RESID32, false};
     const int reads = Products::P_QKV | Products::P_FC1 | (full_blocks ? 0 : Products::P_KV), adds = Products::P_O | Products::P_FC2;
     Products t = p;
     t.ln = true;
-    if (live > 0 && g_ln_fold && vit_fold_routes(p.dt, p.D) && t.all_h256(c, reads)) {
+    if (live > 0 && g_ln_fold && vit_fold_routes(p.dt, p.D, clip) && t.all_h256(c, reads)) {
         p = t;
         t.stream = true;
         if (g_ln_fold >= 2 && t.all_h256(c, adds)) p = t;
@@ -353,8 +357,13 @@ struct VitChunk : Chunk {
     // index != null: `img` is a resident uint8 catalogue of `rows` images and item m of the chunk is its row index[m]
     int embed(const void* img, int img_u8, const int64_t* index = nullptr, int64_t rows = 0) const {
         const int P = T - 1, pd = vit_patch_ld(w->channels, w->patch);      // (588 -> 640 columns at patch 14: zeros in F1 and in patch_w)
-        if (index) IISAN_TRY(launch_vit_im2col_indexed(dt, (const uint8_t*)img, rows, index, b.F1, mc, w->channels, w->image, w->patch, s));
-        else IISAN_TRY(launch_vit_im2col(dt, img, img_u8, b.F1, mc, w->channels, w->image, w->patch, s));
+        // per-channel statistics of a uint8 source (mean | std are adjacent in the struct); all zero: the reference's transform, the launch as it was
+        bool nz = false;
+        for (int c = 0; c < 3; ++c) nz = nz || w->norm_mean[c] != 0.f || w->norm_std[c] != 0.f;
+        const float norm6[6] = {w->norm_mean[0], w->norm_mean[1], w->norm_mean[2], w->norm_std[0], w->norm_std[1], w->norm_std[2]};
+        const float* norm = nz && img_u8 ? norm6 : nullptr;
+        if (index) IISAN_TRY(launch_vit_im2col_indexed(dt, (const uint8_t*)img, rows, index, b.F1, mc, w->channels, w->image, w->patch, s, norm));
+        else IISAN_TRY(launch_vit_im2col(dt, img, img_u8, b.F1, mc, w->channels, w->image, w->patch, s, norm));
         // patch embedding: resid32 = fp32 token rows with the position embedding added (128x128 kernel); mixed = 16-bit rows on the
         // production GEMM (gemm16_h256, 0.40 against 0.59 ms at bs = 128), the position table is added by block 0's open step
         Product pe = patch(!mixed, pd, D, mc * P, P);
@@ -363,9 +372,14 @@ struct VitChunk : Chunk {
         // CLS rows: cls + pos[0] — into the fp32 stream (token-major) or into the compact fp32 CLS stream
         return launch_vit_cls_rows(mixed ? b.Xc : b.X, w->cls_token, w->pos_emb, mc, mixed ? 1 : T, D, s);
     }
+    // CLIP, a call that taps hidden state 0 alone (no block runs, so no open step): block 0's open step all the same — the kernel every
+    // other call gets hidden state 0 from, so that tap 0 has the same bits whichever taps are asked for
+    int pre_ln_only() const { return mixed ? open_image(0) : open_resid32(0); }
     // ---- VS_RESID32 ------------------------------------------------------------------------------------------------------------
     int open_resid32(int l) const {     // x += dO + dF of block l - 1 ; h = LN1(x)
         const iisan_layer_weights& L = layer(l);
+        // (CLIP under the dev switch: the pre-LayerNorm in place, a launch of its own — the one-pass opening kernel is the mixed stream's)
+        if (l == 0 && w->pre_ln_w) IISAN_TRY(launch_layernorm768(dt, b.X, w->pre_ln_w, w->pre_ln_b, eps, nullptr, b.X, tok, D, s));
         if (l == 0) return launch_add2_layernorm768(dt, b.X, nullptr, nullptr, L.ln1_w, L.ln1_b, eps, nullptr, b.H, nullptr, tok, D, s);
         return launch_add2_layernorm768(dt, b.X, b.D16, b.D16b, L.ln1_w, L.ln1_b, eps, b.X, b.H, nullptr, tok, D, s);
     }
@@ -376,6 +390,8 @@ struct VitChunk : Chunk {
     // ---- VS_IMAGE ----------------------------------------------------------------------------------------------------------------
     int open_image(int l) const {
         const iisan_layer_weights& L = layer(l);
+        if (l == 0 && w->pre_ln_w)      // CLIP: ... -> pre-LayerNorm -> stream (fp16 rows, fp32 CLS rows: hidden state 0) + LN image, one launch
+            return launch_clip_open(dt, w->pos_emb, b.X16, b.Xc, b.D16b, w->pre_ln_w, w->pre_ln_b, L.ln1_w, L.ln1_b, eps, b.H, mc, T, D, s);
         if (l == 0)     // position table + 16-bit patch embedding -> fp16 stream of the patch rows (the CLS rows are in Xc already) + LN image
             return launch_layernorm768_mixed(dt, MX_SRC32 | MX_POSROW | MX_D1 | MX_RESV | MX_LN, w->pos_emb, b.X16, b.Xc, b.D16b, nullptr, L.ln1_w, L.ln1_b, eps, b.H, mc, T, D, s);
         return launch_layernorm768_mixed(dt, MX_D1 | MX_D2 | MX_RESV | MX_LN, nullptr, b.X16, b.Xc, b.D16, b.D16b, L.ln1_w, L.ln1_b, eps, b.H, mc, T, D, s);
@@ -479,10 +495,14 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
     const bool full_blocks = g_full_blocks || w->full_blocks;
     // Blocks after the deepest tapped hidden state are dead code (Versa configurations tap a prefix of the tower)
     const int live = full_blocks ? w->layers : max_tap(tap_layers, n_taps);
-    Products p{w->dtype16, D, w->mlp, T, w->heads};
+    // a CLIP tower: a LayerNorm in front of block 0 and / or quick-GELU in the MLP
+    IISAN_CHECK_SHAPE(!w->pre_ln_w == !w->pre_ln_b, "vit: pre_ln_w and pre_ln_b come together (one of them is null)");
+    IISAN_CHECK_SHAPE(w->act == 0 || w->act == 1, "vit: activation %d is neither erf-GELU (0) nor quick-GELU (1)", w->act);
+    const bool pre = w->pre_ln_w != nullptr;
+    Products p{w->dtype16, D, w->mlp, T, w->heads, w->act};
     // 80-wide heads: the last live block has no CLS-only form and runs on every token (1 / 32 of a ViT-H)
     const bool all_tokens = full_blocks || p.hd80();
-    const VitPlan plan = vit_plan(p, live, all_tokens, w->folded != nullptr, c);
+    const VitPlan plan = vit_plan(p, live, all_tokens, w->folded != nullptr, c, vit_is_clip(w));
     const auto& step = VIT_STEPS[plan.st];
     if (plan.folds) IISAN_TRY(vit_fold_all(w, live, full_blocks, (char*)b.Wf, b.Bf, s));
     const int64_t img_elems = (int64_t)w->channels * w->image * w->image;
@@ -491,12 +511,14 @@ static int vit_forward_taps_impl(const iisan_vit_weights* w, const void* images,
         const VitChunk ch{{p, b, s, w->eps, plan.st != VS_RESID32, m0, mc, mc * T, taps + m0 * n_taps * D, n_taps}, w};
         if (index) IISAN_TRY(ch.embed(images, 1, index + m0, rows));
         else IISAN_TRY(ch.embed(img_u8 ? (const void*)((const uint8_t*)images + m0 * img_elems) : (const void*)((const float*)images + m0 * img_elems), img_u8));
+        // hidden state 0: the embeddings — or, with a pre-LayerNorm, its output, which block 0's open step leaves in the stream
         int k = tap_index(tap_layers, n_taps, 0);
-        if (k >= 0) IISAN_TRY(ch.tap(k));
+        if (k >= 0 && pre && live == 0) IISAN_TRY(ch.pre_ln_only());
+        if (k >= 0 && !(pre && live > 0)) IISAN_TRY(ch.tap(k));
         for (int l = 0; l < live; ++l) {
             IISAN_TRY((ch.*step.open)(l));       // -> the stream is hidden state l
             k = tap_index(tap_layers, n_taps, l);
-            if (k >= 0 && l > 0) IISAN_TRY(ch.tap(k));
+            if (k >= 0 && (l > 0 || pre)) IISAN_TRY(ch.tap(k));
             if (l + 1 < live || all_tokens) IISAN_TRY(ch.full_block(l, step.mid));
             else IISAN_TRY(ch.cls_block(l, tap_index(tap_layers, n_taps, live)));
         }
@@ -640,7 +662,7 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
         iisan_set_error("bert_forward_taps: workspace too small (%zu < %zu)", ws_bytes, cv.off);
         return IISAN_EWORKSPACE;
     }
-    Products p{w->dtype16, D, w->mlp, T, w->heads};
+    Products p{w->dtype16, D, w->mlp, T, w->heads, 0};
     const BertPlan plan = bert_plan(p, c);
     const bool full_blocks = g_full_blocks || w->full_blocks;
     const int live = full_blocks ? w->layers : max_tap(tap_layers, n_taps);     // see the ViT executor
@@ -694,18 +716,20 @@ extern "C" int iisan_bert_forward_taps_dropout(const iisan_bert_weights* w, cons
 // refusals that depend on these inputs, then vit_plan / bert_plan themselves.  `layers` is the shortest tower that has the tap.
 extern "C" int32_t iisan_encoder_plan(int32_t tower, int32_t dtype16, int32_t hidden, int32_t heads, int32_t mlp, int32_t tokens, int64_t M,
                                       int64_t chunk_items, int32_t deepest_tap, int32_t full_blocks, int32_t folded) {
-    IISAN_CHECK_SHAPE(tower == IISAN_TOWER_VIT || tower == IISAN_TOWER_BERT, "encoder_plan: tower %d is neither ViT (0) nor BERT (1)", tower);
+    IISAN_CHECK_SHAPE(tower == IISAN_TOWER_VIT || tower == IISAN_TOWER_BERT || tower == IISAN_TOWER_CLIP,
+                      "encoder_plan: tower %d is neither ViT (0) nor BERT (1) nor CLIP (2)", tower);
+    const bool clip = tower == IISAN_TOWER_CLIP;
     IISAN_CHECK_SHAPE(M > 0, "encoder_plan: M must be positive");
     const int layers = deepest_tap > 1 ? deepest_tap : 1;
-    IISAN_TRY(check_common(tower == IISAN_TOWER_VIT, hidden, layers, heads, mlp, 1, &deepest_tap));
-    IISAN_TRY(tower == IISAN_TOWER_VIT ? vit_check_tokens(tokens) : bert_check_words(tokens, tokens));
+    IISAN_TRY(check_common(tower != IISAN_TOWER_BERT, hidden, layers, heads, mlp, 1, &deepest_tap));
+    IISAN_TRY(tower != IISAN_TOWER_BERT ? vit_check_tokens(tokens) : bert_check_words(tokens, tokens));
     const bool full = g_full_blocks || full_blocks;
     const Chunks c(M, chunk_items);
-    Products p{dtype16, hidden, mlp, tokens, heads};
+    Products p{dtype16, hidden, mlp, tokens, heads, clip ? 1 : 0};
     if (tower == IISAN_TOWER_BERT) {
         const BertPlan plan = bert_plan(p, c);
         return (plan.mixed ? 1 : 0) | (plan.alias ? 2 : 0) | (p.f1blk ? 4 : 0);
     }
-    const VitPlan plan = vit_plan(p, full ? layers : deepest_tap, full || p.hd80(), folded != 0, c);
+    const VitPlan plan = vit_plan(p, full ? layers : deepest_tap, full || p.hd80(), folded != 0, c, clip);
     return (int32_t)plan.st | (p.f1blk ? 4 : 0) | (p.xblk ? 8 : 0) | (plan.folds ? 16 : 0) | (p.hd80() ? 32 : 0);
 }

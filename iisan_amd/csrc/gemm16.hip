@@ -179,10 +179,10 @@ __global__ __launch_bounds__(256, 2) void gemm16_kernel(Gemm16Args p) {
                     v[4 + r] += b1[r];
                 }
             }
-            if constexpr (EPI == EPI_OUT16 || EPI == EPI_GELU16 || EPI == EPI_QKVH16 || EPI == EPI_PATCH16) {
+            if constexpr (EPI == EPI_OUT16 || EPI == EPI_GELU16 || EPI == EPI_QGELU16 || EPI == EPI_QKVH16 || EPI == EPI_PATCH16) {
                 V8 o;
 #pragma unroll
-                for (int r = 0; r < 8; ++r) o[r] = T::from_f32(EPI == EPI_GELU16 ? gelu_erf_fast(v[r]) : v[r]);
+                for (int r = 0; r < 8; ++r) o[r] = T::from_f32(EPI == EPI_GELU16 ? gelu_erf_fast(v[r]) : EPI == EPI_QGELU16 ? quick_gelu(v[r]) : v[r]);
                 if constexpr (EPI == EPI_QKVH16) {
                     const int Dm = p.qkv_heads * 64;
                     const int64_t item = m / p.qkv_S;
@@ -224,7 +224,7 @@ int launch_t(int mode, const Gemm16Args& a, hipStream_t s) {
         else hipLaunchKernelGGL((gemm16_kernel<T, E>), grid, block, 0, s, a);                                                  \
         break
     switch (mode) {
-        V1_CASE(EPI_OUT16); V1_CASE(EPI_GELU16); V1_CASE(EPI_RESID32); V1_CASE(EPI_PATCH32); V1_CASE(EPI_QKVH16); V1_CASE(EPI_PATCH16);
+        V1_CASE(EPI_OUT16); V1_CASE(EPI_GELU16); V1_CASE(EPI_RESID32); V1_CASE(EPI_PATCH32); V1_CASE(EPI_QKVH16); V1_CASE(EPI_PATCH16); V1_CASE(EPI_QGELU16);
         default: iisan_set_error("gemm16: bad epilogue mode %d", mode); return IISAN_EBADSHAPE;
     }
 #undef V1_CASE
@@ -293,7 +293,7 @@ static int reject(const char* what, int mode, const Gemm16Args& a) {
 }
 
 int gemm16_route(int dtype16, int mode, const Gemm16Args& a) {
-    if (mode < EPI_OUT16 || mode > EPI_STREAM16 || mode == EPI_F32) return reject("bad epilogue mode", mode, a);     // (EPI_F32: launch_gemm16_f32)
+    if (mode < EPI_OUT16 || mode > EPI_QGELU16 || mode == EPI_F32) return reject("bad epilogue mode", mode, a);     // (EPI_F32: launch_gemm16_f32)
     if (!(a.M > 0 && a.N > 0 && a.K > 0)) return reject("empty problem", mode, a);
     // N % 128 == 64 below RAG_N_END: a ragged last column tile, on the 128x128 kernel alone (both 256x256 kernels turn down N % 256 != 0) — the
     // 192- and 576-column products of a 192-wide tower.  From 768 columns on every supported width is a multiple of 128 and a ragged N is refused
@@ -319,7 +319,7 @@ int gemm16_route(int dtype16, int mode, const Gemm16Args& a) {
     if ((a.a_blk32 || a.out_blk32) && !h256) return reject("block-major (blk32) operands run on gemm16_h256 only, FC1 output / FC2 A operand", mode, a);
     if (h256) return G16_H256;
     // the staggered kernel without the half-slot boundary: variant 3 (the race-screen reference of gemm16_h256) and the shapes
-    // gemm16_h256_applicable() turns down
+    // gemm16_h256_applicable() turns down (it has no EPI_QGELU16: under variant 3 that mode goes on to the 128x128 kernel)
     if (big && var != 4 && gemm16_s256_applicable(mode, a)) return G16_S256;
     // everything else — small shapes, the fp32 / residual epilogues — on the 128x128 kernel
     return G16_V1;
@@ -411,11 +411,11 @@ extern "C" int iisan_gemm16_lna(int32_t mode, const void* A, const void* W, cons
     return launch_gemm16(IISAN_F16, mode, a, (hipStream_t)stream);
 }
 
-// DEV-section entry of the block-major intermediates: the product of iisan_gemm16 (modes 0 / 1; rowstat != null: LayerNorm in the
+// DEV-section entry of the block-major intermediates: the product of iisan_gemm16 (modes 0 / 1 / 8; rowstat != null: LayerNorm in the
 // epilogue, fp16) with the two layout flags
 extern "C" int iisan_gemm16_blk32(int32_t dtype16, int32_t mode, const void* A, const void* W, const float* bias, void* out,
                                   const float* rowstat, int64_t M, int32_t N, int32_t K, int32_t a_blk32, int32_t out_blk32, void* stream) {
-    IISAN_CHECK_SHAPE(mode == EPI_OUT16 || mode == EPI_GELU16, "iisan_gemm16_blk32: mode must be 0 or 1");
+    IISAN_CHECK_SHAPE(mode == EPI_OUT16 || mode == EPI_GELU16 || mode == EPI_QGELU16, "iisan_gemm16_blk32: mode must be 0, 1 or 8");
     Gemm16Args a = natural_args(M, N, K, a_blk32, out_blk32);
     a.A = A; a.W = W; a.bias = bias; a.out = out; a.rowstat = rowstat;
     return launch_gemm16(dtype16, mode, a, (hipStream_t)stream);
@@ -430,7 +430,7 @@ extern "C" int iisan_fold_ln_weights(const void* W, int32_t w32, const float* bi
 
 extern "C" int iisan_gemm16(int32_t dtype16, int32_t mode, const void* A, const void* W, const float* bias, void* out,
                             const float* resid, int64_t M, int32_t N, int32_t K, void* stream) {
-    IISAN_CHECK_SHAPE(mode >= 0 && mode <= 2, "iisan_gemm16: mode must be 0, 1 or 2");
+    IISAN_CHECK_SHAPE((mode >= 0 && mode <= 2) || mode == EPI_QGELU16, "iisan_gemm16: mode must be 0, 1, 2 or 8");
     Gemm16Args a = natural_args(M, N, K, 0, 0);
     a.A = A; a.W = W; a.bias = bias; a.out = out; a.resid = resid;
     return launch_gemm16(dtype16, mode, a, (hipStream_t)stream);
@@ -440,7 +440,7 @@ extern "C" int iisan_gemm16(int32_t dtype16, int32_t mode, const void* A, const 
 // asks whether the row stride of the operands (1536 B at K = 768) costs L2 channel parallelism.
 extern "C" int iisan_gemm16_ld(int32_t dtype16, int32_t mode, const void* A, const void* W, const float* bias, void* out,
                                int64_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldo, void* stream) {
-    IISAN_CHECK_SHAPE(mode >= 0 && mode <= 1, "iisan_gemm16_ld: mode must be 0 or 1");
+    IISAN_CHECK_SHAPE((mode >= 0 && mode <= 1) || mode == EPI_QGELU16, "iisan_gemm16_ld: mode must be 0, 1 or 8");
     Gemm16Args a{};
     a.A = A; a.W = W; a.bias = bias; a.out = out;
     a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldo = ldo;

@@ -87,7 +87,7 @@ template <typename T, int EPI, bool LNA, int BLK>
 __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int tiles_m, int tiles_n, uint32_t qkv_magic) {
     typedef typename T::v8 V8;
     constexpr bool A_BLK = (BLK & BLK_A) != 0, OUT_BLK = (BLK & BLK_OUT) != 0;
-    static_assert(!OUT_BLK || EPI == EPI_GELU16 || EPI == EPI_STREAM16, "block-major output: F1 (FC1 epilogue) and the ViT stream only");
+    static_assert(!OUT_BLK || EPI == EPI_GELU16 || EPI == EPI_QGELU16 || EPI == EPI_STREAM16, "block-major output: F1 (FC1 epilogue) and the ViT stream only");
     static_assert(!A_BLK || EPI != EPI_PATCH16, "block-major A operand: F1 and the ViT stream only");
     constexpr int A_KSTEP_BYTES = A_BLK ? 4096 : SBK * 2;      // bytes between two K-steps of a 32-row run of A
     // Ablation / experiment bits (Gemm16Args::debug, set through the dev switch gemm16_variant = 4 | bits << 8; tools/gemm_walk.py, gemm_stream.py):
@@ -500,6 +500,7 @@ __global__ __launch_bounds__(512, 2) void gemm16_h256_kernel(Gemm16Args p, int t
                     // (four pairs at a time: the eight-pair form needs 48 temporaries on top of the fragments that stay live
                     //  across this slot, and spilled)
                     if constexpr (EPI == EPI_GELU16) { gelu_erf_fast2xN<4>(g); gelu_erf_fast2xN<4>(g + 4); }
+                    if constexpr (EPI == EPI_QGELU16) { quick_gelu2xN<4>(g); quick_gelu2xN<4>(g + 4); }
 #pragma unroll
                     for (int e = 0; e < 8; e += 2) {
                         o0[e] = T::from_f32(g[e / 2][0]); o0[e + 1] = T::from_f32(g[e / 2][1]);
@@ -743,6 +744,9 @@ int launch_epi(const Gemm16Args& a, hipStream_t s) {
     return IISAN_OK;
 }
 
+#ifdef GEMM16_H256_KERNEL_ONLY      // gemm16_h256_qgelu.hip: the kernel template and launch_epi alone, for the instantiations it owns
+}  // namespace
+#else
 template <typename T>
 int launch_t(int mode, const Gemm16Args& a, hipStream_t s) {
     // block-major operands (gemm16_h256_applicable has turned every other combination down): F1 — FC1 writes, FC2 reads — and the ViT
@@ -751,6 +755,7 @@ int launch_t(int mode, const Gemm16Args& a, hipStream_t s) {
         constexpr bool f16 = std::is_same<T, F16>::value;
         const bool ab = a.a_blk32, ob = a.out_blk32;
         if (mode == EPI_GELU16 && ob && !a.rowstat && !ab) return launch_epi<T, EPI_GELU16, false, BLK_OUT>(a, s);
+        if (mode == EPI_QGELU16 && ob && !a.rowstat && !ab) return launch_gemm16_h256_qgelu(std::is_same<T, BF16>::value ? IISAN_BF16 : IISAN_F16, a, s);
         if (mode == EPI_OUT16 && ab && !ob && !a.rowstat) return launch_epi<T, EPI_OUT16, false, BLK_A>(a, s);
         if constexpr (f16) {
             if (mode == EPI_GELU16 && ob && a.rowstat)
@@ -775,6 +780,8 @@ int launch_t(int mode, const Gemm16Args& a, hipStream_t s) {
     switch (mode) {
         case EPI_OUT16: return launch_epi<T, EPI_OUT16>(a, s);
         case EPI_GELU16: return launch_epi<T, EPI_GELU16>(a, s);
+        // (the quick-GELU instantiations are compiled in gemm16_h256_qgelu.hip: this file's code object holds what it held before the mode)
+        case EPI_QGELU16: return launch_gemm16_h256_qgelu(std::is_same<T, BF16>::value ? IISAN_BF16 : IISAN_F16, a, s);
         case EPI_QKVH16: return launch_epi<T, EPI_QKVH16>(a, s);
         case EPI_PATCH16: return launch_epi<T, EPI_PATCH16>(a, s);
         case EPI_STREAM16:
@@ -787,7 +794,7 @@ int launch_t(int mode, const Gemm16Args& a, hipStream_t s) {
 }  // namespace
 
 bool gemm16_h256_applicable(int mode, const Gemm16Args& a) {
-    if (!((mode == EPI_OUT16 || mode == EPI_GELU16 || mode == EPI_QKVH16 || mode == EPI_PATCH16 || mode == EPI_STREAM16) && a.N % SBN == 0 && a.N * 4 <= STG_BIAS_BYTES && a.K % SBK == 0 &&
+    if (!((mode == EPI_OUT16 || mode == EPI_GELU16 || mode == EPI_QGELU16 || mode == EPI_QKVH16 || mode == EPI_PATCH16 || mode == EPI_STREAM16) && a.N % SBN == 0 && a.N * 4 <= STG_BIAS_BYTES && a.K % SBK == 0 &&
           a.K / SBK >= 2 && (int64_t)a.lda * 2 * SBM < (1ll << 31) && (int64_t)a.ldw * 2 * SBN < (1ll << 31)))
         return false;
     if (a.rowstat && !((mode == EPI_QKVH16 || mode == EPI_GELU16) && a.N <= LNA_MAX_N)) return false;
@@ -795,7 +802,7 @@ bool gemm16_h256_applicable(int mode, const Gemm16Args& a) {
     // epilogue writes them, the A-operand loader of the FC2 products reads them
     // (exactly the combinations launch_t instantiates: out — F1 from FC1, the stream from O / FC2; A — F1 into FC2, the stream into the
     //  QKV / FC1 products with LayerNorm in the epilogue, FC1 then writing F1 block-major as well)
-    if (a.out_blk32 && !((mode == EPI_GELU16 || mode == EPI_STREAM16) && a.ldo == a.N)) return false;
+    if (a.out_blk32 && !((mode == EPI_GELU16 || mode == EPI_QGELU16 || mode == EPI_STREAM16) && a.ldo == a.N)) return false;
     if (a.a_blk32 && !(a.lda == a.K && (a.rowstat ? (mode == EPI_QKVH16 && !a.out_blk32) || (mode == EPI_GELU16 && a.out_blk32)
                                                   : (mode == EPI_OUT16 || mode == EPI_STREAM16)))) return false;
     const int64_t rows = ceil_div(a.M, SBM) * SBM;
@@ -833,3 +840,4 @@ extern "C" int32_t iisan_gemm16_h256_applicable_blk32(int32_t mode, int64_t M, i
     a.a_blk32 = a_blk32 != 0; a.out_blk32 = out_blk32 != 0;
     return gemm16_h256_applicable(mode, a) ? 1 : 0;
 }
+#endif  // GEMM16_H256_KERNEL_ONLY

@@ -279,6 +279,118 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
     }
 }
 
+// ---- the opening step of a CLIP vision tower: embeddings -> pre-LayerNorm -> stream, and block 0's LN1 image, in one pass -------------
+// x0 = LN_pre(v),  v = pos[tok] + patch embedding (16-bit, `patch16`: the EPI_PATCH16 product) — or, on a CLS row, cls + pos[0], which
+// vit_cls_rows_kernel has left in xc.  x0 is hidden state 0 (`hidden_states[0]` of HF's CLIPVisionTransformer is the output of
+// pre_layrnorm) and becomes the mixed residual stream exactly as layernorm768_mixed_kernel writes it: fp32 in xc for the CLS rows (tap 0
+// is a copy of it), fp16 in x16 for the others.  The same lanes then normalise x0 — the fp32 values in their registers, not the rounded
+// stream, as every LN1 of the image route does — with block 0's ln1 and write the 16-bit image `out16`.  Row layout, workgroup shape and
+// reductions are those of the mixed kernel (half a wave per row from 768 on); four reductions per row instead of two, one read of the
+// row, no second launch.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void clip_open_kernel(const float* __restrict__ pos, _Float16* __restrict__ x16, float* xc,
+                                                        const typename T::elem* __restrict__ patch16,
+                                                        const float* __restrict__ pg, const float* __restrict__ pb,
+                                                        const float* __restrict__ g, const float* __restrict__ b, float eps,
+                                                        typename T::elem* __restrict__ out16, int64_t items, int Ttok) {
+    constexpr int NP = row_np(D, 8, 32), LPR = row_lpr(D, 8, 32), PW = LPR * 8, TPW = 256 / LPR, TSH = ilog2(TPW);
+    static_assert(row_width_ok(D, 8, 32), "row width: LPR * NP * 8 with LPR a power of two, at most 1280 (the row lives in registers)");
+    typedef typename T::v8 V8;
+    const int lane = threadIdx.x & (LPR - 1), half = threadIdx.x / LPR;
+    const int bpi = (Ttok + TPW - 1) >> TSH;          // a workgroup = TPW consecutive tokens of ONE item, as in the mixed kernel
+    const int64_t item = blockIdx.x / bpi;
+    const int tok = (int)(blockIdx.x - item * bpi) * TPW + half;
+    if (item >= items || tok >= Ttok) return;
+    const int64_t row = item * Ttok + tok;
+    const bool cls = tok == 0;                        // uniform within the LPR lanes of a row
+    float v[NP][8];
+    if (cls) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const f4 a = *(const f4*)(xc + item * D + i * PW + lane * 8), c = *(const f4*)(xc + item * D + i * PW + lane * 8 + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[i][e] = a[e]; v[i][4 + e] = c[e]; }
+        }
+    } else {
+        V8 d1[NP];
+#pragma unroll
+        for (int i = 0; i < NP; ++i) d1[i] = __builtin_nontemporal_load((const V8*)(patch16 + row * D + i * PW + lane * 8));
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const f4 a = *(const f4*)(pos + (int64_t)tok * D + i * PW + lane * 8), c = *(const f4*)(pos + (int64_t)tok * D + i * PW + lane * 8 + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[i][e] = a[e] + T::to_f32(d1[i][e]); v[i][4 + e] = c[e] + T::to_f32(d1[i][4 + e]); }
+        }
+    }
+    auto sum = [](float t) {            // over the LPR lanes of the row
+#pragma unroll
+        for (int o = LPR / 2; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        return t;
+    };
+    // v <- LayerNorm(v; gamma, beta) in place: two-pass mean / centred variance in registers, like every row kernel here
+    auto normalise = [&](const float* __restrict__ gamma, const float* __restrict__ beta) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s += v[i][e];
+        const float mean = sum(s) * (1.0f / (float)D);
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float d = v[i][e] - mean;
+                q += d * d;
+            }
+        const float rstd = rsqrtf(sum(q) * (1.0f / (float)D) + eps);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int c = i * PW + lane * 8;
+            const f4 g0 = *(const f4*)(gamma + c), g1 = *(const f4*)(gamma + c + 4), b0 = *(const f4*)(beta + c), b1 = *(const f4*)(beta + c + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[i][e] = (v[i][e] - mean) * rstd * g0[e] + b0[e];
+                v[i][4 + e] = (v[i][4 + e] - mean) * rstd * g1[e] + b1[e];
+            }
+        }
+    };
+    normalise(pg, pb);                  // x0
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int c = i * PW + lane * 8;
+        if (cls) {
+            *(f4*)(xc + item * D + c) = (f4){v[i][0], v[i][1], v[i][2], v[i][3]};
+            *(f4*)(xc + item * D + c + 4) = (f4){v[i][4], v[i][5], v[i][6], v[i][7]};
+        } else {
+            h8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (_Float16)v[i][e];
+            __builtin_nontemporal_store(o, (h8*)(x16 + row * D + c));
+        }
+    }
+    normalise(g, b);                    // LN1(x0) of block 0
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        V8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = T::from_f32(v[i][e]);
+        *(V8*)(out16 + row * D + i * PW + lane * 8) = o;
+    }
+}
+
+// per-channel normalisation of the uint8 sources of the patch extraction below: none (the reference's (.5, .5) transform, the code as it
+// was) or (p / 255 - mean[c]) / std[c] for 3 channels (a pretrained CLIP's own statistics; iisan_vit_weights::norm_mean / norm_std)
+struct PixNormNone { static constexpr bool on = false; };
+struct PixNorm {
+    static constexpr bool on = true;
+    float mean[3], std[3];
+    __device__ __forceinline__ float operator()(float u, int c) const {
+        const float mu = c == 0 ? mean[0] : c == 1 ? mean[1] : mean[2], sd = c == 0 ? std[0] : c == 1 ? std[1] : std[2];
+        return __fdiv_rn(__fdiv_rn(u, 255.0f) - mu, sd);
+    }
+};
+
 // ---- ViT patch extraction: images fp32 [M,C,R,R] -> patch matrix 16-bit [M*P, C*p*p], col = c*p*p + iy*p + ix ----
 // one thread = 8 consecutive ix (two float4 reads, one 16-byte store)
 // SRC = float: already normalised pixels; SRC = uint8_t: raw pixels, normalised here exactly as the reference's
@@ -287,10 +399,12 @@ __global__ __launch_bounds__(256) void layernorm768_mixed_kernel(const float* __
 // IDX (uint8 only): `img` is a resident catalogue [rows, C, R, R] and item m reads row index[m]; any value outside [0, rows) is a
 // padding slot — never dereferenced, its fragment is the all-zero NORMALISED image the reference ships for pad slots
 // (`Code_Uncached/data_utils/dataset.py:73`; no uint8 pixel normalises to 0).  The plain instantiations compile as before.
-template <typename T, typename SRC, bool IDX = false>
+// NRM (uint8 only; PixNorm above): per-channel statistics in place of (.5, .5).  The default PixNormNone is empty and its one use sits
+// under `if constexpr (NRM::on)`, like the keep functor of the row kernels.
+template <typename T, typename SRC, bool IDX = false, typename NRM = PixNormNone>
 __global__ __launch_bounds__(256) void vit_im2col_kernel(const SRC* __restrict__ img, typename T::elem* __restrict__ out,
                                                          int64_t M, int C, int R, int p,
-                                                         const int64_t* __restrict__ index = nullptr, int64_t rows = 0) {
+                                                         const int64_t* __restrict__ index = nullptr, int64_t rows = 0, NRM nrm = NRM()) {
     const int per_row = C * p * p / 8;        // threads per patch row
     const int gp = R / p;                      // patches per image side
     const int64_t total = M * gp * gp * per_row;
@@ -321,8 +435,13 @@ __global__ __launch_bounds__(256) void vit_im2col_kernel(const SRC* __restrict__
             const U8 u = *(const U8*)src;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                a[e] = __fdiv_rn(__fdiv_rn((float)u[e], 255.0f) - 0.5f, 0.5f);
-                b2[e] = __fdiv_rn(__fdiv_rn((float)u[4 + e], 255.0f) - 0.5f, 0.5f);
+                if constexpr (NRM::on) {
+                    a[e] = nrm((float)u[e], c);
+                    b2[e] = nrm((float)u[4 + e], c);
+                } else {
+                    a[e] = __fdiv_rn(__fdiv_rn((float)u[e], 255.0f) - 0.5f, 0.5f);
+                    b2[e] = __fdiv_rn(__fdiv_rn((float)u[4 + e], 255.0f) - 0.5f, 0.5f);
+                }
             }
         }
         typename T::v8 o;
@@ -339,10 +458,10 @@ __global__ __launch_bounds__(256) void vit_im2col_kernel(const SRC* __restrict__
 // multiple of 64 (640), as the packed patch weight is, so the patch-embedding product keeps K % 64 == 0.  One thread = 8 consecutive
 // columns of the padded row (one 16-byte store), each read on its own: a run of 8 columns crosses pixel rows of 14.  The arithmetic per pixel
 // — the two __fdiv_rn of the uint8 source, the zero fragment of an indexed pad slot — is that of the kernel above.
-template <typename T, typename SRC, bool IDX = false>
+template <typename T, typename SRC, bool IDX = false, typename NRM = PixNormNone>
 __global__ __launch_bounds__(256) void vit_im2col_pad_kernel(const SRC* __restrict__ img, typename T::elem* __restrict__ out,
                                                              int64_t M, int C, int R, int p, int ldp,
-                                                             const int64_t* __restrict__ index = nullptr, int64_t rows = 0) {
+                                                             const int64_t* __restrict__ index = nullptr, int64_t rows = 0, NRM nrm = NRM()) {
     const int pd = C * p * p, per_row = ldp / 8;
     const int gp = R / p;
     const int64_t total = M * gp * gp * per_row;
@@ -367,6 +486,7 @@ __global__ __launch_bounds__(256) void vit_im2col_pad_kernel(const SRC* __restri
                 const int c = col / (p * p), rem = col % (p * p), iy = rem / p, ix = rem % p;
                 const SRC v = img[((sm * C + c) * R + (py * p + iy)) * (int64_t)R + px * p + ix];
                 if constexpr (sizeof(SRC) == 4) a = v;
+                else if constexpr (NRM::on) a = nrm((float)v, c);
                 else a = __fdiv_rn(__fdiv_rn((float)v, 255.0f) - 0.5f, 0.5f);
             }
             o[e] = T::from_f32(a);
@@ -628,6 +748,27 @@ int launch_layernorm768_mixed(int dtype16, int V, const float* x32, void* x16, f
     return IISAN_EBADSHAPE;
 }
 
+// the opening step of a CLIP tower (clip_open_kernel): every instantiated width, both operand types
+int launch_clip_open(int dtype16, const float* pos, void* x16, float* xc, const void* patch16, const float* pre_g, const float* pre_b,
+                     const float* g, const float* b, float eps, void* out16, int64_t items, int Ttok, int width, hipStream_t s) {
+    IISAN_CHECK_SHAPE(row_width_instantiated(width), "clip_open: " ROW_WIDTH_MSG, width);
+    IISAN_CHECK_SHAPE(pre_g && pre_b && g && b, "clip_open: null LayerNorm weights");
+    if (items <= 0) return IISAN_OK;
+    const int tpw = 256 / row_lpr(width, 8, 32);
+    const int64_t blocks = items * ((Ttok + tpw - 1) / tpw);
+    IISAN_CHECK_SHAPE(blocks < (1ll << 31), "clip_open: grid too large");
+    dim3 grid((unsigned)blocks), block(256);
+#define CLIP_OPEN_AT(W, A)                                                                                                     \
+    if (dtype16 == IISAN_BF16)                                                                                                 \
+        hipLaunchKernelGGL((clip_open_kernel<BF16, W>), grid, block, 0, s, pos, (_Float16*)x16, xc, (const __bf16*)patch16, pre_g, pre_b, g, b, eps, (__bf16*)out16, items, Ttok); \
+    else                                                                                                                       \
+        hipLaunchKernelGGL((clip_open_kernel<F16, W>), grid, block, 0, s, pos, (_Float16*)x16, xc, (const _Float16*)patch16, pre_g, pre_b, g, b, eps, (_Float16*)out16, items, Ttok)
+    ROW_WIDTH_SWITCH(width, CLIP_OPEN_AT, 0)
+#undef CLIP_OPEN_AT
+    IISAN_LAUNCH_OK();
+    return IISAN_OK;
+}
+
 int launch_add_layernorm768(int dtype16, const float* x, const void* delta16, const float* g, const float* b, float eps,
                             float* sum32, void* out16, float* out32, int64_t rows, int width, hipStream_t s, const RowKeep* keep) {
     return launch_add2_layernorm768(dtype16, x, delta16, nullptr, g, b, eps, sum32, out16, out32, rows, width, s, keep);
@@ -642,7 +783,31 @@ int launch_layernorm768(int dtype16, const float* x, const float* g, const float
 // patch side is no multiple of 8
 int vit_patch_ld(int C, int p) { return p % 8 == 0 ? C * p * p : (int)ceil_div(C * p * p, 64) * 64; }
 
-int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64_t M, int C, int R, int p, hipStream_t s) {
+// The uint8 patch extraction with per-channel statistics (norm = mean[3] | std[3], host): direct (index == null) or indexed
+static int vit_im2col_norm(int dtype16, const uint8_t* img, int64_t rows, const int64_t* index, void* out, int64_t M, int C, int R, int p,
+                           const float* norm, hipStream_t s) {
+    IISAN_CHECK_SHAPE(C == 3, "vit: per-channel normalisation statistics are given for 3 channels, the tower has %d", C);
+    IISAN_CHECK_SHAPE(norm[3] != 0.f && norm[4] != 0.f && norm[5] != 0.f, "vit: norm_std (%g, %g, %g) must be non-zero where norm_mean / norm_std are set",
+                      (double)norm[3], (double)norm[4], (double)norm[5]);
+    const PixNorm nrm{{norm[0], norm[1], norm[2]}, {norm[3], norm[4], norm[5]}};
+    const int ldp = vit_patch_ld(C, p);
+    const int64_t total = M * (R / p) * (R / p) * (ldp / 8);
+    const unsigned grid = (unsigned)(ceil_div(total, 256) < 262144 ? ceil_div(total, 256) : 262144);
+#define IM2COL_NORM(TT, EL, IDX)                                                                                               \
+    if (p % 8 != 0) hipLaunchKernelGGL((vit_im2col_pad_kernel<TT, uint8_t, IDX, PixNorm>), dim3(grid), dim3(256), 0, s, img, (EL*)out, M, C, R, p, ldp, index, rows, nrm); \
+    else hipLaunchKernelGGL((vit_im2col_kernel<TT, uint8_t, IDX, PixNorm>), dim3(grid), dim3(256), 0, s, img, (EL*)out, M, C, R, p, index, rows, nrm)
+    if (index) {
+        if (dtype16 == IISAN_BF16) { IM2COL_NORM(BF16, __bf16, true); } else { IM2COL_NORM(F16, _Float16, true); }
+    } else {
+        if (dtype16 == IISAN_BF16) { IM2COL_NORM(BF16, __bf16, false); } else { IM2COL_NORM(F16, _Float16, false); }
+    }
+#undef IM2COL_NORM
+    IISAN_LAUNCH_OK();
+    return IISAN_OK;
+}
+
+int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64_t M, int C, int R, int p, hipStream_t s, const float* norm) {
+    if (norm && img_u8) return vit_im2col_norm(dtype16, (const uint8_t*)img, 0, nullptr, out, M, C, R, p, norm, s);
     if (p % 8 != 0) {
         const int ldp = vit_patch_ld(C, p);
         const int64_t total = M * (R / p) * (R / p) * (ldp / 8);
@@ -679,7 +844,8 @@ int launch_vit_im2col(int dtype16, const void* img, int img_u8, void* out, int64
 }
 
 int launch_vit_im2col_indexed(int dtype16, const uint8_t* catalogue, int64_t rows, const int64_t* index, void* out, int64_t M, int C,
-                              int R, int p, hipStream_t s) {
+                              int R, int p, hipStream_t s, const float* norm) {
+    if (norm) return vit_im2col_norm(dtype16, catalogue, rows, index, out, M, C, R, p, norm, s);
     if (p % 8 != 0) {
         const int ldp = vit_patch_ld(C, p);
         const int64_t total = M * (R / p) * (R / p) * (ldp / 8);

@@ -105,8 +105,19 @@ class PackedVit(_PackedEncoder):
         s.image, s.patch, s.channels, s.dtype16, s.eps = cfg.image, cfg.patch, cfg.channels, dtype16, cfg.eps
         if cfg.patch_ld != cfg.patch_dim:      # patch 14: rows zero-padded like the patch matrix (include/iisan_hip.h)
             self._w = dict(w, patch_w=torch.nn.functional.pad(w["patch_w"].float(), (0, cfg.patch_ld - cfg.patch_dim)))
-        s.patch_w, s.patch_b = self._m16("patch_w"), self._v32("patch_b")
+        s.patch_w = self._m16("patch_w")
+        # a CLIP vision tower (`VitConfig.pre_ln / act / patch_bias`): no patch bias, the pre-LayerNorm, quick-GELU — never guessed from the
+        # dict: a config that asks for a tensor the weights lack, or weights with a tensor the config does not use, is an error
+        if cfg.patch_bias != ("patch_b" in w) or cfg.pre_ln != ("pre_ln_w" in w):
+            raise ValueError(f"PackedVit: the weights {'have' if 'patch_b' in w else 'lack'} patch_b and {'have' if 'pre_ln_w' in w else 'lack'} "
+                             f"pre_ln_w, the config says patch_bias={cfg.patch_bias}, pre_ln={cfg.pre_ln}")
+        s.patch_b = self._v32("patch_b") if cfg.patch_bias else None
         s.cls_token, s.pos_emb = self._v32("cls_token"), self._v32("pos_emb")
+        if cfg.pre_ln:
+            s.pre_ln_w, s.pre_ln_b = self._v32("pre_ln_w"), self._v32("pre_ln_b")
+        s.act = {"gelu": 0, "quick_gelu": 1}[cfg.act]
+        if cfg.norm_mean is not None:       # statistics of the uint8 entry points (all zero = the reference's (.5, .5))
+            s.norm_mean, s.norm_std = (C.c_float * 3)(*cfg.norm_mean), (C.c_float * 3)(*cfg.norm_std)
         # LayerNorm 1 / 2 folded into the QKV / FC1 weights once, here, instead of at the start of every forward call — where the
         # executor has that route (fp16 operands, hidden 768; 0 bytes otherwise: a 1024-wide or a narrow tower keeps no fp32 masters)
         lib = _lib.load()

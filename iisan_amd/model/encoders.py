@@ -1,4 +1,4 @@
-"""Encoders mirroring `Code_Uncached/model/encoders.py`: `MM_Encoder`, `Vit_Encoder`, `Bert_Encoder`,
+"""Encoders mirroring `Code_Uncached/model/encoders.py`: `MM_Encoder`, `Vit_Encoder`, `ClipVit_Encoder`, `Bert_Encoder`,
 `Text_Encoder`, `User_Encoder` — same constructors, attribute paths and state-dict keys.
 
 The frozen ViT/BERT are accepted as HuggingFace modules (`ViTForImageClassification`, `BertModel`, either
@@ -12,7 +12,7 @@ from torch.nn.init import constant_, xavier_normal_
 from .. import _lib, encoders as enc, ops, weights
 from .modules import TransformerEncoder
 
-__all__ = ["MM_Encoder", "Vit_Encoder", "Bert_Encoder", "Text_Encoder", "User_Encoder", "FrozenVit", "FrozenBert"]
+__all__ = ["MM_Encoder", "Vit_Encoder", "ClipVit_Encoder", "Bert_Encoder", "Text_Encoder", "User_Encoder", "FrozenVit", "FrozenBert"]
 
 
 class FrozenVit(nn.Module):
@@ -53,6 +53,24 @@ def _vit_canonical(image_net):
     return weights.vit_from_hf({k: v for k, v in image_net.state_dict().items() if not k.startswith("classifier")}), cfg
 
 
+def _clip_canonical(image_net):
+    """(canonical weights, config) of a CLIP vision tower: a `FrozenVit` on a CLIP config, or an HF `CLIPVisionModel` /
+    `CLIPVisionTransformer` (`clip_model.vision_model`, `Code_Uncached/run.py:47-48`) — either key prefix."""
+    if hasattr(image_net, "canonical_weights"):
+        w, cfg = image_net.canonical_weights()
+        if not cfg.pre_ln:
+            raise ValueError("ClipVit_Encoder: the FrozenVit container holds a plain ViT config (pre_ln = False); wrap it in Vit_Encoder")
+        return w, cfg
+    c = getattr(image_net.config, "vision_config", image_net.config)       # (a whole CLIPModel's config nests the tower's)
+    if c.hidden_act not in ("quick_gelu", "gelu"):
+        raise ValueError(f"ClipVit_Encoder: hidden_act {c.hidden_act!r} is neither 'quick_gelu' (OpenAI) nor 'gelu' (LAION)")
+    w = weights.clip_vit_from_hf({k: v for k, v in image_net.state_dict().items() if not k.startswith("classifier")})
+    cfg = weights.VitConfig(hidden=c.hidden_size, layers=c.num_hidden_layers, heads=c.num_attention_heads,
+                            mlp=c.intermediate_size, image=c.image_size, patch=c.patch_size, channels=c.num_channels,
+                            eps=c.layer_norm_eps, pre_ln=True, act=c.hidden_act, patch_bias="patch_b" in w)
+    return w, cfg
+
+
 def _bert_canonical(bert_model):
     if hasattr(bert_model, "canonical_weights"):
         return bert_model.canonical_weights()
@@ -81,13 +99,16 @@ class Vit_Encoder(nn.Module):                      # encoders.py:23-31
 
     def packed(self, device) -> enc.PackedVit:
         if self._packed is None or self._packed.device != torch.device(device):
-            w, cfg = _vit_canonical(self.image_net)
+            w, cfg = self._canonical()
             self._packed = enc.PackedVit(w, cfg, device, self.dtype16)
         return self._packed
 
+    def _canonical(self):
+        return _vit_canonical(self.image_net)
+
     @property
     def n_layers(self):
-        return _vit_canonical(self.image_net)[1].layers if self._packed is None else self._packed.cfg.layers
+        return self._canonical()[1].layers if self._packed is None else self._packed.cfg.layers
 
     def forward_taps(self, item_content, tap_layers):
         """CLS rows of the requested hidden states, [M, len(tap_layers), D] fp32 (no grad); D = the tower's hidden size (768 or 1024)."""
@@ -111,6 +132,33 @@ class Vit_Encoder(nn.Module):                      # encoders.py:23-31
         L = self.packed(item_content.device).cfg.layers
         taps = self.forward_taps(item_content, range(L + 1))
         return None, tuple(taps[:, l:l + 1] for l in range(L + 1))
+
+
+class ClipVit_Encoder(Vit_Encoder):
+    """The image tower `MM_Encoder` builds when `'clip-vit' in args.CV_model_load` (`Code_Uncached/model/encoders.py:9-10`; the reference
+    calls the class and never defines it): a frozen CLIP vision transformer — pre-LayerNorm, quick-GELU (or erf-GELU, by `hidden_act`), no
+    patch bias — with the `forward` / `forward_taps` / `forward_taps_indexed` surface of `Vit_Encoder`.  `hidden_states[0]` is the
+    pre-LayerNorm's output, as in HF; `post_layernorm` and any projection are not part of it.
+    The trainable head is `classifier`, `Linear(hidden, item_dim)`, where the reference's forward looks for it
+    (`Code_Uncached/model/model.py:261-262`: `self.cv_encoder.classifier`).  The same module is also reachable as
+    `image_net.classifier` — created there when the tower has none (an HF module), taken from there when it has (`FrozenVit`) — the
+    path the side network and the Cached wrapper read for every image tower."""
+
+    def __init__(self, image_net, item_dim, dtype16: int = _lib.IISAN_F16):
+        super().__init__(image_net, dtype16)
+        hidden = _clip_canonical(image_net)[1].hidden
+        head = getattr(image_net, "classifier", None)
+        if head is None:
+            head = nn.Linear(hidden, item_dim)
+            xavier_normal_(head.weight.data)
+            constant_(head.bias.data, 0)
+            image_net.classifier = head
+        elif head.in_features != hidden or head.out_features != item_dim:
+            raise ValueError(f"ClipVit_Encoder: the tower's classifier is {head.in_features} -> {head.out_features}, expected {hidden} -> {item_dim}")
+        self.classifier = head
+
+    def _canonical(self):
+        return _clip_canonical(self.image_net)
 
 
 class User_Encoder(nn.Module):                     # encoders.py:44-65
@@ -238,7 +286,10 @@ class Bert_Encoder(nn.Module):                     # encoders.py:116-159
 class MM_Encoder(nn.Module):                       # encoders.py:6-21
     def __init__(self, args, image_net, bert_model):
         super().__init__()
-        self.cv_encoder = Vit_Encoder(image_net=image_net)
+        if "clip-vit" in getattr(args, "CV_model_load", ""):       # encoders.py:9-12
+            self.cv_encoder = ClipVit_Encoder(image_net=image_net, item_dim=args.embedding_dim)
+        else:
+            self.cv_encoder = Vit_Encoder(image_net=image_net)
         self.bert_encoder = Bert_Encoder(args=args, bert_model=bert_model)
 
     def forward(self, sample_items_images, sample_items_text):

@@ -15,6 +15,7 @@ network, so this module provides
 Canonical names
 ---------------
 ViT  : cls_token[D] pos_emb[T,D] patch_w[D,3*P*P] patch_b[D] lnf_w[D] lnf_b[D]
+       CLIP vision towers (`VitConfig.pre_ln`): + pre_ln_w[D] pre_ln_b[D], no patch_b (`patch_bias = False`)
        L{l}.ln1_w L{l}.ln1_b L{l}.qkv_w[3D,D] L{l}.qkv_b[3D] L{l}.o_w[D,D] L{l}.o_b[D]
        L{l}.ln2_w L{l}.ln2_b L{l}.fc1_w[F,D] L{l}.fc1_b[F] L{l}.fc2_w[D,F] L{l}.fc2_b[D]
 BERT : word_emb[V,D] pos_emb[P,D] type_emb[2,D] emb_ln_w emb_ln_b
@@ -24,7 +25,7 @@ BERT : word_emb[V,D] pos_emb[P,D] type_emb[2,D] emb_ln_w emb_ln_b
 from __future__ import annotations
 
 from dataclasses import dataclass, asdict
-from typing import Dict
+from typing import Dict, Optional, Tuple
 
 import math
 
@@ -43,6 +44,19 @@ class VitConfig:
     patch: int = 16
     channels: int = 3
     eps: float = 1e-12
+    # CLIP vision towers (HF `CLIPVisionModel`); the defaults are HF ViT
+    pre_ln: bool = False            # a LayerNorm between the embeddings and block 0 (`pre_layrnorm`); hidden state 0 is its output
+    act: str = "gelu"               # MLP activation, `config.hidden_act`: "gelu" (erf) or "quick_gelu" (x * sigmoid(1.702 x))
+    patch_bias: bool = True         # the patch convolution has a bias (CLIP: none)
+    # per-channel statistics of the uint8 entry points, None = the reference's transform (mean .5, std .5); fp32 images come normalised
+    norm_mean: Optional[Tuple[float, float, float]] = None
+    norm_std: Optional[Tuple[float, float, float]] = None
+
+    def __post_init__(self):
+        if self.act not in ("gelu", "quick_gelu"):
+            raise ValueError(f"VitConfig.act {self.act!r}: 'gelu' or 'quick_gelu'")
+        if (self.norm_mean is None) != (self.norm_std is None):
+            raise ValueError("VitConfig.norm_mean and norm_std come together")
 
     @property
     def tokens(self) -> int:
@@ -89,6 +103,15 @@ VIT_SMALL = VitConfig(hidden=384, layers=12, heads=6, mlp=1536)
 # ViT-H/14 (`Code_Cached_Asym/preprocess_vectors_vit_large.py:111` caches the CLS rows of all 33 hidden states of
 # `google/vit-huge-patch14-224-in21k`): 16 heads of 80, 14-pixel patches (257 tokens at 224 pixels, a patch vector of 588)
 VIT_HUGE = VitConfig(hidden=1280, layers=32, heads=16, mlp=5120, patch=14)
+# CLIP vision towers (`Code_Uncached/run.py:46-49` loads `openai/clip-vit-base-patch32`): pre-LayerNorm, quick-GELU, no patch bias, eps 1e-5.
+# OpenAI's pixel statistics are CLIP_MEAN / CLIP_STD; the constants keep the reference's (.5, .5) transform of the uint8 entries unless a
+# caller sets them: `dataclasses.replace(CLIP_VIT_B32, norm_mean=CLIP_MEAN, norm_std=CLIP_STD)`
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+_CLIP = dict(eps=1e-5, pre_ln=True, act="quick_gelu", patch_bias=False)
+CLIP_VIT_B32 = VitConfig(patch=32, **_CLIP)
+CLIP_VIT_B16 = VitConfig(patch=16, **_CLIP)
+CLIP_VIT_L14 = VitConfig(hidden=1024, layers=24, heads=16, mlp=4096, patch=14, **_CLIP)
 BERT_TINY = BertConfig(hidden=128, layers=2, heads=2, mlp=512, vocab=30522, eps=1e-12)
 BERT_MINI = BertConfig(hidden=256, layers=4, heads=4, mlp=1024, vocab=30522, eps=1e-12)
 
@@ -125,6 +148,12 @@ def make_vit_weights(cfg: VitConfig = VIT_BASE, seed: int = 1234, std: float = 0
         w[p + "fc1_b"] = _normal(rs, (F,), std)
         w[p + "fc2_w"] = _normal(rs, (D, F), std)
         w[p + "fc2_b"] = _normal(rs, (D,), std)
+    # the extra tensors of a CLIP config are drawn LAST: every tensor above is, for a given seed, what a plain ViT config of the same shape gets
+    if cfg.pre_ln:
+        w["pre_ln_w"] = 1.0 + _normal(rs, (D,), ln_jitter)
+        w["pre_ln_b"] = _normal(rs, (D,), ln_jitter)
+    if not cfg.patch_bias:
+        del w["patch_b"]
     return w
 
 
@@ -211,6 +240,62 @@ def vit_from_hf(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
             w[p + x + "_b"] = sd[names[x] + ".bias"]
         l += 1
     return {k: v.detach().float().contiguous() for k, v in w.items()}
+
+
+def clip_vit_from_hf(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Canonical weights of a CLIP vision tower from a `CLIPVisionModel` / `CLIPVisionTransformer` / `CLIPModel` state dict: keys with or
+    without the `vision_model.` prefix.  `post_layernorm` (applied to the pooled output only, never to a hidden state), `position_ids`,
+    any projection and, of a whole `CLIPModel`, the text tower are dropped; `pre_layrnorm` is HF's own spelling."""
+    if any(k.startswith("vision_model.") for k in sd):
+        sd = {k[len("vision_model."):]: v for k, v in sd.items() if k.startswith("vision_model.")}
+    pos = sd["embeddings.position_embedding.weight"]
+    pw = sd["embeddings.patch_embedding.weight"]
+    w = {
+        "cls_token": sd["embeddings.class_embedding"].reshape(-1),
+        "pos_emb": pos.reshape(-1, pos.shape[-1]),
+        "patch_w": pw.reshape(pw.shape[0], -1),
+        "pre_ln_w": sd["pre_layrnorm.weight"],
+        "pre_ln_b": sd["pre_layrnorm.bias"],
+    }
+    if "embeddings.patch_embedding.bias" in sd:
+        w["patch_b"] = sd["embeddings.patch_embedding.bias"]
+    l = 0
+    while f"encoder.layers.{l}.self_attn.q_proj.weight" in sd:
+        b, p = f"encoder.layers.{l}.", f"L{l}."
+        w[p + "ln1_w"], w[p + "ln1_b"] = sd[b + "layer_norm1.weight"], sd[b + "layer_norm1.bias"]
+        w[p + "ln2_w"], w[p + "ln2_b"] = sd[b + "layer_norm2.weight"], sd[b + "layer_norm2.bias"]
+        w[p + "qkv_w"] = torch.cat([sd[b + f"self_attn.{x}_proj.weight"] for x in "qkv"], 0)
+        w[p + "qkv_b"] = torch.cat([sd[b + f"self_attn.{x}_proj.bias"] for x in "qkv"], 0)
+        w[p + "o_w"], w[p + "o_b"] = sd[b + "self_attn.out_proj.weight"], sd[b + "self_attn.out_proj.bias"]
+        for x in ("fc1", "fc2"):
+            w[p + x + "_w"], w[p + x + "_b"] = sd[b + f"mlp.{x}.weight"], sd[b + f"mlp.{x}.bias"]
+        l += 1
+    return {k: v.detach().float().contiguous() for k, v in w.items()}
+
+
+def clip_vit_to_hf(w: Dict[str, torch.Tensor], cfg: VitConfig, prefix: str = "vision_model.") -> Dict[str, torch.Tensor]:
+    """Canonical -> `CLIPVisionModel` state dict (`prefix = ""`: `CLIPVisionTransformer`), the inverse of `clip_vit_from_hf`;
+    `post_layernorm`, which no hidden state passes through, is left to the caller.  Used by the golden-fixture script and the tests."""
+    D = cfg.hidden
+    sd = {
+        "embeddings.class_embedding": w["cls_token"].reshape(D),
+        "embeddings.position_embedding.weight": w["pos_emb"].reshape(cfg.tokens, D),
+        "embeddings.patch_embedding.weight": w["patch_w"].reshape(D, cfg.channels, cfg.patch, cfg.patch),
+        "pre_layrnorm.weight": w["pre_ln_w"],
+        "pre_layrnorm.bias": w["pre_ln_b"],
+    }
+    if "patch_b" in w:
+        sd["embeddings.patch_embedding.bias"] = w["patch_b"]
+    for l in range(cfg.layers):
+        p, b = f"L{l}.", f"encoder.layers.{l}."
+        for x, ww, bb in zip("qkv", w[p + "qkv_w"].split(D, 0), w[p + "qkv_b"].split(D, 0)):
+            sd[b + f"self_attn.{x}_proj.weight"], sd[b + f"self_attn.{x}_proj.bias"] = ww, bb
+        sd[b + "self_attn.out_proj.weight"], sd[b + "self_attn.out_proj.bias"] = w[p + "o_w"], w[p + "o_b"]
+        sd[b + "layer_norm1.weight"], sd[b + "layer_norm1.bias"] = w[p + "ln1_w"], w[p + "ln1_b"]
+        sd[b + "layer_norm2.weight"], sd[b + "layer_norm2.bias"] = w[p + "ln2_w"], w[p + "ln2_b"]
+        for x in ("fc1", "fc2"):
+            sd[b + f"mlp.{x}.weight"], sd[b + f"mlp.{x}.bias"] = w[p + x + "_w"], w[p + x + "_b"]
+    return {prefix + k: v for k, v in sd.items()}
 
 
 def bert_from_hf(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

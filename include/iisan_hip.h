@@ -61,6 +61,15 @@ const char* iisan_last_error(void);
  * Patch sides: the multiples of 8, and 14 (any other side is IISAN_EBADSHAPE).  At 14 the patch vector of C*P*P (588) elements is
  * zero-padded to the next multiple of 64 (640) in the patch matrix, and patch_w must carry the same padding: [D, 640] with columns
  * 588..639 zero (iisan_amd/encoders.py pads it).
+ * CLIP vision towers (HF CLIPVisionModel: ViT-B/32, ViT-B/16, ViT-L/14 and the toy shapes between) are ViT towers with the trailing fields
+ * of iisan_vit_weights set: a LayerNorm between the embeddings and block 0 (pre_ln_w / pre_ln_b: hidden state 0, i.e. tap 0, is ITS output),
+ * quick-GELU in the MLP (act = 1; the LAION checkpoints keep act = 0), no bias on the patch convolution (patch_b = NULL), eps 1e-5.  The
+ * opening step is one kernel (csrc/rowops.hip, clip_open_kernel: embeddings -> pre-LayerNorm -> stream, and LN1 of block 0), the FC1
+ * products run the epilogue mode 8 (EPI_QGELU16) on the 128x128 and the 256x256 kernel.  A CLIP tower — pre_ln_w != NULL or act != 0 —
+ * runs on the LayerNorm-image route at every width, 768 included: iisan_vit_fold_bytes is 0 for it, `folded` is ignored and the dev switch
+ * ln_fold selects nothing, as for every D != 768 (the folded route has no opening step with a pre-LayerNorm and no quick-GELU twin of its
+ * FC1 epilogue).  Everything else — widths, head widths, patch sides, token counts, the CLS-only last block, chunk_items, the three entry
+ * points, both operand types — is as for a ViT, and so are the refusals.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct {
     const void* qkv_w;  const float* qkv_b;   /* [3D,D] 16-bit, [3D]  (q;k;v stacked)                          */
@@ -82,7 +91,7 @@ typedef struct {
     float   eps;
     int32_t full_blocks;                      /* dead-work policy, see below: 0 = default, 1 = every block on every token */
     const void*  patch_w;                     /* [D, C*P*P] 16-bit (Conv2d kernel flattened (c,py,px)); P % 8 != 0: rows zero-padded to a multiple of 64 */
-    const float* patch_b;                     /* [D]                                                            */
+    const float* patch_b;                     /* [D]; NULL = no bias (CLIP)                                     */
     const float* cls_token;                   /* [D]                                                            */
     const float* pos_emb;                     /* [T, D], T = (image/patch)^2 + 1                                */
     iisan_layer_weights layer[IISAN_MAX_LAYERS];
@@ -90,6 +99,15 @@ typedef struct {
      * caller-owned device buffer of iisan_vit_fold_bytes() bytes.  Without it every forward call folds them again into its workspace
      * (300 MB of traffic, ~0.1 ms for ViT-B; the result is the same). */
     const void* folded;
+    /* ---- CLIP vision towers; all zero = the ViT above ---- */
+    const float* pre_ln_w; const float* pre_ln_b;   /* [D] LayerNorm between the embeddings and block 0 (HF pre_layrnorm); NULL = none   */
+    int32_t act;                              /* MLP activation: 0 = erf-GELU, 1 = quick-GELU x * sigmoid(1.702 x)                     */
+    /* OPTIONAL per-channel statistics of the uint8 entry points (3 channels): all zero (default) = the reference's transform,
+     * (p / 255 - .5) / .5, the code path and the bits of a struct without these fields; otherwise (p / 255 - norm_mean[c]) / norm_std[c]
+     * in fp32 inside the patch-extraction kernel, every norm_std non-zero (else IISAN_EBADSHAPE) — taps identical to the fp32 entry point
+     * fed with the image normalised that way on the host.  A padding slot of the indexed entry stays the all-zero normalised image.
+     * The fp32 entry point takes normalised pixels and does not read them. */
+    float norm_mean[3]; float norm_std[3];
 } iisan_vit_weights;
 
 typedef struct {
@@ -111,7 +129,7 @@ typedef struct {
  * array.  `chunk_items` (0 = whole batch) bounds the activation working set. */
 /* The folded weights of `w` (LayerNorm 1 / 2 of every layer folded into qkv_w / fc1_w: gamma-scaled, centred, fp16, rounded
  * sum-preservingly from the fp32 masters when the layer has them, + the folded biases): [layers][(3D + F) x D] fp16, then
- * [layers][3D + F] fp32.  0 bytes when the executor would not use them (bf16 operands; any hidden size other than 768). */
+ * [layers][3D + F] fp32.  0 bytes when the executor would not use them (bf16 operands; any hidden size other than 768; a CLIP tower). */
 size_t iisan_vit_fold_bytes(const iisan_vit_weights* w);
 int iisan_vit_fold_layernorm(const iisan_vit_weights* w, void* folded, size_t bytes, void* stream);
 /* fp16 operands (dtype16 = IISAN_F16), production sizes: the executor folds LayerNorm 1 / 2 of every block into the QKV / FC1
@@ -390,6 +408,9 @@ int iisan_adam_step(float* p, const float* g, float* m, float* v, int64_t n, con
  * ---------------------------------------------------------------------------------------------------------- */
 /* C = epilogue(A[M,K] · W[N,K]^T + bias): 16-bit operands, fp32 accumulate.
  * mode 0: out16 = acc+bias     1: out16 = gelu_erf(acc+bias)     2: out32 = acc+bias+resid32 (resid may alias out)
+ * mode 8: out16 = quick_gelu(acc+bias), quick_gelu(x) = x * sigmoid(1.702 x) — wherever mode 1 is taken: the 128x128 kernel (ragged tiles
+ * included) and gemm16_h256, plain or with a block-major output (iisan_gemm16_blk32).  gemm16_s256 (dev switch gemm16_variant = 3, the
+ * race screen) has no mode 8: iisan_gemm16_route answers 0 there and the 128x128 kernel runs it.
  * A must be readable for ceil(M/256)*256 rows (tiles are loaded whole; rows >= M are never stored).
  * K % 64 == 0; N % 128 == 0, or N % 64 == 0 below 768 (the 192- and 576-column products of a 192-wide tower: a ragged last column
  * tile on the 128x128 kernel, W and bias read for rows / entries 0..N-1 only).  Anything else: IISAN_EBADSHAPE. */
@@ -501,9 +522,11 @@ int32_t iisan_inbatch_ce_route_e(int64_t bs, int32_t S, int32_t E);
  * ViT: bits 0-1 how the residual stream is carried (0 fp32 stream of resid32, 1 mixed stream + LayerNorm images, 2 LayerNorm in the QKV / FC1
  * epilogues, 3 ... and the residual adds in the O / FC2 epilogues), 4 = the FC1 -> FC2 intermediate is block-major, 8 = the stream is, 16 = the
  * call folds the LayerNorm weights itself, 32 = 80-wide heads (hidden 1280, heads 16): row-major QKV, iisan_attention16_hd80, and the last live
- * block runs on every token instead of on the CLS rows.  BERT: 1 = mixed stream, 2 = stream and 16-bit image share one buffer, 4 = block-major FC1 -> FC2. */
+ * block runs on every token instead of on the CLS rows.  IISAN_TOWER_CLIP: the ViT executor's decision for a CLIP tower (pre-LayerNorm,
+ * quick-GELU FC1), the ViT bit meanings; bits 0-1 are never 2 or 3 and bits 8 and 16 never set.  BERT: 1 = mixed stream, 2 = stream and 16-bit image share one buffer, 4 = block-major FC1 -> FC2. */
 #define IISAN_TOWER_VIT 0
 #define IISAN_TOWER_BERT 1
+#define IISAN_TOWER_CLIP 2
 int32_t iisan_encoder_plan(int32_t tower, int32_t dtype16, int32_t hidden, int32_t heads, int32_t mlp, int32_t tokens, int64_t M,
                            int64_t chunk_items, int32_t deepest_tap, int32_t full_blocks, int32_t folded);
 
@@ -535,9 +558,9 @@ double iisan_timing_last_bytes(void);
  * matrix, Mpad % 32 == 0 and C % 32 == 0, as 32 x 32 blocks of 2 KiB; element (m, c) at byte
  *   ((m >> 5) * (C >> 5) + (c >> 5)) * 2048 + ((c >> 3) & 1) * 1024 + (((c >> 4) & 1) * 32 + (m & 31)) * 16 + (c & 7) * 2.
  * The executors' FC1 -> FC2 intermediate carries it (dev switch blk32 >= 1) and the ViT residual stream of the product route (blk32 = 2,
- * the default; 0 = row-major everywhere).  iisan_gemm16_blk32: iisan_gemm16 (mode 0 / 1; rowstat != NULL: LayerNorm in the epilogue as
+ * the default; 0 = row-major everywhere).  iisan_gemm16_blk32: iisan_gemm16 (mode 0 / 1 / 8; rowstat != NULL: LayerNorm in the epilogue as
  * iisan_gemm16_lna) with "A is block-major" (mode 0; mode 1 with rowstat and a block-major out: the stream into FC1) and "out is
- * block-major" (mode 1); iisan_gemm16_stream_blk32 / iisan_stream_stats_finalize_blk32: iisan_gemm16_stream and its finalize step with
+ * block-major" (mode 1, and mode 8 without rowstat); iisan_gemm16_stream_blk32 / iisan_stream_stats_finalize_blk32: iisan_gemm16_stream and its finalize step with
  * a block-major A and / or a block-major stream x16.  Every combination or kernel route that does not carry a flag returns
  * IISAN_EBADSHAPE. */
 int iisan_gemm16_blk32(int32_t dtype16, int32_t mode, const void* A, const void* W, const float* bias, void* out, const float* rowstat,
