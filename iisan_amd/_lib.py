@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libiisan_hip.so")
 
 IISAN_F16, IISAN_BF16, IISAN_F32 = 0, 1, 2
 IISAN_WIN_TRAIN, IISAN_WIN_EVAL, IISAN_WIN_INPUT = 0, 1, 2
-IISAN_TOWER_VIT, IISAN_TOWER_BERT, IISAN_TOWER_CLIP = 0, 1, 2
+IISAN_TOWER_VIT, IISAN_TOWER_BERT, IISAN_TOWER_CLIP, IISAN_TOWER_DEBERTA = 0, 1, 2, 3
 EPI_OUT16, EPI_GELU16, EPI_QGELU16 = 0, 1, 8      # epilogue modes of iisan_gemm16 (include/iisan_hip.h)
 MAX_LAYERS, MAX_SIDE = 48, 16
 
@@ -37,7 +37,9 @@ class BertWeights(C.Structure):
     _fields_ = [("hidden", i32), ("layers", i32), ("heads", i32), ("mlp", i32),
                 ("vocab", i32), ("max_pos", i32), ("dtype16", i32), ("eps", f32), ("full_blocks", i32),
                 ("word_emb", vp), ("pos_emb", vp), ("type_emb", vp), ("emb_ln_w", vp), ("emb_ln_b", vp),
-                ("layer", LayerWeights * MAX_LAYERS)]
+                ("layer", LayerWeights * MAX_LAYERS),
+                # DeBERTa-v2/v3 towers (all zero = a BERT): the relative-position table, its LayerNorm, position_buckets, the projected tables
+                ("rel_emb", vp), ("rel_ln_w", vp), ("rel_ln_b", vp), ("span", i32), ("rel_proj", vp)]
 
 
 class SideCfg(C.Structure):
@@ -99,6 +101,11 @@ SIGNATURES = {
     "iisan_attention16_long": (i32, [i32, vp, vp, vp, i64, i32, i32, vp]),
     "iisan_attention16_hd80": (i32, [i32, vp, vp, vp, i64, i32, i32, vp]),
     "iisan_attention_cls16": (i32, [i32, vp, vp, vp, i64, i32, i32, vp]),
+    "iisan_attention16_disent": (i32, [i32, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "iisan_attention_cls16_disent": (i32, [i32, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "iisan_deberta_rel_bytes": (sz, [C.POINTER(BertWeights)]),
+    "iisan_deberta_rel_ws_bytes": (sz, [C.POINTER(BertWeights)]),
+    "iisan_deberta_rel_project": (i32, [C.POINTER(BertWeights), vp, vp, sz, vp]),
     "iisan_attention16_dropout": (i32, [i32, vp, vp, vp, i64, i32, i32, f32, u64, i32, i32, vp]),
     "iisan_gemm32": (i32, [vp, vp, vp, vp, i64, i32, i64, i32, i32, i32, i32, vp]),
     "iisan_gemm_x3_ws_bytes": (sz, [i64, i32, i64]),

@@ -444,6 +444,11 @@ int launch_attention16_dma(int dtype16, const void* qkv, void* ctx, int64_t item
 // CLS query only: ctx_cls [items, heads*64] (last executed encoder block)
 int launch_attention_cls16(int dtype16, const void* qkv, const float* key_bias, void* ctx_cls, int64_t items, int S,
                            int heads, hipStream_t s, const void* q_cls = nullptr);   // q_cls: [items, heads*64] 16-bit CLS queries
+// attn16_disent.hip: DeBERTa's disentangled attention, rel = one layer of the projected tables [heads][3][2 span][64]; 1 <= S <= min(128, span)
+int launch_attention16_disent(int dtype16, const void* qkv, const void* rel, const float* key_bias, void* ctx, int64_t items, int S, int heads,
+                              int span, hipStream_t s);
+int launch_attention_cls16_disent(int dtype16, const void* qkv, const void* rel, const float* key_bias, void* ctx_cls, int64_t items, int S,
+                                  int heads, int span, hipStream_t s, const void* q_cls = nullptr);
 // embedding and tap steps of the encoder executors (rowops.hip)
 // columns of a patch row in the patch matrix / the packed patch weight: C p p, zero-padded to a multiple of 64 when p % 8 != 0 (p = 14: 588 -> 640)
 int vit_patch_ld(int C, int p);
@@ -458,6 +463,7 @@ int launch_clip_open(int dtype16, const float* pos, void* x16, float* xc, const 
                      const float* g, const float* b, float eps, void* out16, int64_t items, int Ttok, int width, hipStream_t s);
 int launch_vit_cls_rows(float* X, const float* cls, const float* pos, int64_t M, int T, int D, hipStream_t s);
 // keep (train mode): the keep factor multiplies the fp32 LayerNorm output before it is rounded or stored — width 768
+// pos == null and type0 == null: the DeBERTa instantiation — LayerNorm(word[id]) * mask, eval mode only
 int launch_bert_embed_ln(int dtype16, const int64_t* text, const float* word, const float* pos, const float* type0,
                          const float* g, const float* b, float eps, float* X, void* H, float* key_bias, int64_t M,
                          int W, int vocab, int width, hipStream_t s, void* X16 = nullptr, float* Xc = nullptr, const RowKeep* keep = nullptr);

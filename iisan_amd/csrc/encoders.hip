@@ -223,11 +223,13 @@ struct Chunk : Products {
     // O, both adds, FC1 and FC2 run on one row per item; the result, hidden state l + 1 (before any final LayerNorm), goes to
     // tap k.  The towers differ in the attention launch (attn_drop: the train-mode kernel) and in the adds — pre-LN: x += delta, LN2 in front
     // of FC1; post_ln: x = LN(x + keep * delta) with ln1 / ln2.
+    // rel != null (DeBERTa): the CLS form of the disentangled attention over the layer's projected tables.
     int cls_tail(const iisan_layer_weights& L, const float* key_bias, const DropCfg* attn_drop, bool post_ln, const RowKeep* keep1,
-                 const RowKeep* keep2, int k) const {
+                 const RowKeep* keep2, int k, const void* rel = nullptr, int span = 0) const {
         void* Qc = (char*)b.Cls + (size_t)b.Mcp * D * 2;       // compact [mc, D] 16-bit views in their own scratch: CLS rows of the input, their Q
         IISAN_TRY(launch(plain(EPI_OUT16, D, D, mc), b.Cls, L.qkv_w, L.qkv_b, Qc));
-        if (attn_drop) IISAN_TRY(launch_attention16_drop(dt, b.QKV, key_bias, b.H, mc, T, heads, *attn_drop, m0, true, Qc, s));
+        if (rel) IISAN_TRY(launch_attention_cls16_disent(dt, b.QKV, rel, key_bias, b.H, mc, T, heads, span, s, Qc));
+        else if (attn_drop) IISAN_TRY(launch_attention16_drop(dt, b.QKV, key_bias, b.H, mc, T, heads, *attn_drop, m0, true, Qc, s));
         else IISAN_TRY(launch_attention_cls16(dt, b.QKV, key_bias, b.H, mc, T, heads, s, Qc));
         float* Xc = (float*)b.QKV;      // free once the CLS attention has run (stream order)
         IISAN_TRY(launch(plain(EPI_OUT16, D, D, mc), b.H, L.o_w, L.o_b, b.D16));
@@ -555,11 +557,78 @@ extern "C" int iisan_vit_forward_taps_u8_indexed(const iisan_vit_weights* w, con
     return vit_forward_taps_impl(w, catalogue, 1, M, tap_layers, n_taps, taps, chunk_items, ws, ws_bytes, stream, index, rows);
 }
 
+// ---- DeBERTa: the projected position tables (include/iisan_hip.h, iisan_deberta_rel_project) ---------------------------------------------------
+// one layer's image: [heads][3][2 span][64] 16-bit elements = 3 * 2 span * D
+static size_t deberta_rel_layer_elems(const iisan_bert_weights* w) { return (size_t)3 * 2 * w->span * w->hidden; }
+static bool bert_is_deberta(const iisan_bert_weights* w) { return w->rel_emb != nullptr; }
+static int deberta_check_span(int span) {
+    IISAN_CHECK_SHAPE(span >= 1 && span <= 256, "deberta: span (position_buckets) %d outside 1 .. 256", span);
+    return IISAN_OK;
+}
+// the titles the identity part of HF's log-bucket map covers (|i - j| <= span / 2), and what attn16_disent.hip keeps in LDS
+static int deberta_check_words(int words, int span) {
+    IISAN_CHECK_SHAPE(words <= span / 2, "deberta: %d words > span / 2 = %d: relative positions past position_buckets / 2 fall into HF's log "
+                      "buckets, which this tower does not implement", words, span / 2);
+    IISAN_CHECK_SHAPE(words <= 128, "deberta: %d words > 128 not supported", words);
+    return IISAN_OK;
+}
+
+extern "C" size_t iisan_deberta_rel_bytes(const iisan_bert_weights* w) {
+    return bert_is_deberta(w) && w->span > 0 && w->layers > 0 ? (size_t)w->layers * deberta_rel_layer_elems(w) * 2 : 0;
+}
+// the 16-bit LayerNorm image of the table, rows padded to a GEMM row tile
+extern "C" size_t iisan_deberta_rel_ws_bytes(const iisan_bert_weights* w) {
+    return bert_is_deberta(w) && w->span > 0 ? align_up((size_t)ceil_div(2 * w->span, 256) * 256 * w->hidden * 2, 256) : 0;
+}
+// tables of layers 0 .. layers - 1 into `out`: LayerNorm of the table by the row kernel, then per layer ONE product with the layer's own QKV
+// matrix through the head-major epilogue — the table is a pseudo-item of 2 span tokens
+static int deberta_rel_project(const iisan_bert_weights* w, int layers, void* out, void* ws, hipStream_t s) {
+    const int D = w->hidden, R = 2 * w->span;
+    IISAN_TRY(launch_layernorm768(w->dtype16, w->rel_emb, w->rel_ln_w, w->rel_ln_b, w->eps, ws, nullptr, R, D, s));
+    for (int l = 0; l < layers; ++l) {
+        Gemm16Args a{};
+        a.A = ws; a.W = w->layer[l].qkv_w; a.bias = w->layer[l].qkv_b; a.out = (char*)out + (size_t)l * deberta_rel_layer_elems(w) * 2;
+        a.M = R; a.N = 3 * D; a.K = D; a.lda = D; a.ldw = D; a.ldo = 3 * D;
+        a.qkv_S = R; a.qkv_heads = w->heads; a.qkv_which0 = 0;
+        IISAN_TRY(launch_gemm16(w->dtype16, EPI_QKVH16, a, s));
+    }
+    return IISAN_OK;
+}
+static int deberta_check_struct(const iisan_bert_weights* w) {
+    IISAN_CHECK_SHAPE(w->rel_emb && w->rel_ln_w && w->rel_ln_b, "deberta: rel_emb, rel_ln_w and rel_ln_b come together (one of them is null)");
+    IISAN_CHECK_SHAPE(!w->pos_emb && !w->type_emb, "deberta: a tower with rel_emb has no position and no type table (pos_emb / type_emb must be null)");
+    return deberta_check_span(w->span);
+}
+extern "C" int iisan_deberta_rel_project(const iisan_bert_weights* w, void* out, void* ws, size_t ws_bytes, void* stream) {
+    IISAN_TRY(deberta_check_struct(w));
+    IISAN_CHECK_SHAPE(row_width_instantiated(w->hidden) && w->hidden != 1280 && w->heads > 0 && w->hidden == w->heads * 64,
+                      "deberta_rel_project: hidden %d / heads %d not supported", w->hidden, w->heads);
+    IISAN_CHECK_SHAPE(w->layers >= 1 && w->layers <= IISAN_MAX_LAYERS, "deberta_rel_project: layers %d out of range", w->layers);
+    const size_t need = iisan_deberta_rel_ws_bytes(w);
+    if (!out || !ws || ws_bytes < need) {
+        iisan_set_error("deberta_rel_project: null output or workspace too small (%zu < %zu)", ws_bytes, need);
+        return IISAN_EWORKSPACE;
+    }
+    return deberta_rel_project(w, w->layers, out, ws, (hipStream_t)stream);
+}
+
+// the workspace of a BERT call in chunks of Mc items; a DeBERTa struct without rel_proj: + the projected tables and their scratch
+static size_t bert_carve(WsCarver& c, EncBufs& b, const iisan_bert_weights* w, int64_t Mc, int words, void** rel, void** rel_ws) {
+    carve(c, b, Mc * words, Mc, w->hidden, w->mlp, Mc * words);
+    *rel = *rel_ws = nullptr;
+    if (bert_is_deberta(w) && !w->rel_proj) {
+        *rel = c.take<uint8_t>(iisan_deberta_rel_bytes(w));
+        *rel_ws = c.take<uint8_t>(iisan_deberta_rel_ws_bytes(w));
+    }
+    return c.off;
+}
+
 extern "C" size_t iisan_bert_forward_taps_ws_bytes(const iisan_bert_weights* w, int64_t M, int32_t words, int64_t chunk_items) {
     const int64_t Mc = Chunks(M, chunk_items).Mc;
     WsCarver c(nullptr, 0);
     EncBufs b;
-    return carve(c, b, Mc * words, Mc, w->hidden, w->mlp, Mc * words);
+    void *rel, *rel_ws;
+    return bert_carve(c, b, w, Mc, words, &rel, &rel_ws);
 }
 
 namespace {
@@ -577,8 +646,15 @@ BertPlan bert_plan(Products& p, const Chunks& c) {
 // One chunk of a BERT forward.  Eval mode (dropping = false) is the launch sequence below with null keeps; in train mode the attention kernel of
 // bert_drop.hip takes the place of the eval-mode one, and the embedding and add + LayerNorm steps run their train-mode instantiations (a RowKeep
 // instead of null; rowops.hip) — sites 0, 1 + 3l, 2 + 3l, 3 + 3l and their indices: include/iisan_hip.h, iisan_bert_dropout
+// kind: IISAN_TOWER_BERT, or IISAN_TOWER_DEBERTA — the same block skeleton with three steps switched: the embedding (no position / type table, the
+// mask multiply), the attention of an all-token block and the attention of the CLS tail (disentangled, over `rel`, the projected tables of
+// every layer).  Eval mode only.
 struct BertChunk : Chunk {
     const iisan_bert_weights* w; bool alias, dropping; float hp, ap; uint64_t seed;
+    int kind = IISAN_TOWER_BERT; const void* rel = nullptr;
+
+    bool deberta() const { return kind == IISAN_TOWER_DEBERTA; }
+    const void* rel_layer(int l) const { return (const char*)rel + (size_t)l * deberta_rel_layer_elems(w) * 2; }
 
     void* img() const { return alias ? b.X16 : b.H; }       // the 16-bit image of the stream: the A operand of the QKV / FC1 products
     // train mode: the keep functor of a hidden site, local row r of the launch = token row m0 * T + r * rs of the whole call (rs = 1: the rows of
@@ -593,6 +669,7 @@ struct BertChunk : Chunk {
     // index != null: `text` is a resident table [rows, 2W] and item m of the chunk is its row index[m0 + m]
     int embed(const int64_t* text, const int64_t* index, int64_t rows) const {
         const Keep k = keep(0, 1);
+        // (DeBERTa: pos_emb and type_emb are null — the launchers' DeBERTa instantiation, LayerNorm(word[id]) * mask)
         if (index) return launch_bert_embed_ln_indexed(dt, text, rows, index + m0, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b, w->eps,
                                                        mixed ? nullptr : b.X, img(), b.KB, mc, T, w->vocab, D, s, b.X16, b.Xc, k);
         return launch_bert_embed_ln(dt, text + m0 * 2 * T, w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_w, w->emb_ln_b, w->eps,
@@ -608,7 +685,8 @@ struct BertChunk : Chunk {
         const iisan_layer_weights& L = w->layer[l];
         // a = LN(x + O(attn(x)))
         IISAN_TRY(launch(qkv(tok), img(), L.qkv_w, L.qkv_b, b.QKV));
-        if (dropping) IISAN_TRY(launch_attention16_drop(dt, b.QKV, b.KB, b.H, mc, T, heads, attn_drop(l), m0, false, nullptr, s));
+        if (deberta()) IISAN_TRY(launch_attention16_disent(dt, b.QKV, rel_layer(l), b.KB, b.H, mc, T, heads, w->span, s));
+        else if (dropping) IISAN_TRY(launch_attention16_drop(dt, b.QKV, b.KB, b.H, mc, T, heads, attn_drop(l), m0, false, nullptr, s));
         else IISAN_TRY(launch_attention16(dt, b.QKV, b.KB, b.H, mc, T, heads, s));
         IISAN_TRY(launch(o(tok), b.H, L.o_w, L.o_b, b.D16));
         IISAN_TRY(add_ln(L.ln1_w, L.ln1_b, 2 + 3 * l));
@@ -624,7 +702,7 @@ struct BertChunk : Chunk {
         IISAN_TRY(launch(qkv(tok, 1), img(), (const char*)L.qkv_w + (size_t)D * D * 2, L.qkv_b + D, b.QKV));
         const DropCfg ad = attn_drop(l);
         const Keep k1 = keep(2 + 3 * l, T), k2 = keep(3 + 3 * l, T);
-        return cls_tail(L, b.KB, dropping ? &ad : nullptr, true, k1, k2, k);
+        return cls_tail(L, b.KB, dropping ? &ad : nullptr, true, k1, k2, k, deberta() ? rel_layer(l) : nullptr, w->span);
     }
 };
 
@@ -647,9 +725,17 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
     // ... and for 768-wide rows only (rowops.hip): tap caches of the wide and the narrow towers are built in eval mode
     IISAN_CHECK_SHAPE(!(dropping && w->hidden != 768), "bert dropout: no train-mode instantiation at this width, hidden size %d runs in eval mode only "
                       "(drop == NULL or both probabilities 0)", w->hidden);
+    // a DeBERTa struct (rel_emb != NULL): eval only — there is no train-mode instantiation of its embedding step or of its attention
+    const bool deb = bert_is_deberta(w);
+    IISAN_CHECK_SHAPE(!(dropping && deb), "deberta: the tower runs in eval mode only (drop == NULL or both probabilities 0): no train-mode "
+                      "instantiation of the disentangled attention");
     IISAN_CHECK_SHAPE(M > 0, "bert_forward_taps: M must be positive");
     IISAN_TRY(check_common(false, w->hidden, w->layers, w->heads, w->mlp, n_taps, tap_layers));
-    IISAN_TRY(bert_check_words(words, w->max_pos));
+    if (deb) {
+        IISAN_TRY(deberta_check_struct(w));
+        IISAN_CHECK_SHAPE(words >= 1, "deberta: %d words unsupported", words);
+        IISAN_TRY(deberta_check_words(words, w->span));
+    } else IISAN_TRY(bert_check_words(words, w->max_pos));
     // ... and the train-mode attention kernel keeps a whole head in LDS (bert_drop.hip): refused here, before any launch, never a silent fall-back
     IISAN_CHECK_SHAPE(!(dropping && words > 224), "bert dropout: no train-mode attention kernel past 224 words, titles of %d words run in eval mode only "
                       "(drop == NULL or both probabilities 0)", words);
@@ -657,7 +743,8 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
     const Chunks c(M, chunk_items);
     WsCarver cv(ws, ws_bytes);
     EncBufs b;
-    carve(cv, b, c.Mc * T, c.Mc, D, w->mlp, c.Mc * T);
+    void *rel_own, *rel_ws;
+    bert_carve(cv, b, w, c.Mc, T, &rel_own, &rel_ws);
     if (cv.overflow || !ws) {
         iisan_set_error("bert_forward_taps: workspace too small (%zu < %zu)", ws_bytes, cv.off);
         return IISAN_EWORKSPACE;
@@ -666,10 +753,14 @@ static int bert_forward_taps_impl(const iisan_bert_weights* w, const int64_t* te
     const BertPlan plan = bert_plan(p, c);
     const bool full_blocks = g_full_blocks || w->full_blocks;
     const int live = full_blocks ? w->layers : max_tap(tap_layers, n_taps);     // see the ViT executor
+    // DeBERTa without the caller's projected tables: the call projects those of its live layers into its workspace, once, before the chunks
+    if (deb && !w->rel_proj && live > 0) IISAN_TRY(deberta_rel_project(w, live, rel_own, rel_ws, s));
+    const void* rel = deb ? (w->rel_proj ? w->rel_proj : rel_own) : nullptr;
     for (int64_t m0 = 0; m0 < M; m0 += c.Mc) {
         const int64_t mc = (M - m0 < c.Mc) ? M - m0 : c.Mc;
         const BertChunk ch{{p, b, s, w->eps, plan.mixed, m0, mc, mc * T, taps + m0 * n_taps * D, n_taps}, w, plan.alias, dropping,
-                           dropping ? drop->hidden_p : 0.f, dropping ? drop->attn_p : 0.f, dropping ? drop->seed : 0};
+                           dropping ? drop->hidden_p : 0.f, dropping ? drop->attn_p : 0.f, dropping ? drop->seed : 0,
+                           deb ? IISAN_TOWER_DEBERTA : IISAN_TOWER_BERT, rel};
         IISAN_TRY(ch.embed(text, index, rows));
         int k = tap_index(tap_layers, n_taps, 0);
         if (k >= 0) IISAN_TRY(ch.tap(k));
@@ -716,11 +807,18 @@ extern "C" int iisan_bert_forward_taps_dropout(const iisan_bert_weights* w, cons
 // refusals that depend on these inputs, then vit_plan / bert_plan themselves.  `layers` is the shortest tower that has the tap.
 extern "C" int32_t iisan_encoder_plan(int32_t tower, int32_t dtype16, int32_t hidden, int32_t heads, int32_t mlp, int32_t tokens, int64_t M,
                                       int64_t chunk_items, int32_t deepest_tap, int32_t full_blocks, int32_t folded) {
-    IISAN_CHECK_SHAPE(tower == IISAN_TOWER_VIT || tower == IISAN_TOWER_BERT || tower == IISAN_TOWER_CLIP,
-                      "encoder_plan: tower %d is neither ViT (0) nor BERT (1) nor CLIP (2)", tower);
+    IISAN_CHECK_SHAPE(tower == IISAN_TOWER_VIT || tower == IISAN_TOWER_BERT || tower == IISAN_TOWER_CLIP || tower == IISAN_TOWER_DEBERTA,
+                      "encoder_plan: tower %d is neither ViT (0) nor BERT (1) nor CLIP (2) nor DeBERTa (3)", tower);
     const bool clip = tower == IISAN_TOWER_CLIP;
     IISAN_CHECK_SHAPE(M > 0, "encoder_plan: M must be positive");
     const int layers = deepest_tap > 1 ? deepest_tap : 1;
+    if (tower == IISAN_TOWER_DEBERTA) {     // the BERT executor's plan behind the DeBERTa refusals; `folded` carries the span
+        IISAN_TRY(check_common(false, hidden, layers, heads, mlp, 1, &deepest_tap));
+        IISAN_TRY(deberta_check_span(folded));
+        IISAN_CHECK_SHAPE(tokens >= 1, "deberta: %d words unsupported", tokens);
+        IISAN_TRY(deberta_check_words(tokens, folded));
+        tower = IISAN_TOWER_BERT;
+    }
     IISAN_TRY(check_common(tower != IISAN_TOWER_BERT, hidden, layers, heads, mlp, 1, &deepest_tap));
     IISAN_TRY(tower != IISAN_TOWER_BERT ? vit_check_tokens(tokens) : bert_check_words(tokens, tokens));
     const bool full = g_full_blocks || full_blocks;

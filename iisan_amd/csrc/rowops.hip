@@ -510,6 +510,13 @@ __global__ void vit_cls_rows_kernel(float* __restrict__ X, const float* __restri
 // dereferenced, all-zero ids and mask (what `dataset.py:79-84` ships for pad slots).
 // KEEP on (train mode): drop(LN(...)) — the keep factor multiplies the fp32 LayerNorm output BEFORE it is rounded, so every copy the
 // executor keeps of the row (the 16-bit image H, the fp16 stream X16, the fp32 CLS rows Xc that become tap 0) holds the dropped value.
+// DEB (DeBERTa-v2/v3, HF DebertaV2Embeddings with position_biased_input = False and type_vocab_size = 0): LN(word[id]) * mask — no position and
+// no type table (pos / type0 are not read), and the row of a masked token is exactly zero.  The key bias is written as for BERT.  The
+// instantiation rides on the KEEP parameter (RowKeepDeberta: no dropout, eval mode only): the kernel's template list, and with it the
+// symbol names of the BERT instantiations, stay as they are.
+struct RowKeepDeberta { static constexpr bool on = false; };
+template <class K> struct EmbedIsDeberta { static constexpr bool value = false; };
+template <> struct EmbedIsDeberta<RowKeepDeberta> { static constexpr bool value = true; };
 template <typename T, bool IDX = false, int D = 768, typename KEEP = RowKeepNone>
 __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __restrict__ text, const float* __restrict__ word,
                                                             const float* __restrict__ pos, const float* __restrict__ type0,
@@ -522,6 +529,7 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __res
     constexpr int NP = row_np(D, 4, 64), LPR = row_lpr(D, 4, 64), PW = LPR * 4;        // as layernorm768_kernel
     static_assert(row_width_ok(D, 4, 64), "row width: LPR * NP * 4 with LPR a power of two, at most 1024");
     static_assert(!KEEP::on || D == 768, "train mode: 768 wide only");
+    constexpr bool DEB = EmbedIsDeberta<KEEP>::value;
     const int lane = threadIdx.x & (LPR - 1);
     const int64_t row = (int64_t)blockIdx.x * (256 / LPR) + (threadIdx.x / LPR);
     if (row >= M * W) return;
@@ -540,15 +548,19 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __res
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     if (lane == 0) key_bias[row] = msk != 0 ? 0.0f : -1.0f;
     const float* wr = word + id * D;
-    const float* pr = pos + (int64_t)t * D;
+    const float* pr = DEB ? nullptr : pos + (int64_t)t * D;
     f4 v[NP];
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         const int c = i * PW + lane * 4;
-        const f4 a = *(const f4*)(wr + c), p2 = *(const f4*)(pr + c), ty = *(const f4*)(type0 + c);
+        if constexpr (DEB) {
+            v[i] = *(const f4*)(wr + c);
+        } else {
+            const f4 a = *(const f4*)(wr + c), p2 = *(const f4*)(pr + c), ty = *(const f4*)(type0 + c);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[i][e] = a[e] + p2[e] + ty[e];
+            for (int e = 0; e < 4; ++e) v[i][e] = a[e] + p2[e] + ty[e];
+        }
         s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
     }
     const float mean = row_sum<LPR>(s) * (1.0f / (float)D);
@@ -571,6 +583,7 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int64_t* __res
         for (int e = 0; e < 4; ++e) {
             y[e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
             if constexpr (KEEP::on) y[e] *= keep(keep.index(row, D, c) + e);
+            if constexpr (DEB) y[e] = msk != 0 ? y[e] : 0.f;
             o[e] = T::from_f32(y[e]);
         }
         if (X) {
@@ -884,7 +897,16 @@ static int bert_embed_ln_any(int dtype16, const int64_t* text, int64_t rows, con
     hipLaunchKernelGGL((bert_embed_ln_kernel<TT, IDX, WD>), grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (EL*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows)
 #define EMBED_KEEP(TT, EL)                                                                                                     \
     hipLaunchKernelGGL((bert_embed_ln_kernel<TT, IDX, 768, RowKeep>), grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (EL*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows, *keep)
-    if (keep) {         // train mode: 768 or a refusal, never a silent eval launch
+#define EMBED_DEB(TT, EL, WD)                                                                                                  \
+    hipLaunchKernelGGL((bert_embed_ln_kernel<TT, IDX, WD, RowKeepDeberta>), grid, block, 0, s, text, word, pos, type0, g, b, eps, X, (EL*)H, key_bias, M, W, vocab, (_Float16*)X16, Xc, index, rows)
+    IISAN_CHECK_SHAPE(!pos == !type0, "bert_embed_ln: the position and the type table come together (BERT) or not at all (DeBERTa)");
+    if (!pos) {         // DeBERTa: eval mode only
+        IISAN_CHECK_SHAPE(!keep, "bert_embed_ln: no train-mode instantiation of the DeBERTa embedding step");
+#define EMBED_DEB_AT(WD, TT)                                                                                                   \
+    if (dtype16 == IISAN_BF16) EMBED_DEB(BF16, __bf16, WD); else EMBED_DEB(TT, _Float16, WD)
+        ROW_WIDTH_SWITCH_64(width, EMBED_DEB_AT, F16)
+#undef EMBED_DEB_AT
+    } else if (keep) {         // train mode: 768 or a refusal, never a silent eval launch
         IISAN_CHECK_SHAPE(width == 768, "bert_embed_ln: no train-mode instantiation at row width %d", width);
         if (dtype16 == IISAN_BF16) EMBED_KEEP(BF16, __bf16); else EMBED_KEEP(F16, _Float16);
         iisan_count_bert_drop();
@@ -894,6 +916,7 @@ static int bert_embed_ln_any(int dtype16, const int64_t* text, int64_t rows, con
         ROW_WIDTH_SWITCH_64(width, EMBED_AT, F16)
 #undef EMBED_AT
     }
+#undef EMBED_DEB
 #undef EMBED_KEEP
 #undef EMBED_LAUNCH
     IISAN_LAUNCH_OK();

@@ -3,6 +3,8 @@
 Host-side counterpart of `Vit_Encoder` / `Bert_Encoder` (`Code_Uncached/model/encoders.py:23-31,116-159`) for the
 IISAN mode, where only the per-layer CLS rows of the hidden states are consumed (`model.py:212-213`).  PyTorch is
 used for device memory and the stream only; all arithmetic happens in libiisan_hip.so.
+`PackedBert(w, cfg)` serves both text-tower families: a `weights.DebertaConfig` makes a `PackedDeberta` (the BERT executor with the
+DeBERTa fields of `iisan_bert_weights` set; eval mode only).
 """
 from __future__ import annotations
 
@@ -12,7 +14,7 @@ from typing import Dict, Sequence
 import torch
 
 from . import _lib
-from .weights import BertConfig, VitConfig
+from .weights import BertConfig, DebertaConfig, VitConfig
 
 _TORCH16 = {_lib.IISAN_F16: torch.float16, _lib.IISAN_BF16: torch.bfloat16}
 DTYPE_NAMES = {"fp16": _lib.IISAN_F16, "f16": _lib.IISAN_F16, "bf16": _lib.IISAN_BF16}
@@ -171,17 +173,26 @@ class PackedVit(_PackedEncoder):
 
 
 class PackedBert(_PackedEncoder):
+    def __new__(cls, w=None, cfg=None, *args, **kw):
+        # a DebertaConfig makes a PackedDeberta: `PackedBert(w, cfg)` serves both text-tower families
+        if cls is PackedBert and isinstance(cfg, DebertaConfig):
+            return super().__new__(PackedDeberta)
+        return super().__new__(cls)
+
     def __init__(self, w: Dict[str, torch.Tensor], cfg: BertConfig, device="cuda", dtype16: int = _lib.IISAN_F16):
         super().__init__(w, device, dtype16)
         self.cfg = cfg
         s = _lib.BertWeights()
         s.hidden, s.layers, s.heads, s.mlp = cfg.hidden, cfg.layers, cfg.heads, cfg.mlp
         s.vocab, s.max_pos, s.dtype16, s.eps = cfg.vocab, cfg.max_pos, dtype16, cfg.eps
-        s.word_emb, s.pos_emb, s.type_emb = self._v32("word_emb"), self._v32("pos_emb"), self._v32("type_emb")
+        self._tables(s)
         s.emb_ln_w, s.emb_ln_b = self._v32("emb_ln_w"), self._v32("emb_ln_b")
         self._layers(s, cfg.layers)
         self.struct = s
         self._w = None
+
+    def _tables(self, s):
+        s.word_emb, s.pos_emb, s.type_emb = self._v32("word_emb"), self._v32("pos_emb"), self._v32("type_emb")
 
     @staticmethod
     def _drop_struct(dropout):
@@ -218,3 +229,46 @@ class PackedBert(_PackedEncoder):
             return self._taps_call("iisan_bert_forward_taps_dropout", head, M, tap_layers, chunk_items, nbytes, index.device,
                                    extra=(C.byref(self._drop_struct(dropout)),))
         return self._taps_call("iisan_bert_forward_taps_indexed", head, M, tap_layers, chunk_items, nbytes, index.device)
+
+
+class PackedDeberta(PackedBert):
+    """A DeBERTa-v2/v3 text tower (`weights.DebertaConfig`; canonical names of `make_deberta_weights` / `deberta_from_hf`): the BERT executor
+    with the trailing fields of `iisan_bert_weights` set.  The position tables are projected by every layer's query / key matrices ONCE here
+    (`iisan_deberta_rel_project`), not at the start of every forward call.  Eval mode only: `dropout` must stay None."""
+
+    def __init__(self, w: Dict[str, torch.Tensor], cfg: DebertaConfig, device="cuda", dtype16: int = _lib.IISAN_F16,
+                 project_tables: bool = True):
+        """project_tables = False leaves `rel_proj` null: every forward projects the tables into its workspace (tests; the same bits)."""
+        for k in ("pos_emb", "type_emb"):
+            if k in w:
+                raise ValueError(f"PackedDeberta: the weights have {k!r}; a DeBERTa tower (position_biased_input = False, type_vocab_size = 0) has none")
+        super().__init__(w, cfg, device, dtype16)
+        if project_tables and self.device.type == "cuda":
+            lib, s = _lib.load(), self.struct
+            self._rel = torch.empty(int(lib.iisan_deberta_rel_bytes(C.byref(s))), dtype=torch.uint8, device=self.device)
+            ws = torch.empty(int(lib.iisan_deberta_rel_ws_bytes(C.byref(s))), dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(lib.iisan_deberta_rel_project(C.byref(s), _ptr(self._rel), _ptr(ws), ws.numel(), _stream()), "iisan_deberta_rel_project")
+                # forwards may be issued on any other stream later: make the tables visible to all of them once, at pack time
+                torch.cuda.current_stream(self.device).synchronize()
+            s.rel_proj = _ptr(self._rel)
+
+    def _tables(self, s):
+        s.word_emb = self._v32("word_emb")
+        s.rel_emb, s.rel_ln_w, s.rel_ln_b = self._v32("rel_emb"), self._v32("rel_ln_w"), self._v32("rel_ln_b")
+        s.span = self.cfg.position_buckets
+
+    def _check(self, words: int, dropout):
+        if dropout is not None and (dropout[0] > 0 or dropout[1] > 0):
+            raise ValueError("PackedDeberta: the tower runs in eval mode only (no train-mode dropout)")
+        if words > self.cfg.max_words:
+            raise ValueError(f"PackedDeberta: titles of {words} words; at most position_buckets / 2 = {self.cfg.position_buckets // 2} "
+                             "(and 128) are served")
+
+    def forward_taps(self, text, tap_layers, chunk_items: int = 0, dropout=None):
+        self._check(text.shape[1] // 2, dropout)
+        return super().forward_taps(text, tap_layers, chunk_items, dropout)
+
+    def forward_taps_indexed(self, table, index, tap_layers, chunk_items: int = 0, dropout=None):
+        self._check(table.shape[1] // 2, dropout)
+        return super().forward_taps_indexed(table, index, tap_layers, chunk_items, dropout)

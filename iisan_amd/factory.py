@@ -23,9 +23,10 @@ def make_args(**kw):
 def build_model(args, item_num, pop, vit_w=None, vit_cfg=None, bert_w=None, bert_cfg=None, cached=False, device="cuda"):
     """Product `ModelMM` on canonical encoder weights (`iisan_amd.weights`); `cached`: False | True | "versa"."""
     from . import trainer
-    from .model import FrozenBert, FrozenVit, ModelMM
+    from .model import FrozenBert, FrozenDeberta, FrozenVit, ModelMM
     vit = FrozenVit(vit_w or {}, vit_cfg or weights.VIT_BASE, args.embedding_dim)
-    bert = FrozenBert(bert_w or {}, bert_cfg or weights.BERT_BASE)
+    text_tower = FrozenDeberta if isinstance(bert_cfg, weights.DebertaConfig) else FrozenBert      # (run.py:71-81: by the checkpoint's family)
+    bert = text_tower(bert_w or {}, bert_cfg or weights.BERT_BASE)
     model = ModelMM(args, item_num, True, vit, bert, pop)
     trainer.apply_iisan_freeze_rules(model, args, cached=cached)
     return model.to(device)

@@ -1,8 +1,8 @@
 """Encoders mirroring `Code_Uncached/model/encoders.py`: `MM_Encoder`, `Vit_Encoder`, `ClipVit_Encoder`, `Bert_Encoder`,
 `Text_Encoder`, `User_Encoder` — same constructors, attribute paths and state-dict keys.
 
-The frozen ViT/BERT are accepted as HuggingFace modules (`ViTForImageClassification`, `BertModel`, either
-state-dict layout) or as the light `FrozenVit` / `FrozenBert` containers below; their weights are packed once into
+The frozen ViT/BERT are accepted as HuggingFace modules (`ViTForImageClassification`, `BertModel` or `DebertaV2Model`, either
+state-dict layout) or as the light `FrozenVit` / `FrozenBert` / `FrozenDeberta` containers below; their weights are packed once into
 kernel layout (`iisan_amd.encoders.PackedVit/PackedBert`) the first time a forward runs on the GPU.
 """
 import torch
@@ -12,7 +12,7 @@ from torch.nn.init import constant_, xavier_normal_
 from .. import _lib, encoders as enc, ops, weights
 from .modules import TransformerEncoder
 
-__all__ = ["MM_Encoder", "Vit_Encoder", "ClipVit_Encoder", "Bert_Encoder", "Text_Encoder", "User_Encoder", "FrozenVit", "FrozenBert"]
+__all__ = ["MM_Encoder", "Vit_Encoder", "ClipVit_Encoder", "Bert_Encoder", "Text_Encoder", "User_Encoder", "FrozenVit", "FrozenBert", "FrozenDeberta"]
 
 
 class FrozenVit(nn.Module):
@@ -71,9 +71,51 @@ def _clip_canonical(image_net):
     return w, cfg
 
 
+class FrozenDeberta(FrozenBert):
+    """The same stand-in for `DebertaV2Model` (`Code_Uncached/run.py:71-81`): canonical DeBERTa weights + a `weights.DebertaConfig`."""
+
+    def __init__(self, w: dict, cfg: weights.DebertaConfig):
+        if not isinstance(cfg, weights.DebertaConfig):
+            raise ValueError(f"FrozenDeberta: a weights.DebertaConfig is needed, not {type(cfg).__name__}")
+        super().__init__(w, cfg)
+
+
+def _deberta_canonical(bert_model):
+    """(canonical weights, DebertaConfig) of an HF `DebertaV2Model` in the one configuration the executor implements — what the v3 xsmall /
+    small / base / large checkpoints carry; anything else is refused here, naming the config field, never run approximately."""
+    c = bert_model.config
+    pos_att = set(c.pos_att_type or ())
+    refusals = (
+        ("conv_kernel_size", int(getattr(c, "conv_kernel_size", 0) or 0) > 0, "the convolutional v2-xlarge / xxlarge variants are not implemented"),
+        ("position_biased_input", bool(c.position_biased_input), "absolute position embeddings in the input are not implemented"),
+        ("relative_attention", not c.relative_attention, "the tower is built around relative attention"),
+        ("share_att_key", not getattr(c, "share_att_key", False), "separate pos_key_proj / pos_query_proj matrices are not implemented"),
+        ("pos_att_type", pos_att != {"c2p", "p2c"}, f"{sorted(pos_att)}: both terms, c2p and p2c, are needed"),
+        ("embedding_size", getattr(c, "embedding_size", c.hidden_size) != c.hidden_size, "embedding_size != hidden_size (embed_proj) is not implemented"),
+        ("norm_rel_ebd", "layer_norm" not in str(getattr(c, "norm_rel_ebd", "none")).lower(), "the relative-position table must be LayerNorm'd (layer_norm)"),
+        ("type_vocab_size", int(c.type_vocab_size) > 0, "token-type embeddings are not implemented"),
+    )
+    for field, bad, why in refusals:
+        if bad:
+            raise ValueError(f"DeBERTa tower: config.{field} = {getattr(c, field, None)!r} is not supported: {why}")
+    buckets = int(c.position_buckets) if c.position_buckets > 0 else int(c.max_relative_positions)
+    cfg = weights.DebertaConfig(hidden=c.hidden_size, layers=c.num_hidden_layers, heads=c.num_attention_heads, mlp=c.intermediate_size,
+                                vocab=c.vocab_size, max_pos=c.max_position_embeddings, position_buckets=buckets, eps=c.layer_norm_eps,
+                                hidden_dropout=float(c.hidden_dropout_prob), attn_dropout=float(c.attention_probs_dropout_prob))
+    return weights.deberta_from_hf(bert_model.state_dict()), cfg
+
+
+def _is_deberta(bert_model) -> bool:
+    if hasattr(bert_model, "canonical_weights"):
+        return isinstance(bert_model.canonical_weights()[1], weights.DebertaConfig)
+    return getattr(bert_model.config, "model_type", "") == "deberta-v2"
+
+
 def _bert_canonical(bert_model):
     if hasattr(bert_model, "canonical_weights"):
         return bert_model.canonical_weights()
+    if _is_deberta(bert_model):
+        return _deberta_canonical(bert_model)
     c = bert_model.config
     cfg = weights.BertConfig(hidden=c.hidden_size, layers=c.num_hidden_layers, heads=c.num_attention_heads,
                              mlp=c.intermediate_size, vocab=c.vocab_size, max_pos=c.max_position_embeddings,
@@ -209,8 +251,13 @@ class Text_Encoder(nn.Module):                     # encoders.py:68-91
         seed)` with a fresh seed.  Only the training forward (`IISANAdaptedMModel.forward_item3[_indexed]`) asks for it: a bare
         `forward_taps(...)` is deterministic whatever the module's mode (evaluate.py builds its tap caches through it).  A forward
         under `torch.no_grad()` is not a training step either: `evaluate.item_table` goes through `forward_item3` that way, without
-        `model.eval()`, and must give the same table whatever the switch says."""
+        `model.eval()`, and must give the same table whatever the switch says.
+        A DeBERTa tower answers None whatever `train_dropout` says: its embedding step and its disentangled attention have no train-mode
+        instantiation, the executor refuses a non-zero probability on such a tower, and the tower is eval only — like every BERT tower of a
+        width other than 768 ("Numeric deviations")."""
         if not (self.train_dropout and self.training and torch.is_grad_enabled()):
+            return None
+        if _is_deberta(self.bert_model):
             return None
         hidden_p, attn_p = self.dropout_probs()
         if hidden_p <= 0.0 and attn_p <= 0.0:

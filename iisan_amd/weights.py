@@ -21,6 +21,8 @@ ViT  : cls_token[D] pos_emb[T,D] patch_w[D,3*P*P] patch_b[D] lnf_w[D] lnf_b[D]
 BERT : word_emb[V,D] pos_emb[P,D] type_emb[2,D] emb_ln_w emb_ln_b
        L{l}.qkv_w L{l}.qkv_b L{l}.o_w L{l}.o_b L{l}.ln1_w L{l}.ln1_b   (post-attention LayerNorm)
        L{l}.fc1_w L{l}.fc1_b L{l}.fc2_w L{l}.fc2_b L{l}.ln2_w L{l}.ln2_b (post-FFN LayerNorm)
+DeBERTa-v2/v3 (`DebertaConfig`): the BERT names without pos_emb / type_emb, + rel_emb[2*position_buckets, D] rel_ln_w rel_ln_b
+       (encoder.rel_embeddings, encoder.LayerNorm); qkv_w stacks query_proj / key_proj / value_proj
 """
 from __future__ import annotations
 
@@ -112,6 +114,33 @@ _CLIP = dict(eps=1e-5, pre_ln=True, act="quick_gelu", patch_bias=False)
 CLIP_VIT_B32 = VitConfig(patch=32, **_CLIP)
 CLIP_VIT_B16 = VitConfig(patch=16, **_CLIP)
 CLIP_VIT_L14 = VitConfig(hidden=1024, layers=24, heads=16, mlp=4096, patch=14, **_CLIP)
+@dataclass(frozen=True)
+class DebertaConfig:
+    """Shape of a DeBERTa-v2/v3 text tower (`Code_Uncached/run.py:71-81`: `DebertaV2Model` when 'deberta' is in `bert_model_load`), in the
+    one configuration the v3 checkpoints carry: relative_attention, share_att_key, pos_att_type = c2p|p2c, norm_rel_ebd = layer_norm,
+    position_biased_input = False, type_vocab_size = 0.  `position_buckets` is the `span` of the relative-position table [2 span, D];
+    titles of at most span / 2 words are served (there HF's log-bucket map is the identity)."""
+    hidden: int = 768
+    layers: int = 12
+    heads: int = 12
+    mlp: int = 3072
+    vocab: int = 128100
+    max_pos: int = 512
+    position_buckets: int = 256
+    eps: float = 1e-7
+    # of the HF config, for completeness: the tower runs in eval mode only (`Text_Encoder.step_dropout`)
+    hidden_dropout: float = 0.1
+    attn_dropout: float = 0.1
+
+    @property
+    def max_words(self) -> int:
+        return min(self.position_buckets // 2, 128)
+
+
+DEBERTA_V3_XSMALL = DebertaConfig(hidden=384, layers=12, heads=6, mlp=1536)
+DEBERTA_V3_SMALL = DebertaConfig(hidden=768, layers=6, heads=12, mlp=3072)
+DEBERTA_V3_BASE = DebertaConfig(hidden=768, layers=12, heads=12, mlp=3072)
+DEBERTA_V3_LARGE = DebertaConfig(hidden=1024, layers=24, heads=16, mlp=4096)
 BERT_TINY = BertConfig(hidden=128, layers=2, heads=2, mlp=512, vocab=30522, eps=1e-12)
 BERT_MINI = BertConfig(hidden=256, layers=4, heads=4, mlp=1024, vocab=30522, eps=1e-12)
 
@@ -167,6 +196,36 @@ def make_bert_weights(cfg: BertConfig = BERT_BASE, seed: int = 4321, std: float 
         "type_emb": _normal(rs, (2, D), std),
         "emb_ln_w": 1.0 + _normal(rs, (D,), ln_jitter),
         "emb_ln_b": _normal(rs, (D,), ln_jitter),
+    }
+    for l in range(cfg.layers):
+        p = f"L{l}."
+        w[p + "qkv_w"] = _normal(rs, (3 * D, D), std)
+        w[p + "qkv_b"] = _normal(rs, (3 * D,), std)
+        w[p + "o_w"] = _normal(rs, (D, D), std)
+        w[p + "o_b"] = _normal(rs, (D,), std)
+        w[p + "ln1_w"] = 1.0 + _normal(rs, (D,), ln_jitter)
+        w[p + "ln1_b"] = _normal(rs, (D,), ln_jitter)
+        w[p + "fc1_w"] = _normal(rs, (F, D), std)
+        w[p + "fc1_b"] = _normal(rs, (F,), std)
+        w[p + "fc2_w"] = _normal(rs, (D, F), std)
+        w[p + "fc2_b"] = _normal(rs, (D,), std)
+        w[p + "ln2_w"] = 1.0 + _normal(rs, (D,), ln_jitter)
+        w[p + "ln2_b"] = _normal(rs, (D,), ln_jitter)
+    return w
+
+
+def make_deberta_weights(cfg: DebertaConfig = DEBERTA_V3_BASE, seed: int = 2468, std: float = 0.02,
+                         ln_jitter: float = 0.05) -> Dict[str, torch.Tensor]:
+    """Seeded random DeBERTa weights: the BERT layer names, no pos_emb / type_emb, + rel_emb [2 span, D] and its LayerNorm rel_ln_w / rel_ln_b."""
+    rs = np.random.RandomState(seed)
+    D, F = cfg.hidden, cfg.mlp
+    w = {
+        "word_emb": _normal(rs, (cfg.vocab, D), std),
+        "emb_ln_w": 1.0 + _normal(rs, (D,), ln_jitter),
+        "emb_ln_b": _normal(rs, (D,), ln_jitter),
+        "rel_emb": _normal(rs, (2 * cfg.position_buckets, D), std),
+        "rel_ln_w": 1.0 + _normal(rs, (D,), ln_jitter),
+        "rel_ln_b": _normal(rs, (D,), ln_jitter),
     }
     for l in range(cfg.layers):
         p = f"L{l}."
@@ -378,6 +437,74 @@ def bert_to_hf(w: Dict[str, torch.Tensor], cfg: BertConfig) -> Dict[str, torch.T
         sd[b + "output.dense.weight"], sd[b + "output.dense.bias"] = w[p + "fc2_w"], w[p + "fc2_b"]
         sd[b + "output.LayerNorm.weight"], sd[b + "output.LayerNorm.bias"] = w[p + "ln2_w"], w[p + "ln2_b"]
     return sd
+
+
+_DEBERTA_LAYER_KEYS = (("o_w", "attention.output.dense.weight"), ("o_b", "attention.output.dense.bias"),
+                       ("ln1_w", "attention.output.LayerNorm.weight"), ("ln1_b", "attention.output.LayerNorm.bias"),
+                       ("fc1_w", "intermediate.dense.weight"), ("fc1_b", "intermediate.dense.bias"),
+                       ("fc2_w", "output.dense.weight"), ("fc2_b", "output.dense.bias"),
+                       ("ln2_w", "output.LayerNorm.weight"), ("ln2_b", "output.LayerNorm.bias"))
+
+
+def deberta_from_hf(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Canonical DeBERTa weights from a `DebertaV2Model` state dict (`deberta.` prefix tolerated): query_proj / key_proj / value_proj are
+    stacked into qkv_w / qkv_b.  A checkpoint outside the supported configuration is named by the key that shows it."""
+    sd = _strip_prefix(sd, ("deberta.",))
+    for bad, why in (("embeddings.position_embeddings.weight", "position_biased_input"), ("encoder.conv.conv.weight", "conv_kernel_size > 0"),
+                     ("embeddings.embed_proj.weight", "embedding_size != hidden_size"),
+                     ("encoder.layer.0.attention.self.pos_key_proj.weight", "share_att_key = False")):
+        if bad in sd:
+            raise ValueError(f"deberta_from_hf: the state dict has {bad!r} ({why}): not a supported DeBERTa-v2/v3 configuration")
+    for need in ("encoder.rel_embeddings.weight", "encoder.LayerNorm.weight"):
+        if need not in sd:
+            raise ValueError(f"deberta_from_hf: the state dict lacks {need!r} (relative_attention with norm_rel_ebd = layer_norm is required)")
+    w = {
+        "word_emb": sd["embeddings.word_embeddings.weight"],
+        "emb_ln_w": sd["embeddings.LayerNorm.weight"],
+        "emb_ln_b": sd["embeddings.LayerNorm.bias"],
+        "rel_emb": sd["encoder.rel_embeddings.weight"],
+        "rel_ln_w": sd["encoder.LayerNorm.weight"],
+        "rel_ln_b": sd["encoder.LayerNorm.bias"],
+    }
+    l = 0
+    while f"encoder.layer.{l}.attention.self.query_proj.weight" in sd:
+        b, p = f"encoder.layer.{l}.", f"L{l}."
+        w[p + "qkv_w"] = torch.cat([sd[b + f"attention.self.{x}_proj.weight"] for x in ("query", "key", "value")], 0)
+        w[p + "qkv_b"] = torch.cat([sd[b + f"attention.self.{x}_proj.bias"] for x in ("query", "key", "value")], 0)
+        for ours, theirs in _DEBERTA_LAYER_KEYS:
+            w[p + ours] = sd[b + theirs]
+        l += 1
+    return {k: v.detach().float().contiguous() for k, v in w.items()}
+
+
+def deberta_to_hf(w: Dict[str, torch.Tensor], cfg: DebertaConfig, prefix: str = "") -> Dict[str, torch.Tensor]:
+    """Canonical -> `DebertaV2Model` state dict (prefix "deberta.": the key names of a task model's checkpoint)."""
+    D = cfg.hidden
+    sd = {
+        "embeddings.word_embeddings.weight": w["word_emb"],
+        "embeddings.LayerNorm.weight": w["emb_ln_w"],
+        "embeddings.LayerNorm.bias": w["emb_ln_b"],
+        "encoder.rel_embeddings.weight": w["rel_emb"],
+        "encoder.LayerNorm.weight": w["rel_ln_w"],
+        "encoder.LayerNorm.bias": w["rel_ln_b"],
+    }
+    for l in range(cfg.layers):
+        p, b = f"L{l}.", f"encoder.layer.{l}."
+        for n, ww, bb in zip(("query", "key", "value"), w[p + "qkv_w"].split(D, 0), w[p + "qkv_b"].split(D, 0)):
+            sd[b + f"attention.self.{n}_proj.weight"], sd[b + f"attention.self.{n}_proj.bias"] = ww, bb
+        for ours, theirs in _DEBERTA_LAYER_KEYS:
+            sd[b + theirs] = w[p + ours]
+    return {prefix + k: v for k, v in sd.items()}
+
+
+def deberta_hf_config_kwargs(cfg: DebertaConfig) -> dict:
+    """The `DebertaV2Config` arguments of the supported configuration at the shape of `cfg` (the golden generator and the tests build HF
+    modules from it)."""
+    return dict(vocab_size=cfg.vocab, hidden_size=cfg.hidden, num_hidden_layers=cfg.layers, num_attention_heads=cfg.heads,
+                intermediate_size=cfg.mlp, max_position_embeddings=cfg.max_pos, layer_norm_eps=cfg.eps, type_vocab_size=0,
+                relative_attention=True, position_buckets=cfg.position_buckets, max_relative_positions=-1, norm_rel_ebd="layer_norm",
+                share_att_key=True, pos_att_type=["p2c", "c2p"], position_biased_input=False, hidden_act="gelu",
+                hidden_dropout_prob=cfg.hidden_dropout, attention_probs_dropout_prob=cfg.attn_dropout, pad_token_id=0)
 
 
 def config_dict(cfg) -> dict:

@@ -121,7 +121,33 @@ typedef struct {
     const float* type_emb;                    /* [2, D] (row 0 used)                                            */
     const float* emb_ln_w; const float* emb_ln_b;
     iisan_layer_weights layer[IISAN_MAX_LAYERS];
+    /* ---- DeBERTa-v2/v3 towers (HF DebertaV2Model: relative_attention, share_att_key, pos_att_type c2p|p2c, norm_rel_ebd = layer_norm,
+     * position_biased_input = False, type_vocab_size = 0); all zero = the BERT above.  rel_emb != NULL makes the struct a DeBERTa tower:
+     * pos_emb / type_emb are then NULL and are not read, hidden state 0 is LayerNorm(word_emb[id]) * mask, and every block's attention is
+     * iisan_attention16_disent (csrc/attn16_disent.hip).  The rest of the block is BERT's post-LN block — all three entry points, chunk_items,
+     * full_blocks, both operand types and the dev switch resid32 work as for BERT.  IISAN_EBADSHAPE before any launch: words > span / 2 (there
+     * HF's log-bucket map of relative positions stops being the identity; no approximation is attempted) or words > 128; span < 1 or
+     * span > 256; any non-zero dropout probability (iisan_bert_forward_taps_dropout: the tower is eval only, like every non-768 BERT); a
+     * hidden size outside the BERT executor's set; rel_ln_w / rel_ln_b missing, or pos_emb / type_emb set beside rel_emb. ---- */
+    const float* rel_emb;                     /* [2 span, D] fp32: encoder.rel_embeddings.weight                */
+    const float* rel_ln_w; const float* rel_ln_b;   /* [D]: encoder.LayerNorm, applied to the table once         */
+    int32_t span;                             /* position_buckets: 1 .. 256; titles of at most span / 2 (and 128) words */
+    /* OPTIONAL (null = none): the projected tables of every layer, filled ONCE by iisan_deberta_rel_project into a caller-owned device
+     * buffer of iisan_deberta_rel_bytes() bytes.  Without it every forward call projects them again into its workspace
+     * (iisan_bert_forward_taps_ws_bytes grows by that much for such a struct only; the result is the same). */
+    const void* rel_proj;
 } iisan_bert_weights;
+
+/* The position tables of a DeBERTa tower, projected by every layer's own query / key matrices (HF: pos_key_layer = key_proj(rel),
+ * pos_query_layer = query_proj(rel), rel = LayerNorm(rel_embeddings.weight)).  Layout of `out`, 16-bit in the tower's operand type:
+ *     [layers][heads][3][2 span][64]      third 0 = PQ = query_proj(rel), third 1 = PK = key_proj(rel), third 2 = value_proj(rel) (unused)
+ * — per layer the head-major QKV image of ONE pseudo-item of 2 span tokens, written by the QKV epilogue of iisan_gemm16 itself; row d of a
+ * table belongs to the relative position i - j = d - span.  `ws`: iisan_deberta_rel_ws_bytes() bytes (the 16-bit LayerNorm image of the table,
+ * padded to a GEMM row tile).  IISAN_EBADSHAPE before any launch: no rel_emb / rel_ln_w / rel_ln_b, span outside 1 .. 256, an unsupported
+ * hidden size; IISAN_EWORKSPACE: out == NULL or a workspace that is too small. */
+size_t iisan_deberta_rel_bytes(const iisan_bert_weights* w);
+size_t iisan_deberta_rel_ws_bytes(const iisan_bert_weights* w);
+int iisan_deberta_rel_project(const iisan_bert_weights* w, void* out, void* ws, size_t ws_bytes, void* stream);
 
 /* Replaces Vit_Encoder.forward + `[:,0]` tap selection (Code_Uncached/model/encoders.py:29-31, model.py:210,212):
  * images fp32 [M,C,R,R] -> taps fp32 [M, n_taps, D], taps[:,k] = CLS row of hidden state tap_layers[k]
@@ -444,6 +470,17 @@ int iisan_attention16_hd80(int32_t dtype16, const void* qkv, const float* key_bi
  * 1 <= S <= 1024 (a score row of 256 keys per wave up to S = 256, of 1,024 beyond); S > 1024: IISAN_EBADSHAPE, nothing launched. */
 int iisan_attention_cls16(int32_t dtype16, const void* qkv, const float* key_bias, void* ctx_cls, int64_t items,
                           int32_t S, int32_t heads, void* stream);
+/* Disentangled attention of DeBERTa-v2/v3 (csrc/attn16_disent.hip), per (item, head), with delta(i, j) = i - j + span:
+ *     score[i][j] = (Q_i . K_j + Q_i . PK[delta] + K_j . PQ[delta]) / sqrt(3 * 64) + key_bias[j],   ctx = softmax_j(score) V
+ * qkv, key_bias and ctx exactly as for iisan_attention16; `rel` = ONE layer of the iisan_deberta_rel_project image, 16-bit
+ * [heads][3][2 span][64] (third 0 = PQ, third 1 = PK).  The three products accumulate in fp32 on the matrix cores; P and the context are
+ * rounded to the operand type as in iisan_attention16.  1 <= S <= min(128, span) and 1 <= span <= 256 (the pairs of a title then reach rows
+ * 1 .. 2 span - 1 of a table, all of them inside it); anything else is IISAN_EBADSHAPE, nothing launched. */
+int iisan_attention16_disent(int32_t dtype16, const void* qkv, const void* rel, const float* key_bias, void* ctx, int64_t items,
+                             int32_t S, int32_t heads, int32_t span, void* stream);
+/* the same for the CLS query (token 0) of every item only — both positional indices are span - j —: ctx_cls 16-bit [items, H*64] */
+int iisan_attention_cls16_disent(int32_t dtype16, const void* qkv, const void* rel, const float* key_bias, void* ctx_cls, int64_t items,
+                                 int32_t S, int32_t heads, int32_t span, void* stream);
 /* iisan_attention16 (cls_only == 0) / iisan_attention_cls16 (cls_only != 0; the query is token 0 of the q block) with the
  * probabilities dropped at `site` (iisan_bert_dropout; slot m = item); p = 0 gives the bits of iisan_attention16.  S <= 224. */
 int iisan_attention16_dropout(int32_t dtype16, const void* qkv, const float* key_bias, void* ctx, int64_t items, int32_t S,
@@ -527,6 +564,10 @@ int32_t iisan_inbatch_ce_route_e(int64_t bs, int32_t S, int32_t E);
 #define IISAN_TOWER_VIT 0
 #define IISAN_TOWER_BERT 1
 #define IISAN_TOWER_CLIP 2
+/* IISAN_TOWER_DEBERTA: the BERT executor's decision for a DeBERTa tower (rel_emb != NULL), the BERT bit meanings.  The last argument is then
+ * the tower's `span` (position_buckets) instead of `folded`: tokens > span / 2, tokens > 128 or a span outside 1 .. 256 are refused like
+ * the forward refuses them. */
+#define IISAN_TOWER_DEBERTA 3
 int32_t iisan_encoder_plan(int32_t tower, int32_t dtype16, int32_t hidden, int32_t heads, int32_t mlp, int32_t tokens, int64_t M,
                            int64_t chunk_items, int32_t deepest_tap, int32_t full_blocks, int32_t folded);
 
