@@ -34,7 +34,13 @@ def _stream():
 # number of (item, head) pairs, the idle half of the last workgroup of the two-pair kernel
 ATTN_CASES = [(3, 1, 2, 256, False), (3, 2, 12, 256, True), (1, 15, 2, 256, True), (3, 16, 2, 256, False), (3, 17, 12, 256, True),
               (130, 30, 12, 256, True), (130, 30, 2, 256, False), (1, 30, 3, 256, True), (3, 33, 2, 256, True), (3, 64, 2, 256, False),
-              (1, 127, 2, 256, True), (3, 128, 12, 256, True), (3, 128, 2, 256, False), (3, 17, 2, 32, True), (3, 32, 12, 32, False)]
+              (1, 127, 2, 256, True), (3, 128, 12, 256, True), (3, 128, 2, 256, False), (3, 17, 2, 32, True), (3, 32, 12, 32, False),
+              # more workgroups than the 256 CUs hold on the 64- and the 128-word instantiations too: 840 and 540 (the 128-word image takes
+              # 118 KiB of LDS: one workgroup per CU)
+              (70, 64, 12, 256, True), (45, 128, 12, 256, True),
+              # spans shorter than the padded title (S <= span < SP = 16 ceil(S / 16)): both ends of the table image in LDS are clamped
+              # re-reads, and S == span reaches table row 2 span - 1
+              (3, 5, 2, 5, True), (3, 17, 2, 17, False), (2, 100, 2, 100, True)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -108,6 +114,76 @@ def test_disentangled_attention_negative_controls(lib, dt, case):
         assert (got[:, 0] - wrong[:, 0]).abs().max().item() > tol, what
 
 
+UNREACHABLE_CASES = [(3, 30, 12, 256, True), (3, 17, 2, 32, True), (2, 100, 2, 256, False)]
+POISON_ROW = 30000.0        # finite in fp16 and bf16; a 64-term dot product with |q| < 8 stays finite in fp32 (64 * 8 * 30,000 = 1.5e7)
+
+
+@functools.lru_cache(maxsize=None)
+def _unreachable_problem(items, S, heads, span, masked, dt):
+    """q, k, v (|.| < 8) and two table images that agree on the rows a real (query, key) pair of an S-word title reads, d = i - j + span in
+    [span - S + 1, span + S - 1]: every other row is zero in the first and +-30,000 in alternating sign in the second."""
+    g = torch.Generator().manual_seed(S * 17 + heads + span)
+    qkv = (torch.randn(items, heads, 3, S, 64, generator=g) * 1.5).clamp_(-7.5, 7.5).to(T16[dt])
+    rel = (torch.randn(heads, 3, 2 * span, 64, generator=g) * 1.5).to(T16[dt])
+    d = torch.arange(2 * span)
+    dead = (d < span - S + 1) | (d > span + S - 1)
+    assert dead.sum() == 2 * span - (2 * S - 1) and not dead[span]
+    sign = torch.where(torch.arange(64) % 2 == 0, 1.0, -1.0) * torch.where(d % 2 == 0, 1.0, -1.0)[:, None]
+    zero, poison = rel.clone(), rel.clone()
+    zero[:, :, dead] = 0
+    poison[:, :, dead] = (sign[dead] * POISON_ROW).to(T16[dt])
+    assert torch.isfinite(poison).all() and poison[:, :, dead].float().abs().min() > 29000
+    kb = None
+    if masked:
+        kb = torch.zeros(items, S)
+        for i in range(1, items):
+            kb[i, int(torch.randint(1, S + 1, (1,), generator=g)):] = -1.0
+        kb[0, :] = -1.0
+    return qkv, zero, poison, kb
+
+
+def _disent_ref(qkv, rel, kb, span):
+    q, k, v = (qkv[:, :, i].double() for i in range(3))
+    items, heads, S = q.shape[:3]
+    return DO.disentangled_attention(q, k, v, rel[:, 0].double(), rel[:, 1].double(), kb, span).transpose(1, 2).reshape(items, S, heads * 64)
+
+
+@pytest.mark.parametrize("dt", [F16, BF16])
+@pytest.mark.parametrize("case", UNREACHABLE_CASES)
+def test_unreachable_table_rows_have_no_influence(lib, dt, case):
+    """The kernel header's promise: table rows no real (query, key) pair can reach — the rows the LDS image holds for pad keys and pad
+    queries, and every row the image never holds — have no influence.  The full kernel and the CLS form, run on a table whose unreachable
+    rows are zero and on one where they hold +-30,000, give the same, finite bits."""
+    items, S, heads, span, masked = case
+    qkv, zero, poison, kb = _unreachable_problem(*case, dt)
+    assert qkv.float().abs().max() < 8
+    for cls in (False, True):
+        a = _run_attn(lib, dt, qkv, zero, kb, items, S, heads, span, cls=cls)
+        b = _run_attn(lib, dt, qkv, poison, kb, items, S, heads, span, cls=cls)
+        what = f"{'cls form' if cls else 'full kernel'} dt={dt} {case}"
+        assert torch.isfinite(a).all() and torch.isfinite(b).all(), what
+        assert torch.equal(a, b), f"{what}: {(a != b).sum().item()} elements depend on rows no real pair reaches"
+
+
+@pytest.mark.parametrize("dt", [F16, BF16])
+@pytest.mark.parametrize("case", UNREACHABLE_CASES)
+def test_control_a_reachable_table_row_has_influence(dt, case):
+    """On the CPU, so that the row classification above cannot be vacuous: the float64 reference does not see the unreachable rows either,
+    and with ONE reachable row changed (d = span, the diagonal i == j) it moves by more than the bound of the primitive test."""
+    items, S, heads, span, masked = case
+    qkv, zero, poison, kb = _unreachable_problem(*case, dt)
+    ref = _disent_ref(qkv, zero, kb, span)
+    assert torch.equal(_disent_ref(qkv, poison, kb, span), ref)
+    tol = 2.5 * PRIM_TOL[dt] * ref.abs().max().item()
+    moved = zero.clone()
+    moved[:, :, span] = -moved[:, :, span]
+    sep = (_disent_ref(qkv, moved, kb, span) - ref).abs().max().item()
+    print(f"dt={dt} {case}: one reachable row changed moves the reference by {sep:.3e}, bound {tol:.3e}")
+    assert sep > tol
+    # ... on the CLS row too (the CLS form reads d = span - j: the row is reachable from query 0 through key 0)
+    assert (_disent_ref(qkv, moved, kb, span)[:, 0] - ref[:, 0]).abs().max().item() > tol
+
+
 @pytest.mark.parametrize("cls", [False, True])
 @pytest.mark.parametrize("S,span,why", [(129, 256, "sequence length 129"), (17, 16, "sequence length 17"), (8, 257, "span 257"), (0, 16, "sequence length 0")])
 def test_disentangled_attention_refusals(lib, cls, S, span, why):
@@ -124,10 +200,11 @@ def test_disentangled_attention_refusals(lib, cls, S, span, why):
 # ---- b. the table projection -------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("dt", [F16, BF16])
-@pytest.mark.parametrize("span,D", [(16, 128), (256, 128), (16, 768), (256, 768)])
+@pytest.mark.parametrize("span,D", [(16, 128), (256, 128), (16, 768), (256, 768), (100, 384), (1, 128), (256, 1024)])
 def test_table_projection_vs_float64(lib, dt, span, D):
     """iisan_deberta_rel_project: [layers][heads][3][2 span][64], third 0 = query_proj(LN(table)), third 1 = key_proj(LN(table)), against
-    float64 LayerNorm + Linear on the 16-bit-rounded matrices, relative to the output scale."""
+    float64 LayerNorm + Linear on the 16-bit-rounded matrices, relative to the output scale.  (100, 384): a table that ends inside a
+    256-row tile; (1, 128): the smallest table, two rows; 384 and 1024: every width a DeBERTa tower has."""
     cfg = weights.DebertaConfig(hidden=D, layers=2, heads=D // 64, mlp=256, vocab=64, position_buckets=span)
     w = weights.make_deberta_weights(cfg, seed=71, std=0.05)
     pk = encoders.PackedDeberta(w, cfg, "cuda", dt)

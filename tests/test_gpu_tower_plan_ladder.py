@@ -9,8 +9,8 @@ of each step) with no development switch set — every case first asserts its pl
   A  duplicates     the content of one item planted into slot 1, the last slot and the slots either side of every 256-row tile boundary and
                     32-row block boundary of the first and the last tile: all copies carry identical taps (bitwise)
   B  permutation    taps(x[perm]) == taps(x)[perm] (bitwise)
-  C  composition    a same-plan sub-batch (the first M - 40 items; where M - 40 lies below the case's step or does not exist — 13 of the
-                    20 cases — the step's first M or half the batch, and where the case IS the step's first M, the case inside M + 5
+  C  composition    a same-plan sub-batch (the first M - 40 items; where M - 40 lies below the case's step or does not exist — 22 of the
+                    35 cases — the step's first M or half the batch, and where the case IS the step's first M, the case inside M + 5
                     items: profiles/tower_plan_ladder.md) gives the same bits;
                     the chunked call equals the unchunked one; the indexed entry equals the materialised call
   D  stale scratch  the workspace filled with 0x00, 0xFF (NaN in fp16 / bf16 / fp32) and 0x7B (61,280 in fp16, 1.3e36 in bf16 / fp32: finite,
@@ -24,7 +24,13 @@ of each step) with no development switch set — every case first asserts its pl
                     tools/tower_plan_ladder.py, recorded per case and tap in profiles/tower_plan_ladder.md.
 
 Same seeded 2-layer towers and taps [0, 1, 2] as the other encoder tests; what varies is batch size, slot position and what lies behind the
-live rows.  Negative controls at the end show that each comparison can fail."""
+live rows.  Negative controls at the end show that each comparison can fail.
+
+Four tower families run here: the plain ViT and BERT towers, the CLIP vision towers (the ViT executor behind a pre-LayerNorm, quick-GELU, no
+patch bias: oracle tests/clip_oracle.py) and the DeBERTa-v2/v3 text towers (the BERT executor with the masked-LayerNorm embedding step and
+the disentangled attention kernel: oracle tests/deberta_oracle.py).  The CLIP-L/14 case at its real 257 tokens compares 8 slots in E, not
+24 — slot 0, the last slot, the planted item and its tile-boundary duplicates come first in the subset, so these stay — which keeps the
+float64 oracle of 257 x 1024-wide tokens per slot to seconds on the CPU."""
 from collections import namedtuple
 from types import SimpleNamespace
 
@@ -34,18 +40,22 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import clip_oracle as CO  # noqa: E402
+import deberta_oracle as DO  # noqa: E402
 from iisan_amd import _lib, encoders, synth, weights  # noqa: E402
 from oracle import iisan_oracle as O  # noqa: E402
-from test_tower_plan_ladder_host import BERT, VIT, plan_code  # noqa: E402
+from test_tower_plan_ladder_host import BERT, CLIP, DEBERTA, VIT, plan_code  # noqa: E402
 
 TAPS = [0, 1, 2]
 TAP_TOL = {_lib.IISAN_F16: 1.5e-3, _lib.IISAN_BF16: 1.2e-2}      # relative Frobenius error per tap (tests/test_gpu_long_towers.py)
 TAP0_VIT, TAP0_BERT = 1e-6, 1e-5                                  # tap 0: no 16-bit arithmetic on the CLS row / fp32 gather + LayerNorm
+TAP0 = {VIT: TAP0_VIT, BERT: TAP0_BERT, CLIP: 1e-5, DEBERTA: 1e-5}  # CLIP: the pre-LayerNorm of the CLS row; DeBERTa: LayerNorm(word row) * mask
 F16, BF16 = _lib.IISAN_F16, _lib.IISAN_BF16
 SRC = 2                 # the item whose content is planted
 OTHERS = 2203           # items of the larger call of the grow-only sequence
 POISON = (0x00, 0xFF, 0x7B)
 
+_CLIP = dict(eps=1e-5, pre_ln=True, act="quick_gelu", patch_bias=False)
 TOWERS = {
     "vit5": weights.VitConfig(hidden=768, layers=2, heads=12, mlp=3072, image=32, patch=16),
     "vit10": weights.VitConfig(hidden=768, layers=2, heads=12, mlp=3072, image=48, patch=16),
@@ -54,8 +64,19 @@ TOWERS = {
     "vit5n": weights.VitConfig(hidden=192, layers=2, heads=3, mlp=768, image=32, patch=16),
     "bert30": weights.BertConfig(hidden=768, layers=2, heads=12, mlp=3072, vocab=512, max_pos=64),
     "bert8n": weights.BertConfig(hidden=128, layers=2, heads=2, mlp=512, vocab=512, max_pos=64),
+    "deb30": weights.DebertaConfig(hidden=768, layers=2, heads=12, mlp=3072, vocab=DO.VOCAB, position_buckets=256),
+    "deb128": weights.DebertaConfig(hidden=768, layers=2, heads=12, mlp=3072, vocab=DO.VOCAB, position_buckets=256),
+    "debL30": weights.DebertaConfig(hidden=1024, layers=2, heads=16, mlp=4096, vocab=DO.VOCAB, position_buckets=256),
+    "debX30": weights.DebertaConfig(hidden=384, layers=2, heads=6, mlp=1536, vocab=DO.VOCAB, position_buckets=256),
+    "clip5": weights.VitConfig(hidden=768, layers=2, heads=12, mlp=3072, image=32, patch=16, **_CLIP),
+    "clip50": weights.VitConfig(hidden=768, layers=2, heads=12, mlp=3072, image=224, patch=32, **_CLIP),           # B/32 at 224 px
+    "clipL5": weights.VitConfig(hidden=1024, layers=2, heads=16, mlp=4096, image=28, patch=14, **_CLIP),
+    "clipL257": weights.VitConfig(hidden=1024, layers=2, heads=16, mlp=4096, image=224, patch=14, **_CLIP),        # L/14 at 224 px
 }
-WORDS = {"bert30": 30, "bert8n": 8}
+WORDS = {"bert30": 30, "bert8n": 8, "deb30": 30, "deb128": 128, "debL30": 30, "debX30": 30}
+# weight and pool seeds: the seven towers of the first twenty cases keep theirs (80 + their rank by name), the later towers follow
+SEEDS = {name: 80 + i for i, name in enumerate(["bert30", "bert8n", "vit10", "vit197", "vit5", "vit5n", "vit5w",
+                                                "deb30", "deb128", "debL30", "debX30", "clip5", "clip50", "clipL5", "clipL257"])}
 
 Case = namedtuple("Case", "name tower dt M plan chunk full", defaults=(0, 0))
 CASES = [
@@ -79,7 +100,23 @@ CASES = [
     Case("vit5-chunk-2300", "vit5", F16, 2300, "I", 2200),
     Case("vit5n-37", "vit5n", F16, 37, "I"),                # the narrow towers: row kernels that share a wave between rows, odd row counts
     Case("bert8n-37", "bert8n", F16, 37, "Ma"),
+    Case("deb30-358", "deb30", F16, 358, "Ma"),             # 10,740 rows of the masked-LayerNorm embedding step, every product on 128x128
+    Case("deb30-367", "deb30", F16, 367, "Maf"),            # head-major QKV of gemm16_h256 into the disentangled kernel, block-major F1
+    Case("deb30-bf16-367", "deb30", BF16, 367, "Mf"),
+    Case("deb128-85", "deb128", F16, 85, "Maf"),            # the 128-word instantiation: one workgroup per CU
+    Case("debL30-265", "debL30", F16, 265, "Maf"),
+    Case("debX30-367", "debX30", F16, 367, "Ma"),           # N % 256 != 0: never f
+    Case("deb30-chunk-759", "deb30", F16, 759, "Maf", 400), # the tables projected once, read by both chunks
+    Case("clip5-2150", "clip5", F16, 2150, "I"),
+    Case("clip5-2203", "clip5", F16, 2203, "If"),
+    Case("clip5-full-2203", "clip5", F16, 2203, "If", 0, 1),
+    Case("clip5-bf16-2203", "clip5", BF16, 2203, "If"),
+    Case("clip50-216", "clip50", F16, 216, "If"),
+    Case("clipL5-1603", "clipL5", F16, 1603, "If"),         # 14-pixel patches: the padded patch matrix
+    Case("clipL257-31", "clipL257", F16, 31, "If"),         # streaming-softmax attention, 14-pixel patches, quick-GELU on gemm16_h256 at once
+    Case("clip5-chunk-4363", "clip5", F16, 4363, "If", 2200),
 ]
+SUBSET = {"clipL257-31": 8}     # slots E compares where it is not 24 (module docstring)
 BY_NAME = {c.name: c for c in CASES}
 CONTROL = "vit5-2203"           # the Sfx case whose recorded taps the negative controls and the indexed entry use
 
@@ -106,6 +143,21 @@ SLOT_TOL = {
     "vit5-chunk-2300": (1.602e-03, 1.683e-03),
     "vit5n-37": (1.365e-03, 1.556e-03),
     "bert8n-37": (7.623e-05, 1.101e-04),
+    "deb30-358": (6.153e-04, 7.396e-04),
+    "deb30-367": (6.153e-04, 7.396e-04),
+    "deb30-bf16-367": (4.758e-03, 5.914e-03),
+    "deb128-85": (5.837e-04, 7.354e-04),
+    "debL30-265": (6.183e-04, 8.439e-04),
+    "debX30-367": (5.025e-04, 5.478e-04),
+    "deb30-chunk-759": (6.153e-04, 7.396e-04),
+    "clip5-2150": (3.832e-04, 5.350e-04),
+    "clip5-2203": (3.931e-04, 5.289e-04),
+    "clip5-full-2203": (3.931e-04, 5.289e-04),
+    "clip5-bf16-2203": (3.188e-03, 4.170e-03),
+    "clip50-216": (3.389e-04, 4.643e-04),
+    "clipL5-1603": (5.035e-04, 6.901e-04),
+    "clipL257-31": (4.405e-04, 5.949e-04),
+    "clip5-chunk-4363": (4.033e-04, 5.292e-04),
 }
 
 _TOWER, _PACKED, _REC = {}, {}, {}
@@ -153,8 +205,15 @@ def check_oracle(t, o, dt, tap0, slot_tol, what=""):
 
 # ---- towers and inputs ------------------------------------------------------------------------------------------------------------------
 
+def _family(cfg):
+    if isinstance(cfg, weights.VitConfig):
+        return CLIP if cfg.pre_ln else VIT
+    return DEBERTA if isinstance(cfg, weights.DebertaConfig) else BERT
+
+
 def _is_vit(cfg):
-    return isinstance(cfg, weights.VitConfig)
+    """An image tower (ViT or CLIP): image inputs, the ViT executor."""
+    return _family(cfg) in (VIT, CLIP)
 
 
 def _tokens(case):
@@ -176,12 +235,12 @@ def _tower(name):
     if name not in _TOWER:
         cfg = TOWERS[name]
         n = max(c.M for c in CASES if c.tower == name) + 5
-        seed = 80 + sorted(TOWERS).index(name)
+        seed = SEEDS[name]
         if _is_vit(cfg):
             w = weights.make_vit_weights(cfg, seed=seed)
             pool = synth.make_images(np.arange(n), cfg.image, seed=seed)          # slot 0 (id 0) is the zero image
         else:
-            w = weights.make_bert_weights(cfg, seed=seed)
+            w = (weights.make_deberta_weights if _family(cfg) == DEBERTA else weights.make_bert_weights)(cfg, seed=seed)
             pool = _titles(n, WORDS[name], cfg.vocab, seed)
         _TOWER[name] = SimpleNamespace(cfg=cfg, w=w, w64={k: v.double() for k, v in w.items()}, pool=pool)
     return _TOWER[name]
@@ -214,11 +273,13 @@ def _boundary_slots(M, T, chunk):
 
 def _plan(case, M=None):
     cfg = TOWERS[case.tower]
-    vit = _is_vit(cfg)
-    folded = int(vit and case.dt == F16 and cfg.hidden == 768)        # PackedVit supplies the folded set where the executor has the route
-    got = _lib.load().iisan_encoder_plan(VIT if vit else BERT, case.dt, cfg.hidden, cfg.heads, cfg.mlp, _tokens(case), M or case.M, case.chunk,
-                                         2, case.full, folded)
-    return plan_code(VIT if vit else BERT, got)
+    fam = _family(cfg)
+    # the last argument: PackedVit supplies the folded set where the executor has the route; a CLIP tower has none; DeBERTa: the span
+    last = {VIT: int(case.dt == F16 and cfg.hidden == 768), CLIP: 0, BERT: 0}.get(fam)
+    if fam == DEBERTA:
+        last = cfg.position_buckets
+    got = _lib.load().iisan_encoder_plan(fam, case.dt, cfg.hidden, cfg.heads, cfg.mlp, _tokens(case), M or case.M, case.chunk, 2, case.full, last)
+    return plan_code(fam, got)
 
 
 def _inputs(case):
@@ -237,7 +298,7 @@ def _inputs(case):
     near = [s for s in near if 0 < s < M]
     g = torch.Generator().manual_seed(1000 + M)
     others = [s for s in torch.randperm(M, generator=g).tolist() if s not in (0, SRC, M - 1) and s not in dups and s not in near][:10]
-    subset = list(dict.fromkeys([0, M - 1, SRC] + dups + near + others))[:24]
+    subset = list(dict.fromkeys([0, M - 1, SRC] + dups + near + others))[:SUBSET.get(case.name, 24)]
     return x, [SRC] + dups, subset
 
 
@@ -257,8 +318,13 @@ def _other_items(case):
 
 def _oracle(case, x, subset):
     tw = _tower(case.tower)
+    fam = _family(tw.cfg)
     with torch.no_grad():
-        if _is_vit(tw.cfg):
+        if fam == CLIP:
+            return CO.clip_cls_taps(x[subset].double(), tw.w64, tw.cfg)
+        if fam == DEBERTA:
+            return DO.deberta_cls_taps(x[subset], tw.w64, tw.cfg)
+        if fam == VIT:
             return O.vit_cls_taps(x[subset].double(), tw.w64, tw.cfg)
         return O.bert_cls_taps(x[subset], tw.w64, tw.cfg)
 
@@ -382,14 +448,84 @@ def test_indexed_entry_equals_the_materialised_call(lib):
         enc.ws = encoders._Workspace()
 
 
+def test_deberta_chunked_call_equals_the_unchunked_one(lib):
+    """C: 759 titles in chunks of 400 (a 359-title last chunk) against the same titles in one call, both on Maf: every chunk reads the
+    position tables that were projected once."""
+    case = BY_NAME["deb30-chunk-759"]
+    assert _lib.dev_state() == ""
+    assert _plan(case) == "Maf" and _plan(case._replace(chunk=0)) == "Maf"
+    enc = _packed(case.tower, case.dt)
+    enc.ws = encoders._Workspace()
+    xg = _inputs(case)[0].cuda()
+    try:
+        check_bits(_call(enc, xg, case.chunk), _call(enc, xg, 0), "759 titles: chunks of 400 against one call")
+    finally:
+        enc.ws = encoders._Workspace()
+
+
+def test_deberta_indexed_entry_equals_the_materialised_call(lib):
+    """C: `forward_taps_indexed` over a 64-row title table on Maf: the index holds the planted duplicates and two out-of-range values
+    (padding slots: ids and mask zero), the materialised call sees the same rows."""
+    case = BY_NAME["deb30-367"]
+    assert _lib.dev_state() == ""
+    assert _plan(case) == "Maf"
+    enc = _packed(case.tower, case.dt)
+    enc.ws = encoders._Workspace()
+    _, dups, _ = _inputs(case)
+    table = _titles(64, WORDS[case.tower], DO.VOCAB, 11)
+    index = torch.randint(0, 64, (case.M,), generator=torch.Generator().manual_seed(11))
+    index[dups] = 7
+    index[0], index[300] = -1, 64 + 5
+    assert 300 not in dups
+    pad = (index < 0) | (index >= 64)
+    direct = table[index.clamp(0, 63)].clone()
+    direct[pad] = 0
+    try:
+        want = _call(enc, direct.cuda())
+        got = enc.forward_taps_indexed(table.cuda(), index.cuda(), TAPS).cpu()
+        check_bits(got, want, "indexed against materialised")
+        check_dups(got, dups, "indexed")
+        check_bits(got[300], got[0], "the two padding slots")
+    finally:
+        enc.ws = encoders._Workspace()
+
+
+def test_deberta_tables_projected_by_the_call_give_the_same_bits(lib):
+    """D: the Maf case on a `PackedDeberta(..., project_tables=False)`: the position tables live in the call's workspace and are projected
+    on every call, behind the chunk buffers.  The same bits as the tower that projected them once, under all three poisons, and in chunks
+    of 200 titles (200 + 167: both towers on Ma)."""
+    case = BY_NAME["deb30-367"]
+    assert _lib.dev_state() == ""
+    assert _plan(case) == "Maf" and _plan(case._replace(chunk=200)) == "Ma"
+    tw, enc = _tower(case.tower), _packed(case.tower, case.dt)
+    own = encoders.PackedDeberta(tw.w, tw.cfg, "cuda", case.dt, project_tables=False)
+    assert enc.struct.rel_proj and not own.struct.rel_proj
+    enc.ws = encoders._Workspace()
+    xg = _inputs(case)[0].cuda()
+    try:
+        want, want200 = _call(enc, xg), _call(enc, xg, 200)
+        assert torch.isfinite(want).all() and torch.isfinite(want200).all()
+        check_bits(_call(own, xg), want, "tables projected by the call")
+        need = own.ws.buf.numel()
+        assert need > enc.ws.buf.numel()
+        for byte in POISON:
+            own.ws.buf.fill_(byte)
+            check_bits(_call(own, xg), want, f"tables projected by the call: workspace filled with 0x{byte:02X}")
+            own.ws.buf.fill_(byte)
+            check_bits(_call(own, xg, 200), want200, f"tables projected by the call, chunks of 200: workspace filled with 0x{byte:02X}")
+            assert own.ws.buf.numel() == need
+    finally:
+        enc.ws = encoders._Workspace()
+
+
 # ---- E ---------------------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("name", list(BY_NAME))
 def test_slots_match_the_float64_oracle(lib, name):
     case = BY_NAME[name]
     rec = _record(case)[0]
-    assert len(rec.subset) <= 24
-    check_oracle(rec.t_sub, rec.o, case.dt, TAP0_VIT if _is_vit(TOWERS[case.tower]) else TAP0_BERT, SLOT_TOL.get(name), name)
+    assert len(rec.subset) <= SUBSET.get(name, 24)
+    check_oracle(rec.t_sub, rec.o, case.dt, TAP0[_family(TOWERS[case.tower])], SLOT_TOL.get(name), name)
 
 
 # ---- negative controls: on the CPU, on the recorded taps of the Sfx case -----------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The plan ladders of the two frozen-tower executors at the library defaults, as literal `(case, M) -> plan` rows.
+"""The plan ladders of the two frozen-tower executors (four tower families) at the library defaults, as literal `(case, M) -> plan` rows.
 
 At the defaults (`_lib.dev_state() == ""`) the plan of a call (encoders.hip: vit_plan / bert_plan, asked through `iisan_encoder_plan`) is a
 function of the batch size alone, because gemm16_route hands a product to the 256x256 kernel `gemm16_h256` — the only kernel with LayerNorm
@@ -28,12 +28,23 @@ rows, the first row count at which a product of N columns reaches 128 tiles is (
   * A chunked call has two chunk sizes, Mc and the last one, and the smaller decides: M = 2,300 in chunks of 2,200 ends on 100 items (`I`),
     3,300 on 1,100 (>= 1,076, < 2,151: `F`), 4,363 on 2,163 (>= 2,151: `Sfx`).
   * The narrow towers (hidden 128 - 384) have no 256x256 route at these sizes at all.
+  * A CLIP vision tower (tower kind 2, the ViT letters) never takes the folded routes (vit_fold_routes: its pre-LayerNorm stream keeps the
+    LayerNorm images), at 768 with fp16 operands included: `I` throughout, and `f` where FC1 and FC2 are on gemm16_h256, quick-GELU
+    epilogue and all; `full_blocks` changes neither.  768: 10,753 rows, 1024: 7,937 rows.  First M = ceil(rows / T):
+        768, T = 5 (32 px, patch 16):     ceil(10,753 / 5) = 2,151        768, T = 50 (B/32 at 224 px):    ceil(10,753 / 50) = 216
+        1024, T = 5 (28 px, patch 14):    ceil(7,937 / 5) = 1,588         1024, T = 257 (L/14 at 224 px):  ceil(7,937 / 257) = 31
+        768, T = 5, chunks of 2,200:      2,200 + 2,151 = 4,351 (the last chunk decides)
+  * A DeBERTa text tower (tower kind 3, the BERT letters; the last argument of `iisan_encoder_plan` carries the span) runs the BERT
+    executor's plan: `a` with fp16 operands, `f` from the same row counts.
+        768, 30 words:   ceil(10,753 / 30) = 359       768, 128 words:  ceil(10,753 / 128) = 85       1024, 30 words:  ceil(7,937 / 30) = 265
+        768, 30 words, chunks of 400:  400 + 359 = 759
+        384 (N = 384, 1,536: N % 256 != 0, no 256x256 route): never `f`.
 
 A changed rule moves a threshold and fails the row at the step's first M or at M - 1.  Plan letters: tests/test_host_logic.py::
 test_encoder_plan_table.  The GPU file tests/test_gpu_tower_plan_ladder.py runs one case per step and asserts the same strings."""
 import pytest
 
-VIT, BERT, F16, BF16 = 0, 1, 0, 1
+VIT, BERT, CLIP, DEBERTA, F16, BF16 = 0, 1, 2, 3, 0, 1
 
 
 def vit(dt=F16, hidden=768, tokens=5, chunk=0, full=0):
@@ -44,6 +55,16 @@ def vit(dt=F16, hidden=768, tokens=5, chunk=0, full=0):
 
 def bert(dt=F16, hidden=768, words=30):
     return (BERT, dt, hidden, hidden // 64, 4 * hidden, words, 0, 2, 0, 0)
+
+
+def clip(dt=F16, hidden=768, tokens=5, chunk=0, full=0):
+    """A CLIP vision tower: the ViT executor, never the folded set."""
+    return (CLIP, dt, hidden, hidden // 64, 4 * hidden, tokens, chunk, 2, full, 0)
+
+
+def deberta(dt=F16, hidden=768, words=30, chunk=0, span=256):
+    """A DeBERTa-v2/v3 text tower: the BERT executor; the last argument carries the span."""
+    return (DEBERTA, dt, hidden, hidden // 64, 4 * hidden, words, chunk, 2, 0, span)
 
 
 LADDERS = [
@@ -67,6 +88,28 @@ LADDERS = [
     # the narrow towers of the GPU file
     (vit(hidden=192), [(37, "I")]),
     (bert(hidden=128, words=8), [(37, "Ma")]),
+    # DeBERTa 768, 30 words, span 256: fp16 Ma from 1, Maf from 359; bf16 M, then Mf
+    (deberta(), [(1, "Ma"), (358, "Ma"), (359, "Maf"), (367, "Maf")]),
+    (deberta(dt=BF16), [(358, "M"), (359, "Mf")]),
+    # DeBERTa 768, 128 words (the longest title): Maf from 85
+    (deberta(words=128), [(84, "Ma"), (85, "Maf")]),
+    # DeBERTa 1024 (v2-large's width), 30 words: Maf from 265
+    (deberta(hidden=1024), [(264, "Ma"), (265, "Maf")]),
+    # DeBERTa 384 (v3-xsmall's width): N % 256 != 0, never f
+    (deberta(hidden=384), [(367, "Ma"), (1408, "Ma")]),
+    # 30 words in chunks of 400 titles: the last chunk decides
+    (deberta(chunk=400), [(758, "Ma"), (759, "Maf")]),
+    # CLIP 768, fp16, 5 tokens: no folded route, I from 1, If from 2,151; full_blocks changes nothing
+    (clip(), [(2150, "I"), (2151, "If"), (2203, "If")]),
+    (clip(full=1), [(2150, "I"), (2151, "If"), (2203, "If")]),
+    (clip(dt=BF16), [(2150, "I"), (2151, "If")]),
+    # CLIP 768, 50 tokens (B/32 at 224 px): If from 216
+    (clip(tokens=50), [(215, "I"), (216, "If")]),
+    # CLIP 1024, 5 tokens (28 px, patch 14) and 257 tokens (L/14 at 224 px)
+    (clip(hidden=1024), [(1587, "I"), (1588, "If")]),
+    (clip(hidden=1024, tokens=257), [(30, "I"), (31, "If")]),
+    # CLIP 768, 5 tokens in chunks of 2,200 items
+    (clip(chunk=2200), [(4350, "I"), (4351, "If")]),
 ]
 
 
@@ -74,7 +117,7 @@ def plan_code(tower, w):
     """The letters of tests/test_host_logic.py::test_encoder_plan_table."""
     if w < 0:
         return "!"
-    if tower == VIT:
+    if tower in (VIT, CLIP):
         return "RIFS"[w & 3] + ("f" if w & 4 else "") + ("x" if w & 8 else "") + ("w" if w & 16 else "")
     return ("M" if w & 1 else "P") + ("a" if w & 2 else "") + ("f" if w & 4 else "")
 
@@ -111,3 +154,6 @@ def test_thresholds_follow_the_half_a_tile_per_cu_rule():
     assert (up(5377, 5), up(3585, 5), up(10753, 5)) == (1076, 717, 2151)
     assert (up(7937, 5), up(10753, 30)) == (1588, 359)
     assert (2300 % 2200, 3300 % 2200, 4363 % 2200) == (100, 1100, 2163) and 2200 + 1076 == 3276 and 2200 + 2151 == 4351
+    # the CLIP and DeBERTa ladders: B/32 at 224 px, 128-word titles, the 1024-wide towers, the chunked sums
+    assert (up(10753, 50), up(10753, 128), up(7937, 30), up(7937, 257)) == (216, 85, 265, 31)
+    assert 2200 + up(10753, 5) == 4351 and 400 + up(10753, 30) == 759 and 759 % 400 == 359 and 758 % 400 == 358

@@ -4,6 +4,9 @@ Frobenius error of the plan under test over the compared slots, its worst per-sl
 fixtures pin to the reference (gemm16_variant = 1, chunk_items = 8) on the SAME slots against the SAME float64 oracle.
 
     python3 tools/tower_plan_ladder.py              prints the table of profiles/tower_plan_ladder.md and the SLOT_TOL literal (2 x the last figure)
+    python3 tools/tower_plan_ladder.py deb clip     ... for the cases whose names start with one of the given prefixes only
+
+The cases of all four tower families (ViT, BERT, CLIP, DeBERTa) are measured the same way: the pinned route is set here and nowhere else.
 
 Reads the cases, inputs and oracle from the test module, so the two cannot drift apart."""
 import os
@@ -22,7 +25,8 @@ def main():
     assert torch.cuda.is_available(), "tower_plan_ladder: needs the GPU"
     _lib.load()
     rows, tol = [], []
-    for case in L.CASES:
+    prefixes = tuple(sys.argv[1:])
+    for case in [c for c in L.CASES if not prefixes or c.name.startswith(prefixes)]:
         rec, _, _ = L._record(case)
         x, _, subset = L._inputs(case)
         per_slot, per_tap = L.slot_errors(rec.t_sub, rec.o)
